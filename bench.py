@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark: range-images/sec of the reverse-process sampler (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1,2,4}]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1,2,4}] [--dump-outputs DIR] [--full]
 
 A "step" (driver vocabulary) is ONE reverse step over the whole per-GPU batch: one U-Net forward
 (r2dm_unet_forward) + RNG draw + fused posterior update.  Workloads (BASELINE.json `configs`):
@@ -19,7 +19,11 @@ sustained 256-step rate it is scaled to (round 2: 4.75 vs 4.53 images/s in one j
 For N > 1 launch under torch.distributed.run (one rank per GPU): rank 0 packs the weights, the packed blob is
 broadcast over RCCL/xGMI, every rank samples its own seeds; no collective in the step loop.
 
-Two baselines ride on the same JSON line at N = 1 (rank 0): `cpu_baseline` = the oracle (torch CPU ops) on the host
+A plain run does only what the headline needs: set-up, clock pre-warm, W warm-up steps, the K timed steps, the outputs
+(`--dump-outputs DIR`: the timed call's samples as DIR/samples.npy, float32) and the JSON line.  Everything below -- the
+roofline (an extra profiled pass), the baselines and the other configurations -- runs only with `--full`.
+
+With `--full`, two baselines ride on the same JSON line at N = 1 (rank 0): `cpu_baseline` = the oracle (torch CPU ops) on the host
 cores, and `torch_rocm_baseline` = the same oracle on the MI355X through stock PyTorch-ROCm (MIOpen / rocBLAS) -- the
 stand-in for north_star's "reference single-GPU PyTorch sampler" (the reference's own files never travel to the GPU
 box; the oracle is pinned to it by tests/golden); `vs_torch_rocm_baseline` = value / that (`vs_baseline` is null: BASELINE.md
@@ -241,10 +245,23 @@ def pmc_traffic(what="bytes_per_launch"):
         return None
 
 
+def dump_outputs(path, t, budget):
+    """`--dump-outputs`: t as a float32 .npy; a t larger than `budget` bytes is written as a fixed, seeded sample of its elements
+    (flattened, in index order), the same elements in every run of the same arguments."""
+    import numpy as np
+
+    a = t.detach().float().cpu().numpy()
+    if a.nbytes > budget:
+        idx = np.sort(np.random.default_rng(0).choice(a.size, budget // a.itemsize, replace=False))
+        a = a.reshape(-1)[idx]
+    np.save(path, a)
+
+
 def launch_ranks(args):
     """`--gpus N` stands on its own (the reference gets its ranks from `accelerate launch`, /root/reference/sample_and_save.py:25-46):
     * WORLD_SIZE set (torch.distributed.run started us): it must equal --gpus, or the line would report a world the caller did not ask for;
-    * WORLD_SIZE unset and N > 1: re-execute under `torch.distributed.run --nproc-per-node N` with the same arguments;
+    * WORLD_SIZE unset and N > 1: run `torch.distributed.run --nproc-per-node N` with the same arguments as a child process and exit
+      with its status (a child, not an exec: this process has already initialised the HIP runtime through device_count());
     * RCCL wants one device per rank: N > torch.cuda.device_count() fails here, in seconds, naming the device count (R2DM_DIST_BACKEND=gloo
       lets ranks share a GPU: the tests' two-ranks-on-one-GPU layout)."""
     env_world = os.environ.get("WORLD_SIZE")
@@ -271,14 +288,16 @@ def launch_ranks(args):
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+    import subprocess
+
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    sys.exit(subprocess.call(cmd))
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None, help="number of GPUs = ranks of ONE node.  Under torch.distributed.run it must equal WORLD_SIZE; "
-                    "without a launcher (WORLD_SIZE unset) and N > 1 this process re-executes itself under torch.distributed.run with N ranks")
+                    "without a launcher (WORLD_SIZE unset) and N > 1 this process runs itself under torch.distributed.run with N ranks")
     ap.add_argument("--steps", type=int, default=16)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", type=int, choices=sorted(CONFIGS), default=1, help="BASELINE.json configs[i] (see module docstring)")
@@ -286,7 +305,7 @@ def main():
     ap.add_argument("--prewarm-s", type=float, default=2.0, help="minimum seconds of untimed sampling before the warm-up steps; continues "
                     "(up to 4x as long) until two consecutive 0.5 s windows agree within 1 %% in shader clock and board power")
     ap.add_argument("--no-exact-baseline", action="store_true", help="skip the fp32-bf16x3 (exact 24-bit operand split) timing")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short runs of BASELINE configs[2] and configs[4] that ride on the default line")
+    ap.add_argument("--no-other-configs", action="store_true", help="skip the short runs of BASELINE configs[2] and configs[4] that ride on the --full line")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-torch-baseline", action="store_true")
     ap.add_argument("--no-compile-baseline", action="store_true", help="skip the torch.compile + fp16 autocast form of the PyTorch-ROCm baseline (its compilation takes a minute or two)")
@@ -296,6 +315,10 @@ def main():
                          "reduced-precision bulk mode (one fp16 product per MAC, the reference's autocast mode): never the headline")
     ap.add_argument("--seed-base", type=int, default=0, help="first global seed (tests: reproduce one rank's shard alone)")
     ap.add_argument("--dump-samples", default=None, help="directory: every rank saves {seeds, samples} of the timed call (tests)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="directory: the samples the timed call returned (its last step's "
+                    "output) as DIR/samples.npy, float32 (rank r > 0 of a multi-rank run: samples_rank<r>.npy), at most 64 MB in all")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the roofline (an extra profiled "
+                    "pass), the hipBLASLt / PyTorch-ROCm / exact-split / CPU baselines and the other configurations")
     args = ap.parse_args()
     cf = CONFIGS[args.config]
     launch_ranks(args)
@@ -379,11 +402,14 @@ def main():
     if args.dump_samples:
         os.makedirs(args.dump_samples, exist_ok=True)
         torch.save({"seeds": seeds, "samples": out.cpu()}, os.path.join(args.dump_samples, f"rank{rank}.pt"))
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        dump_outputs(os.path.join(args.dump_outputs, "samples.npy" if rank == 0 else f"samples_rank{rank}.npy"), out, (64 << 20) // world)
 
     # The convolution launches (~96 % of the FLOPs and of the step time), per kernel class: an extra, untimed pass of a few
     # steps with every conv launch bracketed by HIP events on the sampling stream (r2dm_profile_*).
     conv = None
-    if rank == 0:
+    if rank == 0 and args.full:
         ddpm.model.profile_convs(True)
         psteps = min(args.steps, 4)
         run(psteps)
@@ -452,110 +478,111 @@ def main():
                                               "reference's fp16 autocast (sample_and_save.py:70); own tolerance class (tests/test_hip_fp16_mode.py)"}[args.precision],
                        "parallelism": f"dp{world} (independent seeds, no step-loop collective)"},
         }
-        dom = conv[0]
-        bsum = board.summary()
-        line["roofline"] = {
-            "bound": "mfma", "achieved": dom["tflops"], "peak": dom["peak_tflops"], "unit": "TFLOP/s", "frac": dom["frac"],
-            "traffic": pmc_traffic() if args.config == 1 else None,
-            "traffic_measured": False,  # (replayed from the committed PMC passes, see traffic_source: not a measurement of THIS run)
-            "traffic_source": "replayed: profiles/conv_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this same command, evidence set %s; "
-                              "PMC counters cannot be collected inside the timed process)" % pmc_traffic("source") if args.config == 1 else None,
-            "peak_definition": "dominant kernel %s: dense 16-bit MFMA peak 2500 TF/s (2.4 GHz) / %d matrix products per algorithmic "
-                               "fp32 product" % (dom["kernel"], dom.get("products_per_fp32_product", 1)),
-            "frac_of_round1_peak": dom["tflops"] / (PEAK_BF16 / 6 / 1e12),  # round 1 priced the same algorithmic FLOPs at 2500/6 = 416.7 TF/s
-            "frac_of_fp32_mfma_peak": dom["tflops"] * 1e12 / PEAK_FP32,
-            "dominant_kernel": dom, "other_conv_kernels": conv[1:],
-            "all_convs": {"tflops": sum(e["tflops"] * e["ms_per_step"] for e in conv) / sum(e["ms_per_step"] for e in conv),
-                          "ms_per_step": sum(e["ms_per_step"] for e in conv), "launches_per_step": sum(e["launches_per_step"] for e in conv)},
-            "whole_step": {"achieved": step_flops / 1e12, "frac_of_fp32_mfma_peak": step_flops / PEAK_FP32,
-                           "note": "%.2f GFLOP/image-step x batch / HIP-event time of the timed sample() call" % (cf["flop"] / 1e9)},
-            "board": bsum,
-            "note": "achieved = algorithmic conv FLOPs / kernel time of the dominant kernel class (HIP events on the sampling "
-                    "stream, rank 0, extra untimed pass); peak is the NOMINAL matrix-pipe peak at 2.4 GHz -- the board power "
-                    "limit holds the shader clock below that while these kernels run (`board`, sampled during the timed "
-                    "region; profiles/r02_power_clock.txt), as it does for hipBLASLt's bf16 GEMM (`hipblaslt_bf16_gemm`); "
-                    "traffic = HBM bytes per conv launch from the last committed rocprofv3 PMC passes "
-                    "(profiles/conv_traffic.json), config 1 only"}
-        # The event pair that brackets a launch spans more than the kernel: reconciled here with rocprofv3's kernel durations (profiles/*_rocprof_summary.txt).
-        # `frac` above stays the raw figure (the method of every round); the band is what it becomes with the pair's own span taken off.
-        lo, hi = dom["avg_launch_us"] - ev_pair[1], dom["avg_launch_us"] - ev_pair[0]
-        line["roofline"]["event_bracket"] = {
-            "empty_pair_us": ev_pair[0], "empty_kernel_pair_us": ev_pair[1], "avg_launch_us_raw": dom["avg_launch_us"], "avg_launch_us_band": [lo, hi],
-            "frac_band": [dom["frac"] * dom["avg_launch_us"] / hi, dom["frac"] * dom["avg_launch_us"] / lo],
-            "note": "an event pair on an idle stream spans empty_pair_us around nothing and empty_kernel_pair_us around an empty kernel (marker processing + one dispatch + "
-                    "that kernel's ~1 us), medians of 33 in this process; rocprofv3's average duration of the same kernel lies at the band's lower end (profiles/r06d_*: 93.0 us where this figure was 99.1, band 93.0-94.6; "
-                    "r06b: 94.8 against a band of 96.1-97.7 -- a pair costs up to ~1.5 us more on a busy stream than on an idle one)"}
-        if bsum and dom.get("products_per_fp32_product"):
-            pk = PEAK_BF16 * bsum["sclk_mhz"] / 2400.0 / dom["products_per_fp32_product"] / 1e12
-            line["roofline"]["peak_at_sustained_clock"] = pk
-            line["roofline"]["frac_at_sustained_clock"] = dom["tflops"] / pk
-        if world == 1 and not args.no_torch_baseline:
-            line["roofline"]["hipblaslt_bf16_gemm"] = hipblaslt_reference(dev)
-        if world == 1 and not args.no_torch_baseline:
-            tb = torch_rocm_baseline(ck, cf, B, dev, compiled=not args.no_compile_baseline)
-            tb["speedup"] = value / tb["value"]
-            line["torch_rocm_baseline"] = tb
-            # north_star: ">= N x the reference single-GPU PyTorch sampler" -- BASELINE.md / BASELINE.json ("published": {}) hold no
-            # published number for this metric, so `vs_baseline` stays null (the bench contract); the ratio against the baseline
-            # measured beside it in this run is reported under its own name
-            line["vs_torch_rocm_baseline"] = value / tb["value"]
-            line["vs_torch_rocm_baseline_definition"] = "value / torch_rocm_baseline.value (the reference's sampler as stock PyTorch-ROCm runs it on this GPU, fp32, same run)"
-            ac = tb.get("fp16_autocast", {})
-            if "value" in ac:
-                ac["speedup"] = value / ac["value"]
-                if args.precision == "fp16":  # the reduced mode is compared with the reference's reduced mode
-                    line["vs_torch_rocm_baseline"] = value / ac["value"]
-                    line["vs_torch_rocm_baseline_definition"] = "value / torch_rocm_baseline.fp16_autocast.value (the reference's fp16-autocast bulk mode on this GPU, same run)"
-            cc = tb.get("compiled_fp16_autocast", {})
-            if "value" in cc:
-                cc["speedup"] = value / cc["value"]
-                if args.precision == "fp16" and cc["value"] > ac.get("value", 0.0):  # (against the FASTER form of the reference's bulk mode)
-                    line["vs_torch_rocm_baseline"] = value / cc["value"]
-                    line["vs_torch_rocm_baseline_definition"] = "value / torch_rocm_baseline.compiled_fp16_autocast.value (torch.compile + fp16 autocast: the reference's bulk sampler as sample_and_save.py runs it, same run)"
-        if world == 1 and not args.no_exact_baseline and args.precision == "fp32":
-            ddpm.model.set_precision("fp32-bf16x3")
-            prewarm(1.0)
-            run(max(args.warmup, 1))
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            run(args.steps)
-            torch.cuda.synchronize()
-            dte = time.perf_counter() - t1
-            ddpm.model.set_precision("fp32")
-            line["exact_split_baseline"] = {"value": B / (dte / args.steps * S), "unit": "images/s", "ms_per_step": dte / args.steps * 1e3,
-                                            "precision": "fp32-bf16x3", "headline_speedup": value / (B / (dte / args.steps * S)),
-                                            "what": "the same timed sample() call with exact 24-bit operands: three bf16 pieces, six products per fp32 "
-                                                    "product (conv_bf16x3.hip), fp32-input MFMA for 1x1 convolutions and attention"}
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(ck, cf)
-        if world == 1 and args.config == 1 and args.precision == "fp32" and args.batch is None and not args.no_other_configs:
-            # BASELINE configs[2] and configs[4] (per-GPU shard) beside the headline, same process and board state: one timed
-            # sample() call each after a 1 s pre-warm (their full lines incl. baselines: `--config 2` / `--config 4`)
-            del ddpm
-            torch.cuda.empty_cache()
-            others = {}
-            for ci, osteps in ((2, 32), (4, 8)):
-                oc = CONFIGS[ci]
-                ock = synthetic.synthetic_checkpoint(seed=0, resolution=oc["res"])
-                om, _, _ = r2dm_amd.setup_model(ock, device=dev, show_info=False, max_batch=oc["batch"], precision=args.precision)
-                oseeds = list(range(oc["batch"]))
-                orun = lambda n: om.sample(batch_size=oc["batch"], num_steps=n, progress=False, mode=oc["mode"], rng=r2dm_amd.setup_rng(oseeds, dev))
-                t_pw = time.perf_counter()
-                while time.perf_counter() - t_pw < 1.0:
-                    orun(4)
-                    torch.cuda.synchronize()
-                orun(osteps)  # (same step count as the timed call: its schedule table is then cached, as for any repeated call)
+        if args.full:
+            dom = conv[0]
+            bsum = board.summary()
+            line["roofline"] = {
+                "bound": "mfma", "achieved": dom["tflops"], "peak": dom["peak_tflops"], "unit": "TFLOP/s", "frac": dom["frac"],
+                "traffic": pmc_traffic() if args.config == 1 else None,
+                "traffic_measured": False,  # (replayed from the committed PMC passes, see traffic_source: not a measurement of THIS run)
+                "traffic_source": "replayed: profiles/conv_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this same command, evidence set %s; "
+                                  "PMC counters cannot be collected inside the timed process)" % pmc_traffic("source") if args.config == 1 else None,
+                "peak_definition": "dominant kernel %s: dense 16-bit MFMA peak 2500 TF/s (2.4 GHz) / %d matrix products per algorithmic "
+                                   "fp32 product" % (dom["kernel"], dom.get("products_per_fp32_product", 1)),
+                "frac_of_round1_peak": dom["tflops"] / (PEAK_BF16 / 6 / 1e12),  # round 1 priced the same algorithmic FLOPs at 2500/6 = 416.7 TF/s
+                "frac_of_fp32_mfma_peak": dom["tflops"] * 1e12 / PEAK_FP32,
+                "dominant_kernel": dom, "other_conv_kernels": conv[1:],
+                "all_convs": {"tflops": sum(e["tflops"] * e["ms_per_step"] for e in conv) / sum(e["ms_per_step"] for e in conv),
+                              "ms_per_step": sum(e["ms_per_step"] for e in conv), "launches_per_step": sum(e["launches_per_step"] for e in conv)},
+                "whole_step": {"achieved": step_flops / 1e12, "frac_of_fp32_mfma_peak": step_flops / PEAK_FP32,
+                               "note": "%.2f GFLOP/image-step x batch / HIP-event time of the timed sample() call" % (cf["flop"] / 1e9)},
+                "board": bsum,
+                "note": "achieved = algorithmic conv FLOPs / kernel time of the dominant kernel class (HIP events on the sampling "
+                        "stream, rank 0, extra untimed pass); peak is the NOMINAL matrix-pipe peak at 2.4 GHz -- the board power "
+                        "limit holds the shader clock below that while these kernels run (`board`, sampled during the timed "
+                        "region; profiles/r02_power_clock.txt), as it does for hipBLASLt's bf16 GEMM (`hipblaslt_bf16_gemm`); "
+                        "traffic = HBM bytes per conv launch from the last committed rocprofv3 PMC passes "
+                        "(profiles/conv_traffic.json), config 1 only"}
+            # The event pair that brackets a launch spans more than the kernel: reconciled here with rocprofv3's kernel durations (profiles/*_rocprof_summary.txt).
+            # `frac` above stays the raw figure (the method of every round); the band is what it becomes with the pair's own span taken off.
+            lo, hi = dom["avg_launch_us"] - ev_pair[1], dom["avg_launch_us"] - ev_pair[0]
+            line["roofline"]["event_bracket"] = {
+                "empty_pair_us": ev_pair[0], "empty_kernel_pair_us": ev_pair[1], "avg_launch_us_raw": dom["avg_launch_us"], "avg_launch_us_band": [lo, hi],
+                "frac_band": [dom["frac"] * dom["avg_launch_us"] / hi, dom["frac"] * dom["avg_launch_us"] / lo],
+                "note": "an event pair on an idle stream spans empty_pair_us around nothing and empty_kernel_pair_us around an empty kernel (marker processing + one dispatch + "
+                        "that kernel's ~1 us), medians of 33 in this process; rocprofv3's average duration of the same kernel lies at the band's lower end (profiles/r06d_*: 93.0 us where this figure was 99.1, band 93.0-94.6; "
+                        "r06b: 94.8 against a band of 96.1-97.7 -- a pair costs up to ~1.5 us more on a busy stream than on an idle one)"}
+            if bsum and dom.get("products_per_fp32_product"):
+                pk = PEAK_BF16 * bsum["sclk_mhz"] / 2400.0 / dom["products_per_fp32_product"] / 1e12
+                line["roofline"]["peak_at_sustained_clock"] = pk
+                line["roofline"]["frac_at_sustained_clock"] = dom["tflops"] / pk
+            if world == 1 and not args.no_torch_baseline:
+                line["roofline"]["hipblaslt_bf16_gemm"] = hipblaslt_reference(dev)
+            if world == 1 and not args.no_torch_baseline:
+                tb = torch_rocm_baseline(ck, cf, B, dev, compiled=not args.no_compile_baseline)
+                tb["speedup"] = value / tb["value"]
+                line["torch_rocm_baseline"] = tb
+                # north_star: ">= N x the reference single-GPU PyTorch sampler" -- BASELINE.md / BASELINE.json ("published": {}) hold no
+                # published number for this metric, so `vs_baseline` stays null (the bench contract); the ratio against the baseline
+                # measured beside it in this run is reported under its own name
+                line["vs_torch_rocm_baseline"] = value / tb["value"]
+                line["vs_torch_rocm_baseline_definition"] = "value / torch_rocm_baseline.value (the reference's sampler as stock PyTorch-ROCm runs it on this GPU, fp32, same run)"
+                ac = tb.get("fp16_autocast", {})
+                if "value" in ac:
+                    ac["speedup"] = value / ac["value"]
+                    if args.precision == "fp16":  # the reduced mode is compared with the reference's reduced mode
+                        line["vs_torch_rocm_baseline"] = value / ac["value"]
+                        line["vs_torch_rocm_baseline_definition"] = "value / torch_rocm_baseline.fp16_autocast.value (the reference's fp16-autocast bulk mode on this GPU, same run)"
+                cc = tb.get("compiled_fp16_autocast", {})
+                if "value" in cc:
+                    cc["speedup"] = value / cc["value"]
+                    if args.precision == "fp16" and cc["value"] > ac.get("value", 0.0):  # (against the FASTER form of the reference's bulk mode)
+                        line["vs_torch_rocm_baseline"] = value / cc["value"]
+                        line["vs_torch_rocm_baseline_definition"] = "value / torch_rocm_baseline.compiled_fp16_autocast.value (torch.compile + fp16 autocast: the reference's bulk sampler as sample_and_save.py runs it, same run)"
+            if world == 1 and not args.no_exact_baseline and args.precision == "fp32":
+                ddpm.model.set_precision("fp32-bf16x3")
+                prewarm(1.0)
+                run(max(args.warmup, 1))
                 torch.cuda.synchronize()
                 t1 = time.perf_counter()
-                oo = orun(osteps)
+                run(args.steps)
                 torch.cuda.synchronize()
-                odt = time.perf_counter() - t1
-                assert torch.isfinite(oo).all()
-                others["configs[%d]" % ci] = {"workload": oc["workload"], "metric": oc["metric"], "value": oc["batch"] / (odt / osteps * oc["sampler_steps"]),
-                                              "unit": "images/s per GPU", "ms_per_step": odt / osteps * 1e3, "steps": osteps}
-                del om
+                dte = time.perf_counter() - t1
+                ddpm.model.set_precision("fp32")
+                line["exact_split_baseline"] = {"value": B / (dte / args.steps * S), "unit": "images/s", "ms_per_step": dte / args.steps * 1e3,
+                                                "precision": "fp32-bf16x3", "headline_speedup": value / (B / (dte / args.steps * S)),
+                                                "what": "the same timed sample() call with exact 24-bit operands: three bf16 pieces, six products per fp32 "
+                                                        "product (conv_bf16x3.hip), fp32-input MFMA for 1x1 convolutions and attention"}
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(ck, cf)
+            if world == 1 and args.config == 1 and args.precision == "fp32" and args.batch is None and not args.no_other_configs:
+                # BASELINE configs[2] and configs[4] (per-GPU shard) beside the headline, same process and board state: one timed
+                # sample() call each after a 1 s pre-warm (their full lines incl. baselines: `--full --config 2` / `--full --config 4`)
+                del ddpm
                 torch.cuda.empty_cache()
-            line["other_configs"] = others
+                others = {}
+                for ci, osteps in ((2, 32), (4, 8)):
+                    oc = CONFIGS[ci]
+                    ock = synthetic.synthetic_checkpoint(seed=0, resolution=oc["res"])
+                    om, _, _ = r2dm_amd.setup_model(ock, device=dev, show_info=False, max_batch=oc["batch"], precision=args.precision)
+                    oseeds = list(range(oc["batch"]))
+                    orun = lambda n: om.sample(batch_size=oc["batch"], num_steps=n, progress=False, mode=oc["mode"], rng=r2dm_amd.setup_rng(oseeds, dev))
+                    t_pw = time.perf_counter()
+                    while time.perf_counter() - t_pw < 1.0:
+                        orun(4)
+                        torch.cuda.synchronize()
+                    orun(osteps)  # (same step count as the timed call: its schedule table is then cached, as for any repeated call)
+                    torch.cuda.synchronize()
+                    t1 = time.perf_counter()
+                    oo = orun(osteps)
+                    torch.cuda.synchronize()
+                    odt = time.perf_counter() - t1
+                    assert torch.isfinite(oo).all()
+                    others["configs[%d]" % ci] = {"workload": oc["workload"], "metric": oc["metric"], "value": oc["batch"] / (odt / osteps * oc["sampler_steps"]),
+                                                  "unit": "images/s per GPU", "ms_per_step": odt / osteps * 1e3, "steps": osteps}
+                    del om
+                    torch.cuda.empty_cache()
+                line["other_configs"] = others
         line["rccl"] = rccl
         print(json.dumps(line))
     if dist:

@@ -7,7 +7,7 @@ out = []
 rows = list(csv.DictReader(open(d + 'bench_kt_kernel_stats.csv')))
 jk = json.load(open(d + 'bench_kt.json'))
 nsteps = sum(int(r['Calls']) for r in rows if 'posterior_kernel' in r['Name'])  # one posterior update per reverse step
-out.append(f"# rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu-baseline --no-torch-baseline   (1x MI355X, batch 8; {nsteps} reverse steps in the trace: "
+out.append(f"# rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu-baseline --no-torch-baseline   (1x MI355X, batch 8; {nsteps} reverse steps in the trace: "
            f"clock pre-warm + {jk['warmup']} warm-up + {jk['steps']} timed + {min(jk['steps'], 4)} profiled)\n")
 out.append("%-86s %7s %9s %11s %10s %7s" % ("kernel", "calls", "per step", "total_ms", "avg_us", "pct"))
 tot = sum(float(r['TotalDurationNs']) for r in rows)
@@ -83,8 +83,8 @@ for pat, (mb, what) in MB.items():
 
 # ---- bench lines
 out.append("\n# bench.py lines of this job")
-for fn, what in (("bench_n1", "python bench.py  (default: config 1, 16 steps)"), ("bench_256", "python bench.py --steps 256 --warmup 8  (the full 256-step sampler in one timed call)"),
-                 ("bench_c2", "python bench.py --config 2  (DDIM-32, batch 32)"), ("bench_c4", "python bench.py --config 4 --steps 8  (128x2048, per-GPU batch 2)")):
+for fn, what in (("bench_n1", "python bench.py --full  (config 1, 16 steps)"), ("bench_256", "python bench.py --full --steps 256 --warmup 8  (the full 256-step sampler in one timed call)"),
+                 ("bench_c2", "python bench.py --full --config 2  (DDIM-32, batch 32)"), ("bench_c4", "python bench.py --full --config 4 --steps 8  (128x2048, per-GPU batch 2)")):
     try:
         b = json.load(open(d + fn + '.json'))
     except OSError:

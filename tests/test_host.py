@@ -490,6 +490,23 @@ def test_conv_f16x2_blocks_own_their_cu(tmp_path):
     assert re.search(r"LDS_TOTAL >= 156 \* 1024 \|\| lds_exact \? GEO::LDS_TOTAL : 156 \* 1024", src), "the launcher's LDS padding"
 
 
+def test_bench_dump_outputs_is_float32_and_capped(tmp_path):
+    """bench.py --dump-outputs: an output within the byte budget is written whole as float32; a larger one as the same seeded
+    sample of its elements (in index order) on every call."""
+    import numpy as np
+
+    import bench
+
+    t = torch.arange(1000, dtype=torch.float64).reshape(10, 100)
+    bench.dump_outputs(str(tmp_path / "whole.npy"), t, 4000)
+    a = np.load(tmp_path / "whole.npy")
+    assert a.dtype == np.float32 and a.shape == (10, 100) and (a == t.numpy()).all()
+    for name in ("s1.npy", "s2.npy"):
+        bench.dump_outputs(str(tmp_path / name), t, 400)
+    s1, s2 = np.load(tmp_path / "s1.npy"), np.load(tmp_path / "s2.npy")
+    assert s1.dtype == np.float32 and s1.shape == (100,) and (s1 == s2).all() and (np.diff(s1) > 0).all() and s1.max() < 1000
+
+
 def test_bench_gpus_flag_is_checked_before_anything_runs():
     """VERDICT round 5, item 2 (no GPU needed): `--gpus N` must agree with the launcher's WORLD_SIZE, and N ranks under RCCL need N devices --
     both fail in seconds, non-zero, with a message that names the numbers (here the device count is 0: no GPU in the CPU tier)."""
