@@ -1,0 +1,125 @@
+#!/usr/bin/env python3
+"""Drop-in for the BEV part of the reference's evaluation script (evaluate.py): scores a directory of generated
+``samples_*.pth`` files (sample_and_save.py's (5,H,W) [depth, x, y, z, reflectance] tensors) against a real set with the
+bird's-eye-view JSD and MMD of metrics/bev.py, on the GPU (r2dm_amd.metrics).
+
+Same CLI (``--ckpt``, ``--sample_dir``, ``--dataset``, ``--batch_size``, ``--num_workers``) and the same output file,
+``{sample_dir}_{timestamp}.json``.  The real set comes from either
+  - the reference's own cache pickle ``real_set_{dataset}_{projection}_{H}x{W}_{split}.pkl`` (its ``bev_hists``), looked for
+    in the working directory under that name as the reference writes it, or given with ``--real_set PATH``; or
+  - ``--real_dir DIR``: a directory of (5,H,W) scans in the sample layout, histogrammed here.
+The dataset itself is not read.  FRD and FPD need the RangeNet-53 / PointNet weights and are not computed here."""
+import datetime
+import json
+import pickle
+import random
+from argparse import ArgumentParser
+from pathlib import Path
+
+import numpy as np
+import torch
+
+# from LiDARGen (reference evaluate.py:19-22)
+MAX_DEPTH = 63.0
+MIN_DEPTH = 0.5
+MAX_SAMPLES = 10_000
+
+
+def sample_files(root, limit=MAX_SAMPLES):
+    """The first ``limit`` sorted ``*.pth`` files of ``root`` (the reference's Samples dataset)."""
+    return sorted(Path(root).glob("*.pth"))[:limit]
+
+
+def load_batches(files, batch_size, num_workers):
+    """(B,5,H,W) fp32 batches of the files, read by a DataLoader as the reference does."""
+
+    class Files(torch.utils.data.Dataset):
+        def __len__(self):
+            return len(files)
+
+        def __getitem__(self, i):
+            img = torch.load(files[i], map_location="cpu")
+            assert img.shape[0] == 5, img.shape
+            return img.float()
+
+    return torch.utils.data.DataLoader(Files(), batch_size=batch_size, num_workers=num_workers)
+
+
+def histograms_of(files, batch_size, num_workers, device):
+    """int32 (N,100,100) BEV histograms of the sample files: depth mask, then point_cloud_to_histogram (evaluate.py:22-41,145-155)."""
+    from r2dm_amd import metrics
+
+    if not files:
+        raise SystemExit("no *.pth files to evaluate")
+    out = [metrics.bev_histograms(imgs.to(device, non_blocking=True), image_min_depth=MIN_DEPTH, image_max_depth=MAX_DEPTH)
+           for imgs in load_batches(files, batch_size, num_workers)]
+    return torch.cat(out)
+
+
+def real_cache_name(cfg, split):
+    H, W = cfg.data.resolution
+    return f"real_set_{cfg.data.dataset}_{cfg.data.projection}_{H}x{W}_{split}.pkl"
+
+
+@torch.no_grad()
+def evaluate(args):
+    from r2dm_amd import metrics
+    from r2dm_amd.option import Config
+
+    device = torch.device("cuda")
+    ckpt = torch.load(args.ckpt, map_location="cpu")
+    cfg = Config(**ckpt["cfg"])
+
+    results = dict(img=dict(), pts=dict(), bev=dict(), info=dict())
+    results["info"]["phase"] = args.dataset
+    results["info"]["directory"] = args.sample_dir
+
+    # real set: the reference's cache, or a directory of scans
+    if args.real_dir is not None:
+        real_hists = histograms_of(sample_files(args.real_dir, limit=None), args.batch_size, args.num_workers, device)
+        results["info"]["real"] = str(args.real_dir)
+    else:
+        path = Path(args.real_set) if args.real_set is not None else Path(real_cache_name(cfg, args.dataset))
+        if not path.exists():
+            raise SystemExit(f"no real set: {path} not found (run the reference's evaluate.py once to cache it, or give "
+                             "--real_set PATH / --real_dir DIR)")
+        print(f"found cached {path}")
+        with open(path, "rb") as f:
+            real_set = pickle.load(f)
+        real_hists = torch.from_numpy(np.ascontiguousarray(real_set["bev_hists"])).to(device)
+        results["info"]["real"] = str(path)
+    results["info"]["#real"] = len(real_hists)
+
+    # generated set
+    gen_hists = histograms_of(sample_files(args.sample_dir), args.batch_size, args.num_workers, device)
+    results["info"]["#fake"] = len(gen_hists)
+
+    # the real subset as the reference takes it (evaluate.py:185-187)
+    perm = list(range(len(real_hists)))
+    random.Random(0).shuffle(perm)
+    perm = perm[:MAX_SAMPLES]
+    real_sub = real_hists[torch.tensor(perm, device=device)]
+
+    results["bev"]["jsd"] = metrics.compute_jsd_2d(real_sub, gen_hists)
+    results["bev"]["mmd"] = metrics.compute_mmd_2d(real_sub, gen_hists)
+    results["info"]["note"] = ("img (FRD) and pts (FPD) are not computed: they need the RangeNet-53 and PointNet weights")
+
+    print(results)
+    save_path = args.sample_dir + f"_{datetime.datetime.now().strftime('%Y%m%dT%H%M%S')}.json"
+    with open(save_path, "w") as f:
+        json.dump(results, f, indent=4)
+    return save_path
+
+
+if __name__ == "__main__":
+    parser = ArgumentParser()
+    parser.add_argument("--ckpt", type=Path, required=True)
+    parser.add_argument("--sample_dir", type=str, required=True)
+    parser.add_argument("--dataset", choices=["train", "test", "all"], default="all")
+    parser.add_argument("--batch_size", type=int, default=64)
+    parser.add_argument("--num_workers", type=int, default=4)
+    parser.add_argument("--real_set", type=str, default=None,
+                        help="extension: the reference's real-set cache pickle (default: its own name in the working directory)")
+    parser.add_argument("--real_dir", type=str, default=None,
+                        help="extension: a directory of (5,H,W) real scans in the sample layout, instead of the cache")
+    evaluate(parser.parse_args())

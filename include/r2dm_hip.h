@@ -162,6 +162,24 @@ int r2dm_lidar_postprocess(const float* x, const float* ray_angles, float* out, 
 int r2dm_lidar_postprocess_fmt(const float* x, const float* ray_angles, float* out, int32_t batch, int32_t height,
                                int32_t width, float min_depth, float max_depth, int32_t depth_format, void* stream);
 
+/* -- BEV metrics of the evaluation script (metrics/bev.py; evaluate.py:22-41,131-196) ---------------------------------------
+ * r2dm_bev_histogram: point_cloud_to_histogram on a batch -- the (x, y) occupancy histogram, bins x bins over the edges
+ *    `edges` (bins + 1 fp32 values in device memory, as torch.linspace computes them), of the points with
+ *    min_depth < |xyz| < max_depth.  layout 0: src (B,5,H,W) samples [depth, x, y, z, reflectance], xyz first masked by
+ *    image_min_depth < depth < image_max_depth (points = H*W); layout 1: src (B,points,3).  hist (B,bins,bins) int32 counts,
+ *    bit-identical to torch.histogramdd on the CPU; sum (bins,bins) int64 over the batch, or NULL.  bins <= 128.
+ * r2dm_bev_hist_sum: sum (cells,) int64 of a batch of histograms hist (batch,cells), int32 (is_int32 = 1) or fp32 counts.
+ * r2dm_bev_mmd: the three means of 1 - k over P x Q, P x P and Q x Q (out[3], fp64) of the RBF kernel
+ *    k = exp(-|p - q|^2 / (2 sigma^2)) between the rows of p (np,bins) and q (nq,bins), each normalised by its sum;
+ *    MMD = 2 out[0] - out[1] - out[2].  scratch: r2dm_bev_mmd_scratch_bytes() of device memory. */
+int r2dm_bev_histogram(const float* src, int32_t layout, const float* edges, int32_t* hist, int64_t* sum, int32_t batch,
+                       int64_t points, int32_t bins, float min_depth, float max_depth, float image_min_depth,
+                       float image_max_depth, void* stream);
+int r2dm_bev_hist_sum(const void* hist, int32_t is_int32, int64_t* sum, int64_t batch, int64_t cells, void* stream);
+size_t r2dm_bev_mmd_scratch_bytes(int32_t np, int32_t nq);
+int r2dm_bev_mmd(const float* p, const float* q, int32_t np, int32_t nq, int64_t bins, double sigma, void* scratch,
+                 size_t scratch_bytes, double* out, void* stream);
+
 /* -- single kernels, exported for per-op parity tests against the oracle -------------------- */
 /* ops.Conv2d(ring) 3x3 / 1x1 (models/ops.py:149-173) with optional fused GroupNorm-affine(+SiLU)
  * prologue (aff: (B,Cin,2) or NULL; prologue 0 none, 1 affine, 2 affine+SiLU) and optional

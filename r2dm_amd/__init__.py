@@ -8,6 +8,7 @@ from .inference import setup_model, setup_rng
 from .lidar import LiDARUtility
 from .option import Config
 from .unet import EfficientUNet
+from . import metrics  # noqa: E402  (BEV metrics of evaluate.py)
 
 __all__ = [
     "ContinuousTimeGaussianDiffusion", "DiscreteTimeGaussianDiffusion", "GaussianDiffusion", "EfficientUNet",

@@ -94,6 +94,11 @@ SIGNATURES = {
     "r2dm_fir_up2": (c_int32, [_P, _P, c_int32, c_int32, c_int32, c_int32, _P]),
     "r2dm_attention": (c_int32, [_P, _P, c_int32, c_int32, c_int32, c_int32, _P]),
     "r2dm_time_embedding": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, _P]),
+    "r2dm_bev_histogram": (c_int32, [_P, c_int32, _P, _P, _P, c_int32, c_int64, c_int32, c_float, c_float, c_float, c_float,
+                                     _P]),
+    "r2dm_bev_hist_sum": (c_int32, [_P, c_int32, _P, c_int64, c_int64, _P]),
+    "r2dm_bev_mmd_scratch_bytes": (c_size_t, [c_int32, c_int32]),
+    "r2dm_bev_mmd": (c_int32, [_P, _P, c_int32, c_int32, c_int64, ctypes.c_double, _P, c_size_t, _P, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -270,4 +270,11 @@ hipError_t launch_q_step(const float* x, const float* noise, const float* coef, 
 hipError_t launch_lidar_postprocess(const float* x, const float* angles, float* y, int B, int H, int W,
                                     float min_depth, float max_depth, hipStream_t s, int depth_format = 0);  // 0 log_depth, 1 inverse_depth, 2 depth
 
+// BEV metrics of evaluate.py (metrics.hip): histograms (layout 0: (B,5,H,W) samples, 1: (B,N,3) clouds), their batch sum, the MMD's three means
+hipError_t launch_bev_histogram(const float* src, int layout, const float* edges, int32_t* hist, int64_t* sum, int B, long n, int bins,
+                                float min_d, float max_d, float img_min, float img_max, hipStream_t s);
+hipError_t launch_bev_hist_sum(const void* hist, int is_int32, int64_t* sum, long batch, long cells, hipStream_t s);
+size_t mmd_scratch_bytes(int np, int nq);
+hipError_t launch_bev_mmd(const float* P, const float* Q, int np, int nq, long D, double sigma, void* scratch, double* out, hipStream_t s);
+
 }  // namespace r2dm

@@ -1182,6 +1182,38 @@ int r2dm_lidar_postprocess_fmt(const float* x, const float* ang, float* out, int
     return 0;
 }
 
+int r2dm_bev_histogram(const float* src, int32_t layout, const float* edges, int32_t* hist, int64_t* sum, int32_t batch,
+                       int64_t points, int32_t bins, float min_depth, float max_depth, float image_min_depth,
+                       float image_max_depth, void* stream) {
+    if (!src || !edges || !hist) return fail(1, "null argument");
+    if (layout != 0 && layout != 1) return fail(1, "layout must be 0 ((B,5,H,W) samples) or 1 ((B,N,3) point clouds)");
+    if (batch < 1 || points < 1) return fail(1, "empty batch");
+    if (bins < 1 || bins > 128) return fail(1, "bins must be in [1, 128] (one histogram per block in LDS), got %d", bins);
+    HIP_TRY(launch_bev_histogram(src, layout, edges, hist, sum, batch, points, bins, min_depth, max_depth, image_min_depth,
+                                 image_max_depth, (hipStream_t)stream));
+    return 0;
+}
+
+int r2dm_bev_hist_sum(const void* hist, int32_t is_int32, int64_t* sum, int64_t batch, int64_t cells, void* stream) {
+    if (!hist || !sum) return fail(1, "null argument");
+    if (batch < 1 || cells < 1) return fail(1, "empty histogram batch");
+    HIP_TRY(launch_bev_hist_sum(hist, is_int32, sum, batch, cells, (hipStream_t)stream));
+    return 0;
+}
+
+size_t r2dm_bev_mmd_scratch_bytes(int32_t np, int32_t nq) { return np < 1 || nq < 1 ? 0 : mmd_scratch_bytes(np, nq); }
+
+int r2dm_bev_mmd(const float* p, const float* q, int32_t np, int32_t nq, int64_t bins, double sigma, void* scratch,
+                 size_t scratch_bytes, double* out, void* stream) {
+    if (!p || !q || !scratch || !out) return fail(1, "null argument");
+    if (np < 1 || nq < 1 || bins < 1) return fail(1, "empty histogram set");
+    if (!(sigma > 0.0)) return fail(1, "sigma must be > 0");
+    if (scratch_bytes < mmd_scratch_bytes(np, nq)) return fail(1, "scratch too small: %zu < %zu bytes", scratch_bytes, mmd_scratch_bytes(np, nq));
+    if ((uintptr_t)scratch & 255) return fail(1, "scratch must be 256-byte aligned");
+    HIP_TRY(launch_bev_mmd(p, q, np, nq, bins, sigma, scratch, out, (hipStream_t)stream));
+    return 0;
+}
+
 static int g_single_kernel_pieces = 2;  // r2dm_conv2d_ring (per-op tests)
 
 int r2dm_set_conv_pieces(r2dm_handle* h, int32_t pieces) {

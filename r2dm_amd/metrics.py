@@ -1,0 +1,128 @@
+"""BEV metrics of the reference's ``evaluate.py`` (metrics/bev.py) as HIP kernels: the bird's-eye-view occupancy
+histograms, their Jensen-Shannon distance (JSD) and the RBF-kernel maximum mean discrepancy (MMD).
+
+Same names and signatures as the reference module; inputs are ROCm tensors and nothing falls back to the CPU.
+
+- Histogram counts are bit-identical to ``torch.histogramdd`` on the CPU (same fp32 bin edges, same binning rules,
+  the depth in the CPU's fp32 operation order).
+- JSD sums the counts exactly (int64 on the GPU) and normalises them in fp64 on the host.
+- MMD sums ``1 - k = -expm1(-gamma d^2)`` in fp64 with ``d^2 = sum_k (p_k - q_k)^2`` taken directly, never as
+  ``|p|^2 + |q|^2 - 2 p.q``, and never forms the N x N matrix; the result is deterministic.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _lib
+
+# evaluate.py:20-22 (from LiDARGen): the image mask applied to generated samples before the histogram
+MIN_DEPTH = 0.5
+MAX_DEPTH = 63.0
+
+_LAYOUT_SAMPLES, _LAYOUT_CLOUDS = 0, 1
+
+
+def bin_edges(field_size: float = 160.0, bins: int = 100) -> torch.Tensor:
+    """The fp32 bin edges torch.histogramdd uses for ``range=[-field_size/2, field_size/2]`` (a linspace), on the CPU."""
+    bound = field_size / 2
+    return torch.linspace(-bound, bound, bins + 1, dtype=torch.float32)
+
+
+def bev_histograms(samples_or_clouds: torch.Tensor, field_size: float = 160.0, bins: int = 100, min_depth: float = 3.0,
+                   max_depth: float = 70.0, image_min_depth: float = MIN_DEPTH, image_max_depth: float = MAX_DEPTH,
+                   return_sum: bool = False):
+    """Batched ``point_cloud_to_histogram`` as evaluate.py applies it.
+
+    ``samples_or_clouds`` is either a batch of samples ``(B,5,H,W)`` [depth, x, y, z, reflectance] (what
+    ``LiDARUtility.postprocess`` and sample_and_save.py write), whose xyz is first masked by
+    ``image_min_depth < depth < image_max_depth`` (evaluate.py:22-41,150-151), or a batch of point clouds ``(B,N,3)``.
+    Returns int32 counts ``(B,bins,bins)`` indexed [x bin, y bin]; with ``return_sum`` also their exact int64 sum over
+    the batch ``(bins,bins)``."""
+    x = samples_or_clouds
+    _lib.require_gpu(x, "samples_or_clouds")
+    if x.ndim == 4 and x.shape[1] == 5:
+        layout, B, n = _LAYOUT_SAMPLES, x.shape[0], x.shape[2] * x.shape[3]
+    elif x.ndim == 3 and x.shape[2] == 3:
+        layout, B, n = _LAYOUT_CLOUDS, x.shape[0], x.shape[1]
+    else:
+        raise ValueError(f"expected (B,5,H,W) samples or (B,N,3) point clouds, got {tuple(x.shape)}")
+    if bins % 2:
+        raise ValueError("bins must be even (metrics/bev.py)")
+    x = _lib.f32c(x)
+    edges = bin_edges(field_size, bins).to(x.device)
+    hist = torch.empty(B, bins, bins, dtype=torch.int32, device=x.device)
+    total = torch.empty(bins, bins, dtype=torch.int64, device=x.device) if return_sum else None
+    if B and n:
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().r2dm_bev_histogram(_lib.ptr(x), layout, _lib.ptr(edges), _lib.ptr(hist), _lib.ptr(total), B, n,
+                                                     bins, float(min_depth), float(max_depth), float(image_min_depth),
+                                                     float(image_max_depth), _lib.stream_ptr(x.device)))
+    else:
+        hist.zero_()
+        if total is not None:
+            total.zero_()
+    return (hist, total) if return_sum else hist
+
+
+def point_cloud_to_histogram(point_cloud: torch.Tensor, field_size: float = 160.0, bins: int = 100, min_depth: float = 3.0,
+                             max_depth: float = 70.0) -> torch.Tensor:
+    """metrics/bev.py: the (bins,bins) fp32 histogram of one ``(N,3)`` point cloud (on the cloud's device)."""
+    assert point_cloud.ndim == 2, "must be (N, 3)"
+    return bev_histograms(point_cloud[None], field_size, bins, min_depth, max_depth)[0].float()
+
+
+def _as_counts(hist: torch.Tensor, what: str) -> torch.Tensor:
+    _lib.require_gpu(hist, what)
+    h = hist.detach().flatten(1)
+    if h.dtype != torch.int32:
+        h = h.to(torch.float32)
+    return h.contiguous()
+
+
+def histogram_sum(hist: torch.Tensor) -> torch.Tensor:
+    """Exact int64 sum over the batch of ``(N, ...)`` histograms of counts (int32, or fp32 holding integers)."""
+    h = _as_counts(hist, "hist")
+    if h.dtype == torch.float32 and bool(((h < 0) | (h != h.trunc())).any()):
+        raise ValueError("histogram_sum takes counts: non-negative integers")
+    out = torch.empty(h.shape[1], dtype=torch.int64, device=h.device)
+    with torch.cuda.device(h.device):
+        _lib.check(_lib.lib().r2dm_bev_hist_sum(_lib.ptr(h), int(h.dtype == torch.int32), _lib.ptr(out), h.shape[0], h.shape[1],
+                                                _lib.stream_ptr(h.device)))
+    return out
+
+
+@torch.no_grad()
+def compute_jsd_2d(hist1: torch.Tensor, hist2: torch.Tensor) -> float:
+    """BEV-based Jensen-Shannon distance between the summed histograms of two sets (metrics/bev.py)."""
+    from scipy.spatial.distance import jensenshannon
+
+    s1 = histogram_sum(hist1).cpu().numpy().astype(np.float64)
+    s2 = histogram_sum(hist2).cpu().numpy().astype(np.float64)
+    return float(jensenshannon(s1 / s1.sum(), s2 / s2.sum()))
+
+
+@torch.no_grad()
+def mmd_terms(hist1: torch.Tensor, hist2: torch.Tensor, sigma: float = 0.5):
+    """(mean 1-k(p,q), mean 1-k(p,p), mean 1-k(q,q)) over all pairs of the row-normalised histograms, in fp64."""
+    p, q = _as_counts(hist1, "hist1").float(), _as_counts(hist2, "hist2").float()
+    if p.device != q.device:
+        raise ValueError(f"hist1 on {p.device}, hist2 on {q.device}")
+    if p.shape[1] != q.shape[1]:
+        raise ValueError(f"histograms of {p.shape[1]} and {q.shape[1]} bins")
+    L = _lib.lib()
+    scratch = torch.empty(L.r2dm_bev_mmd_scratch_bytes(p.shape[0], q.shape[0]) + 256, dtype=torch.uint8, device=p.device)
+    base = (-scratch.data_ptr()) % 256  # 256-byte aligned start
+    out = torch.empty(3, dtype=torch.float64, device=p.device)
+    with torch.cuda.device(p.device):
+        _lib.check(L.r2dm_bev_mmd(_lib.ptr(p), _lib.ptr(q), p.shape[0], q.shape[0], p.shape[1], float(sigma),
+                                  scratch.data_ptr() + base, scratch.numel() - base, _lib.ptr(out), _lib.stream_ptr(p.device)))
+    pq, pp, qq = out.tolist()
+    return pq, pp, qq
+
+
+@torch.no_grad()
+def compute_mmd_2d(hist1: torch.Tensor, hist2: torch.Tensor) -> float:
+    """BEV-based maximum mean discrepancy (metrics/bev.py): mean k_pp + mean k_qq - 2 mean k_pq, biased, sigma 0.5."""
+    pq, pp, qq = mmd_terms(hist1, hist2)
+    return 2.0 * pq - pp - qq
