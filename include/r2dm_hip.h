@@ -210,6 +210,17 @@ int r2dm_fir_up2(const float* x, float* y, int32_t batch, int32_t channels, int3
 int32_t r2dm_fir_down2_stat_slots(int32_t channels, int32_t groups, int32_t height, int32_t width);
 int r2dm_fir_down2_stats(const float* x, float* y, double* stat, int32_t batch, int32_t channels, int32_t groups,
                          int32_t height, int32_t width, void* stream);
+/* The down stages' Conv3x3(ring) + ops.Resample(down=2) (models/efficient_unet.py:132-136) with the FIR FIRST: r2dm_down_planes writes the nine
+ * filtered planes per channel the stride-2 convolution reads -- planes: (B, 9 C, H/2, W/2), plane (ky 3 + kx) C + c; height % 4 == 0,
+ * width % 8 == 0 --, r2dm_down_gemm runs that pass and the (Cout, 9 Cin) product with the bias scaled by the FIR's row factor (7/8 on the first
+ * and last output row): y (B, Cout, H/2, W/2) = Resample(down=2)(Conv2d(x, w, bias)).  w is OIHW; w_packed: caller scratch of 9 cin cout + 64 floats;
+ * planes: caller scratch of B 9 cin (H/2) (W/2) floats; cin % 32 == 0, cout % 64 == 0, height % 8 == 0, width % 128 == 0.  stat (optional): the
+ * GroupNorm statistics of y in the convolution epilogues' slot grid, (B, groups, r2dm_down_gemm_stat_slots(), 2) doubles (0 slots: not available).
+ * The engine takes this pair in the default precision unless R2DM_DOWN_GEMM=0 (read at r2dm_create). */
+int r2dm_down_planes(const float* x, float* planes, int32_t batch, int32_t channels, int32_t height, int32_t width, void* stream);
+int32_t r2dm_down_gemm_stat_slots(int32_t cin, int32_t cout, int32_t groups, int32_t height, int32_t width);
+int r2dm_down_gemm(const float* x, const float* w, const float* bias, float* w_packed, float* planes, float* y, double* stat,
+                   int32_t batch, int32_t cin, int32_t cout, int32_t groups, int32_t height, int32_t width, void* stream);
 /* attention core of nn.MultiheadAttention on channel-major qkv (B,3C,N) -> (B,C,N)
  * (models/efficient_unet.py:34-38,46) */
 int r2dm_attention(const float* qkv, float* out, int32_t batch, int32_t channels, int32_t heads, int32_t tokens,

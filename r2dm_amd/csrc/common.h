@@ -190,8 +190,10 @@ hipError_t launch_presplit_fold(const Src& x, int prologue, float* xs, int B, in
                                 float eps, const float* gamma, const float* beta, const float* ada, long ada_stride, int* range, hipStream_t s);
 bool proj_f16x2_supported(int Cin, int Cout, int taps, int H, int W);
 long proj_f16x2_packed_floats(int Cin, int Cout);
-hipError_t launch_pack_proj_f16x2(const float* w_oi, float* dst, int Cout, int Cin, int* range_flag, hipStream_t s, float* wscale = nullptr);
-hipError_t launch_proj_f16x2(const ConvParams& p, hipStream_t s);
+// taps = 9: w is the OIHW tensor of a 3x3 convolution over Cin / 9 channels, packed as the (Cout, Cin) matrix of the down-sampling GEMM (column = tap * Cin / 9 + ci)
+hipError_t launch_pack_proj_f16x2(const float* w_oi, float* dst, int Cout, int Cin, int* range_flag, hipStream_t s, float* wscale = nullptr, int taps = 1);
+// bias_rowfac: the bias is scaled by the FIR's row factor (7/8 on the first and last row) -- the down-sampling GEMM over launch_down_planes' output
+hipError_t launch_proj_f16x2(const ConvParams& p, hipStream_t s, bool bias_rowfac = false);
 
 struct GNParams {
     Src x;
@@ -223,6 +225,11 @@ hipError_t launch_gn_apply(const float* x, const float2* aff, float* y, int B, i
 hipError_t launch_fir_down2(const float* x, long xbs, float* y, long ybs, int B, int C, int H, int W,
                             hipStream_t s, double* stat = nullptr, int G = 0, int x16 = 0, int y16 = 0);  // x16 / y16: fp16 storage of the input / output (round 6)
 int fir_down2_stat_slots(int C, int G, int H, int W);
+// FIR-down BEFORE the stage's 3x3 convolution (resample.hip): a <- [B][9 C][H/2][W/2], the nine filtered planes per channel the stride-2 convolution reads
+// (plane (ky 3 + kx) C + c); FIR(conv(x) + b) = the 1x1 convolution of `a` with the weights permuted to [Cout][(ky, kx, ci)] + b x row factor.
+// range (optional): range[1] takes the running maximum of |a| as float bits.  Needs H % 4 == 0, W % 8 == 0.
+bool down_planes_supported(int H, int W);
+hipError_t launch_down_planes(const float* x, long xbs, float* a, long abs_, int B, int C, int H, int W, hipStream_t s, int* range = nullptr);
 hipError_t launch_fir_up2(const float* x, long xbs, float* y, long ybs, int B, int C, int H, int W,
                           hipStream_t s, int* range = nullptr, int x16 = 0, int y16 = 0);  // range[1]: running max |output| as float bits (may be nullptr)
 

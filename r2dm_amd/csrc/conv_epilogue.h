@@ -162,7 +162,11 @@ __device__ __forceinline__ void epi_stat_write_bfly8(const ConvParams& p, float 
 // instructions, which count on lgkmcnt as well and turn every LDS wait into a wait for HBM.
 // conv_f16x2.hip has its own arrangement of the same steps (one quarter at the tile's end, three deferred into the next tile).
 // Y16 (round 6): the output -- and the residual -- are stored as fp16 (the one-plane mode's activation storage); statistics and range of the values as stored.
-template <int TH, int TW, int MR, int NR, bool ACC2, bool Y16 = false>
+// FIRB: the epilogue of the down-sampling GEMM (resample.hip down_planes_kernel + proj_f16x2.hip), which stands where fir_down2 stood.  The bias is
+// scaled by the FIR's row factor -- 7/8 on the first and on the last image row (both on an image of one row), 1 elsewhere: it went through the
+// zero-padded [1,3,3,1]/8 window -- with one fmaf per element, in fp32 (never through the split operands); and the statistics are fp64 from the first
+// addition, as fir_down2_stats_kernel's are (64 values per lane and tile: nothing next to the product).
+template <int TH, int TW, int MR, int NR, bool ACC2, bool Y16 = false, bool FIRB = false>
 __device__ __forceinline__ void conv_epilogue_wide(const ConvParams& p, f32x16 (&acc)[MR][NR],
                                                    f32x16 (&acc2)[ACC2 ? MR : 1][ACC2 ? NR : 1], int b, int th, int tw,
                                                    int nTw, int co_u, int wave_px, int lane, float* patch,
@@ -179,10 +183,15 @@ __device__ __forceinline__ void conv_epilogue_wide(const ConvParams& p, f32x16 (
     const gf4 yu = (gf4)(p.y + b * p.y_bs + (long)co_u * HW);
     const gcf4 ru = (gcf4)(p.res + b * p.res_bs + (long)co_u * HW);  // (only dereferenced if p.res)
     int loff[NR];  // in units of 4 floats
+    float rowf[FIRB ? NR : 1];
 #pragma unroll
     for (int n = 0; n < NR; ++n) {
         const int s = wave_px * NR + n;
         loff[n] = (tq_c * HW + (th * TH + s / SEGW) * W + tw * TW + (s % SEGW) * 32 + tq_p) >> 2;
+        if constexpr (FIRB) {
+            const int row = th * TH + s / SEGW;
+            rowf[n] = 1.0f - (row == 0 ? 0.125f : 0.f) - (row == H - 1 ? 0.125f : 0.f);
+        }
     }
     float bias[MR][4];
 #pragma unroll
@@ -225,13 +234,28 @@ __device__ __forceinline__ void conv_epilogue_wide(const ConvParams& p, f32x16 (
             }
 #pragma unroll
             for (int k8 = 0; k8 < 4; ++k8) {
-                f32x4 v = t[k8] * out_scale + bias[m][k8];
+                f32x4 v;
+                if constexpr (FIRB) {
+                    v = t[k8] * out_scale;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = __builtin_fmaf(bias[m][k8], rowf[n], v[e]);
+                } else
+                    v = t[k8] * out_scale + bias[m][k8];
                 if (p.res) v = rv[q & 1][k8] + v;
                 if (p.scale) v *= sc;
                 if constexpr (Y16) v = store4<true>(p.y, b * p.y_bs + (long)co_u * HW + 4 * ((long)(m * 32 + k8 * 8) * (HW >> 2) + loff[n]), v);
                 else (yu + (long)(m * 32 + k8 * 8) * (HW >> 2))[loff[n]] = v;
                 if (p.range) amax = fmaxf(fmaxf(amax, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
-                if (p.stat) {
+                if constexpr (FIRB) {
+                    if (p.stat) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const double d = (double)v[e];
+                            st_s[k8] += d;
+                            st_q[k8] = fma(d, d, st_q[k8]);
+                        }
+                    }
+                } else if (p.stat) {
                     const float s4 = (v[0] + v[1]) + (v[2] + v[3]);
                     const float q4 = fmaf(v[3], v[3], fmaf(v[2], v[2], fmaf(v[1], v[1], v[0] * v[0])));
                     st_s[k8] += (double)s4;

@@ -58,6 +58,10 @@ struct ConvLayer {
     // ... and for ALGO_P1F16 (proj_f16x2.hip): the 1x1 projections of the attention block
     bool p1 = false;
     size_t w_p1 = 0, ws_p1 = 0;
+    // ... and, for a stage's down-sampling 3x3 convolution, the (Cout, 9 Cin) matrix of the down-sampling GEMM (FIR first, then a 1x1 convolution over the nine
+    // filtered planes at the output resolution: resample.hip down_planes_kernel + proj_f16x2.hip), columns (ky, kx, ci)
+    bool dg = false;
+    size_t w_dg = 0, ws_dg = 0;
     size_t packed_elems() const { return (size_t)conv_packed_floats(algo, cin, cout, taps, co_tile, cin_pad); }
 };
 
@@ -118,6 +122,8 @@ struct r2dm_handle {
     // residual (ALGO_F16X2 / ALGO_P1F16) wherever a second packing exists, three bf16 pieces elsewhere; 3 = three bf16 pieces
     // everywhere; 1 = the kernels of mode 2 with the fp16 piece alone (one product per MAC: reduced precision, bulk sampling)
     int conv_pieces = 2;
+    // R2DM_DOWN_GEMM=0 (read once, at r2dm_create): the down stages keep Conv3x3 at the finer resolution + fir_down2, as until round 6 (A/B, the parity test)
+    bool down_gemm = true;
     bool f16_path() const { return conv_pieces != 3; }  // operands go through fp16: their range is guarded
     bool flags_fresh = false;  // the blob's range flags have been cleared since the last r2dm_bind_blob (first load does it)
     size_t range_flag = 0;  // blob slot (RANGE_SITES pairs of ints, ALGO_F16X2): [0] != 0: a weight outside the fp16 range; [2 k + 1]: float
@@ -173,7 +179,8 @@ struct r2dm_handle {
         return L;
     }
     // H, W > 0: a convolution behind a GroupNorm at that resolution -- gets the ALGO_F16X2 packing too if the shape fits
-    ConvLayer conv(const std::string& wkey, const std::string& bkey, int cin, int cout, int ksize, long px_batch, int H = 0, int W = 0) {
+    // down: a stage's down-sampling convolution (followed by fir_down2) -- gets the down-sampling GEMM's packing too if the geometry fits its tiles
+    ConvLayer conv(const std::string& wkey, const std::string& bkey, int cin, int cout, int ksize, long px_batch, int H = 0, int W = 0, bool down = false) {
         ConvLayer L;
         L.cin = cin;
         L.cout = cout;
@@ -197,6 +204,12 @@ struct r2dm_handle {
             L.p1 = true;
             L.w_p1 = take((size_t)proj_f16x2_packed_floats(cin, cout));
             L.ws_p1 = take(2);
+        }
+        // (from the planned geometry alone, never from a call's batch: a sample's bits must not depend on the batch it is part of)
+        if (down && down_gemm && L.taps == 9 && H > 0 && down_planes_supported(H, W) && proj_f16x2_supported(9 * cin, cout, 1, H / 2, W / 2)) {
+            L.dg = true;
+            L.w_dg = take((size_t)proj_f16x2_packed_floats(9 * cin, cout));
+            L.ws_dg = take(2);
         }
         slots.push_back({wkey, (int64_t)cout * cin * L.taps, SLOT_CONV, L.w, L});
         L.b = raw(bkey, cout);
@@ -263,7 +276,7 @@ void build_plan(r2dm_handle* h) {
         const long px = px1 >> (2 * d.level);  // pixels*batch at the level the residual blocks run on
         const std::string p = std::string(d.name) + ".";
         if (d.down)  // the stage's first conv runs at the resolution above (efficient_unet.py:132-136)
-            st.dconv = h->conv(p + "downsample.0.weight", p + "downsample.0.bias", d.cin, d.cout, 3, px << 2, c.height >> (d.level - 1), c.width >> (d.level - 1));
+            st.dconv = h->conv(p + "downsample.0.weight", p + "downsample.0.bias", d.cin, d.cout, 3, px << 2, c.height >> (d.level - 1), c.width >> (d.level - 1), /*down=*/true);
         for (int i = 0; i < d.n; ++i) {
             ResLayer r;
             const std::string q = p + "residual_blocks." + std::to_string(i) + ".";
@@ -301,7 +314,7 @@ void build_plan(r2dm_handle* h) {
     for (int s = 0; s + 1 < 8; ++s) {
         Stage& a = h->stages[s];
         const Stage& b = h->stages[s + 1];
-        a.out_tracked = b.down && b.dconv.f2 && !a.attn && !a.up && !a.res.empty() && a.res.back().conv2.f2;
+        a.out_tracked = b.down && (b.dconv.f2 || b.dconv.dg) && !a.attn && !a.up && !a.res.empty() && a.res.back().conv2.f2;
     }
     // up stages: input of stage 4 = output of stage 3; of stage 4 + k (k = 1..3) = [output of stage 3 + k | output of stage 3 - k]
     for (int s = 4; s < 8; ++s) {
@@ -499,6 +512,26 @@ struct Ctx {
         const float *gamma, *beta, *ada;
     };
 
+    // in-stream timing of a launch: records the opening event and returns the closing one (nullptr: profiling off)
+    hipEvent_t prof_begin(int cls, double flop) {
+        if (!h->prof_on) return nullptr;
+        if (h->prof_used + 2 > h->prof_ev.size()) {
+            hipEvent_t a, c;
+            if (hipEventCreate(&a) == hipSuccess && hipEventCreate(&c) == hipSuccess) {
+                h->prof_ev.push_back(a);
+                h->prof_ev.push_back(c);
+            }
+        }
+        if (h->prof_used + 2 > h->prof_ev.size()) return nullptr;
+        hipEvent_t e0 = h->prof_ev[h->prof_used], e1 = h->prof_ev[h->prof_used + 1];
+        h->prof_used += 2;
+        h->prof_flop += flop;
+        h->prof_cls.push_back(cls);
+        h->prof_lflop.push_back(flop);
+        (void)hipEventRecord(e0, st);
+        return e1;
+    }
+
     Tensor conv(const ConvLayer& L, const Src& x, int H, int W, int pro, const float2* aff, const Tensor* res,
                 size_t scale_off, bool has_scale, float* dst = nullptr, const Sink* sink = nullptr, int goff = 0,
                 bool res_broadcast = false, bool input_bounded = false,  // input_bounded: its producer tracked max|x| in the range flag
@@ -638,28 +671,9 @@ struct Ctx {
             }
             if ((x16 || y16) && p.algo != ALGO_F16X2 && p.algo != ALGO_DIRECT && p.algo != ALGO_P1F16) note(hipErrorInvalidValue, "fp16 storage on a kernel without it");
             if (x16 && !fold && !pre_fold && own_aff && !(ns && *ns->stats)) note(hipErrorInvalidValue, "fp16 storage behind a streaming GroupNorm");
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            if (h->prof_on) {
-                if (h->prof_used + 2 > h->prof_ev.size()) {
-                    hipEvent_t a, c;
-                    if (hipEventCreate(&a) == hipSuccess && hipEventCreate(&c) == hipSuccess) {
-                        h->prof_ev.push_back(a);
-                        h->prof_ev.push_back(c);
-                    }
-                }
-                if (h->prof_used + 2 <= h->prof_ev.size()) {
-                    e0 = h->prof_ev[h->prof_used];
-                    e1 = h->prof_ev[h->prof_used + 1];
-                    h->prof_used += 2;
-                    // ALGORITHMIC flops of the reference's convolution (in_conv: all 34 input channels, although the
-                    // constant Fourier half is folded into a bias map here)
-                    const double lf = 2.0 * B * (double)L.cout * (L.src_cin ? L.src_cin : L.cin) * L.taps * H * W;
-                    h->prof_flop += lf;
-                    h->prof_cls.push_back(p.algo == ALGO_F16X2 ? 0 : p.algo == ALGO_BF16X3 ? 1 : 2);
-                    h->prof_lflop.push_back(lf);
-                    (void)hipEventRecord(e0, st);
-                }
-            }
+            // ALGORITHMIC flops of the reference's convolution (in_conv: all 34 input channels, although the
+            // constant Fourier half is folded into a bias map here)
+            hipEvent_t e1 = prof_begin(p.algo == ALGO_F16X2 ? 0 : p.algo == ALGO_BF16X3 ? 1 : 2, 2.0 * B * (double)L.cout * (L.src_cin ? L.src_cin : L.cin) * L.taps * H * W);
             if (g_debug_sync)
                 fprintf(stderr, "[r2dm] conv algo %d %d->%d taps %d co_tile %d %dx%d B %d pro %d w %p bias %p gn %p blob [%p, +%zu) x %p/%p (c0 %d) y %p res %p aff %p stat %p ws [%p, +%zu)\n", p.algo, p.Cin,
                         p.Cout, p.taps, p.co_tile, H, W, B, pro, (const void*)p.w, (const void*)p.bias, (const void*)p.gn_partial, (void*)h->blob, h->blob_floats * 4, (const void*)p.x.p0, (const void*)p.x.p1, p.x.c0, (void*)p.y, (const void*)p.res, (const void*)p.aff,
@@ -755,7 +769,66 @@ struct Ctx {
         bool c16 = in16;  // the current tensor (stage input or `cur`) is stored as fp16
         Sink carry = in_stats;  // statistics of the current tensor, owned elsewhere for the stage input
         bool carry_owned = false;
-        if (s.down) {
+        // FIR first, then the stride-2 convolution as a GEMM over the nine filtered planes (resample.hip down_planes_kernel): a quarter of the MACs of
+        // conv + fir_down2.  Taken where the plan packed the matrix (geometry, R2DM_DOWN_GEMM), the precision is the default three-product split and
+        // the input's producer tracks max|x|; everything else -- fp32-bf16x3, the one-plane mode with its fp16 storage, a tripped guard's fallback --
+        // keeps conv + FIR.  Leaves what the FIR launch leaves: the tensor and, where fir_down2 would, the statistics of the first block's norm.
+        // (a two-source input never reaches a down stage today; if one does it keeps conv + FIR: the pre-pass reads one tensor)
+        if (s.down && s.dconv.dg && h->conv_pieces == 2 && in_tracked && !in16 && !in.p1) {
+            ctx = s.name + ".downsample";
+            const ConvLayer& L = s.dconv;
+            Tensor a = make(9 * L.cin, H / 2, W / 2);
+            cur = make(s.cout, H / 2, W / 2);
+            Sink fs;
+            if (fir_down2_stat_slots(s.cout, h->cfg.gn_num_groups, H, W)) fs = make_sink(s.cout, H / 2, W / 2);
+            if (!dry()) {
+                // Range: the FIR weights are non-negative and sum to at most 1 per axis, so max|a| <= max|x|, which the producer has recorded at its own site;
+                // the pass records max|a| itself all the same (one guarded atomic per wave), so the report names the GEMM's operand.
+                // (profiling: both launches in class 2, "1x1 / in / out convolutions" -- the pass with no FLOPs of its own, the GEMM with those it executes)
+                int* site = range_site("max|FIR planes| (operand of the down-sampling GEMM)");
+                hipEvent_t e0 = prof_begin(2, 0.0);
+                note(launch_down_planes(in.p0, in.bs0, a.p, a.bs(), B, L.cin, H, W, st, site), "down_planes");
+                if (e0) (void)hipEventRecord(e0, st);
+                ConvParams p;
+                p.x = src1(a);
+                p.w = blob(L.w_dg);
+                p.bias = blob(L.b);
+                p.aff = nullptr;
+                p.res = nullptr;
+                p.res_bs = 0;
+                p.scale = nullptr;
+                p.y = cur.p;
+                p.y_bs = cur.bs();
+                p.B = B;
+                p.H = H / 2;
+                p.W = W / 2;
+                p.Cin = p.CinPad = 9 * L.cin;
+                p.Cout = L.cout;
+                p.taps = 1;
+                p.co_tile = 64;
+                p.prologue = PRO_NONE;
+                p.algo = ALGO_P1F16;
+                p.pieces = 2;
+                p.wscale = blob(L.ws_dg) + 1;
+                if (fs.p) {
+                    p.stat = fs.p;
+                    p.stat_G = h->cfg.gn_num_groups;
+                    p.stat_goff = 0;
+                    p.stat_cpg = fs.cpg;
+                    p.stat_slots = fs.slots;
+                }
+                last_reverse = -1;
+                hipEvent_t e1 = prof_begin(2, 2.0 * B * (double)L.cout * 9 * L.cin * (H / 2) * (W / 2));
+                note(launch_proj_f16x2(p, st, /*bias_rowfac=*/true), "down_gemm");
+                if (e1) (void)hipEventRecord(e1, st);
+            }
+            drop(a);
+            H /= 2;
+            W /= 2;
+            have = true;
+            carry = fs;
+            carry_owned = fs.p != nullptr;
+        } else if (s.down) {
             ctx = s.name + ".downsample";
             Tensor t = conv(s.dconv, in, H, W, PRO_NONE, nullptr, nullptr, 0, false, nullptr, nullptr, 0, false, in_tracked, false, nullptr, in16, in16 && lvl16(H));
             cur = make(s.cout, H / 2, W / 2, t.f16 && lvl16(H / 2));
@@ -971,6 +1044,7 @@ int r2dm_create(r2dm_handle** out, const r2dm_config* cfg) {
     if (int rc = check_config(*cfg)) return rc;
     r2dm_handle* h = new r2dm_handle();
     h->cfg = *cfg;
+    if (const char* e = getenv("R2DM_DOWN_GEMM")) h->down_gemm = atoi(e) != 0;
     (void)hipGetDevice(&h->device);
     build_plan(h);
     *out = h;
@@ -1016,7 +1090,7 @@ uint64_t r2dm_blob_layout_hash(const r2dm_handle* h) {
         if (s.kind == SLOT_CONV) {
             const ConvLayer& L = s.conv;
             const uint64_t f[] = {(uint64_t)L.cin, (uint64_t)L.cout, (uint64_t)L.taps, (uint64_t)L.co_tile, (uint64_t)L.cin_pad, (uint64_t)L.algo, (uint64_t)L.src_cin,
-                                  (uint64_t)L.src_off, L.w, L.b, (uint64_t)L.f2, (uint64_t)L.f2_cot, (uint64_t)L.f2_rows, L.w_f2, L.ws_f2, (uint64_t)L.p1, L.w_p1, L.ws_p1};
+                                  (uint64_t)L.src_off, L.w, L.b, (uint64_t)L.f2, (uint64_t)L.f2_cot, (uint64_t)L.f2_rows, L.w_f2, L.ws_f2, (uint64_t)L.p1, L.w_p1, L.ws_p1, (uint64_t)L.dg, L.w_dg, L.ws_dg};
             for (uint64_t x : f) mix(x);
         }
     }
@@ -1118,6 +1192,9 @@ int r2dm_load_tensor(r2dm_handle* h, int64_t i, const float* src, int64_t numel,
         if (s.conv.p1)
             HIP_TRY(launch_pack_proj_f16x2(src, h->blob + s.conv.w_p1, s.conv.cout, s.conv.cin, (int*)(h->blob + h->range_flag), st,
                                            h->blob + s.conv.ws_p1));
+        if (s.conv.dg)
+            HIP_TRY(launch_pack_proj_f16x2(src, h->blob + s.conv.w_dg, s.conv.cout, 9 * s.conv.cin, (int*)(h->blob + h->range_flag), st,
+                                           h->blob + s.conv.ws_dg, 9));
     }
     h->cmap_ready = false;  // (any reload: cheap to recompute)
     return 0;
@@ -1445,6 +1522,64 @@ int32_t r2dm_fir_down2_stat_slots(int32_t C, int32_t G, int32_t H, int32_t W) {
 int r2dm_fir_down2_stats(const float* x, float* y, double* stat, int32_t B, int32_t C, int32_t G, int32_t H, int32_t W, void* stream) {
     if (!stat || !fir_down2_stat_slots(C, G, H, W)) return fail(1, "fir_down2_stats: geometry without a statistics variant");
     HIP_TRY(launch_fir_down2(x, (long)C * H * W, y, (long)C * (H / 2) * (W / 2), B, C, H, W, (hipStream_t)stream, stat, G, test_io16() & 1, (test_io16() >> 1) & 1));
+    return 0;
+}
+
+int r2dm_down_planes(const float* x, float* planes, int32_t B, int32_t C, int32_t H, int32_t W, void* stream) {
+    if (!x || !planes) return fail(1, "null argument");
+    if (B < 1 || C < 1 || !down_planes_supported(H, W)) return fail(1, "down_planes: needs height %% 4 == 0 and width %% 8 == 0 (>= 16)");
+    HIP_TRY(launch_down_planes(x, (long)C * H * W, planes, 9L * C * (H / 2) * (W / 2), B, C, H, W, (hipStream_t)stream));
+    return 0;
+}
+
+int32_t r2dm_down_gemm_stat_slots(int32_t cin, int32_t cout, int32_t G, int32_t H, int32_t W) {
+    if (H < 4 || W < 16 || !down_planes_supported(H, W) || !proj_f16x2_supported(9 * cin, cout, 1, H / 2, W / 2)) return 0;
+    const int cpg = G > 0 && cout % G == 0 ? cout / G : 0;
+    return cpg >= 8 && cpg <= 64 && !(cpg & (cpg - 1)) ? conv_stat_slots(H / 2, W / 2) : 0;
+}
+
+int r2dm_down_gemm(const float* x, const float* w, const float* bias, float* w_packed, float* planes, float* y, double* stat, int32_t B, int32_t cin,
+                   int32_t cout, int32_t G, int32_t H, int32_t W, void* stream) {
+    if (!x || !w || !bias || !w_packed || !planes || !y) return fail(1, "null argument");
+    if (B < 1 || H < 4 || W < 16 || !down_planes_supported(H, W) || !proj_f16x2_supported(9 * cin, cout, 1, H / 2, W / 2))
+        return fail(1, "down_gemm: needs cin %% 32 == 0, cout %% 64 == 0, height %% 8 == 0, width %% 128 == 0");
+    if (stat && !r2dm_down_gemm_stat_slots(cin, cout, G, H, W)) return fail(1, "down_gemm: no statistics for %d groups of %d channels", G, cout);
+    hipStream_t st = (hipStream_t)stream;
+    // the range flag and the weight scale: behind the packed weights (the caller reserves 64 floats), as r2dm_conv2d_ring
+    float* tail = w_packed + proj_f16x2_packed_floats(9 * cin, cout);
+    HIP_TRY(hipMemsetAsync(tail, 0, sizeof(int), st));
+    HIP_TRY(launch_pack_proj_f16x2(w, w_packed, cout, 9 * cin, (int*)tail, st, tail + 2, 9));
+    const int Ho = H / 2, Wo = W / 2;
+    HIP_TRY(launch_down_planes(x, (long)cin * H * W, planes, 9L * cin * Ho * Wo, B, cin, H, W, st));
+    ConvParams p;
+    p.x = Src{planes, nullptr, 9 * cin, 0, 9L * cin * Ho * Wo, 0};
+    p.w = w_packed;
+    p.bias = bias;
+    p.aff = nullptr;
+    p.res = nullptr;
+    p.res_bs = 0;
+    p.scale = nullptr;
+    p.y = y;
+    p.y_bs = (long)cout * Ho * Wo;
+    p.B = B;
+    p.H = Ho;
+    p.W = Wo;
+    p.Cin = p.CinPad = 9 * cin;
+    p.Cout = cout;
+    p.taps = 1;
+    p.co_tile = 64;
+    p.prologue = PRO_NONE;
+    p.algo = ALGO_P1F16;
+    p.pieces = 2;
+    p.wscale = tail + 3;
+    if (stat) {
+        p.stat = stat;
+        p.stat_G = G;
+        p.stat_goff = 0;
+        p.stat_cpg = cout / G;
+        p.stat_slots = conv_stat_slots(Ho, Wo);
+    }
+    HIP_TRY(launch_proj_f16x2(p, st, /*bias_rowfac=*/true));
     return 0;
 }
 

@@ -36,7 +36,8 @@ constexpr int LDS_TOTAL = PATCH0 + 4 * 1024;  // 55 296
 
 // NPLK = operand planes in use: 2 = the split arithmetic (parity path), 1 = the h plane alone: one fp16 product per MAC, the
 // reduced-precision bulk mode (conv_f16x2.hip); the l planes are then neither written nor read.
-template <int PRO, int NPLK, int IOM = 0>
+// FIRB: the bias takes the FIR's row factor (conv_epilogue.h) -- the down-sampling GEMM over the nine filtered planes of resample.hip's down_planes_kernel
+template <int PRO, int NPLK, int IOM = 0, bool FIRB = false>
 __global__ __launch_bounds__(256, 2) void proj_f16x2_kernel(const ConvParams p) {
     constexpr bool X16 = (IOM & 1) != 0, Y16 = (IOM & 2) != 0;  // (round 6) fp16 storage of the input tensor(s) / of the output (+ residual): the one-plane mode's skip convolutions
     using namespace p1;
@@ -160,7 +161,7 @@ __global__ __launch_bounds__(256, 2) void proj_f16x2_kernel(const ConvParams p) 
     }
     const float wsc = p.wscale ? *p.wscale : 1.0f;  // inverse of the packer's power-of-two weight scale (exact)
     if constexpr (NPLK == 2) {
-        conv_epilogue_wide<TH, TW, MR, NR, true>(p, acc, acl, b, th, tw, nTw, cot * CO_T, wave, lane,
+        conv_epilogue_wide<TH, TW, MR, NR, true, false, FIRB>(p, acc, acl, b, th, tw, nTw, cot * CO_T, wave, lane,
                                                    reinterpret_cast<float*>(smem + PATCH0) + wave * 256, f2::LINV, wsc);
     } else {
         f32x16 none[1][1];
@@ -187,7 +188,7 @@ constexpr int PATCH0T = 2 * XPLT + 2 * WPLT;  // 51 200
 constexpr int LDS_TALL = PATCH0T + 4 * 1024;  // 55 296: two blocks per CU
 }  // namespace p1
 
-template <int PRO, int NPLK>
+template <int PRO, int NPLK, bool FIRB = false>
 __global__ __launch_bounds__(256, 2) void proj_tall_f16x2_kernel(const ConvParams p) {
     using namespace p1;
     using gcf = const float __attribute__((address_space(1)))*;
@@ -305,7 +306,7 @@ __global__ __launch_bounds__(256, 2) void proj_tall_f16x2_kernel(const ConvParam
     const float wsc = p.wscale ? *p.wscale : 1.0f;  // inverse of the packer's power-of-two weight scale (exact)
     // the epilogue of the other convolution kernels: this wave owns channels cob * 256 + wave * 64 .. + 63 of pixel row `row` of the tile
     if constexpr (NPLK == 2) {
-        conv_epilogue_wide<TH, TW, MR, NR, true>(p, acc, acl, b, th, tw, nTw, cob * COB + wave * CO_T, row, lane,
+        conv_epilogue_wide<TH, TW, MR, NR, true, false, FIRB>(p, acc, acl, b, th, tw, nTw, cob * COB + wave * CO_T, row, lane,
                                                    reinterpret_cast<float*>(smem + PATCH0T) + wave * 256, f2::LINV, wsc);
     } else {
         f32x16 none[1][1];
@@ -317,8 +318,10 @@ __global__ __launch_bounds__(256, 2) void proj_tall_f16x2_kernel(const ConvParam
 // ---- weight packing: (Cout, Cin) fp32 -> [co tile][chunk][plane h / l][co 64][32 ch] f16 ----
 // range[0] is raised to 1 if a weight does not fit the fp16 range (|w| >= 65504); the packed value saturates.
 // wscale: as pack_conv_f16x2_kernel (conv_f16x2.hip) -- the layer's weights are scaled by a power of two, [1] <- its inverse
+// taps = 9: w is the OIHW tensor of a 3x3 convolution with Cin / 9 input channels, packed as the (Cout, 9 Cin') matrix of the down-sampling GEMM --
+// column (ky 3 + kx) Cin' + ci, the plane order of down_planes_kernel (resample.hip)
 __global__ void pack_proj_f16x2_kernel(const float* __restrict__ w, unsigned* __restrict__ dst, int Cout, int Cin, long pairs,
-                                       int* __restrict__ range, float* __restrict__ wscale) {
+                                       int* __restrict__ range, float* __restrict__ wscale, int taps) {
     using namespace p1;
     f16_saturate_mode();
     float inv = 1.0f;
@@ -334,7 +337,9 @@ __global__ void pack_proj_f16x2_kernel(const float* __restrict__ w, unsigned* __
         const int c = r % nchunks;
         const int cot = r / nchunks;
         const int co = cot * CO_T + col, ci = c * CKP + 2 * cp;
-        const float v0 = w[(long)co * Cin + ci] * ws, v1 = w[(long)co * Cin + ci + 1] * ws;
+        const int cs = Cin / taps;  // (even: a pair of columns shares its tap)
+        const long s0 = taps == 1 ? (long)co * Cin + ci : ((long)co * cs + ci % cs) * taps + ci / cs;
+        const float v0 = w[s0] * ws, v1 = w[s0 + taps] * ws;
         if ((!(fabsf(v0) < 65504.f) || !(fabsf(v1) < 65504.f)) && range) atomicOr(range, 1);
         unsigned ph, pl;
         split_f16x2(v0, v1, ph, pl);
@@ -349,21 +354,21 @@ bool proj_f16x2_supported(int Cin, int Cout, int taps, int H, int W) {
 }
 long proj_f16x2_packed_floats(int Cin, int Cout) { return (long)Cin * Cout; }
 
-hipError_t launch_pack_proj_f16x2(const float* w, float* dst, int Cout, int Cin, int* range_flag, hipStream_t s, float* wscale) {
-    if (Cin % p1::CKP || Cout % p1::CO_T) return hipErrorInvalidValue;
+hipError_t launch_pack_proj_f16x2(const float* w, float* dst, int Cout, int Cin, int* range_flag, hipStream_t s, float* wscale, int taps) {
+    if (Cin % p1::CKP || Cout % p1::CO_T || (taps != 1 && taps != 9) || Cin % (2 * taps)) return hipErrorInvalidValue;
     const long pairs = (long)Cout * Cin / 2;
     if (wscale) {
         hipError_t e = launch_weight_absmax(w, (long)Cout * Cin, reinterpret_cast<int*>(wscale), s);
         if (e != hipSuccess) return e;
     }
     const int blocks = (int)((pairs + 255) / 256 < 2048 ? (pairs + 255) / 256 : 2048);
-    pack_proj_f16x2_kernel<<<blocks, 256, 0, s>>>(w, reinterpret_cast<unsigned*>(dst), Cout, Cin, pairs, range_flag, wscale);
+    pack_proj_f16x2_kernel<<<blocks, 256, 0, s>>>(w, reinterpret_cast<unsigned*>(dst), Cout, Cin, pairs, range_flag, wscale, taps);
     return hipGetLastError();
 }
 
-template <int PRO, int NPLK>
+template <int PRO, int NPLK, bool FIRB = false>
 static hipError_t launch_p1_tall(const ConvParams& p, hipStream_t s) {
-    auto kern = proj_tall_f16x2_kernel<PRO, NPLK>;
+    auto kern = proj_tall_f16x2_kernel<PRO, NPLK, FIRB>;
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, p1::LDS_TALL);
@@ -375,9 +380,9 @@ static hipError_t launch_p1_tall(const ConvParams& p, hipStream_t s) {
     return hipGetLastError();
 }
 
-template <int PRO, int NPLK, int IOM = 0>
+template <int PRO, int NPLK, int IOM = 0, bool FIRB = false>
 static hipError_t launch_p1(const ConvParams& p, hipStream_t s) {
-    auto kern = proj_f16x2_kernel<PRO, NPLK, IOM>;
+    auto kern = proj_f16x2_kernel<PRO, NPLK, IOM, FIRB>;
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, p1::LDS_TOTAL);
@@ -389,7 +394,7 @@ static hipError_t launch_p1(const ConvParams& p, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_proj_f16x2(const ConvParams& p, hipStream_t s) {
+hipError_t launch_proj_f16x2(const ConvParams& p, hipStream_t s, bool bias_rowfac) {
     if (!proj_f16x2_supported(p.Cin, p.Cout, p.taps, p.H, p.W)) return hipErrorInvalidValue;
     if (p.x.p1 && p.x.c0 % 8) return hipErrorInvalidValue;  // a thread's 8 channels must not straddle the concat seam
     if (p.prologue == PRO_AFFINE_SILU || (p.prologue != PRO_NONE && p.aff == nullptr)) return hipErrorInvalidValue;
@@ -399,6 +404,10 @@ hipError_t launch_proj_f16x2(const ConvParams& p, hipStream_t s) {
         return launch_p1<PRO_NONE, 1, 3>(p, s);
     }
     static const bool tall_on = getenv("R2DM_PROJ_TALL") == nullptr || atoi(getenv("R2DM_PROJ_TALL")) != 0;  // (0: experiments)
+    if (bias_rowfac) {  // the down-sampling GEMM: plain input, the split arithmetic, no residual
+        if (p.pieces == 1 || p.prologue != PRO_NONE || p.res || p.x16 || p.y16) return hipErrorInvalidValue;
+        return tall_on && p.Cout % p1::COB == 0 ? launch_p1_tall<PRO_NONE, 2, true>(p, s) : launch_p1<PRO_NONE, 2, 0, true>(p, s);
+    }
     if (tall_on && p.Cout % p1::COB == 0) {  // 256-channel blocks: every pixel staged Cout / 256 times instead of Cout / 64
         if (p.pieces == 1) return p.prologue == PRO_NONE ? launch_p1_tall<PRO_NONE, 1>(p, s) : launch_p1_tall<PRO_AFFINE, 1>(p, s);
         return p.prologue == PRO_NONE ? launch_p1_tall<PRO_NONE, 2>(p, s) : launch_p1_tall<PRO_AFFINE, 2>(p, s);

@@ -228,6 +228,96 @@ __global__ __launch_bounds__(256) void fir_down2_stats_kernel(const float* __res
     }
 }
 
+// ---- down_planes: the operand of the down-sampling GEMM (FIR BEFORE the stage's 3x3 convolution) ---------------------------------
+// Reference: efficient_unet.py:132-136 -- Conv3x3(ring) at the finer resolution, then Resample(down=2).  The FIR is depthwise with one
+// window for every channel, so it commutes with the channel-mixing convolution; only the two border rows need care, where the FIR
+// zero-pads the convolution's OUTPUT (a conv row outside [0, H) counts as 0 although the convolution of the zero-padded input -- and the
+// bias -- would not be).  With f = [1,3,3,1]/8, x zero outside rows [0, H), columns mod W:
+//   V[ky][i][c]     = sum_t f[t] [0 <= 2i-1+t < H] x[2i-1+t + ky-1][c]           one vertically filtered row plane per conv tap row
+//   A[ky][kx][i][j] = sum_t f[t] V[ky][i][(2j + t + kx - 2) mod W]                one horizontally filtered plane per conv tap column
+//   FIR(conv(x) + b)[co][i][j] = sum_{ky,kx,ci} w[co][ci][ky][kx] A[ky][kx][ci][i][j] + b[co] rowfac[i],   rowfac[i] = sum_t f[t] [0 <= 2i-1+t < H]
+// i.e. a 1x1 convolution over 9 Cin planes at the OUTPUT resolution: a quarter of the MACs (proj_f16x2.hip runs it; the bias factor is
+// its epilogue's).  a: [B][9 Cin][H/2][W/2] fp32, plane (ky 3 + kx) Cin + ci.
+// One thread -> a 2 x 4 patch of all nine planes of one channel: input rows 4 i2 - 2 .. 4 i2 + 5, columns 8t - 2 .. 8t + 9 (two 16-byte and
+// two 8-byte loads per row -- the halo pairs never straddle the seam: W % 8 == 0), eighteen 16-byte stores.  Every row is loaded from a clamped
+// index and zeroed behind the load (as fir_down2_patch); every sum is the fir4 chain.  range (optional): running max |a| as float bits into
+// range[1] -- the GEMM's fp16 operand (f >= 0 and sums to at most 1 per axis: max|a| <= max|x| in exact arithmetic; recorded all the same).
+__global__ __launch_bounds__(256) void down_planes_kernel(const float* __restrict__ x, long xbs, float* __restrict__ a, long abs_, int C, int H, int W,
+                                                          int* __restrict__ range) {
+    using f32x2 = __attribute__((ext_vector_type(2))) float;
+    const int Ho = H >> 1, Wo = W >> 1, Wq = Wo >> 2, Hq = Ho >> 1;
+    const long per_plane = (long)Hq * Wq, total = per_plane * C, plane = (long)Ho * Wo;
+    const int b = blockIdx.y;
+    float amax = 0.f;
+    for (long idx = blockIdx.x * 256L + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const int c = idx / per_plane;
+        const long rem = idx % per_plane;
+        const int i2 = rem / Wq, t = rem % Wq;
+        const float* xp = x + b * xbs + (long)c * H * W;
+        const int cl = t == 0 ? W - 2 : 8 * t - 2, cr = t == Wq - 1 ? 0 : 8 * t + 8;
+        float v[8][12];  // input rows 4 i2 - 2 + a, columns 8t - 2 .. 8t + 9; rows outside the image are zero
+#pragma unroll
+        for (int r8 = 0; r8 < 8; ++r8) {
+            const int r = 4 * i2 - 2 + r8;
+            const bool in = r >= 0 && r < H;
+            const float* row = xp + (long)(r < 0 ? 0 : r >= H ? H - 1 : r) * W;
+            const f32x2 l = *reinterpret_cast<const f32x2*>(row + cl), rr = *reinterpret_cast<const f32x2*>(row + cr);
+            const f32x4 m0 = *reinterpret_cast<const f32x4*>(row + 8 * t), m1 = *reinterpret_cast<const f32x4*>(row + 8 * t + 4);
+            v[r8][0] = in ? l[0] : 0.f;
+            v[r8][1] = in ? l[1] : 0.f;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                v[r8][2 + e] = in ? m0[e] : 0.f;
+                v[r8][6 + e] = in ? m1[e] : 0.f;
+            }
+            v[r8][10] = in ? rr[0] : 0.f;
+            v[r8][11] = in ? rr[1] : 0.f;
+        }
+#pragma unroll
+        for (int o = 0; o < 2; ++o) {
+            const int i = 2 * i2 + o;
+            bool on[4];  // FIR tap t falls on a real row of the convolution's output
+#pragma unroll
+            for (int tt = 0; tt < 4; ++tt) on[tt] = 2 * i - 1 + tt >= 0 && 2 * i - 1 + tt < H;
+#pragma unroll
+            for (int ky = 0; ky < 3; ++ky) {
+                float vv[12];  // V[ky][i] at the twelve columns: input row 2i - 2 + tt + ky = v[2 o + tt + ky]
+#pragma unroll
+                for (int e = 0; e < 12; ++e)
+                    vv[e] = fir4(on[0] ? v[2 * o + ky][e] : 0.f, on[1] ? v[2 * o + ky + 1][e] : 0.f, on[2] ? v[2 * o + ky + 2][e] : 0.f,
+                                 on[3] ? v[2 * o + ky + 3][e] : 0.f);
+#pragma unroll
+                for (int kx = 0; kx < 3; ++kx) {
+                    f32x4 out;  // output column 4t + j: input columns 2 (4t + j) + tt + kx - 2 = vv[2 j + kx + tt]
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        out[j] = fir4(vv[2 * j + kx], vv[2 * j + kx + 1], vv[2 * j + kx + 2], vv[2 * j + kx + 3]);
+                        amax = fmaxf(amax, fabsf(out[j]));
+                    }
+                    *reinterpret_cast<f32x4*>(a + b * abs_ + ((long)(ky * 3 + kx) * C + c) * plane + (long)i * Wo + 4 * t) = out;
+                }
+            }
+        }
+    }
+    if (range) {
+        amax = wave_max_f32(amax);
+        if ((threadIdx.x & 63) == 0) {
+            const int bits = __float_as_int(amax);
+            if (bits > __atomic_load_n(range + 1, __ATOMIC_RELAXED)) atomicMax(range + 1, bits);
+        }
+    }
+}
+
+static int grid_for(long total);
+
+bool down_planes_supported(int H, int W) { return H >= 4 && H % 4 == 0 && W >= 16 && W % 8 == 0; }
+
+hipError_t launch_down_planes(const float* x, long xbs, float* a, long abs_, int B, int C, int H, int W, hipStream_t s, int* range) {
+    if (!down_planes_supported(H, W)) return hipErrorInvalidValue;
+    down_planes_kernel<<<dim3(grid_for((long)C * (H / 4) * (W / 8)), B), 256, 0, s>>>(x, xbs, a, abs_, C, H, W, range);
+    return hipGetLastError();
+}
+
 // The bilinear weights of the up-sampler as ONE spelled-out chain, shared by its two kernels (round 6; as fir4 for the down-samplers): which kernel a map
 // takes depends on its size, and a sample must come out the same bits whatever batch it is part of (tests/test_hip_configs.py).
 __device__ __forceinline__ float up1(float far, float near) { return __builtin_fmaf(0.75f, near, 0.25f * far); }  // 3/4 of the nearer sample + 1/4 of the farther one
