@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Drop-in for the tensor-producing half of the reference's generate.py (/root/reference/generate.py:16-42):
-same CLI, same sampling call, same post-processing of the returned (S+1,B,2,H,W) stack.  The PNG / BEV / mp4
-rendering half (generate.py:44-76; kornia, imageio, torchvision) is out of scope: tensors are saved instead."""
+"""Drop-in for the reference's generate.py: same CLI, same sampling call, same post-processing of
+the returned (S+1,B,2,H,W) stack, which is saved as tensors.  With ``--render_dir DIR`` the last frame is also rendered as the
+reference renders it (generate.py:44-63, r2dm_amd/render.py): ``samples_img.png``, the turbo-coloured range / reflectance
+images, and ``samples_bev.png``, the bird's-eye views; ``--render_frames`` adds ``frames/bev_%04d.png`` for every frame of the
+stack.  Still missing from the reference's script: the mp4 (no encoder here) and the antialiased 512-pixel resize of its frames."""
 import argparse
 from pathlib import Path
 
@@ -12,6 +14,8 @@ import r2dm_amd
 
 def main(args):
     torch.set_grad_enabled(False)
+    if args.seed is not None:
+        torch.manual_seed(args.seed)
     ddpm, lidar_utils, _ = r2dm_amd.setup_model(args.ckpt, device=args.device, max_batch=args.batch_size)
     xs = ddpm.sample(batch_size=args.batch_size, num_steps=args.sampling_steps, mode=args.mode, return_all=True).clamp(-1, 1)
     xs = lidar_utils.denormalize(xs)
@@ -19,6 +23,29 @@ def main(args):
     points = lidar_utils.postprocess(_last_sample_normalized(xs, lidar_utils))
     torch.save({"frames": xs.cpu(), "points": points.cpu()}, args.output)
     print(f"saved {tuple(xs.shape)} frames and {tuple(points.shape)} [depth,x,y,z,reflectance] maps to {args.output}")
+    if args.render_dir is not None:
+        render(xs, lidar_utils, args)
+
+
+def render(xs, lidar_utils, args):
+    """generate.py:61-63 on the last frame; with --render_frames the BEV of every frame, a few sampling steps per launch."""
+    from r2dm_amd.render import make_grid, render_frames, save_png
+
+    args.render_dir.mkdir(parents=True, exist_ok=True)
+    img, bev = render_frames(xs[-1], lidar_utils, size=args.bev_size)
+    save_png(make_grid(img, nrow=1), args.render_dir / "samples_img.png")
+    save_png(make_grid(bev, nrow=4), args.render_dir / "samples_bev.png")
+    written = 2
+    if args.render_frames:
+        (args.render_dir / "frames").mkdir(exist_ok=True)
+        S1, B = xs.shape[:2]
+        steps = max(1, 64 // B)
+        for s0 in range(0, S1, steps):
+            _, bev = render_frames(xs[s0:s0 + steps].flatten(0, 1), lidar_utils, size=args.bev_size)
+            for k, frame in enumerate(bev.unflatten(0, (-1, B))):
+                save_png(make_grid(frame, nrow=B, pad_value=1.0), args.render_dir / "frames" / f"bev_{s0 + k:04d}.png")
+                written += 1
+    print(f"rendered {written} images to {args.render_dir}")
 
 
 def _last_sample_normalized(xs, lidar_utils):
@@ -36,6 +63,10 @@ if __name__ == "__main__":
     parser.add_argument("--batch_size", type=int, default=1)
     parser.add_argument("--sampling_steps", type=int, default=256)
     parser.add_argument("--output", type=Path, default=Path("samples.pt"))
+    parser.add_argument("--seed", type=int, default=None, help="seed of torch's global generators (default: not seeded, as the reference)")
+    parser.add_argument("--render_dir", type=Path, default=None, help="also write samples_img.png and samples_bev.png there")
+    parser.add_argument("--bev_size", type=int, default=800, help="side of a bird's-eye view in pixels")
+    parser.add_argument("--render_frames", action="store_true", help="with --render_dir: frames/bev_%%04d.png for every frame of the stack")
     args = parser.parse_args()
     args.device = torch.device(args.device)
     main(args)

@@ -180,6 +180,32 @@ size_t r2dm_bev_mmd_scratch_bytes(int32_t np, int32_t nq);
 int r2dm_bev_mmd(const float* p, const float* q, int32_t np, int32_t nq, int64_t bins, double sigma, void* scratch,
                  size_t scratch_bytes, double* out, void* stream);
 
+/* -- rendering of generate.py (utils/render.py; generate.py:44-59) -------------------------------------------------------------
+ * All arithmetic is fp32 with one rounding per operation.  The splat accumulates 64-bit fixed-point integers (scale from the
+ * largest |value| of the call, taken on the device): the same bits on every call and for every order of the points.
+ * r2dm_colorize: x (batch, pixels) -> out (batch, 3, pixels) uint8 = trunc(clamp(lut[trunc(clamp(x 256, 0, 255))] 255, 0, 255)),
+ *    lut (256,3) fp32 in device memory.
+ * r2dm_bilinear_rasterize: coords (B,N,2) [row, column], values (B,N,C) -> out (B,C,H,W): every point adds value x bilinear
+ *    weight at its four neighbours (weights of clamped indices and products below 1e-3 are zero; non-finite coordinates add
+ *    nothing).  ratio = 1 (C = 4): out (B,3,H,W) = sum_c / (sum_3 + 1e-8).  scratch: r2dm_rasterize_scratch_bytes(), 256-byte aligned.
+ * r2dm_project_points: the per-point half of render_point_clouds: points (B,N,3), colors (B,N,3) or NULL (ones), view = 12 HOST
+ *    floats (R row-major, then t): p' = (x, y, -z) R + t, pinhole projection with K = diag(f, f, 1), cx = cy = 0.5 ->
+ *    uv (B,N,2) = size - size * projection, vals (B,N,4) = [w c0 m, w c1 m, w c2 m, w], w = exp(-3 |p'|), m the border mask.
+ * r2dm_render_frames: generate.py's render() in one pass over x (frames,2,H,W) (depth / max_depth, reflectance; both in [0,1]):
+ *    img (frames,3,2H,W) = turbo of the stacked channels / 255, bev (frames,3,size,size) = 1 - render_point_clouds(xyz, 1 - viridis(z)).
+ *    trig (4,H,W): cos / sin of the elevation, cos / sin of the azimuth; turbo, viridis (256,3).  Frames are taken as many at a
+ *    time as scratch (at least r2dm_render_frames_scratch_bytes(1, size), 256-byte aligned) holds. */
+int r2dm_colorize(const float* x, const float* lut, uint8_t* out, int64_t batch, int64_t pixels, void* stream);
+size_t r2dm_rasterize_scratch_bytes(int32_t batch, int32_t channels, int32_t height, int32_t width);
+int r2dm_bilinear_rasterize(const float* coords, const float* values, float* out, int32_t batch, int64_t points, int32_t channels,
+                            int32_t height, int32_t width, void* scratch, size_t scratch_bytes, int32_t ratio, void* stream);
+int r2dm_project_points(const float* points, const float* colors, const float* view, float focal_length, int32_t size, float* uv,
+                        float* vals, int64_t total_points, void* stream);
+size_t r2dm_render_frames_scratch_bytes(int32_t frames, int32_t size);
+int r2dm_render_frames(const float* x, const float* trig, const float* turbo, const float* viridis, float* img, float* bev,
+                       int64_t frames, int32_t height, int32_t width, int32_t size, float min_depth, float max_depth,
+                       const float* view, float focal_length, void* scratch, size_t scratch_bytes, void* stream);
+
 /* -- single kernels, exported for per-op parity tests against the oracle -------------------- */
 /* ops.Conv2d(ring) 3x3 / 1x1 (models/ops.py:149-173) with optional fused GroupNorm-affine(+SiLU)
  * prologue (aff: (B,Cin,2) or NULL; prologue 0 none, 1 affine, 2 affine+SiLU) and optional

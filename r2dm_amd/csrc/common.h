@@ -284,4 +284,18 @@ hipError_t launch_bev_hist_sum(const void* hist, int is_int32, int64_t* sum, lon
 size_t mmd_scratch_bytes(int np, int nq);
 hipError_t launch_bev_mmd(const float* P, const float* Q, int np, int nq, long D, double sigma, void* scratch, double* out, hipStream_t s);
 
+// rendering of generate.py (render.hip): colour maps, the bilinear splat with 64-bit fixed-point accumulators, the fused frame renderer
+hipError_t launch_colorize(const float* x, const float* lut, uint8_t* out, long B, long hw, hipStream_t s);
+size_t rasterize_scratch_bytes(int B, int C, int H, int W);
+// ratio 0: out (B,C,H,W) sums; 1 (C = 4): out (B,3,H,W) = sum_c / (sum_3 + 1e-8)
+hipError_t launch_rasterize(const float* coords, const float* values, float* out, int B, long N, int C, int H, int W, void* scratch, int ratio,
+                            hipStream_t s);
+// Rt: 12 HOST floats, R row-major then t
+hipError_t launch_project_points(const float* points, const float* colors, const float* Rt, float focal, int size, float* uv, float* vals, long n,
+                                 hipStream_t s);
+size_t render_frames_scratch_bytes(int frames, int size);
+hipError_t launch_render_frames(const float* x, const float* trig, const float* turbo, const float* viridis, float* img, float* bev, long N, int H, int W,
+                                int size, float min_depth, float max_depth, const float* Rt, float focal, void* scratch, size_t scratch_bytes,
+                                hipStream_t s);
+
 }  // namespace r2dm

@@ -1291,6 +1291,55 @@ int r2dm_bev_mmd(const float* p, const float* q, int32_t np, int32_t nq, int64_t
     return 0;
 }
 
+int r2dm_colorize(const float* x, const float* lut, uint8_t* out, int64_t batch, int64_t pixels, void* stream) {
+    if (!x || !lut || !out) return fail(1, "null argument");
+    if (batch < 1 || pixels < 1) return fail(1, "empty image batch");
+    HIP_TRY(launch_colorize(x, lut, out, batch, pixels, (hipStream_t)stream));
+    return 0;
+}
+
+size_t r2dm_rasterize_scratch_bytes(int32_t batch, int32_t channels, int32_t height, int32_t width) {
+    return batch < 1 || channels < 1 || height < 1 || width < 1 ? 0 : rasterize_scratch_bytes(batch, channels, height, width);
+}
+
+int r2dm_bilinear_rasterize(const float* coords, const float* values, float* out, int32_t batch, int64_t points, int32_t channels, int32_t height,
+                            int32_t width, void* scratch, size_t scratch_bytes, int32_t ratio, void* stream) {
+    if (!coords || !values || !out || !scratch) return fail(1, "null argument");
+    if (batch < 1 || batch > 65535 || points < 1 || channels < 1 || height < 1 || width < 1) return fail(1, "rasterize: empty or oversized batch");
+    if (points > (1L << 36)) return fail(1, "rasterize: more than 2^36 points per image");
+    if (ratio != 0 && ratio != 1) return fail(1, "ratio must be 0 (sums) or 1 (channels 0-2 over channel 3)");
+    if (ratio && channels != 4) return fail(1, "the ratio form takes 4 channels, got %d", channels);
+    const size_t need = rasterize_scratch_bytes(batch, channels, height, width);
+    if (scratch_bytes < need) return fail(1, "scratch too small: %zu < %zu bytes", scratch_bytes, need);
+    if ((uintptr_t)scratch & 255) return fail(1, "scratch must be 256-byte aligned");
+    HIP_TRY(launch_rasterize(coords, values, out, batch, points, channels, height, width, scratch, ratio, (hipStream_t)stream));
+    return 0;
+}
+
+int r2dm_project_points(const float* points, const float* colors, const float* view, float focal_length, int32_t size, float* uv, float* vals,
+                        int64_t total_points, void* stream) {
+    if (!points || !view || !uv || !vals) return fail(1, "null argument");
+    if (total_points < 1 || size < 1) return fail(1, "project_points: empty cloud or image");
+    HIP_TRY(launch_project_points(points, colors, view, focal_length, size, uv, vals, total_points, (hipStream_t)stream));
+    return 0;
+}
+
+size_t r2dm_render_frames_scratch_bytes(int32_t frames, int32_t size) { return frames < 1 || size < 1 ? 0 : render_frames_scratch_bytes(frames, size); }
+
+int r2dm_render_frames(const float* x, const float* trig, const float* turbo, const float* viridis, float* img, float* bev, int64_t frames,
+                       int32_t height, int32_t width, int32_t size, float min_depth, float max_depth, const float* view, float focal_length,
+                       void* scratch, size_t scratch_bytes, void* stream) {
+    if (!x || !trig || !turbo || !viridis || !img || !bev || !view || !scratch) return fail(1, "null argument");
+    if (frames < 1 || height < 1 || width < 1 || size < 1) return fail(1, "render_frames: empty batch or image");
+    if (!(max_depth > 0.f)) return fail(1, "max_depth must be > 0");
+    if (scratch_bytes < render_frames_scratch_bytes(1, size))
+        return fail(1, "scratch too small: %zu bytes hold no frame of %zu", scratch_bytes, render_frames_scratch_bytes(1, size));
+    if ((uintptr_t)scratch & 255) return fail(1, "scratch must be 256-byte aligned");
+    HIP_TRY(launch_render_frames(x, trig, turbo, viridis, img, bev, frames, height, width, size, min_depth, max_depth, view, focal_length, scratch,
+                                 scratch_bytes, (hipStream_t)stream));
+    return 0;
+}
+
 static int g_single_kernel_pieces = 2;  // r2dm_conv2d_ring (per-op tests)
 
 int r2dm_set_conv_pieces(r2dm_handle* h, int32_t pieces) {
