@@ -1,0 +1,110 @@
+#!/usr/bin/env python3
+"""Drop-in for the reference's completion_demo.py: RePaint completion of one real scan under four simulated corruptions (the full
+scan, every 4th beam, a random half of the beams, a random 10 % of the points).
+
+Same options (``--ckpt --num_steps --num_resample_steps --jump_length --seed``); the scan comes from ``--scan FILE.bin`` (a raw
+Velodyne file, projected on the GPU by r2dm_amd.projection with the checkpoint's ``cfg.data.projection``) instead of the
+HuggingFace dataset lookup, and ``--out`` names the image.  The corruption masks are drawn as the reference draws them
+(completion_demo.py:81-87: the same CPU draws after ``torch.manual_seed(seed)``), the completion is the same
+``ddpm.repaint(..., rng=setup_rng(range(4)))`` call, clamped.
+
+Written: one PNG with a column per corruption -- input image (depth over reflectance), input bird's-eye view, completed image,
+completed bird's-eye view (r2dm_amd.render; the views coloured by height) -- and, next to it, ``completion.pt`` with ``x_in``,
+``mask`` and ``x_out``.  There is no segmentation row: the reference colours its last two rows with RangeNet-53 labels, and those
+weights are not part of this package."""
+import math
+from argparse import ArgumentParser
+from pathlib import Path
+
+import torch
+
+import r2dm_amd
+
+BATCH = 4
+
+
+def corruption_masks(x_orig, seed):
+    """completion_demo.py:19,81-87: four masks (4,2,H,W) on the CPU -- full, 25 % beams, random 50 % beams, random 10 % points."""
+    torch.manual_seed(seed)
+    H, W = x_orig.shape[-2:]
+    mask = torch.zeros(1, *x_orig.shape[1:]).repeat_interleave(BATCH, dim=0)
+    mask[0, ...] = 1
+    mask[1, :, ::4] = 1
+    mask[2, :] = torch.empty(H, 1).bernoulli_(0.5)
+    mask[3, :] = torch.empty(H, W).bernoulli_(0.1)
+    return mask
+
+
+def known_of_scan(path, lidar_utils, cfg, device):
+    """The scan as the dataset serves it (64 rows, the projection's width, masked), then completion_demo.py:66-75."""
+    unfolding, width = r2dm_amd.parse_projection(cfg.data.projection)
+    points, offsets = r2dm_amd.load_scans([path])
+    xyzrdm = r2dm_amd.project_scans(points, offsets, H=64, W=width, scan_unfolding=unfolding, min_depth=lidar_utils.min_depth,
+                                    max_depth=lidar_utils.max_depth, apply_mask=True, device=device)
+    return r2dm_amd.known_from_scan(xyzrdm, lidar_utils, cfg.data.resolution)
+
+
+def to_img(x, lidar_utils):
+    """completion_demo.py:112-115,135: (B,2,H,W) in [-1,1] -> turbo-coloured (B,3,2H,W) in [0,1], depth over reflectance"""
+    from r2dm_amd.render import colorize
+
+    img = lidar_utils.denormalize(x)
+    img[:, [0]] = lidar_utils.revert_depth(img[:, [0]]) / lidar_utils.max_depth
+    return colorize(img.clamp(0, 1).flatten(1, 2), "turbo").float() / 255
+
+
+def to_bev(x, lidar_utils, size):
+    """completion_demo.py:117-133 with the height colouring: (B,2,H,W) -> (B,3,size,size)"""
+    from r2dm_amd.render import colorize, make_Rt, render_point_clouds
+
+    R, t = make_Rt(pitch=math.pi / 4, yaw=math.pi / 4, z=0.6)
+    depth = lidar_utils.revert_depth(lidar_utils.denormalize(x)[:, [0]])
+    xyz = lidar_utils.to_xyz(depth) / lidar_utils.max_depth
+    z_min, z_max = -2 / lidar_utils.max_depth, 0.5 / lidar_utils.max_depth
+    z = (xyz[:, [2]] - z_min) / (z_max - z_min)
+    colors = colorize(z.clamp(0, 1), "viridis").float() / 255
+    points = xyz.flatten(2).transpose(1, 2)
+    colors = 1 - colors.flatten(2).transpose(1, 2)
+    return (1 - render_point_clouds(points, colors, size=size, R=R, t=t)).clamp(0, 1)
+
+
+def main(args):
+    from r2dm_amd.render import make_grid, save_png
+
+    torch.set_grad_enabled(False)
+    device = torch.device("cuda")
+    ddpm, lidar_utils, cfg = r2dm_amd.setup_model(args.ckpt, device=device, max_batch=BATCH, show_info=False)
+    x_orig = known_of_scan(args.scan, lidar_utils, cfg, device)
+
+    mask = corruption_masks(x_orig, args.seed).to(device)
+    x_in = mask * x_orig + (1 - mask) * -1
+    x_out = ddpm.repaint(known=x_in, mask=mask, num_steps=args.num_steps, num_resample_steps=args.num_resample_steps,
+                         jump_length=args.jump_length, rng=r2dm_amd.setup_rng(range(BATCH), device=device)).clamp(-1, 1)
+
+    W = x_in.shape[-1]
+    columns = torch.cat([to_img(x_in, lidar_utils), to_bev(x_in, lidar_utils, W), to_img(x_out, lidar_utils), to_bev(x_out, lidar_utils, W)], dim=2)
+    args.out.parent.mkdir(parents=True, exist_ok=True)
+    save_png(make_grid(columns, nrow=BATCH, pad_value=1.0), args.out)
+    state = args.out.parent / "completion.pt"
+    torch.save({"x_in": x_in.cpu(), "mask": mask.cpu(), "x_out": x_out.cpu()}, state)
+    print(f'Saved to "{args.out}" and "{state}"')
+
+
+def parser():
+    p = ArgumentParser()
+    p.add_argument("--ckpt", type=Path, required=True)
+    p.add_argument("--num_steps", type=int, default=32)
+    p.add_argument("--num_resample_steps", type=int, default=16)
+    p.add_argument("--jump_length", type=int, default=1)
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--scan", type=Path, required=True, help="a raw Velodyne scan (*.bin: float32 x, y, z, reflectance), instead of --sample_id")
+    p.add_argument("--out", type=Path, default=None, help="the image (default: the reference's completion_T-..._r-..._j-....png)")
+    return p
+
+
+if __name__ == "__main__":
+    args = parser().parse_args()
+    if args.out is None:
+        args.out = Path(f"completion_T-{args.num_steps:04d}_r-{args.num_resample_steps:04d}_j-{args.jump_length:04d}.png")
+    print(vars(args))
+    main(args)

@@ -7,8 +7,11 @@ Same CLI (``--ckpt``, ``--sample_dir``, ``--dataset``, ``--batch_size``, ``--num
 ``{sample_dir}_{timestamp}.json``.  The real set comes from either
   - the reference's own cache pickle ``real_set_{dataset}_{projection}_{H}x{W}_{split}.pkl`` (its ``bev_hists``), looked for
     in the working directory under that name as the reference writes it, or given with ``--real_set PATH``; or
-  - ``--real_dir DIR``: a directory of (5,H,W) scans in the sample layout, histogrammed here.
-The dataset itself is not read.  FRD and FPD need the RangeNet-53 / PointNet weights and are not computed here."""
+  - ``--real_dir DIR``: a directory of (5,H,W) scans in the sample layout, histogrammed here; or
+  - ``--real_scans DIR``: a directory tree of raw Velodyne ``*.bin`` scans (KITTI-360's ``data_3d_raw``, say), projected here on the
+    GPU (r2dm_amd.projection) with the checkpoint's ``cfg.data.projection`` and resized to ``cfg.data.resolution`` as the reference's
+    dataset and evaluate.py do, ``--batch_size`` scans at a time.
+The HuggingFace dataset builders are not used.  FRD and FPD need the RangeNet-53 / PointNet weights and are not computed here."""
 import datetime
 import json
 import pickle
@@ -56,6 +59,33 @@ def histograms_of(files, batch_size, num_workers, device):
     return torch.cat(out)
 
 
+def scan_files(root):
+    """All ``*.bin`` files below ``root``, sorted."""
+    return sorted(Path(root).rglob("*.bin"))
+
+
+def histograms_of_scans(files, cfg, batch_size, device):
+    """int32 (N,100,100) BEV histograms of raw scans: the dataset builder's projection (64 rows, the projection's own width, masked by
+    its depth window), evaluate.py's resize to the model's resolution (nearest-exact), then the depth mask and histogram as above."""
+    import torch.nn.functional as F
+
+    from r2dm_amd import metrics, projection
+
+    if not files:
+        raise SystemExit("no *.bin files below --real_scans")
+    unfolding, width = projection.parse_projection(cfg.data.projection)
+    H, W = cfg.data.resolution
+    out = []
+    for k in range(0, len(files), batch_size):
+        points, offsets = projection.load_scans(files[k:k + batch_size])
+        imgs = projection.project_scans(points, offsets, H=64, W=width, scan_unfolding=unfolding, apply_mask=True,
+                                        out_width=W if W <= width else None, layout="sample", device=device)
+        if tuple(imgs.shape[-2:]) != (H, W):
+            imgs = F.interpolate(imgs, size=(H, W), mode="nearest-exact")
+        out.append(metrics.bev_histograms(imgs, image_min_depth=MIN_DEPTH, image_max_depth=MAX_DEPTH))
+    return torch.cat(out)
+
+
 def real_cache_name(cfg, split):
     H, W = cfg.data.resolution
     return f"real_set_{cfg.data.dataset}_{cfg.data.projection}_{H}x{W}_{split}.pkl"
@@ -75,14 +105,17 @@ def evaluate(args):
     results["info"]["directory"] = args.sample_dir
 
     # real set: the reference's cache, or a directory of scans
-    if args.real_dir is not None:
+    if args.real_scans is not None:
+        real_hists = histograms_of_scans(scan_files(args.real_scans), cfg, args.batch_size, device)
+        results["info"]["real"] = str(args.real_scans)
+    elif args.real_dir is not None:
         real_hists = histograms_of(sample_files(args.real_dir, limit=None), args.batch_size, args.num_workers, device)
         results["info"]["real"] = str(args.real_dir)
     else:
         path = Path(args.real_set) if args.real_set is not None else Path(real_cache_name(cfg, args.dataset))
         if not path.exists():
             raise SystemExit(f"no real set: {path} not found (run the reference's evaluate.py once to cache it, or give "
-                             "--real_set PATH / --real_dir DIR)")
+                             "--real_set PATH / --real_dir DIR / --real_scans DIR)")
         print(f"found cached {path}")
         with open(path, "rb") as f:
             real_set = pickle.load(f)
@@ -122,4 +155,6 @@ if __name__ == "__main__":
                         help="extension: the reference's real-set cache pickle (default: its own name in the working directory)")
     parser.add_argument("--real_dir", type=str, default=None,
                         help="extension: a directory of (5,H,W) real scans in the sample layout, instead of the cache")
+    parser.add_argument("--real_scans", type=str, default=None,
+                        help="extension: a directory tree of raw Velodyne *.bin scans, projected here with the checkpoint's projection")
     evaluate(parser.parse_args())

@@ -206,6 +206,30 @@ int r2dm_render_frames(const float* x, const float* trig, const float* turbo, co
                        int64_t frames, int32_t height, int32_t width, int32_t size, float min_depth, float max_depth,
                        const float* view, float focal_length, void* scratch, size_t scratch_bytes, void* stream);
 
+/* -- raw scans to range images (data/kitti_360/kitti_360.py:34-93,164-165; the same in data/kitti_raw) -------------------------
+ * r2dm_project_scans: load_points_as_images on a batch of scans held in one buffer: points (total,4) fp32 [x, y, z, reflectance]
+ *    in device memory (16-byte aligned), scan b = rows offsets[b] .. offsets[b + 1] - 1; offsets = batch + 1 HOST values, offsets[0] = 0,
+ *    non-decreasing (an empty scan gives an empty image), read before the call returns.
+ *    depth = sqrt((x x + y y) + z z) in fp32, one rounding per operation (np.linalg.norm), mask = min_depth <= depth <= max_depth.
+ *    Column: floor(((-atan2(y, x)) / pi + 1) / 2 mod 1 * width), fp32.  Row, scan_unfolding = 0: floor((1 - (asin(z / depth) + 25 deg) /
+ *    28 deg) * height), fp32 asin, the rest fp64 (numpy >= 2); scan_unfolding = 1: by the point's position in the file -- a delimiter is a
+ *    point in the 1st quadrant whose predecessor (cyclically) is in the 4th; with D delimiters in the scan and seg of them at positions
+ *    <= i: row 0 if seg = 0, else r = height - 1 - (D - seg) -> r if r >= 0, height - 1 if r = -1, 0 below (the reference's loop).  Both
+ *    clipped to the grid.  Every cell keeps its NEAREST point, inside the depth window or not; among equal depths the lowest index wins
+ *    (64-bit integer atomic min of depth bits : index): the same bits on every call and for every order of the launch.
+ *    A point whose depth is not a finite number > 0 (NaN / inf coordinates, (0,0,0)) never wins a cell; under scan unfolding it still
+ *    counts in the sequence (quadrant 0 where a comparison with NaN decides).
+ *    layout 0: out (batch,6,height,out_width) [x, y, z, reflectance, depth, mask], layout 1: out (batch,5,height,out_width)
+ *    [depth, x, y, z, reflectance] (r2dm_bev_histogram's layout 0); empty cells are 0.  apply_mask = 1 multiplies every value by the mask
+ *    (the dataset builder), 0 leaves them (the function's raw return value).  out_width <= width writes column j from source column
+ *    floor((j + 0.5) width / out_width) (F.interpolate, mode "nearest-exact").
+ *    scratch: r2dm_project_scratch_bytes() of device memory (0: geometry refused), 256-byte aligned.
+ *    Limits: batch <= 65535; fewer than 2^31 points and fewer than 2^31 cells over the batch. */
+size_t r2dm_project_scratch_bytes(int64_t total_points, int32_t batch, int32_t height, int32_t width, int32_t scan_unfolding);
+int r2dm_project_scans(const float* points, const int64_t* offsets, float* out, int32_t batch, int32_t height, int32_t width,
+                       int32_t out_width, int32_t scan_unfolding, float min_depth, float max_depth, int32_t apply_mask, int32_t layout,
+                       void* scratch, size_t scratch_bytes, void* stream);
+
 /* -- single kernels, exported for per-op parity tests against the oracle -------------------- */
 /* ops.Conv2d(ring) 3x3 / 1x1 (models/ops.py:149-173) with optional fused GroupNorm-affine(+SiLU)
  * prologue (aff: (B,Cin,2) or NULL; prologue 0 none, 1 affine, 2 affine+SiLU) and optional

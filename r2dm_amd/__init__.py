@@ -9,9 +9,12 @@ from .lidar import LiDARUtility
 from .option import Config
 from .unet import EfficientUNet
 from . import metrics  # noqa: E402  (BEV metrics of evaluate.py)
+from . import projection  # noqa: E402  (raw scans -> range images)
+from .projection import known_from_scan, load_points_as_images, load_scans, parse_projection, project_scans
 
 __all__ = [
     "ContinuousTimeGaussianDiffusion", "DiscreteTimeGaussianDiffusion", "GaussianDiffusion", "EfficientUNet",
     "LiDARUtility", "Config", "setup_model", "setup_rng",
+    "load_scans", "project_scans", "load_points_as_images", "parse_projection", "known_from_scan",
 ]
 __version__ = "0.4.0"

@@ -298,4 +298,9 @@ hipError_t launch_render_frames(const float* x, const float* trig, const float* 
                                 int size, float min_depth, float max_depth, const float* Rt, float focal, void* scratch, size_t scratch_bytes,
                                 hipStream_t s);
 
+// raw scans -> range images (projection.hip): offsets are B + 1 HOST values (validated by the caller), Wo <= W the written width
+size_t project_scratch_bytes(long long total, int B, int H, int W, int unfold);
+hipError_t launch_project_scans(const float* points, const long long* offsets, float* out, int B, int H, int W, int Wo, int unfold, float min_depth,
+                                float max_depth, int apply_mask, int layout, void* scratch, hipStream_t s);
+
 }  // namespace r2dm

@@ -1340,6 +1340,40 @@ int r2dm_render_frames(const float* x, const float* trig, const float* turbo, co
     return 0;
 }
 
+static const char* project_geometry_error(int64_t total, int32_t batch, int32_t H, int32_t W) {
+    if (batch < 1 || batch > 65535) return "project: batch must be in [1, 65535]";
+    if (H < 1 || W < 1 || (int64_t)batch * H * W >= (1LL << 31)) return "project: the grid must have 1 to 2^31 - 1 cells over the batch";
+    if (total < 0 || total >= (1LL << 31)) return "project: 0 to 2^31 - 1 points over the batch";
+    return nullptr;
+}
+
+size_t r2dm_project_scratch_bytes(int64_t total_points, int32_t batch, int32_t height, int32_t width, int32_t scan_unfolding) {
+    return project_geometry_error(total_points, batch, height, width) ? 0 : project_scratch_bytes(total_points, batch, height, width, scan_unfolding);
+}
+
+int r2dm_project_scans(const float* points, const int64_t* offsets, float* out, int32_t batch, int32_t height, int32_t width, int32_t out_width,
+                       int32_t scan_unfolding, float min_depth, float max_depth, int32_t apply_mask, int32_t layout, void* scratch,
+                       size_t scratch_bytes, void* stream) {
+    if (!offsets || !out || !scratch) return fail(1, "null argument");
+    if (batch < 1 || batch > 65535) return fail(1, "project: batch must be in [1, 65535]");
+    if (offsets[0] != 0) return fail(1, "project: offsets[0] must be 0, got %lld", (long long)offsets[0]);
+    for (int32_t b = 0; b < batch; ++b)
+        if (offsets[b + 1] < offsets[b]) return fail(1, "project: offsets decrease at scan %d (%lld after %lld)", b, (long long)offsets[b + 1], (long long)offsets[b]);
+    const int64_t total = offsets[batch];
+    if (const char* msg = project_geometry_error(total, batch, height, width)) return fail(1, "%s", msg);
+    if (total > 0 && !points) return fail(1, "null argument");
+    if ((uintptr_t)points & 15) return fail(1, "project: points must be 16-byte aligned");
+    if (out_width < 1 || out_width > width) return fail(1, "project: out_width must be in [1, width], got %d", out_width);
+    if (layout != 0 && layout != 1) return fail(1, "layout must be 0 ((B,6,H,W) xyzrdm) or 1 ((B,5,H,W) samples)");
+    if ((scan_unfolding != 0 && scan_unfolding != 1) || (apply_mask != 0 && apply_mask != 1)) return fail(1, "project: scan_unfolding and apply_mask are 0 or 1");
+    const size_t need = project_scratch_bytes(total, batch, height, width, scan_unfolding);
+    if (scratch_bytes < need) return fail(1, "scratch too small: %zu < %zu bytes", scratch_bytes, need);
+    if ((uintptr_t)scratch & 255) return fail(1, "scratch must be 256-byte aligned");
+    HIP_TRY(launch_project_scans(points, reinterpret_cast<const long long*>(offsets), out, batch, height, width, out_width, scan_unfolding, min_depth,
+                                 max_depth, apply_mask, layout, scratch, (hipStream_t)stream));
+    return 0;
+}
+
 static int g_single_kernel_pieces = 2;  // r2dm_conv2d_ring (per-op tests)
 
 int r2dm_set_conv_pieces(r2dm_handle* h, int32_t pieces) {
