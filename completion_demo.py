@@ -11,7 +11,8 @@ HuggingFace dataset lookup, and ``--out`` names the image.  The corruption masks
 Written: one PNG with a column per corruption -- input image (depth over reflectance), input bird's-eye view, completed image,
 completed bird's-eye view (r2dm_amd.render; the views coloured by height) -- and, next to it, ``completion.pt`` with ``x_in``,
 ``mask`` and ``x_out``.  There is no segmentation row: the reference colours its last two rows with RangeNet-53 labels, and those
-weights are not part of this package."""
+weights are not part of this package.  ``--out_scan FILE.bin`` (extension) also writes the completed scan -- the completion of
+the full input, the first column -- as a Velodyne file in scan order (r2dm_amd.pointcloud)."""
 import math
 from argparse import ArgumentParser
 from pathlib import Path
@@ -88,6 +89,11 @@ def main(args):
     state = args.out.parent / "completion.pt"
     torch.save({"x_in": x_in.cpu(), "mask": mask.cpu(), "x_out": x_out.cpu()}, state)
     print(f'Saved to "{args.out}" and "{state}"')
+    if args.out_scan is not None:
+        points, offsets = r2dm_amd.images_to_points(x_out[:1], lidar_utils, layout="model", order="scan")
+        args.out_scan.parent.mkdir(parents=True, exist_ok=True)
+        r2dm_amd.save_scans(points, offsets, [args.out_scan])
+        print(f'Saved {int(offsets[-1])} points to "{args.out_scan}"')
 
 
 def parser():
@@ -99,6 +105,7 @@ def parser():
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--scan", type=Path, required=True, help="a raw Velodyne scan (*.bin: float32 x, y, z, reflectance), instead of --sample_id")
     p.add_argument("--out", type=Path, default=None, help="the image (default: the reference's completion_T-..._r-..._j-....png)")
+    p.add_argument("--out_scan", type=Path, default=None, help="also write the completed scan (of the full input) as a Velodyne .bin file")
     return p
 
 

@@ -3,7 +3,9 @@
 the returned (S+1,B,2,H,W) stack, which is saved as tensors.  With ``--render_dir DIR`` the last frame is also rendered as the
 reference renders it (generate.py:44-63, r2dm_amd/render.py): ``samples_img.png``, the turbo-coloured range / reflectance
 images, and ``samples_bev.png``, the bird's-eye views; ``--render_frames`` adds ``frames/bev_%04d.png`` for every frame of the
-stack.  Still missing from the reference's script: the mp4 (no encoder here) and the antialiased 512-pixel resize of its frames."""
+stack.  With ``--points_dir DIR`` the final samples are also written as Velodyne scans ``DIR/samples_%04d.bin`` (fp32 [x, y, z,
+reflectance] rows in scan order, r2dm_amd.pointcloud), with ``--points_ply`` also as ``.ply`` coloured by the bird's-eye views' viridis
+height map.  Still missing from the reference's script: the mp4 (no encoder here) and the antialiased 512-pixel resize of its frames."""
 import argparse
 from pathlib import Path
 
@@ -25,6 +27,23 @@ def main(args):
     print(f"saved {tuple(xs.shape)} frames and {tuple(points.shape)} [depth,x,y,z,reflectance] maps to {args.output}")
     if args.render_dir is not None:
         render(xs, lidar_utils, args)
+    if args.points_dir is not None:
+        save_points(points, lidar_utils, args)
+
+
+def save_points(samples, lidar_utils, args):
+    """The final samples (B,5,H,W) as one Velodyne scan each, in scan order; with --points_ply the same cloud as a coloured PLY."""
+    from r2dm_amd.pointcloud import height_colors
+
+    args.points_dir.mkdir(parents=True, exist_ok=True)
+    cloud, offsets = r2dm_amd.images_to_points(samples, lidar_utils, layout="sample", order="scan")
+    names = [args.points_dir / f"samples_{k:04d}" for k in range(len(samples))]
+    r2dm_amd.save_scans(cloud, offsets, [n.with_suffix(".bin") for n in names])
+    if args.points_ply:
+        colors = height_colors(cloud, lidar_utils.max_depth)
+        for k, n in enumerate(names):
+            r2dm_amd.save_ply(cloud[offsets[k]:offsets[k + 1]], n.with_suffix(".ply"), colors[offsets[k]:offsets[k + 1]])
+    print(f"wrote {len(names)} scans ({int(offsets[-1])} points) to {args.points_dir}")
 
 
 def render(xs, lidar_utils, args):
@@ -67,6 +86,8 @@ if __name__ == "__main__":
     parser.add_argument("--render_dir", type=Path, default=None, help="also write samples_img.png and samples_bev.png there")
     parser.add_argument("--bev_size", type=int, default=800, help="side of a bird's-eye view in pixels")
     parser.add_argument("--render_frames", action="store_true", help="with --render_dir: frames/bev_%%04d.png for every frame of the stack")
+    parser.add_argument("--points_dir", type=Path, default=None, help="also write the final samples as Velodyne scans samples_%%04d.bin there")
+    parser.add_argument("--points_ply", action="store_true", help="with --points_dir: also samples_%%04d.ply, coloured by height")
     args = parser.parse_args()
     args.device = torch.device(args.device)
     main(args)

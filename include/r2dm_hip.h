@@ -230,6 +230,28 @@ int r2dm_project_scans(const float* points, const int64_t* offsets, float* out, 
                        int32_t out_width, int32_t scan_unfolding, float min_depth, float max_depth, int32_t apply_mask, int32_t layout,
                        void* scratch, size_t scratch_bytes, void* stream);
 
+/* -- range images to point clouds: the inverse of r2dm_project_scans (Velodyne .bin rows out of samples) -----------------------
+ * r2dm_unproject: a batch of range images -> the batch's valid pixels as [x, y, z, reflectance] rows, compacted into ONE buffer:
+ *    points (batch*height*width,4) fp32 capacity in device memory (16-byte aligned), scan b = rows offsets[b] .. offsets[b + 1] - 1;
+ *    offsets = batch + 1 int64 values written to DEVICE memory (offsets[batch] = the number of points; read them after the stream
+ *    has run); index (batch*height*width) int32 or NULL: row i's pixel h*width + w inside its scan.
+ *    Order, a part of the contract: position p in [0, height*width) of a scan is pixel h = p / width and
+ *    w = p % width (row_start = NULL: image order) or w = (row_start[h] - p % width) mod width (scan order: row_start = height int32
+ *    values in device memory, the last column of row h whose azimuth is >= 0; rows top to bottom, the azimuth rising from 0 inside a
+ *    row, so that a ring ends in the 4th quadrant and the next starts in the 1st -- the delimiter r2dm_project_scans counts under
+ *    scan_unfolding); the valid positions keep that order.  The same bits on every call: no atomics, no block waits for another.
+ *    layout 0: src (batch,2,height,width), the model's sample in [-1,1]; the point is r2dm_lidar_postprocess_fmt's, bit for bit
+ *    (ray_angles (2,height,width), min_depth, max_depth, depth_format as there); valid: inside the depth window (that entry's xyz
+ *    mask is 1), keep_min < depth < keep_max, x, y, z finite.  layout 1: src (batch,5,height,width) [depth, x, y, z, reflectance]
+ *    (r2dm_lidar_postprocess's output, r2dm_project_scans' layout 1), values copied; valid: keep_min < depth < keep_max, x, y, z
+ *    finite; ray_angles, min_depth, max_depth, depth_format unused.  NaN never compares true: such a pixel is dropped.
+ *    scratch: r2dm_unproject_scratch_bytes() of device memory (0: geometry refused), 256-byte aligned.  No host synchronisation.
+ *    Limits: batch <= 65535; fewer than 2^31 pixels over the batch. */
+size_t r2dm_unproject_scratch_bytes(int32_t batch, int32_t height, int32_t width);
+int r2dm_unproject(const float* src, int32_t layout, const float* ray_angles, const int32_t* row_start, float* points, int32_t* index,
+                   int64_t* offsets, int32_t batch, int32_t height, int32_t width, float min_depth, float max_depth,
+                   int32_t depth_format, float keep_min, float keep_max, void* scratch, size_t scratch_bytes, void* stream);
+
 /* -- single kernels, exported for per-op parity tests against the oracle -------------------- */
 /* ops.Conv2d(ring) 3x3 / 1x1 (models/ops.py:149-173) with optional fused GroupNorm-affine(+SiLU)
  * prologue (aff: (B,Cin,2) or NULL; prologue 0 none, 1 affine, 2 affine+SiLU) and optional

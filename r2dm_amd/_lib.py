@@ -112,6 +112,9 @@ SIGNATURES = {
     "r2dm_project_scratch_bytes": (c_size_t, [c_int64, c_int32, c_int32, c_int32, c_int32]),
     "r2dm_project_scans": (c_int32, [_P, POINTER(c_int64), _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_int32, c_int32,
                                      _P, c_size_t, _P]),
+    "r2dm_unproject_scratch_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "r2dm_unproject": (c_int32, [_P, c_int32, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_float, c_float, c_int32, c_float, c_float,
+                                 _P, c_size_t, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -303,4 +303,10 @@ size_t project_scratch_bytes(long long total, int B, int H, int W, int unfold);
 hipError_t launch_project_scans(const float* points, const long long* offsets, float* out, int B, int H, int W, int Wo, int unfold, float min_depth,
                                 float max_depth, int apply_mask, int layout, void* scratch, hipStream_t s);
 
+// range images -> point clouds (pointcloud.hip): layout 0 (B,2,H,W) model samples, 1 (B,5,H,W) post-processed; row_start nullptr = image order
+size_t unproject_scratch_bytes(int B, int H, int W);
+hipError_t launch_unproject(const float* src, int layout, const float* angles, const int* row_start, float* points, int* index, long long* offsets,
+                            int B, int H, int W, float min_depth, float max_depth, int depth_format, float keep_min, float keep_max, void* scratch,
+                            hipStream_t s);
+
 }  // namespace r2dm

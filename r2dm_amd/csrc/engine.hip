@@ -1374,6 +1374,34 @@ int r2dm_project_scans(const float* points, const int64_t* offsets, float* out, 
     return 0;
 }
 
+static const char* unproject_geometry_error(int32_t batch, int32_t H, int32_t W) {
+    if (batch < 1 || batch > 65535) return "unproject: batch must be in [1, 65535]";
+    if (H < 1 || W < 1 || (int64_t)batch * H * W >= (1LL << 31)) return "unproject: the images must have 1 to 2^31 - 1 pixels over the batch";
+    return nullptr;
+}
+
+size_t r2dm_unproject_scratch_bytes(int32_t batch, int32_t height, int32_t width) {
+    return unproject_geometry_error(batch, height, width) ? 0 : unproject_scratch_bytes(batch, height, width);
+}
+
+int r2dm_unproject(const float* src, int32_t layout, const float* ray_angles, const int32_t* row_start, float* points, int32_t* index,
+                   int64_t* offsets, int32_t batch, int32_t height, int32_t width, float min_depth, float max_depth, int32_t depth_format,
+                   float keep_min, float keep_max, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!src || !points || !offsets || !scratch) return fail(1, "null argument");
+    if (layout != 0 && layout != 1) return fail(1, "layout must be 0 ((B,2,H,W) model samples) or 1 ((B,5,H,W) post-processed samples)");
+    if (layout == 0 && !ray_angles) return fail(1, "unproject: layout 0 needs ray_angles (null argument)");
+    if (depth_format < 0 || depth_format > 2) return fail(1, "depth_format must be 0 (log_depth), 1 (inverse_depth) or 2 (depth)");
+    if (const char* msg = unproject_geometry_error(batch, height, width)) return fail(1, "%s", msg);
+    if ((uintptr_t)points & 15) return fail(1, "unproject: points must be 16-byte aligned");
+    if ((uintptr_t)offsets & 7) return fail(1, "unproject: offsets must be 8-byte aligned");
+    const size_t need = unproject_scratch_bytes(batch, height, width);
+    if (scratch_bytes < need) return fail(1, "scratch too small: %zu < %zu bytes", scratch_bytes, need);
+    if ((uintptr_t)scratch & 255) return fail(1, "scratch must be 256-byte aligned");
+    HIP_TRY(launch_unproject(src, layout, ray_angles, row_start, points, index, reinterpret_cast<long long*>(offsets), batch, height, width, min_depth,
+                             max_depth, depth_format, keep_min, keep_max, scratch, (hipStream_t)stream));
+    return 0;
+}
+
 static int g_single_kernel_pieces = 2;  // r2dm_conv2d_ring (per-op tests)
 
 int r2dm_set_conv_pieces(r2dm_handle* h, int32_t pieces) {

@@ -9,7 +9,9 @@ Precision: fp32 parity by default (``--precision fp32``: 22-bit split fp16 opera
 ``fp32-bf16x3``: three bf16 pieces, fp32 operand range).  The reference runs this script under fp16 autocast (:70,
 utils/option.py:49); ``--precision fp16`` is that bulk mode here: one fp16 product per MAC, fp32 accumulation and tensors,
 its own tolerance class (tests/test_hip_fp16_mode.py).
-``--max-batch`` / the batch size fix the layer tilings: per-seed results are bit-reproducible for a fixed batch size only."""
+``--max-batch`` / the batch size fix the layer tilings: per-seed results are bit-reproducible for a fixed batch size only.
+``--points_dir DIR`` (extension) also writes every sample as a Velodyne scan ``DIR/samples_{seed:010d}.bin``: the pixels inside the
+checkpoint's depth window as fp32 [x, y, z, reflectance] rows in scan order (r2dm_amd.pointcloud)."""
 import os
 from argparse import ArgumentParser
 from pathlib import Path
@@ -40,8 +42,11 @@ def sample(args):
     broadcast_packed_weights(ddpm.model, device, src=0)
 
     save_dir = Path(args.output_dir)
+    points_dir = None if args.points_dir is None else Path(args.points_dir)
     if rank == 0:
         save_dir.mkdir(parents=True, exist_ok=True)
+        if points_dir is not None:
+            points_dir.mkdir(parents=True, exist_ok=True)
     if world > 1:
         td.barrier()
 
@@ -53,6 +58,9 @@ def sample(args):
         samples = lidar_utils.postprocess(samples)  # denormalize -> revert_depth -> to_xyz -> concat, one kernel
         for seed, s in zip(seeds, samples):
             torch.save(s.clone(), save_dir / f"samples_{seed:010d}.pth")
+        if points_dir is not None:
+            points, offsets = r2dm_amd.images_to_points(samples, lidar_utils, layout="sample", order="scan")
+            r2dm_amd.save_scans(points, offsets, [points_dir / f"samples_{seed:010d}.bin" for seed in seeds])
     if world > 1:
         td.barrier()
         td.destroy_process_group()
@@ -68,4 +76,5 @@ if __name__ == "__main__":
     parser.add_argument("--mode", choices=["ddpm", "ddim"], default="ddpm")
     parser.add_argument("--precision", choices=["fp32", "fp32-bf16x3", "fp16"], default="fp32")
     parser.add_argument("--max-batch", type=int, default=0, help="extension: the batch size the layer tilings are planned for (default: --batch_size)")
+    parser.add_argument("--points_dir", type=str, default=None, help="extension: also write every sample as a Velodyne scan samples_<seed>.bin there")
     sample(parser.parse_args())
