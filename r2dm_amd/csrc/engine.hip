@@ -1,29 +1,16 @@
-// C ABI (include/r2dm_hip.h) and the U-Net execution plan.
-//
-// r2dm_unet_forward replaces EfficientUNet.forward (/root/reference/models/efficient_unet.py:269-295):
-// it walks the eight U-Net stages and enqueues the HIP kernels of this library on the caller's
-// stream.  Nothing here allocates or synchronises: weights live in a caller-owned blob, activations
-// in a caller-owned workspace carved by a deterministic first-fit arena (the same walk run "dry"
-// yields r2dm_workspace_bytes).
-#include <math.h>
+// The model's C ABI (include/r2dm_hip.h): create / bind / load / workspace / forward / range guard / profiling.  The plan is built in plan.hip,
+// the forward walk lives in forward.hip; the stand-alone operators and the single-kernel test entries are in ops_abi.hip and kernel_abi.hip.
 #include <stdarg.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include <algorithm>
-#include <map>
-#include <string>
-#include <vector>
 
-#include "../../include/r2dm_hip.h"
-#include "common.h"
+#include "engine.h"
 
 using namespace r2dm;
 
-namespace {
+namespace r2dm {
 
-thread_local char g_err[512] = "";
+static thread_local char g_err[512] = "";  // what r2dm_last_error returns: the only definition, written by every file's fail()
 
 int fail(int code, const char* fmt, ...) {
     va_list ap;
@@ -33,1005 +20,9 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
-#define HIP_TRY(expr)                                                                             \
-    do {                                                                                          \
-        hipError_t _e = (expr);                                                                   \
-        if (_e != hipSuccess) return fail(2, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
+int g_single_kernel_pieces = 2;  // r2dm_conv2d_ring (per-op tests)
 
-static const bool g_debug_sync = getenv("R2DM_DEBUG_SYNC") != nullptr;  // fault hunting: wait for and name every launch (read once)
-
-constexpr size_t kAlign = 256;
-inline size_t align_up(size_t v, size_t a = kAlign) { return (v + a - 1) / a * a; }
-
-// ---- plan -----------------------------------------------------------------------------------
-struct ConvLayer {
-    int cin = 0, cout = 0, taps = 0, co_tile = 0, cin_pad = 0, algo = 0;
-    int src_cin = 0, src_off = 0;  // packs input channels [src_off, src_off + cin) of a (cout, src_cin, k, k) tensor
-    size_t w = 0, b = 0;  // blob offsets in floats
-    // second packing of the same weights for ALGO_F16X2 (conv_f16x2.hip): the residual blocks' 3x3 convolutions, whose
-    // input is GroupNorm-normalised; selected per launch by the handle's precision mode (r2dm_set_conv_pieces)
-    bool f2 = false;
-    int f2_cot = 64;  // output channels per tile of that packing: 64 or 128 (conv_f16x2_pick_co_tile)
-    int f2_rows = 4;  // ... and its image rows: 4, or 8 (the one-accumulator 64 x 8 tile: its own packing, residual planes at their true scale)
-    size_t w_f2 = 0, ws_f2 = 0;  // ws_*: two floats -- [0] max|w| (packer scratch), [1] inverse of the packer's power-of-two weight scale
-    // ... and for ALGO_P1F16 (proj_f16x2.hip): the 1x1 projections of the attention block
-    bool p1 = false;
-    size_t w_p1 = 0, ws_p1 = 0;
-    // ... and, for a stage's down-sampling 3x3 convolution, the (Cout, 9 Cin) matrix of the down-sampling GEMM (FIR first, then a 1x1 convolution over the nine
-    // filtered planes at the output resolution: resample.hip down_planes_kernel + proj_f16x2.hip), columns (ky, kx, ci)
-    bool dg = false;
-    size_t w_dg = 0, ws_dg = 0;
-    size_t packed_elems() const { return (size_t)conv_packed_floats(algo, cin, cout, taps, co_tile, cin_pad); }
-};
-
-struct ResLayer {
-    int cin = 0, cout = 0;
-    size_t g1 = 0, b1 = 0, scale = 0;
-    int ada_row = 0;  // first row of this block's [scale|shift] projection in the packed matrix
-    ConvLayer conv1, conv2, skip;
-    bool has_skip = false;
-};
-
-struct AttnLayer {
-    int C = 0;
-    size_t gamma = 0, beta = 0, scale = 0;
-    ConvLayer qkv, proj;
-};
-
-struct Stage {
-    std::string name;
-    int cin = 0, cout = 0;
-    bool down = false, up = false, attn = false;
-    ConvLayer dconv, uconv;
-    bool out_tracked = false;  // the stage's last convolution records max|output| in the range flag (its consumer is the next
-                               // stage's down-sampling convolution on the f16x2 path)
-    // the 1x1 skip convolution of an up stage's first block reads the raw concatenation [previous up stage | down-path skip
-    // tensor]: it runs on the fp16 matrix pipe (proj_f16x2.hip) if BOTH tensors' producers record max|output|
-    bool track_final = false;     // whichever convolution produces the stage's output records max|output|
-    bool skip_in_bounded = false;  // ... which every producer of this stage's input does
-    std::vector<ResLayer> res;
-    AttnLayer at;
-};
-
-enum SlotKind { SLOT_RAW, SLOT_CONV };
-struct Slot {
-    std::string key;
-    int64_t numel;
-    SlotKind kind;
-    size_t off;  // destination offset in floats
-    ConvLayer conv;  // for SLOT_CONV
-};
-
-}  // namespace
-
-struct r2dm_handle {
-    r2dm_config cfg;
-    int device = 0;
-    std::vector<Slot> slots;
-    size_t blob_floats = 0;
-    float* blob = nullptr;
-    Stage stages[8];
-    ConvLayer in_conv, out_conv;
-    // in_conv over cat([x, cenc]) = conv(x, W[:, :C]) + [conv(cenc, W[:, C:]) + bias]: the bracket is constant over steps
-    // and batch (efficient_unet.py:278-281), computed once per weight load into `cmap` (Cout, H, W)
-    ConvLayer in_conv_c;
-    size_t cmap = 0, zero_bias = 0;
-    bool cmap_ready = false;
-    // split of the fp32 operands of the convolutions on the matrix pipe (r2dm_set_conv_pieces): 2 = fp16 + scaled fp16
-    // residual (ALGO_F16X2 / ALGO_P1F16) wherever a second packing exists, three bf16 pieces elsewhere; 3 = three bf16 pieces
-    // everywhere; 1 = the kernels of mode 2 with the fp16 piece alone (one product per MAC: reduced precision, bulk sampling)
-    int conv_pieces = 2;
-    // R2DM_DOWN_GEMM=0 (read once, at r2dm_create): the down stages keep Conv3x3 at the finer resolution + fir_down2, as until round 6 (A/B, the parity test)
-    bool down_gemm = true;
-    bool f16_path() const { return conv_pieces != 3; }  // operands go through fp16: their range is guarded
-    bool flags_fresh = false;  // the blob's range flags have been cleared since the last r2dm_bind_blob (first load does it)
-    size_t range_flag = 0;  // blob slot (RANGE_SITES pairs of ints, ALGO_F16X2): [0] != 0: a weight outside the fp16 range; [2 k + 1]: float
-                            // bits of the largest operand bound site k has recorded since the last r2dm_check_range.  A SITE is one guarded
-                            // producer of a forward, in walk order (round 6: one pair per site instead of one for the whole forward, so that
-                            // r2dm_range_sites can say WHICH layer ran how close to 65504 -- python -m r2dm_amd.check); site 0: the test hook
-                            // and anything beyond the table.  Kernels only ever atomicMax `pair + 1`.
-    static constexpr int RANGE_SITES = 256;
-    std::vector<std::string> site_names;  // labels of the last real walk (index = site)
-    float site_bounds[RANGE_SITES] = {};  // what the last r2dm_check_range read (before it reset the device copy)
-    int sites_read = 0;
-    size_t w1 = 0, b1 = 0, w2 = 0, b2 = 0, freqs = 0, cenc = 0, ada_w = 0, ada_b = 0;
-    int ada_rows = 0;
-    std::map<int, size_t> ws_cache;
-    // optional in-stream timing of the dominant kernel class (r2dm_profile_*)
-    bool prof_on = false;
-    std::vector<hipEvent_t> prof_ev;  // pairs
-    size_t prof_used = 0;
-    double prof_flop = 0.0;
-    std::vector<int> prof_cls;        // per bracketed launch: 0 = f16x2, 1 = bf16x3, 2 = fp32 MFMA / direct
-    std::vector<double> prof_lflop;   // ... and its algorithmic flops
-
-    size_t take(size_t floats) {
-        const size_t off = blob_floats;
-        blob_floats += align_up(floats * sizeof(float)) / sizeof(float);
-        return off;
-    }
-    size_t raw(const std::string& key, int64_t numel) {
-        const size_t off = take(numel);
-        slots.push_back({key, numel, SLOT_RAW, off, {}});
-        return off;
-    }
-    void raw_at(const std::string& key, int64_t numel, size_t off) { slots.push_back({key, numel, SLOT_RAW, off, {}}); }
-    // the weight-only half of a convolution whose source tensor is shared with another layer (no bias slot)
-    // few_in: the slice runs at (H, W) with few input channels -- the direct kernel if the shape fits (conv_direct.hip)
-    ConvLayer conv_slice(const std::string& wkey, int src_cin, int src_off, int cin, int cout, int ksize, long px_batch,
-                         int H = 0, int W = 0) {
-        ConvLayer L;
-        L.cin = cin;
-        L.cout = cout;
-        L.taps = ksize * ksize;
-        static const bool force_f32 = [] {
-            const char* e = getenv("R2DM_CONV_ALGO");
-            return e && e[0] == 'f';
-        }();
-        L.algo = (!force_f32 && H > 0 && conv_few_in_supported(cin, cout, L.taps, H, W)) ? ALGO_DIRECT : ALGO_F32;
-        L.co_tile = conv_pick_co_tile(cout, L.taps, px_batch);
-        L.cin_pad = L.algo == ALGO_DIRECT ? cin : conv_cin_pad(cin, L.taps, L.co_tile);
-        L.src_cin = src_cin;
-        L.src_off = src_off;
-        L.w = take(L.packed_elems());
-        slots.push_back({wkey, (int64_t)cout * src_cin * L.taps, SLOT_CONV, L.w, L});
-        return L;
-    }
-    // H, W > 0: a convolution behind a GroupNorm at that resolution -- gets the ALGO_F16X2 packing too if the shape fits
-    // down: a stage's down-sampling convolution (followed by fir_down2) -- gets the down-sampling GEMM's packing too if the geometry fits its tiles
-    ConvLayer conv(const std::string& wkey, const std::string& bkey, int cin, int cout, int ksize, long px_batch, int H = 0, int W = 0, bool down = false) {
-        ConvLayer L;
-        L.cin = cin;
-        L.cout = cout;
-        L.taps = ksize * ksize;
-        L.algo = conv_pick_algo(cin, cout, L.taps);
-        L.co_tile = L.algo == ALGO_BF16X3 ? conv_bf16x3_co_tile(cin, cout, px_batch) : conv_pick_co_tile(cout, L.taps, px_batch);
-        L.cin_pad = L.algo != ALGO_F32 ? cin : conv_cin_pad(cin, L.taps, L.co_tile);
-        L.w = take(L.packed_elems());
-        // (at least half a wave of tiles per CU at the planned batch: below that the persistent kernel leaves CUs idle)
-        static const long f2_min_tiles = [] {  // (R2DM_F2_MIN_TILES: experiments)
-            const char* e = getenv("R2DM_F2_MIN_TILES");
-            return e ? atol(e) : 128L;
-        }();
-        if (L.algo == ALGO_BF16X3 && H > 0 && conv_f16x2_supported(cin, cout, L.taps, H, W) && (px_batch / 256) * (cout / 64) >= f2_min_tiles) {
-            L.f2 = true;
-            L.f2_cot = conv_f16x2_pick_co_tile(cin, cout, H, W, px_batch, &L.f2_rows);
-            L.w_f2 = take((size_t)conv_f16x2_packed_floats(cin, cout));
-            L.ws_f2 = take(2);
-        }
-        if (L.algo == ALGO_F32 && H > 0 && proj_f16x2_supported(cin, cout, L.taps, H, W)) {
-            L.p1 = true;
-            L.w_p1 = take((size_t)proj_f16x2_packed_floats(cin, cout));
-            L.ws_p1 = take(2);
-        }
-        // (from the planned geometry alone, never from a call's batch: a sample's bits must not depend on the batch it is part of)
-        if (down && down_gemm && L.taps == 9 && H > 0 && down_planes_supported(H, W) && proj_f16x2_supported(9 * cin, cout, 1, H / 2, W / 2)) {
-            L.dg = true;
-            L.w_dg = take((size_t)proj_f16x2_packed_floats(9 * cin, cout));
-            L.ws_dg = take(2);
-        }
-        slots.push_back({wkey, (int64_t)cout * cin * L.taps, SLOT_CONV, L.w, L});
-        L.b = raw(bkey, cout);
-        return L;
-    }
-};
-
-namespace {
-
-void build_plan(r2dm_handle* h) {
-    const r2dm_config& c = h->cfg;
-    const int C0 = c.base_channels, T = c.temb_channels;
-    int Cl[5] = {C0, C0 * c.channel_multiplier[0], C0 * c.channel_multiplier[1], C0 * c.channel_multiplier[2],
-                 C0 * c.channel_multiplier[3]};
-    const long px1 = (long)c.height * c.width * c.max_batch;
-
-    h->range_flag = h->take(2 * r2dm_handle::RANGE_SITES);
-    if (c.coord_channels > 0) h->cenc = h->raw("__cenc", (int64_t)c.coord_channels * c.height * c.width);
-    h->freqs = h->raw("__sin_freqs", C0 / 2);
-    h->w1 = h->raw("time_embedding.1.weight", (int64_t)T * C0);
-    h->b1 = h->raw("time_embedding.1.bias", T);
-    h->w2 = h->raw("time_embedding.3.weight", (int64_t)T * T);
-    h->b2 = h->raw("time_embedding.3.bias", T);
-    if (c.coord_channels > 0) {
-        const int cin = c.in_channels + c.coord_channels;
-        h->in_conv = h->conv_slice("in_conv.weight", cin, 0, c.in_channels, C0, 3, px1, c.height, c.width);
-        h->in_conv_c = h->conv_slice("in_conv.weight", cin, c.in_channels, c.coord_channels, C0, 3, (long)c.height * c.width);
-        h->in_conv_c.b = h->raw("in_conv.bias", C0);
-        h->zero_bias = h->take(C0);
-        h->in_conv.b = h->zero_bias;
-        h->cmap = h->take((size_t)C0 * c.height * c.width);
-    } else {
-        h->in_conv = h->conv("in_conv.weight", "in_conv.bias", c.in_channels, C0, 3, px1);
-    }
-
-    struct Def { const char* name; int cin, cout, n, level; bool down, up, attn; };
-    const Def defs[8] = {
-        {"d_block1", Cl[0], Cl[1], c.num_residual_blocks[0], 0, false, false, false},
-        {"d_block2", Cl[1], Cl[2], c.num_residual_blocks[1], 1, true, false, false},
-        {"d_block3", Cl[2], Cl[3], c.num_residual_blocks[2], 2, true, false, false},
-        {"d_block4", Cl[3], Cl[4], c.num_residual_blocks[3], 3, true, false, true},
-        {"u_block4", Cl[4], Cl[3], c.num_residual_blocks[3], 3, false, true, true},
-        {"u_block3", 2 * Cl[3], Cl[2], c.num_residual_blocks[2], 2, false, true, false},
-        {"u_block2", 2 * Cl[2], Cl[1], c.num_residual_blocks[1], 1, false, true, false},
-        {"u_block1", 2 * Cl[1], Cl[0], c.num_residual_blocks[0], 0, false, false, false},
-    };
-    // count AdaGN rows first so the projection matrix is one contiguous [rows][T] block
-    int rows = 0;
-    for (const Def& d : defs) rows += d.n * 2 * d.cout;
-    h->ada_rows = rows;
-    h->ada_w = h->take((size_t)rows * T);
-    h->ada_b = h->take(rows);
-
-    int row = 0;
-    for (int s = 0; s < 8; ++s) {
-        const Def& d = defs[s];
-        Stage& st = h->stages[s];
-        st.name = d.name;
-        st.cin = d.cin;
-        st.cout = d.cout;
-        st.down = d.down;
-        st.up = d.up;
-        st.attn = d.attn;
-        const long px = px1 >> (2 * d.level);  // pixels*batch at the level the residual blocks run on
-        const std::string p = std::string(d.name) + ".";
-        if (d.down)  // the stage's first conv runs at the resolution above (efficient_unet.py:132-136)
-            st.dconv = h->conv(p + "downsample.0.weight", p + "downsample.0.bias", d.cin, d.cout, 3, px << 2, c.height >> (d.level - 1), c.width >> (d.level - 1), /*down=*/true);
-        for (int i = 0; i < d.n; ++i) {
-            ResLayer r;
-            const std::string q = p + "residual_blocks." + std::to_string(i) + ".";
-            r.cin = (i != 0 || d.down) ? d.cout : d.cin;
-            r.cout = d.cout;
-            r.scale = h->raw(q + "scale", 1);
-            r.g1 = h->raw(q + "norm1.weight", r.cin);
-            r.b1 = h->raw(q + "norm1.bias", r.cin);
-            r.conv1 = h->conv(q + "conv1.weight", q + "conv1.bias", r.cin, r.cout, 3, px, c.height >> d.level, c.width >> d.level);
-            r.ada_row = row;
-            h->raw_at(q + "norm2.proj.1.weight", (int64_t)2 * r.cout * T, h->ada_w + (size_t)row * T);
-            h->raw_at(q + "norm2.proj.1.bias", 2 * r.cout, h->ada_b + row);
-            row += 2 * r.cout;
-            r.conv2 = h->conv(q + "conv2.weight", q + "conv2.bias", r.cout, r.cout, 3, px, c.height >> d.level, c.width >> d.level);
-            r.has_skip = r.cin != r.cout;
-            if (r.has_skip) r.skip = h->conv(q + "skip.weight", q + "skip.bias", r.cin, r.cout, 1, px, c.height >> d.level, c.width >> d.level);
-            st.res.push_back(r);
-        }
-        if (d.attn) {
-            const std::string q = p + "self_attn_block.";
-            st.at.C = d.cout;
-            st.at.scale = h->raw(q + "scale", 1);
-            st.at.gamma = h->raw(q + "norm.weight", d.cout);
-            st.at.beta = h->raw(q + "norm.bias", d.cout);
-            st.at.qkv = h->conv(q + "attn.in_proj_weight", q + "attn.in_proj_bias", d.cout, 3 * d.cout, 1, px, c.height >> d.level, c.width >> d.level);
-            st.at.proj = h->conv(q + "attn.out_proj.weight", q + "attn.out_proj.bias", d.cout, d.cout, 1, px, c.height >> d.level, c.width >> d.level);
-        }
-        if (d.up)  // upsample then conv at the finer resolution (efficient_unet.py:169-173)
-            st.uconv = h->conv(p + "upsample.1.weight", p + "upsample.1.bias", d.cout, d.cout, 3, px << 2, c.height >> (d.level - 1), c.width >> (d.level - 1));
-    }
-    h->out_conv = h->conv("out_conv.weight", "out_conv.bias", C0, c.out_channels, 3, px1);
-    // a down-sampling convolution on the f16x2 path needs its input's range guarded: its producer -- the previous stage's
-    // last residual block, second convolution, itself on the f16x2 path (wide epilogue) and no attention block behind it --
-    // records max|output|
-    for (int s = 0; s + 1 < 8; ++s) {
-        Stage& a = h->stages[s];
-        const Stage& b = h->stages[s + 1];
-        a.out_tracked = b.down && (b.dconv.f2 || b.dconv.dg) && !a.attn && !a.up && !a.res.empty() && a.res.back().conv2.f2;
-    }
-    // up stages: input of stage 4 = output of stage 3; of stage 4 + k (k = 1..3) = [output of stage 3 + k | output of stage 3 - k]
-    for (int s = 4; s < 8; ++s) {
-        Stage& a = h->stages[s];
-        if (a.res.empty() || !a.res[0].has_skip || !a.res[0].skip.p1) continue;
-        a.skip_in_bounded = true;
-        h->stages[s - 1].track_final = true;
-        if (s > 4) h->stages[7 - s].track_final = true;
-    }
-}
-
-// ---- workspace arena -------------------------------------------------------------------------
-struct Arena {
-    char* base;
-    size_t cap;
-    bool dry;
-    size_t peak = 0;
-    struct Blk { size_t off, size; bool used; };
-    std::vector<Blk> blks;
-    bool overflow = false;
-
-    void* alloc(size_t bytes) {
-        bytes = align_up(bytes ? bytes : 1);
-        for (size_t i = 0; i < blks.size(); ++i) {
-            if (!blks[i].used && blks[i].size >= bytes) {
-                if (blks[i].size > bytes) {
-                    Blk rest{blks[i].off + bytes, blks[i].size - bytes, false};
-                    blks[i].size = bytes;
-                    blks.insert(blks.begin() + i + 1, rest);
-                }
-                blks[i].used = true;
-                return base + blks[i].off;
-            }
-        }
-        size_t end = blks.empty() ? 0 : blks.back().off + blks.back().size;
-        if (!blks.empty() && !blks.back().used) {  // grow the trailing free block
-            end = blks.back().off;
-            blks.pop_back();
-        }
-        blks.push_back({end, bytes, true});
-        if (end + bytes > peak) peak = end + bytes;
-        if (!dry && end + bytes > cap) overflow = true;
-        return base + end;
-    }
-    void release(const void* p) {
-        const size_t off = (const char*)p - base;
-        for (size_t i = 0; i < blks.size(); ++i) {
-            if (blks[i].off == off && blks[i].used) {
-                blks[i].used = false;
-                if (i + 1 < blks.size() && !blks[i + 1].used) {
-                    blks[i].size += blks[i + 1].size;
-                    blks.erase(blks.begin() + i + 1);
-                }
-                if (i > 0 && !blks[i - 1].used) {
-                    blks[i - 1].size += blks[i].size;
-                    blks.erase(blks.begin() + i);
-                }
-                return;
-            }
-        }
-    }
-};
-
-struct Tensor {
-    float* p = nullptr;
-    int C = 0, H = 0, W = 0;
-    bool f16 = false;  // stored as fp16 (the one-plane mode's activation storage: ConvParams::x16 / y16); `p` stays typed float*
-    long bs() const { return (long)C * H * W; }  // batch stride in ELEMENTS
-    size_t bytes(int B) const { return (size_t)B * C * H * W * (f16 ? 2 : sizeof(float)); }
-};
-
-inline Src src1(const Tensor& t) { return Src{t.p, nullptr, t.C, 0, t.bs(), 0}; }
-inline Src src2(const Tensor& a, const Tensor& b) { return Src{a.p, b.p, a.C, b.C, a.bs(), b.bs()}; }
-
-struct Ctx {
-    r2dm_handle* h;
-    Arena* ar;
-    hipStream_t st;
-    int B;
-    const float* proj;  // [B][ada_rows]
-    double* gn_partial;
-    hipError_t err = hipSuccess;
-    const char* where = "";
-    int f2_launches = 0;  // conv_f16x2 launches of this forward so far (odd ones walk their tiles backwards: ConvParams::reverse)
-    int last_reverse = -1;  // direction of the last conv_f16x2 launch (-1: none yet / another kernel)
-    // the fp16 operand range guard, one slot per guarded producer ("site") of the forward, in walk order; `ctx`: which layer the walk is in
-    int n_sites = 0;
-    std::string ctx;
-    int* range_site(const char* what) {
-        static const bool shared = getenv("R2DM_RANGE_SHARED") != nullptr;  // (probe: one slot for the whole forward, as until round 5 -- profiles/r06_range_slots.txt)
-        const int k = shared ? 0 : n_sites + 1 < r2dm_handle::RANGE_SITES ? ++n_sites : 0;  // (beyond the table: the shared slot 0 -- still guarded, just not named)
-        if ((int)h->site_names.size() <= k) h->site_names.resize(k + 1);
-        h->site_names[k] = ctx.empty() ? std::string(what) : ctx + ": " + what;
-        return (int*)blob(h->range_flag) + 2 * k;
-    }
-
-    // (once the arena has handed out a pointer beyond the caller's workspace NOTHING more is launched -- the walk goes on
-    // dry, so `peak` still comes out right for the error message -- instead of enqueueing kernels that write outside the workspace)
-    bool dry() const { return ar->dry || ar->overflow; }
-    void note(hipError_t e, const char* w) {
-        const bool debug_sync = g_debug_sync;  // fault hunting: wait for and name every launch
-        if (debug_sync && e == hipSuccess && !dry()) {
-            fprintf(stderr, "[r2dm] %s ...", w);
-            fflush(stderr);
-            e = hipStreamSynchronize(st);
-            fprintf(stderr, " %s\n", e == hipSuccess ? "ok" : hipGetErrorString(e));
-        }
-        if (e != hipSuccess && err == hipSuccess) {
-            err = e;
-            where = w;
-        }
-    }
-    const float* blob(size_t off) const { return h->blob + off; }
-
-    Tensor make(int C, int H, int W, bool f16 = false) {
-        Tensor t;
-        t.C = C;
-        t.H = H;
-        t.W = W;
-        t.f16 = f16;
-        t.p = (float*)ar->alloc(t.bytes(B));
-        return t;
-    }
-    // fp16 storage of EVERY activation of the two full-resolution levels (round 6; the one-plane mode = the reference's fp16 autocast, which stores its
-    // activations as fp16: /root/reference/sample_and_save.py:45,70): those levels hold 92 % of a forward's activation bytes and their launches are the ones next
-    // to the HBM roof; levels 3 and 4 (attention, 1 x 1 projections with residuals and statistics) stay fp32.  all16: decided once per forward (run_forward).
-    bool all16 = false;
-    bool lvl16(int Hres) const { return all16 && 2 * Hres >= h->cfg.height; }
-    void drop(const Tensor& t) { ar->release(t.p); }
-
-    // Fused statistics: a convolution whose output feeds a GroupNorm leaves per-(sample, group) partial sums in a
-    // Sink from its epilogue; the GroupNorm then only runs the finalize kernel (no extra pass over the tensor).
-    struct Sink {
-        double* p = nullptr;
-        int C = 0, cpg = 0, slots = 0;  // C: channels of the normalised (possibly concatenated) tensor
-        bool incomplete = false;        // a producer could not emit its share: the consumer runs the streaming pass instead
-        explicit operator bool() const { return p != nullptr && !incomplete; }
-    };
-    Sink make_sink(int C_total, int H, int W) {
-        Sink k;
-        const int G = h->cfg.gn_num_groups;
-        const int cpg = C_total / G;
-        // the epilogue reduction (conv_epilogue.h) merges whole 8-channel blocks of ONE wave: groups must be 8, 16, 32 or
-        // 64 channels so that they never straddle waves; anything else takes the separate streaming pass
-        if (C_total % G || cpg < 8 || cpg > 64 || (cpg & (cpg - 1))) return k;
-        k.C = C_total;
-        k.cpg = cpg;
-        k.slots = conv_stat_slots(H, W);
-        k.p = (double*)ar->alloc((size_t)B * G * k.slots * 2 * sizeof(double));
-        return k;
-    }
-    void drop_sink(Sink& k) {
-        if (k.p) ar->release(k.p);
-        k.p = nullptr;
-    }
-    // which convolution kernels write fused statistics: the split-bf16 kernels and the fp32-MFMA kernel with >= 64-channel
-    // tiles; the 32-channel fp32 tile (Cout <= 32) and the direct kernel do not
-    static bool emits_stats(const ConvLayer& L) {
-        return L.algo == ALGO_BF16X3 || (L.algo == ALGO_F32 && L.co_tile >= 64) || (L.algo == ALGO_DIRECT && L.cout > 4);
-    }  // (and ALGO_F16X2, a second packing of a BF16X3 layer)
-    float2* finalize(const Sink& k, int H, int W, const float* gamma, const float* beta, const float* ada) {
-        float2* aff = (float2*)ar->alloc((size_t)B * k.C * sizeof(float2));
-        if (!dry()) {
-            GNParams g{Src{}, B, H, W, h->cfg.gn_num_groups, h->cfg.gn_eps, gamma, beta, ada, (long)h->ada_rows, k.p, aff,
-                       nullptr};
-            // (range guard of the fp16 consumers: the slot energies bound max|x| -- norm.hip; no separate maximum is recorded)
-            if (h->f16_path()) g.range_flag = range_site("GroupNorm output bound |a| M + |d| (gn_finalize)");  // (only the fp16 operand paths have a range to guard)
-            note(launch_group_norm_finalize(g, k.C, k.slots, st), "group_norm_finalize");
-        }
-        return aff;
-    }
-    // GroupNorm of `x`: from fused statistics when the producer left them, else with the streaming statistics pass
-    float2* norm(const Sink& k, const Src& x, int H, int W, const float* gamma, const float* beta, const float* ada) {
-        return k ? finalize(k, H, W, gamma, beta, ada) : group_norm(x, H, W, gamma, beta, ada);
-    }
-
-    float2* group_norm(const Src& x, int H, int W, const float* gamma, const float* beta, const float* ada) {
-        const int C = x.c0 + x.c1;
-        float2* aff = (float2*)ar->alloc((size_t)B * C * sizeof(float2));
-        if (!dry()) {
-            GNParams g{x, B, H, W, h->cfg.gn_num_groups, h->cfg.gn_eps, gamma, beta, ada, (long)h->ada_rows,
-                       gn_partial, aff, nullptr};
-            g.partial_max = (float*)(gn_partial + (size_t)B * h->cfg.gn_num_groups * 256 * 2);
-            if (h->f16_path()) g.range_flag = range_site("GroupNorm output bound |a| max|x| + |d| (streaming statistics)");  // (only the fp16 operand paths have a range to guard)
-            note(launch_group_norm(g, st), "group_norm");
-        }
-        return aff;
-    }
-
-    // The GroupNorm in front of a convolution: the statistics its producers left (or not: the streaming pass) and its parameters.
-    // conv() with a NormSpec runs the norm itself -- folded into the convolution's staging waves where conv_f16x2.hip can do that (no
-    // gn_finalize launch: 45 of the 50 GroupNorms of a forward at batch 8), else as the separate launch(es) in front of it.
-    struct NormSpec {
-        const Sink* stats;
-        const float *gamma, *beta, *ada;
-    };
-
-    // in-stream timing of a launch: records the opening event and returns the closing one (nullptr: profiling off)
-    hipEvent_t prof_begin(int cls, double flop) {
-        if (!h->prof_on) return nullptr;
-        if (h->prof_used + 2 > h->prof_ev.size()) {
-            hipEvent_t a, c;
-            if (hipEventCreate(&a) == hipSuccess && hipEventCreate(&c) == hipSuccess) {
-                h->prof_ev.push_back(a);
-                h->prof_ev.push_back(c);
-            }
-        }
-        if (h->prof_used + 2 > h->prof_ev.size()) return nullptr;
-        hipEvent_t e0 = h->prof_ev[h->prof_used], e1 = h->prof_ev[h->prof_used + 1];
-        h->prof_used += 2;
-        h->prof_flop += flop;
-        h->prof_cls.push_back(cls);
-        h->prof_lflop.push_back(flop);
-        (void)hipEventRecord(e0, st);
-        return e1;
-    }
-
-    Tensor conv(const ConvLayer& L, const Src& x, int H, int W, int pro, const float2* aff, const Tensor* res,
-                size_t scale_off, bool has_scale, float* dst = nullptr, const Sink* sink = nullptr, int goff = 0,
-                bool res_broadcast = false, bool input_bounded = false,  // input_bounded: its producer tracked max|x| in the range flag
-                bool track_out = false,                                 // track_out: record max|y| there (precision mode 2 only)
-                const NormSpec* ns = nullptr,                           // ns: `aff` comes from this GroupNorm (aff must be nullptr)
-                bool x16 = false, bool y16 = false) {                   // fp16 storage of the input / of the output (+ residual): act16(L) launches only
-        // (decided in the dry walk as well, from shapes and the batch alone: the allocation sequence must be the same in both walks)
-        bool fold = false, pre_fold = false;
-        float2* own_aff = nullptr;
-        if (ns) {
-            const Sink& k = *ns->stats;
-            const int G = h->cfg.gn_num_groups;
-            if (k && L.f2 && h->f16_path() && k.C == L.cin && G == 8) {
-                ConvParams q;
-                q.Cin = L.cin; q.Cout = L.cout; q.taps = L.taps; q.H = H; q.W = W; q.co_tile = L.f2_cot; q.px_rows = L.f2_rows; q.B = B; q.prologue = pro;
-                const int slots = k.cpg < 64 ? k.slots / 2 : k.slots;  // (groups of fewer than 64 channels leave the second half of their slots zero)
-                q.reverse = 0;
-                fold = conv_f16x2_fold_supported(q, G, slots);
-                q.reverse = 1;  // (whichever direction this launch will walk its tiles in)
-                fold = fold && conv_f16x2_fold_supported(q, G, slots);
-            }
-            // Round 6 EXPERIMENT, off by default (R2DM_F2_PRESPLIT_NARROW=1): the launches on 32-channel tiles (u_block4: eight output-channel tiles stage the
-            // same x tile, the stagers bound a chunk at 4.5 k cycles for 1.7 k of MFMAs) take their input through the operand pre-pass with the GroupNorm
-            // folded into THAT pass (presplit_fold_kernel): bit-identical; the convolutions go 43.8 -> 28.7 us and 78.3 -> 51.7 us, and the six 12.4 us passes
-            // (a launch + three dependent round trips over an 8 MB tensor) take it all back: step 5.894 | 5.895 ms (profiles/r06_narrow_presplit.txt).
-            // (=2: also the 512 -> 512 launches of level 4 on 64-channel tiles, eight output-channel tiles per x tile as well)
-            const bool narrow_tile = L.f2_cot == 32 || (narrow_presplit() >= 2 && L.f2_cot == 64 && L.cout >= 512);
-            if (k && narrow_presplit() && L.f2 && narrow_tile && L.f2_rows == 4 && h->conv_pieces == 2 && G == 8 && k.C == L.cin && presplit_supported(x, L.cin, H, W)) {
-                fold = false;
-                pre_fold = true;
-            }
-            if (!fold && !pre_fold) aff = own_aff = norm(k, x, H, W, ns->gamma, ns->beta, ns->ada);
-        }
-        Tensor y;
-        y.C = L.cout;
-        y.H = H;
-        y.W = W;
-        y.f16 = y16;
-        y.p = dst ? dst : (float*)ar->alloc(y.bytes(B));
-        // (decided in the dry walk as well: the consumer's choice between finalize and the streaming pass changes the
-        // allocation sequence, which must be the same in both walks)
-        const bool fused_stats = sink && sink->p && emits_stats(L);
-        if (sink && sink->p && !fused_stats) const_cast<Sink*>(sink)->incomplete = true;
-        // The operand pre-pass (presplit.hip) is an EXPERIMENT, off by default: R2DM_F2_PRESPLIT_MIN_COUT=256 sends the layers with >= 256
-        // output channels through it.  Round-4 A/B (profiles/r04_presplit.txt): bit-identical outputs, conv_f16x2's own roofline fraction
-        // 0.387 -> 0.403, the STEP 1.7 % slower (6.19 -> 6.30 ms): the pass costs more than the staging waves' transform did -- with the
-        // stagers idle a chunk still takes 4.5 k cycles (multipliers + three barriers; 5.2 k before), prologue / tile ends / tail are unchanged.
-        // (decided in both walks: the allocation sequence must be the same)
-        static const int presplit_min_cout = getenv("R2DM_F2_PRESPLIT_MIN_COUT") ? atoi(getenv("R2DM_F2_PRESPLIT_MIN_COUT")) : 0;  // (0: never)
-        const bool f2_launch = L.f2 && h->f16_path() && (pro != PRO_NONE || input_bounded);
-        float* xs = nullptr;
-        if (f2_launch && !fold && L.f2_cot == 64 && L.f2_rows == 4 && presplit_min_cout > 0 && L.cout >= presplit_min_cout && presplit_supported(x, L.cin, H, W))
-            xs = (float*)ar->alloc((size_t)presplit_floats(B, L.cin, H, W) * sizeof(float));
-        if (f2_launch && pre_fold && !xs) xs = (float*)ar->alloc((size_t)presplit_floats(B, L.cin, H, W) * sizeof(float));
-        if (!dry()) {
-            ConvParams p;
-            p.x = x;
-            p.w = blob(L.w);
-            p.bias = blob(L.b);
-            p.aff = aff;
-            p.res = res ? res->p : nullptr;
-            p.res_bs = res && !res_broadcast ? res->bs() : 0;
-            p.scale = has_scale ? blob(scale_off) : nullptr;
-            p.y = y.p;
-            p.y_bs = y.bs();
-            p.B = B;
-            p.H = H;
-            p.W = W;
-            p.Cin = L.cin;
-            p.CinPad = L.cin_pad;
-            p.Cout = L.cout;
-            p.taps = L.taps;
-            p.co_tile = L.co_tile;
-            p.algo = L.algo;
-            p.pieces = 3;
-            p.prologue = pro;
-            p.x16 = x16;  // (conv_f16x2 launches, the direct in / out convolutions and the fp16-operand skip convolutions take them; checked below)
-            p.y16 = y16;
-            // the fp16 split where the input's range is guarded: GroupNorm-normalised (gn_finalize's bound) or tracked by its
-            // producer (fir_up2's running maximum)
-            if (L.f2 && h->f16_path() && (pro != PRO_NONE || input_bounded)) {
-                static const int rev_mode = getenv("R2DM_TILE_ORDER") ? atoi(getenv("R2DM_TILE_ORDER")) : 1;  // 0: always ascending (experiments)
-                p.reverse = rev_mode ? (f2_launches++ & 1) : 0;
-                last_reverse = p.reverse;
-                p.algo = ALGO_F16X2;
-                p.w = blob(L.w_f2);
-                p.wscale = blob(L.ws_f2) + 1;
-                p.co_tile = L.f2_cot;
-                p.px_rows = L.f2_rows;
-                p.pieces = (L.f2_cot == 32 && narrow_split()) ? 2 : h->conv_pieces;
-                p.x16 = x16;
-                p.y16 = y16;
-                if (fold) {
-                    const Sink& k = *ns->stats;
-                    p.gn_partial = k.p;
-                    p.gn_stride = k.slots;
-                    p.gn_slots = k.cpg < 64 ? k.slots / 2 : k.slots;
-                    p.gn_cpg = k.cpg;
-                    p.gn_eps = h->cfg.gn_eps;
-                    p.gn_gamma = ns->gamma;
-                    p.gn_beta = ns->beta;
-                    p.gn_ada = ns->ada;
-                    p.gn_ada_stride = (long)h->ada_rows;
-                    p.gn_range = range_site("GroupNorm output bound |a| M + |d| (folded into the convolution)");
-                }
-            }
-            // deep layers (many 64-channel output tiles): the input transform once, by the pre-pass (presplit.hip)
-            if (xs) {
-                if (pre_fold) {
-                    const Sink& k = *ns->stats;
-                    note(launch_presplit_fold(x, pro, xs, B, L.cin, H, W, k.p, k.slots, k.cpg < 64 ? k.slots / 2 : k.slots, k.cpg, h->cfg.gn_eps, ns->gamma, ns->beta, ns->ada,
-                                              (long)h->ada_rows, range_site("GroupNorm output bound |a| M + |d| (folded into the operand pre-pass)"), st), "presplit_fold");
-                } else
-                    note(launch_presplit(x, aff, pro, xs, B, L.cin, H, W, st), "presplit");
-                p.x = Src{xs, nullptr, L.cin, 0, presplit_floats(1, L.cin, H, W), 0};
-                p.prologue = PRO_PRESPLIT;
-                p.aff = nullptr;
-            }
-            if (L.p1 && h->f16_path() && pro != PRO_AFFINE_SILU && (pro != PRO_NONE || input_bounded)) {
-                p.algo = ALGO_P1F16;
-                // (a skip convolution reads the tensor its block's conv1 has just read: start where that walk ended.  R2DM_PROJ_ORDER=0: always forwards)
-                static const bool proj_rev = !getenv("R2DM_PROJ_ORDER") || atoi(getenv("R2DM_PROJ_ORDER")) != 0;
-                p.reverse = proj_rev && last_reverse == 0 ? 1 : 0;
-                p.w = blob(L.w_p1);
-                p.wscale = blob(L.ws_p1) + 1;
-                p.co_tile = 64;
-                p.pieces = h->conv_pieces;
-            }
-            // (every MFMA kernel records the maximum; the direct kernels' outputs never feed an fp16 operand unnormalised)
-            if (track_out && h->f16_path() && p.algo != ALGO_DIRECT) p.range = range_site("max|output| (raw input of the next fp16-operand kernel)");
-            if (fused_stats) {
-                p.stat = sink->p;
-                p.stat_G = h->cfg.gn_num_groups;
-                p.stat_goff = goff;
-                p.stat_cpg = sink->cpg;
-                p.stat_slots = sink->slots;
-            }
-            if ((x16 || y16) && p.algo != ALGO_F16X2 && p.algo != ALGO_DIRECT && p.algo != ALGO_P1F16) note(hipErrorInvalidValue, "fp16 storage on a kernel without it");
-            if (x16 && !fold && !pre_fold && own_aff && !(ns && *ns->stats)) note(hipErrorInvalidValue, "fp16 storage behind a streaming GroupNorm");
-            // ALGORITHMIC flops of the reference's convolution (in_conv: all 34 input channels, although the
-            // constant Fourier half is folded into a bias map here)
-            hipEvent_t e1 = prof_begin(p.algo == ALGO_F16X2 ? 0 : p.algo == ALGO_BF16X3 ? 1 : 2, 2.0 * B * (double)L.cout * (L.src_cin ? L.src_cin : L.cin) * L.taps * H * W);
-            if (g_debug_sync)
-                fprintf(stderr, "[r2dm] conv algo %d %d->%d taps %d co_tile %d %dx%d B %d pro %d w %p bias %p gn %p blob [%p, +%zu) x %p/%p (c0 %d) y %p res %p aff %p stat %p ws [%p, +%zu)\n", p.algo, p.Cin,
-                        p.Cout, p.taps, p.co_tile, H, W, B, pro, (const void*)p.w, (const void*)p.bias, (const void*)p.gn_partial, (void*)h->blob, h->blob_floats * 4, (const void*)p.x.p0, (const void*)p.x.p1, p.x.c0, (void*)p.y, (const void*)p.res, (const void*)p.aff,
-                        (void*)p.stat, (void*)ar->base, ar->cap);
-            note(launch_conv(p, st), "conv");
-            if (e1) (void)hipEventRecord(e1, st);
-        }
-        if (xs) ar->release(xs);  // (stream-ordered: the next user of that memory is enqueued behind this convolution)
-        if (own_aff) ar->release(own_aff);
-        return y;
-    }
-
-    // efficient_unet.py:95-110.  `in_stats`: fused statistics of x (if its producer left them);
-    // `out` / `out_goff`: where the statistics of this block's output go (the next GroupNorm's sink).
-    // fp16 storage (round 5): in the one-plane mode (the reference's autocast counterpart) the tensor between a residual block's two
-    // convolutions is stored as fp16 -- what autocast stores there (/root/reference/sample_and_save.py:45,70) -- when both run on
-    // conv_f16x2 (R2DM_FP16_STORAGE=0: fp32 everywhere, as until round 4)
-    bool act16(const ConvLayer& L) const {
-        static const bool on = !getenv("R2DM_FP16_STORAGE") || atoi(getenv("R2DM_FP16_STORAGE")) != 0;
-        return on && h->conv_pieces == 1 && L.f2 && !(L.f2_cot == 32 && narrow_split());
-    }
-    static int narrow_presplit() {
-        const char* e = getenv("R2DM_F2_PRESPLIT_NARROW");  // (read per call, like R2DM_GN_FOLD: the bit-identity test builds one model per setting)
-        return e ? atoi(e) : 0;
-    }
-    // (experiment switch, round 5) layers packed for the 32-channel tile run the two-plane kernel in every precision mode
-    static bool narrow_split() {
-        static const bool on = getenv("R2DM_F2_NARROW_SPLIT") && atoi(getenv("R2DM_F2_NARROW_SPLIT")) != 0;
-        return on;
-    }
-
-    Tensor residual_block(const ResLayer& r, const Src& x, int H, int W, const Sink& in_stats, const Sink* out, int out_goff,
-                          bool track_out = false, bool skip_bounded = false, bool x16 = false) {  // x16: the block's input (both sources) is stored as fp16
-        const std::string blk = ctx;
-        ctx = blk + ".conv1";
-        const NormSpec n1{&in_stats, blob(r.g1), blob(r.b1), nullptr};
-        Sink s1 = make_sink(r.cout, H, W);
-        const bool t1_16 = act16(r.conv1) && act16(r.conv2) && s1.p != nullptr;  // (the streaming statistics pass reads fp32)
-        const bool out16 = x16 && lvl16(H) && act16(r.conv2);  // the block's output (and the residual it adds: its input or the skip convolution's output)
-        Tensor t1 = conv(r.conv1, x, H, W, PRO_AFFINE_SILU, nullptr, nullptr, 0, false, nullptr, &s1, 0, false, false, false, &n1, x16, t1_16);
-        const NormSpec n2{&s1, nullptr, nullptr, proj + r.ada_row};
-        Tensor skip;
-        const Tensor* res;
-        Tensor ident;
-        if (r.has_skip) {
-            ctx = blk + ".skip";
-            skip = conv(r.skip, x, H, W, PRO_NONE, nullptr, nullptr, 0, false, nullptr, nullptr, 0, false, skip_bounded, false, nullptr, x16, out16);
-            res = &skip;
-        } else {
-            ident.p = const_cast<float*>(x.p0);  // identity skip: block input is single-source here
-            ident.C = x.c0;
-            ident.H = H;
-            ident.W = W;
-            res = &ident;
-        }
-        ctx = blk + ".conv2";
-        Tensor o = conv(r.conv2, src1(t1), H, W, PRO_AFFINE_SILU, nullptr, res, r.scale, true, nullptr, out, out_goff, false, false, track_out, &n2, t1_16, out16);
-        ctx = blk;
-        drop_sink(s1);
-        drop(t1);
-        if (r.has_skip) drop(skip);
-        return o;
-    }
-
-    // efficient_unet.py:42-53
-    Tensor attention_block(const AttnLayer& a, const Tensor& x, const Sink& in_stats, const Sink* out, int out_goff, bool track_out = false) {
-        const std::string blk = ctx;
-        ctx = blk + ".norm";
-        float2* aff = norm(in_stats, src1(x), x.H, x.W, blob(a.gamma), blob(a.beta), nullptr);
-        ctx = blk + ".qkv";
-        // precision mode 2: the attention core runs on the fp16 matrix pipe (attention.hip) and needs |q|, |k|, |v| < 65504: the
-        // projection's epilogue records max|qkv| in the range flag
-        const bool f2 = h->f16_path();
-        Tensor qkv = conv(a.qkv, src1(x), x.H, x.W, PRO_AFFINE, aff, nullptr, 0, false, nullptr, nullptr, 0, false, false, f2);
-        ar->release(aff);
-        Tensor o = make(a.C, x.H, x.W);
-        if (!dry()) note(launch_attention(qkv.p, o.p, B, a.C, h->cfg.attn_num_heads, x.H * x.W, st, f2 ? h->conv_pieces : 0), "attention");
-        drop(qkv);
-        // (the core's output is a convex combination of v: |o| <= max|qkv|, which the qkv epilogue has recorded)
-        ctx = blk + ".out_proj";
-        Tensor y = conv(a.proj, src1(o), x.H, x.W, PRO_NONE, nullptr, &x, a.scale, true, nullptr, out, out_goff, false, f2, track_out);
-        ctx = blk;
-        drop(o);
-        return y;
-    }
-
-    // efficient_unet.py:178-185.  Never frees `in`; returns a fresh tensor.  `in_stats`: fused statistics of `in` for
-    // the first residual block (stages without downsampling); `out`/`out_goff`: sink of the GroupNorm that will consume
-    // this stage's output (written by whichever convolution produces it last).
-    Tensor stage(const Stage& s, const Src& in, int H, int W, const Sink& in_stats, const Sink* out, int out_goff, bool in_tracked = false, bool in16 = false) {
-        Tensor cur;
-        bool have = false;
-        bool c16 = in16;  // the current tensor (stage input or `cur`) is stored as fp16
-        Sink carry = in_stats;  // statistics of the current tensor, owned elsewhere for the stage input
-        bool carry_owned = false;
-        // FIR first, then the stride-2 convolution as a GEMM over the nine filtered planes (resample.hip down_planes_kernel): a quarter of the MACs of
-        // conv + fir_down2.  Taken where the plan packed the matrix (geometry, R2DM_DOWN_GEMM), the precision is the default three-product split and
-        // the input's producer tracks max|x|; everything else -- fp32-bf16x3, the one-plane mode with its fp16 storage, a tripped guard's fallback --
-        // keeps conv + FIR.  Leaves what the FIR launch leaves: the tensor and, where fir_down2 would, the statistics of the first block's norm.
-        // (a two-source input never reaches a down stage today; if one does it keeps conv + FIR: the pre-pass reads one tensor)
-        if (s.down && s.dconv.dg && h->conv_pieces == 2 && in_tracked && !in16 && !in.p1) {
-            ctx = s.name + ".downsample";
-            const ConvLayer& L = s.dconv;
-            Tensor a = make(9 * L.cin, H / 2, W / 2);
-            cur = make(s.cout, H / 2, W / 2);
-            Sink fs;
-            if (fir_down2_stat_slots(s.cout, h->cfg.gn_num_groups, H, W)) fs = make_sink(s.cout, H / 2, W / 2);
-            if (!dry()) {
-                // Range: the FIR weights are non-negative and sum to at most 1 per axis, so max|a| <= max|x|, which the producer has recorded at its own site;
-                // the pass records max|a| itself all the same (one guarded atomic per wave), so the report names the GEMM's operand.
-                // (profiling: both launches in class 2, "1x1 / in / out convolutions" -- the pass with no FLOPs of its own, the GEMM with those it executes)
-                int* site = range_site("max|FIR planes| (operand of the down-sampling GEMM)");
-                hipEvent_t e0 = prof_begin(2, 0.0);
-                note(launch_down_planes(in.p0, in.bs0, a.p, a.bs(), B, L.cin, H, W, st, site), "down_planes");
-                if (e0) (void)hipEventRecord(e0, st);
-                ConvParams p;
-                p.x = src1(a);
-                p.w = blob(L.w_dg);
-                p.bias = blob(L.b);
-                p.aff = nullptr;
-                p.res = nullptr;
-                p.res_bs = 0;
-                p.scale = nullptr;
-                p.y = cur.p;
-                p.y_bs = cur.bs();
-                p.B = B;
-                p.H = H / 2;
-                p.W = W / 2;
-                p.Cin = p.CinPad = 9 * L.cin;
-                p.Cout = L.cout;
-                p.taps = 1;
-                p.co_tile = 64;
-                p.prologue = PRO_NONE;
-                p.algo = ALGO_P1F16;
-                p.pieces = 2;
-                p.wscale = blob(L.ws_dg) + 1;
-                if (fs.p) {
-                    p.stat = fs.p;
-                    p.stat_G = h->cfg.gn_num_groups;
-                    p.stat_goff = 0;
-                    p.stat_cpg = fs.cpg;
-                    p.stat_slots = fs.slots;
-                }
-                last_reverse = -1;
-                hipEvent_t e1 = prof_begin(2, 2.0 * B * (double)L.cout * 9 * L.cin * (H / 2) * (W / 2));
-                note(launch_proj_f16x2(p, st, /*bias_rowfac=*/true), "down_gemm");
-                if (e1) (void)hipEventRecord(e1, st);
-            }
-            drop(a);
-            H /= 2;
-            W /= 2;
-            have = true;
-            carry = fs;
-            carry_owned = fs.p != nullptr;
-        } else if (s.down) {
-            ctx = s.name + ".downsample";
-            Tensor t = conv(s.dconv, in, H, W, PRO_NONE, nullptr, nullptr, 0, false, nullptr, nullptr, 0, false, in_tracked, false, nullptr, in16, in16 && lvl16(H));
-            cur = make(s.cout, H / 2, W / 2, t.f16 && lvl16(H / 2));
-            // the FIR pass leaves the statistics of its output for the first residual block's norm (resample.hip; where its geometry
-            // does not fit the slot grid: no fused statistics, the streaming pass)
-            Sink fs;
-            if (fir_down2_stat_slots(s.cout, h->cfg.gn_num_groups, H, W)) fs = make_sink(s.cout, H / 2, W / 2);
-            if (!dry()) note(launch_fir_down2(t.p, t.bs(), cur.p, cur.bs(), B, s.cout, H, W, st, fs.p, h->cfg.gn_num_groups, t.f16, cur.f16), "fir_down2");
-            c16 = cur.f16;
-            drop(t);
-            H /= 2;
-            W /= 2;
-            have = true;
-            carry = fs;
-            carry_owned = fs.p != nullptr;
-        }
-        const int n = (int)s.res.size();
-        for (int i = 0; i < n; ++i) {
-            const bool last = i == n - 1;
-            Sink next;  // sink for the GroupNorm that consumes this block's output inside the stage
-            const Sink* dst = nullptr;
-            int goff = 0;
-            if (!last || s.attn) {
-                next = make_sink(s.cout, H, W);
-                dst = &next;
-            } else if (!s.up) {
-                dst = out;
-                goff = out_goff;
-            }
-            const bool tf = h->f16_path() && last && ((s.out_tracked) || (s.track_final && !s.attn && !s.up));
-            ctx = s.name + ".residual_blocks." + std::to_string(i);
-            Tensor nxt = residual_block(s.res[i], have ? src1(cur) : in, H, W, carry, dst, goff, tf, i == 0 && s.skip_in_bounded && h->f16_path(), c16);
-            c16 = nxt.f16;
-            if (carry_owned) drop_sink(carry);
-            if (have) drop(cur);
-            cur = nxt;
-            have = true;
-            carry = next;
-            carry_owned = next.p != nullptr;
-        }
-        if (s.attn) {
-            ctx = s.name + ".self_attn_block";
-            if (cur.f16) note(hipErrorInvalidValue, "attention block behind fp16 storage");
-            Tensor nxt = attention_block(s.at, cur, carry, s.up ? nullptr : out, out_goff, s.track_final && !s.up && h->f16_path());
-            if (carry_owned) drop_sink(carry);
-            carry_owned = false;
-            drop(cur);
-            cur = nxt;
-        }
-        if (carry_owned) drop_sink(carry);
-        if (s.up) {
-            Tensor u = make(s.cout, 2 * H, 2 * W, lvl16(2 * H) && s.uconv.f2);
-            const bool track = s.uconv.f2 && h->f16_path();  // the fp16-operand convolution below needs max|u| < 65504
-            ctx = s.name + ".upsample";
-            if (!dry()) note(launch_fir_up2(cur.p, cur.bs(), u.p, u.bs(), B, s.cout, H, W, st, track ? range_site("max|FIR output| (raw input of the up-sampling convolution)") : nullptr, cur.f16, u.f16), "fir_up2");
-            drop(cur);
-            cur = conv(s.uconv, src1(u), 2 * H, 2 * W, PRO_NONE, nullptr, nullptr, 0, false, nullptr, out, out_goff, false, track, s.track_final && h->f16_path(), nullptr, u.f16, u.f16);
-            drop(u);
-        }
-        return cur;
-    }
-};
-
-int run_forward(r2dm_handle* h, Arena& ar, const float* x, const float* cond, float* out, int B, hipStream_t st) {
-    const r2dm_config& c = h->cfg;
-    Ctx k{h, &ar, st, B, nullptr, nullptr};
-    const int H = c.height, W = c.width, T = c.temb_channels;
-    float* act = (float*)ar.alloc((size_t)2 * B * T * sizeof(float));  // [SiLU(temb) | hidden scratch]
-    float* proj = (float*)ar.alloc((size_t)B * h->ada_rows * sizeof(float));
-    k.gn_partial = (double*)ar.alloc((size_t)B * c.gn_num_groups * 256 * (2 * sizeof(double) + sizeof(float)));  // sums | maxima
-    k.proj = proj;
-    if (!k.dry()) {
-        EmbedParams e{cond, k.blob(h->freqs), k.blob(h->w1), k.blob(h->b1), k.blob(h->w2), k.blob(h->b2), act,
-                      act + (size_t)B * T, B, c.base_channels, T};
-        k.note(launch_time_embedding(e, st), "time_embedding");
-        k.note(launch_ada_proj(act, k.blob(h->ada_w), k.blob(h->ada_b), proj, B, T, h->ada_rows, st), "ada_proj");
-    }
-    // input = cat([x, cenc]) (efficient_unet.py:278-281), never materialised: the constant cenc half of in_conv is the
-    // per-pixel bias map `cmap`, the per-step convolution runs over the in_channels data channels only
-    Src in{x, nullptr, c.in_channels, 0, (long)c.in_channels * H * W, 0};
-    if (c.coord_channels && !h->cmap_ready && !k.dry()) {
-        ConvParams q;
-        q.x = Src{k.blob(h->cenc), nullptr, c.coord_channels, 0, 0, 0};
-        q.w = k.blob(h->in_conv_c.w);
-        q.bias = k.blob(h->in_conv_c.b);
-        q.aff = nullptr;
-        q.res = nullptr;
-        q.res_bs = 0;
-        q.scale = nullptr;
-        q.y = h->blob + h->cmap;
-        q.y_bs = 0;
-        q.B = 1;
-        q.H = H;
-        q.W = W;
-        q.Cin = h->in_conv_c.cin;
-        q.CinPad = h->in_conv_c.cin_pad;
-        q.Cout = h->in_conv_c.cout;
-        q.taps = 9;
-        q.co_tile = h->in_conv_c.co_tile;
-        q.algo = ALGO_F32;
-        q.prologue = PRO_NONE;
-        k.note(hipMemsetAsync(h->blob + h->zero_bias, 0, h->in_conv.cout * sizeof(float), st), "zero bias");
-        k.note(launch_conv(q, st), "in_conv constant map");
-        h->cmap_ready = true;
-    }
-    Tensor cmap_t;
-    cmap_t.p = h->blob + h->cmap;
-    cmap_t.C = h->in_conv.cout;
-    cmap_t.H = H;
-    cmap_t.W = W;
-    const int G = c.gn_num_groups;
-    const Stage* S = h->stages;
-    // GroupNorm sinks that outlive a stage: the first norm of d_block1 (input = in_conv output) and the first norm of
-    // every up stage (input = cat([up-path tensor, skip tensor]): groups [0, G/2) come from the up path, [G/2, G)
-    // from the skip tensor produced much earlier on the down path).
-    Ctx::Sink s_d1 = k.make_sink(S[0].cin, H, W);
-    Ctx::Sink s_u1 = k.make_sink(S[7].cin, H, W);
-    Ctx::Sink s_u2 = k.make_sink(S[6].cin, H / 2, W / 2);
-    Ctx::Sink s_u3 = k.make_sink(S[5].cin, H / 4, W / 4);
-    Ctx::Sink s_u4 = k.make_sink(S[4].cin, H / 8, W / 8);
-    {
-        // fp16 storage of the full-resolution levels (Ctx::lvl16): the one-plane mode, the default network family (every GroupNorm of levels 1 and 2 on fused
-        // statistics -- the streaming pass reads fp32 --, in_conv on the few-input kernel, FIR statistics at both levels).  R2DM_FP16_STORAGE=1: only between a
-        // residual block's two convolutions (round 5); 0: nowhere.  Read per forward like R2DM_GN_FOLD (ws_cache: r2dm_set_conv_pieces clears it; tests build one
-        // model per setting).
-        const char* e = getenv("R2DM_FP16_STORAGE");
-        const int level = e ? atoi(e) : 2;
-        // ... and every convolution of those levels on a kernel that has the second I/O type (at small batches some layers have too few tiles for conv_f16x2
-        // and run the bf16 kernels: then nothing changes)
-        auto blocks_ok = [](const Stage& st) {
-            for (const ResLayer& r : st.res)
-                if (!r.conv1.f2 || !r.conv2.f2 || (r.has_skip && !r.skip.p1)) return false;
-            return true;
-        };
-        k.all16 = level >= 2 && h->conv_pieces == 1 && G == 8 && c.base_channels % 64 == 0 && h->in_conv.algo == ALGO_DIRECT && h->in_conv.cout > 4 &&
-                  h->out_conv.algo == ALGO_DIRECT && W % 4 == 0 && S[1].down && S[2].down && S[1].dconv.f2 && S[2].dconv.f2 && S[5].up && S[6].up &&
-                  S[5].uconv.f2 && S[6].uconv.f2 && !S[0].attn && !S[1].attn && !S[6].attn && !S[7].attn && blocks_ok(S[0]) && blocks_ok(S[1]) && blocks_ok(S[6]) &&
-                  blocks_ok(S[7]) && S[6].skip_in_bounded && S[7].skip_in_bounded &&
-                  fir_down2_stat_slots(S[1].cout, G, H, W) != 0 && fir_down2_stat_slots(S[2].cout, G, H / 2, W / 2) != 0;
-    }
-    k.ctx = "in_conv";
-    Tensor h0 = k.conv(h->in_conv, in, H, W, PRO_NONE, nullptr, c.coord_channels ? &cmap_t : nullptr, 0, false, nullptr, &s_d1, 0, /*res_broadcast=*/true, false, false, nullptr,
-                       false, k.lvl16(H) && s_d1.p != nullptr);
-    Tensor h1 = k.stage(S[0], src1(h0), H, W, s_d1, &s_u1, G / 2, false, h0.f16);
-    k.drop(h0);
-    k.drop_sink(s_d1);
-    Tensor h2 = k.stage(S[1], src1(h1), H, W, Ctx::Sink{}, &s_u2, G / 2, S[0].out_tracked && h->f16_path(), h1.f16);
-    Tensor h3 = k.stage(S[2], src1(h2), H / 2, W / 2, Ctx::Sink{}, &s_u3, G / 2, S[1].out_tracked && h->f16_path(), h2.f16);
-    Tensor h4 = k.stage(S[3], src1(h3), H / 4, W / 4, Ctx::Sink{}, &s_u4, 0, S[2].out_tracked && h->f16_path());
-    Tensor u = k.stage(S[4], src1(h4), H / 8, W / 8, s_u4, &s_u3, 0);
-    k.drop(h4);
-    k.drop_sink(s_u4);
-    Tensor u3 = k.stage(S[5], src2(u, h3), H / 4, W / 4, s_u3, &s_u2, 0);
-    k.drop(u);
-    k.drop(h3);
-    k.drop_sink(s_u3);
-    if (u3.f16 != h2.f16 || h3.f16) k.note(hipErrorInvalidValue, "fp16 storage: the two halves of a skip join differ");
-    Tensor u2 = k.stage(S[6], src2(u3, h2), H / 2, W / 2, s_u2, &s_u1, 0, false, u3.f16 && h2.f16);
-    k.drop(u3);
-    k.drop(h2);
-    k.drop_sink(s_u2);
-    if (u2.f16 != h1.f16) k.note(hipErrorInvalidValue, "fp16 storage: the two halves of a skip join differ");
-    Tensor u1 = k.stage(S[7], src2(u2, h1), H, W, s_u1, nullptr, 0, false, u2.f16 && h1.f16);
-    k.drop(u2);
-    k.drop(h1);
-    k.drop_sink(s_u1);
-    k.ctx = "out_conv";
-    k.conv(h->out_conv, src1(u1), H, W, PRO_NONE, nullptr, nullptr, 0, false, out, nullptr, 0, false, false, false, nullptr, u1.f16, false);
-    k.drop(u1);
-    ar.release(act);
-    ar.release(proj);
-    ar.release(k.gn_partial);
-    if (k.err != hipSuccess) return fail(2, "kernel launch failed in %s: %s", k.where, hipGetErrorString(k.err));
-    if (ar.overflow) return fail(3, "workspace too small: need %zu bytes", ar.peak);
-    return 0;
-}
-
-int check_config(const r2dm_config& c) {
-    if (c.in_channels < 1 || c.out_channels < 1 || c.height < 8 || c.width < 32) return fail(1, "bad image geometry");
-    if ((c.height % 8) || (c.width % 32)) return fail(1, "height must be a multiple of 8 and width of 32 (3 FIR levels, 16-byte rows)");
-    if (c.base_channels % 2 || c.base_channels < 4) return fail(1, "base_channels must be even");
-    if (c.gn_num_groups < 1 || c.max_batch < 1) return fail(1, "bad gn_num_groups / max_batch");
-    int Cl[5] = {c.base_channels, 0, 0, 0, 0};
-    for (int i = 0; i < 4; ++i) {
-        if (c.channel_multiplier[i] < 1 || c.num_residual_blocks[i] < 1) return fail(1, "bad multiplier / block count");
-        Cl[i + 1] = c.base_channels * c.channel_multiplier[i];
-    }
-    for (int i = 0; i < 5; ++i)
-        if (Cl[i] % c.gn_num_groups) return fail(1, "channels %d not divisible by %d groups", Cl[i], c.gn_num_groups);
-    for (int i = 1; i <= 3; ++i)  // concat seam must fall on a group boundary: 2*C / G divides C
-        if (Cl[i] % (2 * Cl[i] / c.gn_num_groups)) return fail(1, "GroupNorm group straddles the skip concat");
-    // an up stage whose concatenated input has as many channels as its output would take the identity skip on a
-    // two-source tensor (reference: nn.Identity on the concatenation); the fused residual reads one source only
-    for (int i = 1; i <= 3; ++i)
-        if (2 * Cl[i] == Cl[i - 1]) return fail(1, "channel_multiplier: 2*%d == %d makes u_block%d's first skip an identity over a concatenation (unsupported)", Cl[i], Cl[i - 1], i);
-    const int N = (c.height / 8) * (c.width / 8);
-    if (!attention_supported(Cl[4], c.attn_num_heads, N) || !attention_supported(Cl[3], c.attn_num_heads, N))
-        return fail(1, "attention: the head size must divide the channels and be at most 128 (got C=%d/%d, heads=%d, N=%d)",
-                    Cl[4], Cl[3], c.attn_num_heads, N);
-    return 0;
-}
-
-}  // namespace
+}  // namespace r2dm
 
 // =================================================================================================
 extern "C" {
@@ -1067,36 +58,6 @@ int r2dm_tensor_at(const r2dm_handle* h, int64_t i, r2dm_tensor_info* out) {
 }
 
 size_t r2dm_blob_bytes(const r2dm_handle* h) { return h ? h->blob_floats * sizeof(float) : 0; }
-
-uint64_t r2dm_blob_layout_hash(const r2dm_handle* h) {
-    if (!h) return 0;
-    uint64_t v = 1469598103934665603ull;  // FNV-1a over the plan
-    auto mix = [&](uint64_t x) {
-        for (int i = 0; i < 8; ++i) {
-            v ^= (x >> (8 * i)) & 0xff;
-            v *= 1099511628211ull;
-        }
-    };
-    mix(h->blob_floats);
-    mix(h->range_flag);
-    mix(h->cmap);
-    mix(h->ada_w);
-    mix(h->ada_b);
-    for (const Slot& s : h->slots) {
-        for (char c : s.key) mix((unsigned char)c);
-        mix((uint64_t)s.numel);
-        mix((uint64_t)s.kind);
-        mix(s.off);
-        if (s.kind == SLOT_CONV) {
-            const ConvLayer& L = s.conv;
-            const uint64_t f[] = {(uint64_t)L.cin, (uint64_t)L.cout, (uint64_t)L.taps, (uint64_t)L.co_tile, (uint64_t)L.cin_pad, (uint64_t)L.algo, (uint64_t)L.src_cin,
-                                  (uint64_t)L.src_off, L.w, L.b, (uint64_t)L.f2, (uint64_t)L.f2_cot, (uint64_t)L.f2_rows, L.w_f2, L.ws_f2, (uint64_t)L.p1, L.w_p1, L.ws_p1, (uint64_t)L.dg, L.w_dg, L.ws_dg};
-            for (uint64_t x : f) mix(x);
-        }
-    }
-    return v;
-}
-
 int r2dm_bind_blob(r2dm_handle* h, void* blob, size_t bytes) {
     if (!h || !blob) return fail(1, "null argument");
     if (bytes < r2dm_blob_bytes(h)) return fail(1, "blob too small: %zu < %zu", bytes, r2dm_blob_bytes(h));
@@ -1223,187 +184,6 @@ int r2dm_unet_forward(r2dm_handle* h, const float* x, const float* cond, float* 
     return run_forward(h, ar, x, cond, out, B, (hipStream_t)stream);
 }
 
-int r2dm_posterior_step(const float* x_t, const float* pred, const float* noise, const float* coef, float* x_s,
-                        int32_t B, int64_t per_sample, int32_t mode, int32_t objective, float clip, void* stream) {
-    if (!x_t || !pred || !coef || !x_s) return fail(1, "null argument");
-    PosteriorParams p{x_t, pred, noise, coef, x_s, B, per_sample, mode, objective, clip};
-    HIP_TRY(launch_posterior(p, (hipStream_t)stream));
-    return 0;
-}
-
-int r2dm_repaint_blend(const float* known, const float* noise, const float* unknown, const float* mask, const float* coef,
-                       float* out, int32_t B, int64_t per_sample, int32_t channels, int32_t mask_channels, void* stream) {
-    if (!known || !noise || !unknown || !mask || !coef || !out) return fail(1, "null argument");
-    HIP_TRY(launch_repaint_blend(known, noise, unknown, mask, coef, out, B, per_sample, channels, mask_channels,
-                                 (hipStream_t)stream));
-    return 0;
-}
-
-int r2dm_q_step(const float* x_s, const float* noise, const float* coef, float* x_t, int32_t B, int64_t per_sample,
-                void* stream) {
-    if (!x_s || !noise || !coef || !x_t) return fail(1, "null argument");
-    HIP_TRY(launch_q_step(x_s, noise, coef, x_t, B, per_sample, (hipStream_t)stream));
-    return 0;
-}
-
-int r2dm_lidar_postprocess(const float* x, const float* ang, float* out, int32_t B, int32_t H, int32_t W,
-                           float min_depth, float max_depth, void* stream) {
-    return r2dm_lidar_postprocess_fmt(x, ang, out, B, H, W, min_depth, max_depth, 0, stream);
-}
-
-int r2dm_lidar_postprocess_fmt(const float* x, const float* ang, float* out, int32_t B, int32_t H, int32_t W,
-                               float min_depth, float max_depth, int32_t depth_format, void* stream) {
-    if (!x || !ang || !out) return fail(1, "null argument");
-    if (depth_format < 0 || depth_format > 2) return fail(1, "depth_format must be 0 (log_depth), 1 (inverse_depth) or 2 (depth)");
-    HIP_TRY(launch_lidar_postprocess(x, ang, out, B, H, W, min_depth, max_depth, (hipStream_t)stream, depth_format));
-    return 0;
-}
-
-int r2dm_bev_histogram(const float* src, int32_t layout, const float* edges, int32_t* hist, int64_t* sum, int32_t batch,
-                       int64_t points, int32_t bins, float min_depth, float max_depth, float image_min_depth,
-                       float image_max_depth, void* stream) {
-    if (!src || !edges || !hist) return fail(1, "null argument");
-    if (layout != 0 && layout != 1) return fail(1, "layout must be 0 ((B,5,H,W) samples) or 1 ((B,N,3) point clouds)");
-    if (batch < 1 || points < 1) return fail(1, "empty batch");
-    if (bins < 1 || bins > 128) return fail(1, "bins must be in [1, 128] (one histogram per block in LDS), got %d", bins);
-    HIP_TRY(launch_bev_histogram(src, layout, edges, hist, sum, batch, points, bins, min_depth, max_depth, image_min_depth,
-                                 image_max_depth, (hipStream_t)stream));
-    return 0;
-}
-
-int r2dm_bev_hist_sum(const void* hist, int32_t is_int32, int64_t* sum, int64_t batch, int64_t cells, void* stream) {
-    if (!hist || !sum) return fail(1, "null argument");
-    if (batch < 1 || cells < 1) return fail(1, "empty histogram batch");
-    HIP_TRY(launch_bev_hist_sum(hist, is_int32, sum, batch, cells, (hipStream_t)stream));
-    return 0;
-}
-
-size_t r2dm_bev_mmd_scratch_bytes(int32_t np, int32_t nq) { return np < 1 || nq < 1 ? 0 : mmd_scratch_bytes(np, nq); }
-
-int r2dm_bev_mmd(const float* p, const float* q, int32_t np, int32_t nq, int64_t bins, double sigma, void* scratch,
-                 size_t scratch_bytes, double* out, void* stream) {
-    if (!p || !q || !scratch || !out) return fail(1, "null argument");
-    if (np < 1 || nq < 1 || bins < 1) return fail(1, "empty histogram set");
-    if (!(sigma > 0.0)) return fail(1, "sigma must be > 0");
-    if (scratch_bytes < mmd_scratch_bytes(np, nq)) return fail(1, "scratch too small: %zu < %zu bytes", scratch_bytes, mmd_scratch_bytes(np, nq));
-    if ((uintptr_t)scratch & 255) return fail(1, "scratch must be 256-byte aligned");
-    HIP_TRY(launch_bev_mmd(p, q, np, nq, bins, sigma, scratch, out, (hipStream_t)stream));
-    return 0;
-}
-
-int r2dm_colorize(const float* x, const float* lut, uint8_t* out, int64_t batch, int64_t pixels, void* stream) {
-    if (!x || !lut || !out) return fail(1, "null argument");
-    if (batch < 1 || pixels < 1) return fail(1, "empty image batch");
-    HIP_TRY(launch_colorize(x, lut, out, batch, pixels, (hipStream_t)stream));
-    return 0;
-}
-
-size_t r2dm_rasterize_scratch_bytes(int32_t batch, int32_t channels, int32_t height, int32_t width) {
-    return batch < 1 || channels < 1 || height < 1 || width < 1 ? 0 : rasterize_scratch_bytes(batch, channels, height, width);
-}
-
-int r2dm_bilinear_rasterize(const float* coords, const float* values, float* out, int32_t batch, int64_t points, int32_t channels, int32_t height,
-                            int32_t width, void* scratch, size_t scratch_bytes, int32_t ratio, void* stream) {
-    if (!coords || !values || !out || !scratch) return fail(1, "null argument");
-    if (batch < 1 || batch > 65535 || points < 1 || channels < 1 || height < 1 || width < 1) return fail(1, "rasterize: empty or oversized batch");
-    if (points > (1L << 36)) return fail(1, "rasterize: more than 2^36 points per image");
-    if (ratio != 0 && ratio != 1) return fail(1, "ratio must be 0 (sums) or 1 (channels 0-2 over channel 3)");
-    if (ratio && channels != 4) return fail(1, "the ratio form takes 4 channels, got %d", channels);
-    const size_t need = rasterize_scratch_bytes(batch, channels, height, width);
-    if (scratch_bytes < need) return fail(1, "scratch too small: %zu < %zu bytes", scratch_bytes, need);
-    if ((uintptr_t)scratch & 255) return fail(1, "scratch must be 256-byte aligned");
-    HIP_TRY(launch_rasterize(coords, values, out, batch, points, channels, height, width, scratch, ratio, (hipStream_t)stream));
-    return 0;
-}
-
-int r2dm_project_points(const float* points, const float* colors, const float* view, float focal_length, int32_t size, float* uv, float* vals,
-                        int64_t total_points, void* stream) {
-    if (!points || !view || !uv || !vals) return fail(1, "null argument");
-    if (total_points < 1 || size < 1) return fail(1, "project_points: empty cloud or image");
-    HIP_TRY(launch_project_points(points, colors, view, focal_length, size, uv, vals, total_points, (hipStream_t)stream));
-    return 0;
-}
-
-size_t r2dm_render_frames_scratch_bytes(int32_t frames, int32_t size) { return frames < 1 || size < 1 ? 0 : render_frames_scratch_bytes(frames, size); }
-
-int r2dm_render_frames(const float* x, const float* trig, const float* turbo, const float* viridis, float* img, float* bev, int64_t frames,
-                       int32_t height, int32_t width, int32_t size, float min_depth, float max_depth, const float* view, float focal_length,
-                       void* scratch, size_t scratch_bytes, void* stream) {
-    if (!x || !trig || !turbo || !viridis || !img || !bev || !view || !scratch) return fail(1, "null argument");
-    if (frames < 1 || height < 1 || width < 1 || size < 1) return fail(1, "render_frames: empty batch or image");
-    if (!(max_depth > 0.f)) return fail(1, "max_depth must be > 0");
-    if (scratch_bytes < render_frames_scratch_bytes(1, size))
-        return fail(1, "scratch too small: %zu bytes hold no frame of %zu", scratch_bytes, render_frames_scratch_bytes(1, size));
-    if ((uintptr_t)scratch & 255) return fail(1, "scratch must be 256-byte aligned");
-    HIP_TRY(launch_render_frames(x, trig, turbo, viridis, img, bev, frames, height, width, size, min_depth, max_depth, view, focal_length, scratch,
-                                 scratch_bytes, (hipStream_t)stream));
-    return 0;
-}
-
-static const char* project_geometry_error(int64_t total, int32_t batch, int32_t H, int32_t W) {
-    if (batch < 1 || batch > 65535) return "project: batch must be in [1, 65535]";
-    if (H < 1 || W < 1 || (int64_t)batch * H * W >= (1LL << 31)) return "project: the grid must have 1 to 2^31 - 1 cells over the batch";
-    if (total < 0 || total >= (1LL << 31)) return "project: 0 to 2^31 - 1 points over the batch";
-    return nullptr;
-}
-
-size_t r2dm_project_scratch_bytes(int64_t total_points, int32_t batch, int32_t height, int32_t width, int32_t scan_unfolding) {
-    return project_geometry_error(total_points, batch, height, width) ? 0 : project_scratch_bytes(total_points, batch, height, width, scan_unfolding);
-}
-
-int r2dm_project_scans(const float* points, const int64_t* offsets, float* out, int32_t batch, int32_t height, int32_t width, int32_t out_width,
-                       int32_t scan_unfolding, float min_depth, float max_depth, int32_t apply_mask, int32_t layout, void* scratch,
-                       size_t scratch_bytes, void* stream) {
-    if (!offsets || !out || !scratch) return fail(1, "null argument");
-    if (batch < 1 || batch > 65535) return fail(1, "project: batch must be in [1, 65535]");
-    if (offsets[0] != 0) return fail(1, "project: offsets[0] must be 0, got %lld", (long long)offsets[0]);
-    for (int32_t b = 0; b < batch; ++b)
-        if (offsets[b + 1] < offsets[b]) return fail(1, "project: offsets decrease at scan %d (%lld after %lld)", b, (long long)offsets[b + 1], (long long)offsets[b]);
-    const int64_t total = offsets[batch];
-    if (const char* msg = project_geometry_error(total, batch, height, width)) return fail(1, "%s", msg);
-    if (total > 0 && !points) return fail(1, "null argument");
-    if ((uintptr_t)points & 15) return fail(1, "project: points must be 16-byte aligned");
-    if (out_width < 1 || out_width > width) return fail(1, "project: out_width must be in [1, width], got %d", out_width);
-    if (layout != 0 && layout != 1) return fail(1, "layout must be 0 ((B,6,H,W) xyzrdm) or 1 ((B,5,H,W) samples)");
-    if ((scan_unfolding != 0 && scan_unfolding != 1) || (apply_mask != 0 && apply_mask != 1)) return fail(1, "project: scan_unfolding and apply_mask are 0 or 1");
-    const size_t need = project_scratch_bytes(total, batch, height, width, scan_unfolding);
-    if (scratch_bytes < need) return fail(1, "scratch too small: %zu < %zu bytes", scratch_bytes, need);
-    if ((uintptr_t)scratch & 255) return fail(1, "scratch must be 256-byte aligned");
-    HIP_TRY(launch_project_scans(points, reinterpret_cast<const long long*>(offsets), out, batch, height, width, out_width, scan_unfolding, min_depth,
-                                 max_depth, apply_mask, layout, scratch, (hipStream_t)stream));
-    return 0;
-}
-
-static const char* unproject_geometry_error(int32_t batch, int32_t H, int32_t W) {
-    if (batch < 1 || batch > 65535) return "unproject: batch must be in [1, 65535]";
-    if (H < 1 || W < 1 || (int64_t)batch * H * W >= (1LL << 31)) return "unproject: the images must have 1 to 2^31 - 1 pixels over the batch";
-    return nullptr;
-}
-
-size_t r2dm_unproject_scratch_bytes(int32_t batch, int32_t height, int32_t width) {
-    return unproject_geometry_error(batch, height, width) ? 0 : unproject_scratch_bytes(batch, height, width);
-}
-
-int r2dm_unproject(const float* src, int32_t layout, const float* ray_angles, const int32_t* row_start, float* points, int32_t* index,
-                   int64_t* offsets, int32_t batch, int32_t height, int32_t width, float min_depth, float max_depth, int32_t depth_format,
-                   float keep_min, float keep_max, void* scratch, size_t scratch_bytes, void* stream) {
-    if (!src || !points || !offsets || !scratch) return fail(1, "null argument");
-    if (layout != 0 && layout != 1) return fail(1, "layout must be 0 ((B,2,H,W) model samples) or 1 ((B,5,H,W) post-processed samples)");
-    if (layout == 0 && !ray_angles) return fail(1, "unproject: layout 0 needs ray_angles (null argument)");
-    if (depth_format < 0 || depth_format > 2) return fail(1, "depth_format must be 0 (log_depth), 1 (inverse_depth) or 2 (depth)");
-    if (const char* msg = unproject_geometry_error(batch, height, width)) return fail(1, "%s", msg);
-    if ((uintptr_t)points & 15) return fail(1, "unproject: points must be 16-byte aligned");
-    if ((uintptr_t)offsets & 7) return fail(1, "unproject: offsets must be 8-byte aligned");
-    const size_t need = unproject_scratch_bytes(batch, height, width);
-    if (scratch_bytes < need) return fail(1, "scratch too small: %zu < %zu bytes", scratch_bytes, need);
-    if ((uintptr_t)scratch & 255) return fail(1, "scratch must be 256-byte aligned");
-    HIP_TRY(launch_unproject(src, layout, ray_angles, row_start, points, index, reinterpret_cast<long long*>(offsets), batch, height, width, min_depth,
-                             max_depth, depth_format, keep_min, keep_max, scratch, (hipStream_t)stream));
-    return 0;
-}
-
-static int g_single_kernel_pieces = 2;  // r2dm_conv2d_ring (per-op tests)
-
 int r2dm_set_conv_pieces(r2dm_handle* h, int32_t pieces) {
     if (!h && (pieces == 4 || pieces == 5)) {  // per-op tests only: the fp32-input MFMA kernel as the yardstick of the split-operand kernels --
         g_single_kernel_pieces = pieces;       // 4: as the library runs it (two-level accumulation above 128 channels), 5: a plain fmaf chain
@@ -1423,10 +203,7 @@ int r2dm_set_conv_pieces(r2dm_handle* h, int32_t pieces) {
 int r2dm_profile_enable(r2dm_handle* h, int32_t on) {
     if (!h) return fail(1, "null argument");
     h->prof_on = on != 0;
-    h->prof_used = 0;
-    h->prof_flop = 0.0;
-    h->prof_cls.clear();
-    h->prof_lflop.clear();
+    h->prof_reset();
     return 0;
 }
 
@@ -1462,254 +239,39 @@ int r2dm_profile_event_overhead(r2dm_handle* h, void* stream, double* empty_pair
     return rc;
 }
 
-int r2dm_profile_read_classes(r2dm_handle* h, double* ms3, double* flop3, int64_t* launches3) {
-    if (!h || !ms3 || !flop3 || !launches3) return fail(1, "null argument");
+// one pass over the bracketed launches since the last read: time, flops and count per class, and the time of all of them
+static int prof_collect(r2dm_handle* h, double* ms3, double* flop3, int64_t* launches3, double* total_ms) {
     for (int c = 0; c < 3; ++c) { ms3[c] = 0.0; flop3[c] = 0.0; launches3[c] = 0; }
+    *total_ms = 0.0;
     for (size_t i = 0; i + 1 < h->prof_used && i / 2 < h->prof_cls.size(); i += 2) {
         HIP_TRY(hipEventSynchronize(h->prof_ev[i + 1]));
         float t = 0.f;
         HIP_TRY(hipEventElapsedTime(&t, h->prof_ev[i], h->prof_ev[i + 1]));
         const int c = h->prof_cls[i / 2];
+        *total_ms += t;
         ms3[c] += t;
         flop3[c] += h->prof_lflop[i / 2];
         launches3[c] += 1;
     }
-    h->prof_used = 0;
-    h->prof_flop = 0.0;
-    h->prof_cls.clear();
-    h->prof_lflop.clear();
+    return 0;
+}
+
+int r2dm_profile_read_classes(r2dm_handle* h, double* ms3, double* flop3, int64_t* launches3) {
+    if (!h || !ms3 || !flop3 || !launches3) return fail(1, "null argument");
+    double total_ms;
+    if (int rc = prof_collect(h, ms3, flop3, launches3, &total_ms)) return rc;
+    h->prof_reset();
     return 0;
 }
 
 int r2dm_profile_read(r2dm_handle* h, double* conv_ms, double* conv_flop, int64_t* launches) {
     if (!h || !conv_ms || !conv_flop || !launches) return fail(1, "null argument");
-    double ms = 0.0;
-    for (size_t i = 0; i + 1 < h->prof_used; i += 2) {
-        HIP_TRY(hipEventSynchronize(h->prof_ev[i + 1]));
-        float t = 0.f;
-        HIP_TRY(hipEventElapsedTime(&t, h->prof_ev[i], h->prof_ev[i + 1]));
-        ms += t;
-    }
-    *conv_ms = ms;
+    double ms3[3], flop3[3];
+    int64_t launches3[3];
+    if (int rc = prof_collect(h, ms3, flop3, launches3, conv_ms)) return rc;
     *conv_flop = h->prof_flop;
     *launches = (int64_t)(h->prof_used / 2);
-    h->prof_used = 0;
-    h->prof_flop = 0.0;
-    h->prof_cls.clear();
-    h->prof_lflop.clear();
-    return 0;
-}
-
-// ---- single-kernel entry points (unit parity tests) ---------------------------------------------
-int64_t r2dm_conv_packed_elems(int32_t cout, int32_t cin, int32_t ksize, int32_t B, int32_t H, int32_t W) {
-    const int taps = ksize * ksize;
-    int algo = conv_pick_algo(cin, cout, taps);
-    if (algo == ALGO_DIRECT) algo = ALGO_F32;  // scratch sized for the larger (fp32-MFMA) packing: either may be chosen
-    const int ct = algo == ALGO_BF16X3 ? conv_bf16x3_co_tile(cin, cout, (long)B * H * W) : conv_pick_co_tile(cout, taps, (long)B * H * W);
-    int64_t n = (int64_t)conv_packed_floats(algo, cin, cout, taps, ct, algo != ALGO_F32 ? cin : conv_cin_pad(cin, taps, ct));
-    if (algo == ALGO_BF16X3 && conv_f16x2_supported(cin, cout, taps, H, W)) n = std::max<int64_t>(n, conv_f16x2_packed_floats(cin, cout) + 64);
-    if (proj_f16x2_supported(cin, cout, taps, H, W)) n = std::max<int64_t>(n, proj_f16x2_packed_floats(cin, cout) + 64);
-    return n;
-}
-
-// (per-kernel tests of the fp16 activation storage: R2DM_TEST_IO16 bit 0 -- x holds fp16, bit 1 -- y will; the caller passes tensors of that type)
-static int test_io16() {
-    const char* e = getenv("R2DM_TEST_IO16");
-    return e ? atoi(e) : 0;
-}
-
-int r2dm_conv2d_ring(const float* x, const float* w, const float* bias, float* w_packed, const float* aff,
-                     int32_t prologue, const float* residual, const float* scale, float* y, int32_t B, int32_t cin,
-                     int32_t cout, int32_t H, int32_t W, int32_t ksize, void* stream) {
-    if (!x || !w || !bias || !w_packed || !y) return fail(1, "null argument");
-    if (ksize != 1 && ksize != 3) return fail(1, "kernel size must be 1 or 3");
-    hipStream_t st = (hipStream_t)stream;
-    ConvParams p;
-    p.taps = ksize * ksize;
-    p.pieces = 3;
-    p.algo = conv_pick_algo(cin, cout, p.taps);
-    if (g_single_kernel_pieces >= 4 && p.algo != ALGO_DIRECT) {  // (test hook: the fp32-input MFMA kernel)
-        p.algo = ALGO_F32;
-        p.pieces = g_single_kernel_pieces;
-    }
-    // (the few-input kernel -- in_conv in the engine -- where the fp16-storage test hook asks for it: plain convolutions only)
-    if (test_io16() && conv_few_in_supported(cin, cout, p.taps, H, W) && prologue == PRO_NONE && !scale) p.algo = ALGO_DIRECT;
-    if (p.algo == ALGO_DIRECT && cout <= 4 && (prologue != PRO_NONE || residual || scale || W % 4 != 0)) p.algo = ALGO_F32;  // plain convolutions of 16-byte rows only
-                                                                                                             // (any other width runs on the fp32-MFMA kernel)
-    // per-op tests: with pieces = 2 every shape the f16x2 kernel covers goes there (the engine restricts it to normalised inputs)
-    if (p.algo == ALGO_BF16X3 && g_single_kernel_pieces != 3 && conv_f16x2_supported(cin, cout, p.taps, H, W)) p.algo = ALGO_F16X2;
-    if (p.algo == ALGO_F32 && g_single_kernel_pieces < 3 && prologue != PRO_AFFINE_SILU && proj_f16x2_supported(cin, cout, p.taps, H, W)) p.algo = ALGO_P1F16;
-    if (p.algo == ALGO_F16X2 || p.algo == ALGO_P1F16) p.pieces = g_single_kernel_pieces;
-    p.co_tile = p.algo == ALGO_F16X2 ? conv_f16x2_pick_co_tile(cin, cout, H, W, (long)B * H * W, &p.px_rows) : p.algo == ALGO_P1F16 ? 64 : p.algo == ALGO_BF16X3 ? conv_bf16x3_co_tile(cin, cout, (long)B * H * W) : conv_pick_co_tile(cout, p.taps, (long)B * H * W);
-    p.CinPad = p.algo != ALGO_F32 ? cin : conv_cin_pad(cin, p.taps, p.co_tile);
-    if (p.algo == ALGO_F16X2) {  // the range flag and the weight scale: behind the packed weights (r2dm_conv_packed_elems reserves 64 floats)
-        float* tail = w_packed + conv_f16x2_packed_floats(cin, cout);
-        HIP_TRY(hipMemsetAsync(tail, 0, sizeof(int), st));
-        HIP_TRY(launch_pack_conv_f16x2(w, w_packed, cout, cin, (int*)tail, st, tail + 2, p.co_tile, p.px_rows));
-        p.wscale = tail + 3;
-    } else if (p.algo == ALGO_P1F16) {
-        float* tail = w_packed + proj_f16x2_packed_floats(cin, cout);
-        HIP_TRY(hipMemsetAsync(tail, 0, sizeof(int), st));
-        HIP_TRY(launch_pack_proj_f16x2(w, w_packed, cout, cin, (int*)tail, st, tail + 2));
-        p.wscale = tail + 3;
-    } else {
-        HIP_TRY(launch_pack_conv(w, w_packed, cout, cin, p.taps, p.co_tile, p.CinPad, st, p.algo));
-    }
-    p.x = Src{x, nullptr, cin, 0, (long)cin * H * W, 0};
-    p.w = w_packed;
-    p.bias = bias;
-    p.aff = (const float2*)aff;
-    p.res = residual;
-    p.res_bs = (long)cout * H * W;
-    p.scale = scale;
-    p.y = y;
-    p.y_bs = (long)cout * H * W;
-    p.B = B;
-    p.H = H;
-    p.W = W;
-    p.Cin = cin;
-    p.Cout = cout;
-    p.prologue = prologue;
-    // per-kernel tests of the fp16 activation storage (conv_f16x2.hip, one-plane mode): R2DM_TEST_IO16 = 1 (x holds fp16), 2 (y and the
-    // residual hold fp16) or 3 -- the caller passes tensors of that type behind the float pointers
-    if (const char* e = getenv("R2DM_TEST_IO16"); e && (atoi(e) & 3)) {  // (bit 2 alone: only the kernel selection above -- the fp32 twin of a storage test)
-        if (!((p.algo == ALGO_F16X2 && p.pieces == 1) || p.algo == ALGO_DIRECT || (p.algo == ALGO_P1F16 && p.pieces == 1)))
-            return fail(1, "R2DM_TEST_IO16: this shape / mode runs on a kernel without fp16 storage");  // (never write a type the caller did not allocate)
-        p.x16 = atoi(e) & 1;  // (round 6: also the in / out convolutions -- bit 1 / bit 0 -- and, with both bits, the fp16-operand 1 x 1 convolution)
-        p.y16 = (atoi(e) >> 1) & 1;
-    }
-    // perf probe (scripts/conv_phases.py): per-block s_memtime stamps into a caller-provided device buffer
-    if (const char* e = getenv("R2DM_CONV_PROF_PTR")) p.prof = (unsigned long long*)strtoull(e, nullptr, 0);
-    // per-kernel tests / probes of the operand pre-pass (presplit.hip + conv_f16x2's PRO_PRESPLIT stagers): R2DM_F2_PRESPLIT=1
-    float* xs = nullptr;
-    if (const char* e = getenv("R2DM_F2_PRESPLIT"); e && atoi(e) && p.algo == ALGO_F16X2 && p.co_tile == 64 && p.px_rows == 4 && presplit_supported(p.x, cin, H, W)) {
-        static float* scratch = nullptr;  // (test entry: one growing scratch buffer, never freed)
-        static size_t scratch_floats = 0;
-        const size_t need = (size_t)presplit_floats(B, cin, H, W);
-        if (need > scratch_floats) {
-            HIP_TRY(hipDeviceSynchronize());
-            if (scratch) HIP_TRY(hipFree(scratch));
-            HIP_TRY(hipMalloc(&scratch, need * sizeof(float)));
-            scratch_floats = need;
-        }
-        xs = scratch;
-        HIP_TRY(launch_presplit(p.x, p.aff, prologue, xs, B, cin, H, W, st));
-        p.x = Src{xs, nullptr, cin, 0, presplit_floats(1, cin, H, W), 0};
-        p.prologue = PRO_PRESPLIT;
-        p.aff = nullptr;
-    }
-    HIP_TRY(launch_conv(p, st));
-    return 0;
-}
-
-size_t r2dm_group_norm_scratch_bytes(int32_t B, int32_t groups) { return (size_t)B * groups * 256 * (2 * sizeof(double) + sizeof(float)); }
-
-int r2dm_group_norm_affine(const float* x, const float* gamma, const float* beta, const float* ada, void* scratch,
-                           float* aff, float* stats, int32_t B, int32_t C, int32_t H, int32_t W, int32_t groups,
-                           float eps, void* stream) {
-    if (!x || !scratch || !aff) return fail(1, "null argument");
-    GNParams g{Src{x, nullptr, C, 0, (long)C * H * W, 0}, B, H, W, groups, eps, gamma, beta, ada, 2L * C,
-               (double*)scratch, (float2*)aff, stats};
-    g.partial_max = (float*)((double*)scratch + (size_t)B * groups * 256 * 2);
-    HIP_TRY(launch_group_norm(g, (hipStream_t)stream));
-    return 0;
-}
-
-int r2dm_affine_act(const float* x, const float* aff, float* y, int32_t B, int32_t C, int64_t hw, int32_t silu,
-                    void* stream) {
-    HIP_TRY(launch_gn_apply(x, (const float2*)aff, y, B, C, hw, silu, (hipStream_t)stream));
-    return 0;
-}
-
-int r2dm_fir_down2(const float* x, float* y, int32_t B, int32_t C, int32_t H, int32_t W, void* stream) {
-    HIP_TRY(launch_fir_down2(x, (long)C * H * W, y, (long)C * (H / 2) * (W / 2), B, C, H, W, (hipStream_t)stream, nullptr, 0, test_io16() & 1, (test_io16() >> 1) & 1));
-    return 0;
-}
-
-int32_t r2dm_fir_down2_stat_slots(int32_t C, int32_t G, int32_t H, int32_t W) {
-    return fir_down2_stat_slots(C, G, H, W) ? conv_stat_slots(H / 2, W / 2) : 0;
-}
-
-int r2dm_fir_down2_stats(const float* x, float* y, double* stat, int32_t B, int32_t C, int32_t G, int32_t H, int32_t W, void* stream) {
-    if (!stat || !fir_down2_stat_slots(C, G, H, W)) return fail(1, "fir_down2_stats: geometry without a statistics variant");
-    HIP_TRY(launch_fir_down2(x, (long)C * H * W, y, (long)C * (H / 2) * (W / 2), B, C, H, W, (hipStream_t)stream, stat, G, test_io16() & 1, (test_io16() >> 1) & 1));
-    return 0;
-}
-
-int r2dm_down_planes(const float* x, float* planes, int32_t B, int32_t C, int32_t H, int32_t W, void* stream) {
-    if (!x || !planes) return fail(1, "null argument");
-    if (B < 1 || C < 1 || !down_planes_supported(H, W)) return fail(1, "down_planes: needs height %% 4 == 0 and width %% 8 == 0 (>= 16)");
-    HIP_TRY(launch_down_planes(x, (long)C * H * W, planes, 9L * C * (H / 2) * (W / 2), B, C, H, W, (hipStream_t)stream));
-    return 0;
-}
-
-int32_t r2dm_down_gemm_stat_slots(int32_t cin, int32_t cout, int32_t G, int32_t H, int32_t W) {
-    if (H < 4 || W < 16 || !down_planes_supported(H, W) || !proj_f16x2_supported(9 * cin, cout, 1, H / 2, W / 2)) return 0;
-    const int cpg = G > 0 && cout % G == 0 ? cout / G : 0;
-    return cpg >= 8 && cpg <= 64 && !(cpg & (cpg - 1)) ? conv_stat_slots(H / 2, W / 2) : 0;
-}
-
-int r2dm_down_gemm(const float* x, const float* w, const float* bias, float* w_packed, float* planes, float* y, double* stat, int32_t B, int32_t cin,
-                   int32_t cout, int32_t G, int32_t H, int32_t W, void* stream) {
-    if (!x || !w || !bias || !w_packed || !planes || !y) return fail(1, "null argument");
-    if (B < 1 || H < 4 || W < 16 || !down_planes_supported(H, W) || !proj_f16x2_supported(9 * cin, cout, 1, H / 2, W / 2))
-        return fail(1, "down_gemm: needs cin %% 32 == 0, cout %% 64 == 0, height %% 8 == 0, width %% 128 == 0");
-    if (stat && !r2dm_down_gemm_stat_slots(cin, cout, G, H, W)) return fail(1, "down_gemm: no statistics for %d groups of %d channels", G, cout);
-    hipStream_t st = (hipStream_t)stream;
-    // the range flag and the weight scale: behind the packed weights (the caller reserves 64 floats), as r2dm_conv2d_ring
-    float* tail = w_packed + proj_f16x2_packed_floats(9 * cin, cout);
-    HIP_TRY(hipMemsetAsync(tail, 0, sizeof(int), st));
-    HIP_TRY(launch_pack_proj_f16x2(w, w_packed, cout, 9 * cin, (int*)tail, st, tail + 2, 9));
-    const int Ho = H / 2, Wo = W / 2;
-    HIP_TRY(launch_down_planes(x, (long)cin * H * W, planes, 9L * cin * Ho * Wo, B, cin, H, W, st));
-    ConvParams p;
-    p.x = Src{planes, nullptr, 9 * cin, 0, 9L * cin * Ho * Wo, 0};
-    p.w = w_packed;
-    p.bias = bias;
-    p.aff = nullptr;
-    p.res = nullptr;
-    p.res_bs = 0;
-    p.scale = nullptr;
-    p.y = y;
-    p.y_bs = (long)cout * Ho * Wo;
-    p.B = B;
-    p.H = Ho;
-    p.W = Wo;
-    p.Cin = p.CinPad = 9 * cin;
-    p.Cout = cout;
-    p.taps = 1;
-    p.co_tile = 64;
-    p.prologue = PRO_NONE;
-    p.algo = ALGO_P1F16;
-    p.pieces = 2;
-    p.wscale = tail + 3;
-    if (stat) {
-        p.stat = stat;
-        p.stat_G = G;
-        p.stat_goff = 0;
-        p.stat_cpg = cout / G;
-        p.stat_slots = conv_stat_slots(Ho, Wo);
-    }
-    HIP_TRY(launch_proj_f16x2(p, st, /*bias_rowfac=*/true));
-    return 0;
-}
-
-int r2dm_fir_up2(const float* x, float* y, int32_t B, int32_t C, int32_t H, int32_t W, void* stream) {
-    HIP_TRY(launch_fir_up2(x, (long)C * H * W, y, (long)C * H * W * 4, B, C, H, W, (hipStream_t)stream, nullptr, test_io16() & 1, (test_io16() >> 1) & 1));
-    return 0;
-}
-
-int r2dm_attention(const float* qkv, float* out, int32_t B, int32_t C, int32_t heads, int32_t N, void* stream) {
-    if (!attention_supported(C, heads, N)) return fail(1, "attention: unsupported shape C=%d heads=%d N=%d", C, heads, N);
-    HIP_TRY(launch_attention(qkv, out, B, C, heads, N, (hipStream_t)stream, g_single_kernel_pieces >= 3 ? 0 : g_single_kernel_pieces));  // (per-op tests cover all three)
-    return 0;
-}
-
-int r2dm_time_embedding(const float* cond, const float* freqs, const float* w1, const float* b1, const float* w2,
-                        const float* b2, float* act, float* hidden, int32_t B, int32_t base, int32_t T, void* stream) {
-    if (!cond || !freqs || !w1 || !b1 || !w2 || !b2 || !act || !hidden) return fail(1, "null argument");
-    EmbedParams e{cond, freqs, w1, b1, w2, b2, act, hidden, B, base, T};
-    HIP_TRY(launch_time_embedding(e, (hipStream_t)stream));
+    h->prof_reset();
     return 0;
 }
 

@@ -1,0 +1,658 @@
+// The forward walk: r2dm_unet_forward replaces EfficientUNet.forward (efficient_unet.py:269-295).  run_forward walks the eight U-Net
+// stages and enqueues the HIP kernels of this library on the caller's stream.  Nothing here allocates or synchronises: weights live
+// in a caller-owned blob, activations in a caller-owned workspace carved by a deterministic first-fit arena (the same walk run "dry"
+// yields r2dm_workspace_bytes).
+#include "engine.h"
+
+using namespace r2dm;
+
+namespace {
+
+const bool g_debug_sync = getenv("R2DM_DEBUG_SYNC") != nullptr;  // fault hunting: wait for and name every launch (read once)
+
+inline Src src1(const Tensor& t) { return Src{t.p, nullptr, t.C, 0, t.bs(), 0}; }
+inline Src src2(const Tensor& a, const Tensor& b) { return Src{a.p, b.p, a.C, b.C, a.bs(), b.bs()}; }
+
+struct Ctx {
+    r2dm_handle* h;
+    Arena* ar;
+    hipStream_t st;
+    int B;
+    const float* proj;  // [B][ada_rows]
+    double* gn_partial;
+    hipError_t err = hipSuccess;
+    const char* where = "";
+    int f2_launches = 0;  // conv_f16x2 launches of this forward so far (odd ones walk their tiles backwards: ConvParams::reverse)
+    int last_reverse = -1;  // direction of the last conv_f16x2 launch (-1: none yet / another kernel)
+    // the fp16 operand range guard, one slot per guarded producer ("site") of the forward, in walk order; `ctx`: which layer the walk is in
+    int n_sites = 0;
+    std::string ctx;
+    int* range_site(const char* what) {
+        static const bool shared = getenv("R2DM_RANGE_SHARED") != nullptr;  // (probe: one slot for the whole forward, as until round 5 -- profiles/r06_range_slots.txt)
+        const int k = shared ? 0 : n_sites + 1 < r2dm_handle::RANGE_SITES ? ++n_sites : 0;  // (beyond the table: the shared slot 0 -- still guarded, just not named)
+        if ((int)h->site_names.size() <= k) h->site_names.resize(k + 1);
+        h->site_names[k] = ctx.empty() ? std::string(what) : ctx + ": " + what;
+        return (int*)blob(h->range_flag) + 2 * k;
+    }
+
+    // (once the arena has handed out a pointer beyond the caller's workspace NOTHING more is launched -- the walk goes on
+    // dry, so `peak` still comes out right for the error message -- instead of enqueueing kernels that write outside the workspace)
+    bool dry() const { return ar->dry || ar->overflow; }
+    void note(hipError_t e, const char* w) {
+        const bool debug_sync = g_debug_sync;  // fault hunting: wait for and name every launch
+        if (debug_sync && e == hipSuccess && !dry()) {
+            fprintf(stderr, "[r2dm] %s ...", w);
+            fflush(stderr);
+            e = hipStreamSynchronize(st);
+            fprintf(stderr, " %s\n", e == hipSuccess ? "ok" : hipGetErrorString(e));
+        }
+        if (e != hipSuccess && err == hipSuccess) {
+            err = e;
+            where = w;
+        }
+    }
+    const float* blob(size_t off) const { return h->blob + off; }
+
+    Tensor make(int C, int H, int W, bool f16 = false) {
+        Tensor t;
+        t.C = C;
+        t.H = H;
+        t.W = W;
+        t.f16 = f16;
+        t.p = (float*)ar->alloc(t.bytes(B));
+        return t;
+    }
+    // fp16 storage of EVERY activation of the two full-resolution levels (round 6; the one-plane mode = the reference's fp16 autocast, which stores its
+    // activations as fp16: sample_and_save.py:45,70): those levels hold 92 % of a forward's activation bytes and their launches are the ones next
+    // to the HBM roof; levels 3 and 4 (attention, 1 x 1 projections with residuals and statistics) stay fp32.  all16: decided once per forward (run_forward).
+    bool all16 = false;
+    bool lvl16(int Hres) const { return all16 && 2 * Hres >= h->cfg.height; }
+    void drop(const Tensor& t) { ar->release(t.p); }
+
+    // Fused statistics: a convolution whose output feeds a GroupNorm leaves per-(sample, group) partial sums in a
+    // Sink from its epilogue; the GroupNorm then only runs the finalize kernel (no extra pass over the tensor).
+    struct Sink {
+        double* p = nullptr;
+        int C = 0, cpg = 0, slots = 0;  // C: channels of the normalised (possibly concatenated) tensor
+        bool incomplete = false;        // a producer could not emit its share: the consumer runs the streaming pass instead
+        explicit operator bool() const { return p != nullptr && !incomplete; }
+    };
+    Sink make_sink(int C_total, int H, int W) {
+        Sink k;
+        const int G = h->cfg.gn_num_groups;
+        const int cpg = C_total / G;
+        // the epilogue reduction (conv_epilogue.h) merges whole 8-channel blocks of ONE wave: groups must be 8, 16, 32 or
+        // 64 channels so that they never straddle waves; anything else takes the separate streaming pass
+        if (C_total % G || cpg < 8 || cpg > 64 || (cpg & (cpg - 1))) return k;
+        k.C = C_total;
+        k.cpg = cpg;
+        k.slots = conv_stat_slots(H, W);
+        k.p = (double*)ar->alloc((size_t)B * G * k.slots * 2 * sizeof(double));
+        return k;
+    }
+    void drop_sink(Sink& k) {
+        if (k.p) ar->release(k.p);
+        k.p = nullptr;
+    }
+    // which convolution kernels write fused statistics: the split-bf16 kernels and the fp32-MFMA kernel with >= 64-channel
+    // tiles; the 32-channel fp32 tile (Cout <= 32) and the direct kernel do not
+    static bool emits_stats(const ConvLayer& L) {
+        return L.algo == ALGO_BF16X3 || (L.algo == ALGO_F32 && L.co_tile >= 64) || (L.algo == ALGO_DIRECT && L.cout > 4);
+    }  // (and ALGO_F16X2, a second packing of a BF16X3 layer)
+    float2* finalize(const Sink& k, int H, int W, const float* gamma, const float* beta, const float* ada) {
+        float2* aff = (float2*)ar->alloc((size_t)B * k.C * sizeof(float2));
+        if (!dry()) {
+            GNParams g{Src{}, B, H, W, h->cfg.gn_num_groups, h->cfg.gn_eps, gamma, beta, ada, (long)h->ada_rows, k.p, aff,
+                       nullptr};
+            // (range guard of the fp16 consumers: the slot energies bound max|x| -- norm.hip; no separate maximum is recorded)
+            if (h->f16_path()) g.range_flag = range_site("GroupNorm output bound |a| M + |d| (gn_finalize)");  // (only the fp16 operand paths have a range to guard)
+            note(launch_group_norm_finalize(g, k.C, k.slots, st), "group_norm_finalize");
+        }
+        return aff;
+    }
+    // GroupNorm of `x`: from fused statistics when the producer left them, else with the streaming statistics pass
+    float2* norm(const Sink& k, const Src& x, int H, int W, const float* gamma, const float* beta, const float* ada) {
+        return k ? finalize(k, H, W, gamma, beta, ada) : group_norm(x, H, W, gamma, beta, ada);
+    }
+
+    float2* group_norm(const Src& x, int H, int W, const float* gamma, const float* beta, const float* ada) {
+        const int C = x.c0 + x.c1;
+        float2* aff = (float2*)ar->alloc((size_t)B * C * sizeof(float2));
+        if (!dry()) {
+            GNParams g{x, B, H, W, h->cfg.gn_num_groups, h->cfg.gn_eps, gamma, beta, ada, (long)h->ada_rows,
+                       gn_partial, aff, nullptr};
+            g.partial_max = (float*)(gn_partial + (size_t)B * h->cfg.gn_num_groups * 256 * 2);
+            if (h->f16_path()) g.range_flag = range_site("GroupNorm output bound |a| max|x| + |d| (streaming statistics)");  // (only the fp16 operand paths have a range to guard)
+            note(launch_group_norm(g, st), "group_norm");
+        }
+        return aff;
+    }
+
+    // The GroupNorm in front of a convolution: the statistics its producers left (or not: the streaming pass) and its parameters.
+    // conv() with a NormSpec runs the norm itself -- folded into the convolution's staging waves where conv_f16x2.hip can do that (no
+    // gn_finalize launch: 45 of the 50 GroupNorms of a forward at batch 8), else as the separate launch(es) in front of it.
+    struct NormSpec {
+        const Sink* stats;
+        const float *gamma, *beta, *ada;
+    };
+
+    // in-stream timing of a launch: records the opening event and returns the closing one (nullptr: profiling off)
+    hipEvent_t prof_begin(int cls, double flop) {
+        if (!h->prof_on) return nullptr;
+        if (h->prof_used + 2 > h->prof_ev.size()) {
+            hipEvent_t a, c;
+            if (hipEventCreate(&a) == hipSuccess && hipEventCreate(&c) == hipSuccess) {
+                h->prof_ev.push_back(a);
+                h->prof_ev.push_back(c);
+            }
+        }
+        if (h->prof_used + 2 > h->prof_ev.size()) return nullptr;
+        hipEvent_t e0 = h->prof_ev[h->prof_used], e1 = h->prof_ev[h->prof_used + 1];
+        h->prof_used += 2;
+        h->prof_flop += flop;
+        h->prof_cls.push_back(cls);
+        h->prof_lflop.push_back(flop);
+        (void)hipEventRecord(e0, st);
+        return e1;
+    }
+
+    // what a convolution launch does beyond its layer, input and resolution
+    struct ConvOpts {
+        int prologue = PRO_NONE;
+        const float2* aff = nullptr;     // (a, d) of the prologue's GroupNorm, unless `norm` gives it
+        const NormSpec* norm = nullptr;  // `aff` comes from this GroupNorm (aff must be nullptr)
+        const Tensor* res = nullptr;     // residual added to the output ...
+        bool res_broadcast = false;      // ... one map for the whole batch
+        const float* scale = nullptr;    // device scalar multiplied after the residual add
+        float* dst = nullptr;            // the output goes here, not into a fresh tensor
+        const Sink* sink = nullptr;      // fused statistics of the output, groups from `goff` on
+        int goff = 0;
+        bool input_bounded = false;      // its producer tracked max|x| in the range flag
+        bool track_out = false;          // record max|y| there (the fp16 operand paths only)
+        bool x16 = false, y16 = false;   // fp16 storage of the input / of the output (+ residual): act16(L) launches only
+    };
+
+    Tensor conv(const ConvLayer& L, const Src& x, int H, int W, const ConvOpts& o) {
+        const int pro = o.prologue;
+        const NormSpec* ns = o.norm;
+        const float2* aff = o.aff;
+        // (decided in the dry walk as well, from shapes and the batch alone: the allocation sequence must be the same in both walks)
+        bool fold = false, pre_fold = false;
+        float2* own_aff = nullptr;
+        if (ns) {
+            const Sink& k = *ns->stats;
+            const int G = h->cfg.gn_num_groups;
+            if (k && L.f2 && h->f16_path() && k.C == L.cin && G == 8) {
+                ConvParams q;
+                q.Cin = L.cin; q.Cout = L.cout; q.taps = L.taps; q.H = H; q.W = W; q.co_tile = L.f2_cot; q.px_rows = L.f2_rows; q.B = B; q.prologue = pro;
+                const int slots = k.cpg < 64 ? k.slots / 2 : k.slots;  // (groups of fewer than 64 channels leave the second half of their slots zero)
+                q.reverse = 0;
+                fold = conv_f16x2_fold_supported(q, G, slots);
+                q.reverse = 1;  // (whichever direction this launch will walk its tiles in)
+                fold = fold && conv_f16x2_fold_supported(q, G, slots);
+            }
+            // Round 6 EXPERIMENT, off by default (R2DM_F2_PRESPLIT_NARROW=1): the launches on 32-channel tiles (u_block4: eight output-channel tiles stage the
+            // same x tile, the stagers bound a chunk at 4.5 k cycles for 1.7 k of MFMAs) take their input through the operand pre-pass with the GroupNorm
+            // folded into THAT pass (presplit_fold_kernel): bit-identical; the convolutions go 43.8 -> 28.7 us and 78.3 -> 51.7 us, and the six 12.4 us passes
+            // (a launch + three dependent round trips over an 8 MB tensor) take it all back: step 5.894 | 5.895 ms (profiles/r06_narrow_presplit.txt).
+            // (=2: also the 512 -> 512 launches of level 4 on 64-channel tiles, eight output-channel tiles per x tile as well)
+            const bool narrow_tile = L.f2_cot == 32 || (narrow_presplit() >= 2 && L.f2_cot == 64 && L.cout >= 512);
+            if (k && narrow_presplit() && L.f2 && narrow_tile && L.f2_rows == 4 && h->conv_pieces == 2 && G == 8 && k.C == L.cin && presplit_supported(x, L.cin, H, W)) {
+                fold = false;
+                pre_fold = true;
+            }
+            if (!fold && !pre_fold) aff = own_aff = norm(k, x, H, W, ns->gamma, ns->beta, ns->ada);
+        }
+        Tensor y;
+        y.C = L.cout;
+        y.H = H;
+        y.W = W;
+        y.f16 = o.y16;
+        y.p = o.dst ? o.dst : (float*)ar->alloc(y.bytes(B));
+        // (decided in the dry walk as well: the consumer's choice between finalize and the streaming pass changes the
+        // allocation sequence, which must be the same in both walks)
+        const bool fused_stats = o.sink && o.sink->p && emits_stats(L);
+        if (o.sink && o.sink->p && !fused_stats) const_cast<Sink*>(o.sink)->incomplete = true;
+        // The operand pre-pass (presplit.hip) is an EXPERIMENT, off by default: R2DM_F2_PRESPLIT_MIN_COUT=256 sends the layers with >= 256
+        // output channels through it.  Round-4 A/B (profiles/r04_presplit.txt): bit-identical outputs, conv_f16x2's own roofline fraction
+        // 0.387 -> 0.403, the STEP 1.7 % slower (6.19 -> 6.30 ms): the pass costs more than the staging waves' transform did -- with the
+        // stagers idle a chunk still takes 4.5 k cycles (multipliers + three barriers; 5.2 k before), prologue / tile ends / tail are unchanged.
+        // (decided in both walks: the allocation sequence must be the same)
+        static const int presplit_min_cout = getenv("R2DM_F2_PRESPLIT_MIN_COUT") ? atoi(getenv("R2DM_F2_PRESPLIT_MIN_COUT")) : 0;  // (0: never)
+        const bool f2_launch = L.f2 && h->f16_path() && (pro != PRO_NONE || o.input_bounded);
+        float* xs = nullptr;
+        if (f2_launch && !fold && L.f2_cot == 64 && L.f2_rows == 4 && presplit_min_cout > 0 && L.cout >= presplit_min_cout && presplit_supported(x, L.cin, H, W))
+            xs = (float*)ar->alloc((size_t)presplit_floats(B, L.cin, H, W) * sizeof(float));
+        if (f2_launch && pre_fold && !xs) xs = (float*)ar->alloc((size_t)presplit_floats(B, L.cin, H, W) * sizeof(float));
+        if (!dry()) {
+            ConvParams p = conv_params(x, blob(L.w), blob(L.b), y.p, y.bs(), B, H, W, L.cin, L.cin_pad, L.cout, L.taps, L.co_tile, L.algo, pro);
+            p.aff = aff;
+            p.res = o.res ? o.res->p : nullptr;
+            p.res_bs = o.res && !o.res_broadcast ? o.res->bs() : 0;
+            p.scale = o.scale;
+            p.x16 = o.x16;  // (conv_f16x2 launches, the direct in / out convolutions and the fp16-operand skip convolutions take them; checked below)
+            p.y16 = o.y16;
+            // the fp16 split where the input's range is guarded: GroupNorm-normalised (gn_finalize's bound) or tracked by its
+            // producer (fir_up2's running maximum)
+            if (f2_launch) {
+                static const int rev_mode = getenv("R2DM_TILE_ORDER") ? atoi(getenv("R2DM_TILE_ORDER")) : 1;  // 0: always ascending (experiments)
+                p.reverse = rev_mode ? (f2_launches++ & 1) : 0;
+                last_reverse = p.reverse;
+                p.algo = ALGO_F16X2;
+                p.w = blob(L.w_f2);
+                p.wscale = blob(L.ws_f2) + 1;
+                p.co_tile = L.f2_cot;
+                p.px_rows = L.f2_rows;
+                p.pieces = (L.f2_cot == 32 && narrow_split()) ? 2 : h->conv_pieces;
+                if (fold) {
+                    const Sink& k = *ns->stats;
+                    p.gn_partial = k.p;
+                    p.gn_stride = k.slots;
+                    p.gn_slots = k.cpg < 64 ? k.slots / 2 : k.slots;
+                    p.gn_cpg = k.cpg;
+                    p.gn_eps = h->cfg.gn_eps;
+                    p.gn_gamma = ns->gamma;
+                    p.gn_beta = ns->beta;
+                    p.gn_ada = ns->ada;
+                    p.gn_ada_stride = (long)h->ada_rows;
+                    p.gn_range = range_site("GroupNorm output bound |a| M + |d| (folded into the convolution)");
+                }
+            }
+            // deep layers (many 64-channel output tiles): the input transform once, by the pre-pass (presplit.hip)
+            if (xs) {
+                if (pre_fold) {
+                    const Sink& k = *ns->stats;
+                    note(launch_presplit_fold(x, pro, xs, B, L.cin, H, W, k.p, k.slots, k.cpg < 64 ? k.slots / 2 : k.slots, k.cpg, h->cfg.gn_eps, ns->gamma, ns->beta, ns->ada,
+                                              (long)h->ada_rows, range_site("GroupNorm output bound |a| M + |d| (folded into the operand pre-pass)"), st), "presplit_fold");
+                } else
+                    note(launch_presplit(x, aff, pro, xs, B, L.cin, H, W, st), "presplit");
+                p.x = Src{xs, nullptr, L.cin, 0, presplit_floats(1, L.cin, H, W), 0};
+                p.prologue = PRO_PRESPLIT;
+                p.aff = nullptr;
+            }
+            if (L.p1 && h->f16_path() && pro != PRO_AFFINE_SILU && (pro != PRO_NONE || o.input_bounded)) {
+                p.algo = ALGO_P1F16;
+                // (a skip convolution reads the tensor its block's conv1 has just read: start where that walk ended.  R2DM_PROJ_ORDER=0: always forwards)
+                static const bool proj_rev = !getenv("R2DM_PROJ_ORDER") || atoi(getenv("R2DM_PROJ_ORDER")) != 0;
+                p.reverse = proj_rev && last_reverse == 0 ? 1 : 0;
+                p.w = blob(L.w_p1);
+                p.wscale = blob(L.ws_p1) + 1;
+                p.co_tile = 64;
+                p.pieces = h->conv_pieces;
+            }
+            // (every MFMA kernel records the maximum; the direct kernels' outputs never feed an fp16 operand unnormalised)
+            if (o.track_out && h->f16_path() && p.algo != ALGO_DIRECT) p.range = range_site("max|output| (raw input of the next fp16-operand kernel)");
+            if (fused_stats) {
+                p.stat = o.sink->p;
+                p.stat_G = h->cfg.gn_num_groups;
+                p.stat_goff = o.goff;
+                p.stat_cpg = o.sink->cpg;
+                p.stat_slots = o.sink->slots;
+            }
+            if ((o.x16 || o.y16) && p.algo != ALGO_F16X2 && p.algo != ALGO_DIRECT && p.algo != ALGO_P1F16) note(hipErrorInvalidValue, "fp16 storage on a kernel without it");
+            if (o.x16 && !fold && !pre_fold && own_aff && !(ns && *ns->stats)) note(hipErrorInvalidValue, "fp16 storage behind a streaming GroupNorm");
+            // ALGORITHMIC flops of the reference's convolution (in_conv: all 34 input channels, although the
+            // constant Fourier half is folded into a bias map here)
+            hipEvent_t e1 = prof_begin(p.algo == ALGO_F16X2 ? 0 : p.algo == ALGO_BF16X3 ? 1 : 2, 2.0 * B * (double)L.cout * (L.src_cin ? L.src_cin : L.cin) * L.taps * H * W);
+            if (g_debug_sync)
+                fprintf(stderr, "[r2dm] conv algo %d %d->%d taps %d co_tile %d %dx%d B %d pro %d w %p bias %p gn %p blob [%p, +%zu) x %p/%p (c0 %d) y %p res %p aff %p stat %p ws [%p, +%zu)\n", p.algo, p.Cin,
+                        p.Cout, p.taps, p.co_tile, H, W, B, pro, (const void*)p.w, (const void*)p.bias, (const void*)p.gn_partial, (void*)h->blob, h->blob_floats * 4, (const void*)p.x.p0, (const void*)p.x.p1, p.x.c0, (void*)p.y, (const void*)p.res, (const void*)p.aff,
+                        (void*)p.stat, (void*)ar->base, ar->cap);
+            note(launch_conv(p, st), "conv");
+            if (e1) (void)hipEventRecord(e1, st);
+        }
+        if (xs) ar->release(xs);  // (stream-ordered: the next user of that memory is enqueued behind this convolution)
+        if (own_aff) ar->release(own_aff);
+        return y;
+    }
+
+    // efficient_unet.py:95-110.  `in_stats`: fused statistics of x (if its producer left them);
+    // `out` / `out_goff`: where the statistics of this block's output go (the next GroupNorm's sink).
+    // fp16 storage (round 5): in the one-plane mode (the reference's autocast counterpart) the tensor between a residual block's two
+    // convolutions is stored as fp16 -- what autocast stores there (sample_and_save.py:45,70) -- when both run on
+    // conv_f16x2 (R2DM_FP16_STORAGE=0: fp32 everywhere, as until round 4)
+    bool act16(const ConvLayer& L) const {
+        static const bool on = !getenv("R2DM_FP16_STORAGE") || atoi(getenv("R2DM_FP16_STORAGE")) != 0;
+        return on && h->conv_pieces == 1 && L.f2 && !(L.f2_cot == 32 && narrow_split());
+    }
+    static int narrow_presplit() {
+        const char* e = getenv("R2DM_F2_PRESPLIT_NARROW");  // (read per call, like R2DM_GN_FOLD: the bit-identity test builds one model per setting)
+        return e ? atoi(e) : 0;
+    }
+    // (experiment switch, round 5) layers packed for the 32-channel tile run the two-plane kernel in every precision mode
+    static bool narrow_split() {
+        static const bool on = getenv("R2DM_F2_NARROW_SPLIT") && atoi(getenv("R2DM_F2_NARROW_SPLIT")) != 0;
+        return on;
+    }
+
+    struct BlockOpts {
+        bool track_out = false;     // the block's last convolution records max|output| in the range flag
+        bool skip_bounded = false;  // every producer of the block's input has done so: the skip convolution may take the fp16 operand path
+        bool x16 = false;           // the block's input (both sources) is stored as fp16
+    };
+    Tensor residual_block(const ResLayer& r, const Src& x, int H, int W, const Sink& in_stats, const Sink* out, int out_goff, const BlockOpts& bo) {
+        const std::string blk = ctx;
+        ctx = blk + ".conv1";
+        const NormSpec n1{&in_stats, blob(r.g1), blob(r.b1), nullptr};
+        Sink s1 = make_sink(r.cout, H, W);
+        const bool t1_16 = act16(r.conv1) && act16(r.conv2) && s1.p != nullptr;  // (the streaming statistics pass reads fp32)
+        const bool out16 = bo.x16 && lvl16(H) && act16(r.conv2);  // the block's output (and the residual it adds: its input or the skip convolution's output)
+        ConvOpts c1;
+        c1.prologue = PRO_AFFINE_SILU;
+        c1.norm = &n1;
+        c1.sink = &s1;
+        c1.x16 = bo.x16;
+        c1.y16 = t1_16;
+        Tensor t1 = conv(r.conv1, x, H, W, c1);
+        const NormSpec n2{&s1, nullptr, nullptr, proj + r.ada_row};
+        Tensor skip;
+        const Tensor* res;
+        Tensor ident;
+        if (r.has_skip) {
+            ctx = blk + ".skip";
+            ConvOpts cs;
+            cs.input_bounded = bo.skip_bounded;
+            cs.x16 = bo.x16;
+            cs.y16 = out16;
+            skip = conv(r.skip, x, H, W, cs);
+            res = &skip;
+        } else {
+            ident.p = const_cast<float*>(x.p0);  // identity skip: block input is single-source here
+            ident.C = x.c0;
+            ident.H = H;
+            ident.W = W;
+            res = &ident;
+        }
+        ctx = blk + ".conv2";
+        ConvOpts c2;
+        c2.prologue = PRO_AFFINE_SILU;
+        c2.norm = &n2;
+        c2.res = res;
+        c2.scale = blob(r.scale);
+        c2.sink = out;
+        c2.goff = out_goff;
+        c2.track_out = bo.track_out;
+        c2.x16 = t1_16;
+        c2.y16 = out16;
+        Tensor o = conv(r.conv2, src1(t1), H, W, c2);
+        ctx = blk;
+        drop_sink(s1);
+        drop(t1);
+        if (r.has_skip) drop(skip);
+        return o;
+    }
+
+    // efficient_unet.py:42-53
+    struct AttnOpts {
+        bool track_out = false;  // the output projection records max|output| in the range flag
+    };
+    Tensor attention_block(const AttnLayer& a, const Tensor& x, const Sink& in_stats, const Sink* out, int out_goff, const AttnOpts& ao) {
+        const std::string blk = ctx;
+        ctx = blk + ".norm";
+        float2* aff = norm(in_stats, src1(x), x.H, x.W, blob(a.gamma), blob(a.beta), nullptr);
+        ctx = blk + ".qkv";
+        // precision mode 2: the attention core runs on the fp16 matrix pipe (attention.hip) and needs |q|, |k|, |v| < 65504: the
+        // projection's epilogue records max|qkv| in the range flag
+        const bool f2 = h->f16_path();
+        ConvOpts cq;
+        cq.prologue = PRO_AFFINE;
+        cq.aff = aff;
+        cq.track_out = f2;
+        Tensor qkv = conv(a.qkv, src1(x), x.H, x.W, cq);
+        ar->release(aff);
+        Tensor o = make(a.C, x.H, x.W);
+        if (!dry()) note(launch_attention(qkv.p, o.p, B, a.C, h->cfg.attn_num_heads, x.H * x.W, st, f2 ? h->conv_pieces : 0), "attention");
+        drop(qkv);
+        // (the core's output is a convex combination of v: |o| <= max|qkv|, which the qkv epilogue has recorded)
+        ctx = blk + ".out_proj";
+        ConvOpts cp;
+        cp.res = &x;
+        cp.scale = blob(a.scale);
+        cp.sink = out;
+        cp.goff = out_goff;
+        cp.input_bounded = f2;
+        cp.track_out = ao.track_out;
+        Tensor y = conv(a.proj, src1(o), x.H, x.W, cp);
+        ctx = blk;
+        drop(o);
+        return y;
+    }
+
+    // efficient_unet.py:178-185.  Never frees `in`; returns a fresh tensor.  `in_stats`: fused statistics of `in` for
+    // the first residual block (stages without downsampling); `out`/`out_goff`: sink of the GroupNorm that will consume
+    // this stage's output (written by whichever convolution produces it last).
+    struct StageIn {
+        bool tracked = false;  // the input's producer recorded max|x| in the range flag
+        bool f16 = false;      // the input is stored as fp16
+    };
+    Tensor stage(const Stage& s, const Src& in, int H, int W, const Sink& in_stats, const Sink* out, int out_goff, const StageIn& si) {
+        Tensor cur;
+        bool have = false;
+        bool c16 = si.f16;  // the current tensor (stage input or `cur`) is stored as fp16
+        Sink carry = in_stats;  // statistics of the current tensor, owned elsewhere for the stage input
+        bool carry_owned = false;
+        // FIR first, then the stride-2 convolution as a GEMM over the nine filtered planes (resample.hip down_planes_kernel): a quarter of the MACs of
+        // conv + fir_down2.  Taken where the plan packed the matrix (geometry, R2DM_DOWN_GEMM), the precision is the default three-product split and
+        // the input's producer tracks max|x|; everything else -- fp32-bf16x3, the one-plane mode with its fp16 storage, a tripped guard's fallback --
+        // keeps conv + FIR.  Leaves what the FIR launch leaves: the tensor and, where fir_down2 would, the statistics of the first block's norm.
+        // (a two-source input never reaches a down stage today; if one does it keeps conv + FIR: the pre-pass reads one tensor)
+        if (s.down && s.dconv.dg && h->conv_pieces == 2 && si.tracked && !si.f16 && !in.p1) {
+            ctx = s.name + ".downsample";
+            const ConvLayer& L = s.dconv;
+            Tensor a = make(9 * L.cin, H / 2, W / 2);
+            cur = make(s.cout, H / 2, W / 2);
+            Sink fs;
+            if (fir_down2_stat_slots(s.cout, h->cfg.gn_num_groups, H, W)) fs = make_sink(s.cout, H / 2, W / 2);
+            if (!dry()) {
+                // Range: the FIR weights are non-negative and sum to at most 1 per axis, so max|a| <= max|x|, which the producer has recorded at its own site;
+                // the pass records max|a| itself all the same (one guarded atomic per wave), so the report names the GEMM's operand.
+                // (profiling: both launches in class 2, "1x1 / in / out convolutions" -- the pass with no FLOPs of its own, the GEMM with those it executes)
+                int* site = range_site("max|FIR planes| (operand of the down-sampling GEMM)");
+                hipEvent_t e0 = prof_begin(2, 0.0);
+                note(launch_down_planes(in.p0, in.bs0, a.p, a.bs(), B, L.cin, H, W, st, site), "down_planes");
+                if (e0) (void)hipEventRecord(e0, st);
+                const ConvParams p = down_gemm_params(a.p, blob(L.w_dg), blob(L.b), blob(L.ws_dg) + 1, cur.p, B, L.cin, L.cout, H / 2, W / 2, fs.p, h->cfg.gn_num_groups);
+                last_reverse = -1;
+                hipEvent_t e1 = prof_begin(2, 2.0 * B * (double)L.cout * 9 * L.cin * (H / 2) * (W / 2));
+                note(launch_proj_f16x2(p, st, /*bias_rowfac=*/true), "down_gemm");
+                if (e1) (void)hipEventRecord(e1, st);
+            }
+            drop(a);
+            H /= 2;
+            W /= 2;
+            have = true;
+            carry = fs;
+            carry_owned = fs.p != nullptr;
+        } else if (s.down) {
+            ctx = s.name + ".downsample";
+            ConvOpts cd;
+            cd.input_bounded = si.tracked;
+            cd.x16 = si.f16;
+            cd.y16 = si.f16 && lvl16(H);
+            Tensor t = conv(s.dconv, in, H, W, cd);
+            cur = make(s.cout, H / 2, W / 2, t.f16 && lvl16(H / 2));
+            // the FIR pass leaves the statistics of its output for the first residual block's norm (resample.hip; where its geometry
+            // does not fit the slot grid: no fused statistics, the streaming pass)
+            Sink fs;
+            if (fir_down2_stat_slots(s.cout, h->cfg.gn_num_groups, H, W)) fs = make_sink(s.cout, H / 2, W / 2);
+            if (!dry()) note(launch_fir_down2(t.p, t.bs(), cur.p, cur.bs(), B, s.cout, H, W, st, fs.p, h->cfg.gn_num_groups, t.f16, cur.f16), "fir_down2");
+            c16 = cur.f16;
+            drop(t);
+            H /= 2;
+            W /= 2;
+            have = true;
+            carry = fs;
+            carry_owned = fs.p != nullptr;
+        }
+        const int n = (int)s.res.size();
+        for (int i = 0; i < n; ++i) {
+            const bool last = i == n - 1;
+            Sink next;  // sink for the GroupNorm that consumes this block's output inside the stage
+            const Sink* dst = nullptr;
+            int goff = 0;
+            if (!last || s.attn) {
+                next = make_sink(s.cout, H, W);
+                dst = &next;
+            } else if (!s.up) {
+                dst = out;
+                goff = out_goff;
+            }
+            BlockOpts bo;
+            bo.track_out = h->f16_path() && last && ((s.out_tracked) || (s.track_final && !s.attn && !s.up));
+            bo.skip_bounded = i == 0 && s.skip_in_bounded && h->f16_path();
+            bo.x16 = c16;
+            ctx = s.name + ".residual_blocks." + std::to_string(i);
+            Tensor nxt = residual_block(s.res[i], have ? src1(cur) : in, H, W, carry, dst, goff, bo);
+            c16 = nxt.f16;
+            if (carry_owned) drop_sink(carry);
+            if (have) drop(cur);
+            cur = nxt;
+            have = true;
+            carry = next;
+            carry_owned = next.p != nullptr;
+        }
+        if (s.attn) {
+            ctx = s.name + ".self_attn_block";
+            if (cur.f16) note(hipErrorInvalidValue, "attention block behind fp16 storage");
+            AttnOpts ao;
+            ao.track_out = s.track_final && !s.up && h->f16_path();
+            Tensor nxt = attention_block(s.at, cur, carry, s.up ? nullptr : out, out_goff, ao);
+            if (carry_owned) drop_sink(carry);
+            carry_owned = false;
+            drop(cur);
+            cur = nxt;
+        }
+        if (carry_owned) drop_sink(carry);
+        if (s.up) {
+            Tensor u = make(s.cout, 2 * H, 2 * W, lvl16(2 * H) && s.uconv.f2);
+            const bool track = s.uconv.f2 && h->f16_path();  // the fp16-operand convolution below needs max|u| < 65504
+            ctx = s.name + ".upsample";
+            if (!dry()) note(launch_fir_up2(cur.p, cur.bs(), u.p, u.bs(), B, s.cout, H, W, st, track ? range_site("max|FIR output| (raw input of the up-sampling convolution)") : nullptr, cur.f16, u.f16), "fir_up2");
+            drop(cur);
+            ConvOpts cu;
+            cu.sink = out;
+            cu.goff = out_goff;
+            cu.input_bounded = track;
+            cu.track_out = s.track_final && h->f16_path();
+            cu.x16 = cu.y16 = u.f16;
+            cur = conv(s.uconv, src1(u), 2 * H, 2 * W, cu);
+            drop(u);
+        }
+        return cur;
+    }
+};
+
+}  // namespace
+
+int r2dm::run_forward(r2dm_handle* h, Arena& ar, const float* x, const float* cond, float* out, int B, hipStream_t st) {
+    const r2dm_config& c = h->cfg;
+    Ctx k{h, &ar, st, B, nullptr, nullptr};
+    const int H = c.height, W = c.width, T = c.temb_channels;
+    float* act = (float*)ar.alloc((size_t)2 * B * T * sizeof(float));  // [SiLU(temb) | hidden scratch]
+    float* proj = (float*)ar.alloc((size_t)B * h->ada_rows * sizeof(float));
+    k.gn_partial = (double*)ar.alloc((size_t)B * c.gn_num_groups * 256 * (2 * sizeof(double) + sizeof(float)));  // sums | maxima
+    k.proj = proj;
+    if (!k.dry()) {
+        EmbedParams e{cond, k.blob(h->freqs), k.blob(h->w1), k.blob(h->b1), k.blob(h->w2), k.blob(h->b2), act,
+                      act + (size_t)B * T, B, c.base_channels, T};
+        k.note(launch_time_embedding(e, st), "time_embedding");
+        k.note(launch_ada_proj(act, k.blob(h->ada_w), k.blob(h->ada_b), proj, B, T, h->ada_rows, st), "ada_proj");
+    }
+    // input = cat([x, cenc]) (efficient_unet.py:278-281), never materialised: the constant cenc half of in_conv is the
+    // per-pixel bias map `cmap`, the per-step convolution runs over the in_channels data channels only
+    Src in{x, nullptr, c.in_channels, 0, (long)c.in_channels * H * W, 0};
+    if (c.coord_channels && !h->cmap_ready && !k.dry()) {
+        const ConvLayer& L = h->in_conv_c;
+        const ConvParams q = conv_params(Src{k.blob(h->cenc), nullptr, c.coord_channels, 0, 0, 0}, k.blob(L.w), k.blob(L.b), h->blob + h->cmap, 0, 1, H, W, L.cin, L.cin_pad, L.cout, 9,
+                                         L.co_tile, ALGO_F32, PRO_NONE);
+        k.note(hipMemsetAsync(h->blob + h->zero_bias, 0, h->in_conv.cout * sizeof(float), st), "zero bias");
+        k.note(launch_conv(q, st), "in_conv constant map");
+        h->cmap_ready = true;
+    }
+    Tensor cmap_t;
+    cmap_t.p = h->blob + h->cmap;
+    cmap_t.C = h->in_conv.cout;
+    cmap_t.H = H;
+    cmap_t.W = W;
+    const int G = c.gn_num_groups;
+    const Stage* S = h->stages;
+    // GroupNorm sinks that outlive a stage: the first norm of d_block1 (input = in_conv output) and the first norm of
+    // every up stage (input = cat([up-path tensor, skip tensor]): groups [0, G/2) come from the up path, [G/2, G)
+    // from the skip tensor produced much earlier on the down path).
+    Ctx::Sink s_d1 = k.make_sink(S[0].cin, H, W);
+    Ctx::Sink s_u1 = k.make_sink(S[7].cin, H, W);
+    Ctx::Sink s_u2 = k.make_sink(S[6].cin, H / 2, W / 2);
+    Ctx::Sink s_u3 = k.make_sink(S[5].cin, H / 4, W / 4);
+    Ctx::Sink s_u4 = k.make_sink(S[4].cin, H / 8, W / 8);
+    {
+        // fp16 storage of the full-resolution levels (Ctx::lvl16): the one-plane mode, the default network family (every GroupNorm of levels 1 and 2 on fused
+        // statistics -- the streaming pass reads fp32 --, in_conv on the few-input kernel, FIR statistics at both levels).  R2DM_FP16_STORAGE=1: only between a
+        // residual block's two convolutions (round 5); 0: nowhere.  Read per forward like R2DM_GN_FOLD (ws_cache: r2dm_set_conv_pieces clears it; tests build one
+        // model per setting).
+        const char* e = getenv("R2DM_FP16_STORAGE");
+        const int level = e ? atoi(e) : 2;
+        // ... and every convolution of those levels on a kernel that has the second I/O type (at small batches some layers have too few tiles for conv_f16x2
+        // and run the bf16 kernels: then nothing changes)
+        auto blocks_ok = [](const Stage& st) {
+            for (const ResLayer& r : st.res)
+                if (!r.conv1.f2 || !r.conv2.f2 || (r.has_skip && !r.skip.p1)) return false;
+            return true;
+        };
+        k.all16 = level >= 2 && h->conv_pieces == 1 && G == 8 && c.base_channels % 64 == 0 && h->in_conv.algo == ALGO_DIRECT && h->in_conv.cout > 4 &&
+                  h->out_conv.algo == ALGO_DIRECT && W % 4 == 0 && S[1].down && S[2].down && S[1].dconv.f2 && S[2].dconv.f2 && S[5].up && S[6].up &&
+                  S[5].uconv.f2 && S[6].uconv.f2 && !S[0].attn && !S[1].attn && !S[6].attn && !S[7].attn && blocks_ok(S[0]) && blocks_ok(S[1]) && blocks_ok(S[6]) &&
+                  blocks_ok(S[7]) && S[6].skip_in_bounded && S[7].skip_in_bounded &&
+                  fir_down2_stat_slots(S[1].cout, G, H, W) != 0 && fir_down2_stat_slots(S[2].cout, G, H / 2, W / 2) != 0;
+    }
+    k.ctx = "in_conv";
+    Ctx::ConvOpts ci;
+    ci.res = c.coord_channels ? &cmap_t : nullptr;
+    ci.res_broadcast = true;
+    ci.sink = &s_d1;
+    ci.y16 = k.lvl16(H) && s_d1.p != nullptr;
+    Tensor h0 = k.conv(h->in_conv, in, H, W, ci);
+    Ctx::StageIn i0, i1, i2, i3, i6, i7;  // (stages 4 and 5 read untracked fp32 tensors)
+    i0.f16 = h0.f16;
+    Tensor h1 = k.stage(S[0], src1(h0), H, W, s_d1, &s_u1, G / 2, i0);
+    k.drop(h0);
+    k.drop_sink(s_d1);
+    i1.tracked = S[0].out_tracked && h->f16_path();
+    i1.f16 = h1.f16;
+    Tensor h2 = k.stage(S[1], src1(h1), H, W, Ctx::Sink{}, &s_u2, G / 2, i1);
+    i2.tracked = S[1].out_tracked && h->f16_path();
+    i2.f16 = h2.f16;
+    Tensor h3 = k.stage(S[2], src1(h2), H / 2, W / 2, Ctx::Sink{}, &s_u3, G / 2, i2);
+    i3.tracked = S[2].out_tracked && h->f16_path();
+    Tensor h4 = k.stage(S[3], src1(h3), H / 4, W / 4, Ctx::Sink{}, &s_u4, 0, i3);
+    Tensor u = k.stage(S[4], src1(h4), H / 8, W / 8, s_u4, &s_u3, 0, Ctx::StageIn{});
+    k.drop(h4);
+    k.drop_sink(s_u4);
+    Tensor u3 = k.stage(S[5], src2(u, h3), H / 4, W / 4, s_u3, &s_u2, 0, Ctx::StageIn{});
+    k.drop(u);
+    k.drop(h3);
+    k.drop_sink(s_u3);
+    if (u3.f16 != h2.f16 || h3.f16) k.note(hipErrorInvalidValue, "fp16 storage: the two halves of a skip join differ");
+    i6.f16 = u3.f16 && h2.f16;
+    Tensor u2 = k.stage(S[6], src2(u3, h2), H / 2, W / 2, s_u2, &s_u1, 0, i6);
+    k.drop(u3);
+    k.drop(h2);
+    k.drop_sink(s_u2);
+    if (u2.f16 != h1.f16) k.note(hipErrorInvalidValue, "fp16 storage: the two halves of a skip join differ");
+    i7.f16 = u2.f16 && h1.f16;
+    Tensor u1 = k.stage(S[7], src2(u2, h1), H, W, s_u1, nullptr, 0, i7);
+    k.drop(u2);
+    k.drop(h1);
+    k.drop_sink(s_u1);
+    k.ctx = "out_conv";
+    Ctx::ConvOpts co;
+    co.dst = out;
+    co.x16 = u1.f16;
+    k.conv(h->out_conv, src1(u1), H, W, co);
+    k.drop(u1);
+    ar.release(act);
+    ar.release(proj);
+    ar.release(k.gn_partial);
+    if (k.err != hipSuccess) return fail(2, "kernel launch failed in %s: %s", k.where, hipGetErrorString(k.err));
+    if (ar.overflow) return fail(3, "workspace too small: need %zu bytes", ar.peak);
+    return 0;
+}

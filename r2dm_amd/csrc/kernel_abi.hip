@@ -1,0 +1,190 @@
+// Single-kernel entry points of the C ABI (include/r2dm_hip.h): one kernel, or one short pair, on caller-provided tensors -- the unit parity tests
+// and the probes under scripts/ drive them.  Their precision mode is r2dm_set_conv_pieces(NULL, ...) (g_single_kernel_pieces).
+#include <algorithm>
+
+#include "engine.h"
+
+using namespace r2dm;
+
+extern "C" {
+
+// ---- single-kernel entry points (unit parity tests) ---------------------------------------------
+int64_t r2dm_conv_packed_elems(int32_t cout, int32_t cin, int32_t ksize, int32_t B, int32_t H, int32_t W) {
+    const int taps = ksize * ksize;
+    int algo = conv_pick_algo(cin, cout, taps);
+    if (algo == ALGO_DIRECT) algo = ALGO_F32;  // scratch sized for the larger (fp32-MFMA) packing: either may be chosen
+    const int ct = algo == ALGO_BF16X3 ? conv_bf16x3_co_tile(cin, cout, (long)B * H * W) : conv_pick_co_tile(cout, taps, (long)B * H * W);
+    int64_t n = (int64_t)conv_packed_floats(algo, cin, cout, taps, ct, algo != ALGO_F32 ? cin : conv_cin_pad(cin, taps, ct));
+    if (algo == ALGO_BF16X3 && conv_f16x2_supported(cin, cout, taps, H, W)) n = std::max<int64_t>(n, conv_f16x2_packed_floats(cin, cout) + 64);
+    if (proj_f16x2_supported(cin, cout, taps, H, W)) n = std::max<int64_t>(n, proj_f16x2_packed_floats(cin, cout) + 64);
+    return n;
+}
+
+// (per-kernel tests of the fp16 activation storage: R2DM_TEST_IO16 bit 0 -- x holds fp16, bit 1 -- y will; the caller passes tensors of that type)
+static int test_io16() {
+    const char* e = getenv("R2DM_TEST_IO16");
+    return e ? atoi(e) : 0;
+}
+
+int r2dm_conv2d_ring(const float* x, const float* w, const float* bias, float* w_packed, const float* aff,
+                     int32_t prologue, const float* residual, const float* scale, float* y, int32_t B, int32_t cin,
+                     int32_t cout, int32_t H, int32_t W, int32_t ksize, void* stream) {
+    if (!x || !w || !bias || !w_packed || !y) return fail(1, "null argument");
+    if (ksize != 1 && ksize != 3) return fail(1, "kernel size must be 1 or 3");
+    hipStream_t st = (hipStream_t)stream;
+    const int taps = ksize * ksize;
+    int pieces = 3, px_rows = 4;
+    int algo = conv_pick_algo(cin, cout, taps);
+    if (g_single_kernel_pieces >= 4 && algo != ALGO_DIRECT) {  // (test hook: the fp32-input MFMA kernel)
+        algo = ALGO_F32;
+        pieces = g_single_kernel_pieces;
+    }
+    // (the few-input kernel -- in_conv in the engine -- where the fp16-storage test hook asks for it: plain convolutions only)
+    if (test_io16() && conv_few_in_supported(cin, cout, taps, H, W) && prologue == PRO_NONE && !scale) algo = ALGO_DIRECT;
+    if (algo == ALGO_DIRECT && cout <= 4 && (prologue != PRO_NONE || residual || scale || W % 4 != 0)) algo = ALGO_F32;  // plain convolutions of 16-byte rows only
+                                                                                                             // (any other width runs on the fp32-MFMA kernel)
+    // per-op tests: with pieces = 2 every shape the f16x2 kernel covers goes there (the engine restricts it to normalised inputs)
+    if (algo == ALGO_BF16X3 && g_single_kernel_pieces != 3 && conv_f16x2_supported(cin, cout, taps, H, W)) algo = ALGO_F16X2;
+    if (algo == ALGO_F32 && g_single_kernel_pieces < 3 && prologue != PRO_AFFINE_SILU && proj_f16x2_supported(cin, cout, taps, H, W)) algo = ALGO_P1F16;
+    if (algo == ALGO_F16X2 || algo == ALGO_P1F16) pieces = g_single_kernel_pieces;
+    const int co_tile = algo == ALGO_F16X2 ? conv_f16x2_pick_co_tile(cin, cout, H, W, (long)B * H * W, &px_rows) : algo == ALGO_P1F16 ? 64 : algo == ALGO_BF16X3 ? conv_bf16x3_co_tile(cin, cout, (long)B * H * W) : conv_pick_co_tile(cout, taps, (long)B * H * W);
+    const int cin_pad = algo != ALGO_F32 ? cin : conv_cin_pad(cin, taps, co_tile);
+    const float* wscale = nullptr;
+    if (algo == ALGO_F16X2) {  // the range flag and the weight scale: behind the packed weights (r2dm_conv_packed_elems reserves 64 floats)
+        float* tail = w_packed + conv_f16x2_packed_floats(cin, cout);
+        HIP_TRY(hipMemsetAsync(tail, 0, sizeof(int), st));
+        HIP_TRY(launch_pack_conv_f16x2(w, w_packed, cout, cin, (int*)tail, st, tail + 2, co_tile, px_rows));
+        wscale = tail + 3;
+    } else if (algo == ALGO_P1F16) {
+        float* tail = w_packed + proj_f16x2_packed_floats(cin, cout);
+        HIP_TRY(hipMemsetAsync(tail, 0, sizeof(int), st));
+        HIP_TRY(launch_pack_proj_f16x2(w, w_packed, cout, cin, (int*)tail, st, tail + 2));
+        wscale = tail + 3;
+    } else {
+        HIP_TRY(launch_pack_conv(w, w_packed, cout, cin, taps, co_tile, cin_pad, st, algo));
+    }
+    ConvParams p = conv_params(Src{x, nullptr, cin, 0, (long)cin * H * W, 0}, w_packed, bias, y, (long)cout * H * W, B, H, W, cin, cin_pad, cout, taps, co_tile, algo, prologue);
+    p.px_rows = px_rows;
+    p.pieces = pieces;
+    p.wscale = wscale;
+    p.aff = (const float2*)aff;
+    p.res = residual;
+    p.res_bs = (long)cout * H * W;
+    p.scale = scale;
+    // per-kernel tests of the fp16 activation storage (conv_f16x2.hip, one-plane mode): R2DM_TEST_IO16 = 1 (x holds fp16), 2 (y and the
+    // residual hold fp16) or 3 -- the caller passes tensors of that type behind the float pointers
+    if (const char* e = getenv("R2DM_TEST_IO16"); e && (atoi(e) & 3)) {  // (bit 2 alone: only the kernel selection above -- the fp32 twin of a storage test)
+        if (!((p.algo == ALGO_F16X2 && p.pieces == 1) || p.algo == ALGO_DIRECT || (p.algo == ALGO_P1F16 && p.pieces == 1)))
+            return fail(1, "R2DM_TEST_IO16: this shape / mode runs on a kernel without fp16 storage");  // (never write a type the caller did not allocate)
+        p.x16 = atoi(e) & 1;  // (round 6: also the in / out convolutions -- bit 1 / bit 0 -- and, with both bits, the fp16-operand 1 x 1 convolution)
+        p.y16 = (atoi(e) >> 1) & 1;
+    }
+    // perf probe (scripts/conv_phases.py): per-block s_memtime stamps into a caller-provided device buffer
+    if (const char* e = getenv("R2DM_CONV_PROF_PTR")) p.prof = (unsigned long long*)strtoull(e, nullptr, 0);
+    // per-kernel tests / probes of the operand pre-pass (presplit.hip + conv_f16x2's PRO_PRESPLIT stagers): R2DM_F2_PRESPLIT=1
+    float* xs = nullptr;
+    if (const char* e = getenv("R2DM_F2_PRESPLIT"); e && atoi(e) && p.algo == ALGO_F16X2 && p.co_tile == 64 && p.px_rows == 4 && presplit_supported(p.x, cin, H, W)) {
+        static float* scratch = nullptr;  // (test entry: one growing scratch buffer, never freed)
+        static size_t scratch_floats = 0;
+        const size_t need = (size_t)presplit_floats(B, cin, H, W);
+        if (need > scratch_floats) {
+            HIP_TRY(hipDeviceSynchronize());
+            if (scratch) HIP_TRY(hipFree(scratch));
+            HIP_TRY(hipMalloc(&scratch, need * sizeof(float)));
+            scratch_floats = need;
+        }
+        xs = scratch;
+        HIP_TRY(launch_presplit(p.x, p.aff, prologue, xs, B, cin, H, W, st));
+        p.x = Src{xs, nullptr, cin, 0, presplit_floats(1, cin, H, W), 0};
+        p.prologue = PRO_PRESPLIT;
+        p.aff = nullptr;
+    }
+    HIP_TRY(launch_conv(p, st));
+    return 0;
+}
+
+size_t r2dm_group_norm_scratch_bytes(int32_t B, int32_t groups) { return (size_t)B * groups * 256 * (2 * sizeof(double) + sizeof(float)); }
+
+int r2dm_group_norm_affine(const float* x, const float* gamma, const float* beta, const float* ada, void* scratch,
+                           float* aff, float* stats, int32_t B, int32_t C, int32_t H, int32_t W, int32_t groups,
+                           float eps, void* stream) {
+    if (!x || !scratch || !aff) return fail(1, "null argument");
+    GNParams g{Src{x, nullptr, C, 0, (long)C * H * W, 0}, B, H, W, groups, eps, gamma, beta, ada, 2L * C,
+               (double*)scratch, (float2*)aff, stats};
+    g.partial_max = (float*)((double*)scratch + (size_t)B * groups * 256 * 2);
+    HIP_TRY(launch_group_norm(g, (hipStream_t)stream));
+    return 0;
+}
+
+int r2dm_affine_act(const float* x, const float* aff, float* y, int32_t B, int32_t C, int64_t hw, int32_t silu,
+                    void* stream) {
+    HIP_TRY(launch_gn_apply(x, (const float2*)aff, y, B, C, hw, silu, (hipStream_t)stream));
+    return 0;
+}
+
+int r2dm_fir_down2(const float* x, float* y, int32_t B, int32_t C, int32_t H, int32_t W, void* stream) {
+    HIP_TRY(launch_fir_down2(x, (long)C * H * W, y, (long)C * (H / 2) * (W / 2), B, C, H, W, (hipStream_t)stream, nullptr, 0, test_io16() & 1, (test_io16() >> 1) & 1));
+    return 0;
+}
+
+int32_t r2dm_fir_down2_stat_slots(int32_t C, int32_t G, int32_t H, int32_t W) {
+    return fir_down2_stat_slots(C, G, H, W) ? conv_stat_slots(H / 2, W / 2) : 0;
+}
+
+int r2dm_fir_down2_stats(const float* x, float* y, double* stat, int32_t B, int32_t C, int32_t G, int32_t H, int32_t W, void* stream) {
+    if (!stat || !fir_down2_stat_slots(C, G, H, W)) return fail(1, "fir_down2_stats: geometry without a statistics variant");
+    HIP_TRY(launch_fir_down2(x, (long)C * H * W, y, (long)C * (H / 2) * (W / 2), B, C, H, W, (hipStream_t)stream, stat, G, test_io16() & 1, (test_io16() >> 1) & 1));
+    return 0;
+}
+
+int r2dm_down_planes(const float* x, float* planes, int32_t B, int32_t C, int32_t H, int32_t W, void* stream) {
+    if (!x || !planes) return fail(1, "null argument");
+    if (B < 1 || C < 1 || !down_planes_supported(H, W)) return fail(1, "down_planes: needs height %% 4 == 0 and width %% 8 == 0 (>= 16)");
+    HIP_TRY(launch_down_planes(x, (long)C * H * W, planes, 9L * C * (H / 2) * (W / 2), B, C, H, W, (hipStream_t)stream));
+    return 0;
+}
+
+int32_t r2dm_down_gemm_stat_slots(int32_t cin, int32_t cout, int32_t G, int32_t H, int32_t W) {
+    if (H < 4 || W < 16 || !down_planes_supported(H, W) || !proj_f16x2_supported(9 * cin, cout, 1, H / 2, W / 2)) return 0;
+    const int cpg = G > 0 && cout % G == 0 ? cout / G : 0;
+    return cpg >= 8 && cpg <= 64 && !(cpg & (cpg - 1)) ? conv_stat_slots(H / 2, W / 2) : 0;
+}
+
+int r2dm_down_gemm(const float* x, const float* w, const float* bias, float* w_packed, float* planes, float* y, double* stat, int32_t B, int32_t cin,
+                   int32_t cout, int32_t G, int32_t H, int32_t W, void* stream) {
+    if (!x || !w || !bias || !w_packed || !planes || !y) return fail(1, "null argument");
+    if (B < 1 || H < 4 || W < 16 || !down_planes_supported(H, W) || !proj_f16x2_supported(9 * cin, cout, 1, H / 2, W / 2))
+        return fail(1, "down_gemm: needs cin %% 32 == 0, cout %% 64 == 0, height %% 8 == 0, width %% 128 == 0");
+    if (stat && !r2dm_down_gemm_stat_slots(cin, cout, G, H, W)) return fail(1, "down_gemm: no statistics for %d groups of %d channels", G, cout);
+    hipStream_t st = (hipStream_t)stream;
+    // the range flag and the weight scale: behind the packed weights (the caller reserves 64 floats), as r2dm_conv2d_ring
+    float* tail = w_packed + proj_f16x2_packed_floats(9 * cin, cout);
+    HIP_TRY(hipMemsetAsync(tail, 0, sizeof(int), st));
+    HIP_TRY(launch_pack_proj_f16x2(w, w_packed, cout, 9 * cin, (int*)tail, st, tail + 2, 9));
+    const int Ho = H / 2, Wo = W / 2;
+    HIP_TRY(launch_down_planes(x, (long)cin * H * W, planes, 9L * cin * Ho * Wo, B, cin, H, W, st));
+    const ConvParams p = down_gemm_params(planes, w_packed, bias, tail + 3, y, B, cin, cout, Ho, Wo, stat, G);
+    HIP_TRY(launch_proj_f16x2(p, st, /*bias_rowfac=*/true));
+    return 0;
+}
+
+int r2dm_fir_up2(const float* x, float* y, int32_t B, int32_t C, int32_t H, int32_t W, void* stream) {
+    HIP_TRY(launch_fir_up2(x, (long)C * H * W, y, (long)C * H * W * 4, B, C, H, W, (hipStream_t)stream, nullptr, test_io16() & 1, (test_io16() >> 1) & 1));
+    return 0;
+}
+
+int r2dm_attention(const float* qkv, float* out, int32_t B, int32_t C, int32_t heads, int32_t N, void* stream) {
+    if (!attention_supported(C, heads, N)) return fail(1, "attention: unsupported shape C=%d heads=%d N=%d", C, heads, N);
+    HIP_TRY(launch_attention(qkv, out, B, C, heads, N, (hipStream_t)stream, g_single_kernel_pieces >= 3 ? 0 : g_single_kernel_pieces));  // (per-op tests cover all three)
+    return 0;
+}
+
+int r2dm_time_embedding(const float* cond, const float* freqs, const float* w1, const float* b1, const float* w2,
+                        const float* b2, float* act, float* hidden, int32_t B, int32_t base, int32_t T, void* stream) {
+    if (!cond || !freqs || !w1 || !b1 || !w2 || !b2 || !act || !hidden) return fail(1, "null argument");
+    EmbedParams e{cond, freqs, w1, b1, w2, b2, act, hidden, B, base, T};
+    HIP_TRY(launch_time_embedding(e, (hipStream_t)stream));
+    return 0;
+}
+
+}  // extern "C"

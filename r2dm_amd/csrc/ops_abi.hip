@@ -1,0 +1,188 @@
+// C ABI of the stand-alone operators (include/r2dm_hip.h): sampler steps, LiDAR post-processing, BEV metrics, rendering, projection and point-cloud
+// export.  Each entry validates its arguments and enqueues the operator's kernels (posterior / metrics / render / projection / pointcloud .hip).
+#include "engine.h"
+
+using namespace r2dm;
+
+extern "C" {
+
+int r2dm_posterior_step(const float* x_t, const float* pred, const float* noise, const float* coef, float* x_s,
+                        int32_t B, int64_t per_sample, int32_t mode, int32_t objective, float clip, void* stream) {
+    if (!x_t || !pred || !coef || !x_s) return fail(1, "null argument");
+    PosteriorParams p{x_t, pred, noise, coef, x_s, B, per_sample, mode, objective, clip};
+    HIP_TRY(launch_posterior(p, (hipStream_t)stream));
+    return 0;
+}
+
+int r2dm_repaint_blend(const float* known, const float* noise, const float* unknown, const float* mask, const float* coef,
+                       float* out, int32_t B, int64_t per_sample, int32_t channels, int32_t mask_channels, void* stream) {
+    if (!known || !noise || !unknown || !mask || !coef || !out) return fail(1, "null argument");
+    HIP_TRY(launch_repaint_blend(known, noise, unknown, mask, coef, out, B, per_sample, channels, mask_channels,
+                                 (hipStream_t)stream));
+    return 0;
+}
+
+int r2dm_q_step(const float* x_s, const float* noise, const float* coef, float* x_t, int32_t B, int64_t per_sample,
+                void* stream) {
+    if (!x_s || !noise || !coef || !x_t) return fail(1, "null argument");
+    HIP_TRY(launch_q_step(x_s, noise, coef, x_t, B, per_sample, (hipStream_t)stream));
+    return 0;
+}
+
+int r2dm_lidar_postprocess(const float* x, const float* ang, float* out, int32_t B, int32_t H, int32_t W,
+                           float min_depth, float max_depth, void* stream) {
+    return r2dm_lidar_postprocess_fmt(x, ang, out, B, H, W, min_depth, max_depth, 0, stream);
+}
+
+int r2dm_lidar_postprocess_fmt(const float* x, const float* ang, float* out, int32_t B, int32_t H, int32_t W,
+                               float min_depth, float max_depth, int32_t depth_format, void* stream) {
+    if (!x || !ang || !out) return fail(1, "null argument");
+    if (depth_format < 0 || depth_format > 2) return fail(1, "depth_format must be 0 (log_depth), 1 (inverse_depth) or 2 (depth)");
+    HIP_TRY(launch_lidar_postprocess(x, ang, out, B, H, W, min_depth, max_depth, (hipStream_t)stream, depth_format));
+    return 0;
+}
+
+int r2dm_bev_histogram(const float* src, int32_t layout, const float* edges, int32_t* hist, int64_t* sum, int32_t batch,
+                       int64_t points, int32_t bins, float min_depth, float max_depth, float image_min_depth,
+                       float image_max_depth, void* stream) {
+    if (!src || !edges || !hist) return fail(1, "null argument");
+    if (layout != 0 && layout != 1) return fail(1, "layout must be 0 ((B,5,H,W) samples) or 1 ((B,N,3) point clouds)");
+    if (batch < 1 || points < 1) return fail(1, "empty batch");
+    if (bins < 1 || bins > 128) return fail(1, "bins must be in [1, 128] (one histogram per block in LDS), got %d", bins);
+    HIP_TRY(launch_bev_histogram(src, layout, edges, hist, sum, batch, points, bins, min_depth, max_depth, image_min_depth,
+                                 image_max_depth, (hipStream_t)stream));
+    return 0;
+}
+
+int r2dm_bev_hist_sum(const void* hist, int32_t is_int32, int64_t* sum, int64_t batch, int64_t cells, void* stream) {
+    if (!hist || !sum) return fail(1, "null argument");
+    if (batch < 1 || cells < 1) return fail(1, "empty histogram batch");
+    HIP_TRY(launch_bev_hist_sum(hist, is_int32, sum, batch, cells, (hipStream_t)stream));
+    return 0;
+}
+
+size_t r2dm_bev_mmd_scratch_bytes(int32_t np, int32_t nq) { return np < 1 || nq < 1 ? 0 : mmd_scratch_bytes(np, nq); }
+
+int r2dm_bev_mmd(const float* p, const float* q, int32_t np, int32_t nq, int64_t bins, double sigma, void* scratch,
+                 size_t scratch_bytes, double* out, void* stream) {
+    if (!p || !q || !scratch || !out) return fail(1, "null argument");
+    if (np < 1 || nq < 1 || bins < 1) return fail(1, "empty histogram set");
+    if (!(sigma > 0.0)) return fail(1, "sigma must be > 0");
+    if (scratch_bytes < mmd_scratch_bytes(np, nq)) return fail(1, "scratch too small: %zu < %zu bytes", scratch_bytes, mmd_scratch_bytes(np, nq));
+    if ((uintptr_t)scratch & 255) return fail(1, "scratch must be 256-byte aligned");
+    HIP_TRY(launch_bev_mmd(p, q, np, nq, bins, sigma, scratch, out, (hipStream_t)stream));
+    return 0;
+}
+
+int r2dm_colorize(const float* x, const float* lut, uint8_t* out, int64_t batch, int64_t pixels, void* stream) {
+    if (!x || !lut || !out) return fail(1, "null argument");
+    if (batch < 1 || pixels < 1) return fail(1, "empty image batch");
+    HIP_TRY(launch_colorize(x, lut, out, batch, pixels, (hipStream_t)stream));
+    return 0;
+}
+
+size_t r2dm_rasterize_scratch_bytes(int32_t batch, int32_t channels, int32_t height, int32_t width) {
+    return batch < 1 || channels < 1 || height < 1 || width < 1 ? 0 : rasterize_scratch_bytes(batch, channels, height, width);
+}
+
+int r2dm_bilinear_rasterize(const float* coords, const float* values, float* out, int32_t batch, int64_t points, int32_t channels, int32_t height,
+                            int32_t width, void* scratch, size_t scratch_bytes, int32_t ratio, void* stream) {
+    if (!coords || !values || !out || !scratch) return fail(1, "null argument");
+    if (batch < 1 || batch > 65535 || points < 1 || channels < 1 || height < 1 || width < 1) return fail(1, "rasterize: empty or oversized batch");
+    if (points > (1L << 36)) return fail(1, "rasterize: more than 2^36 points per image");
+    if (ratio != 0 && ratio != 1) return fail(1, "ratio must be 0 (sums) or 1 (channels 0-2 over channel 3)");
+    if (ratio && channels != 4) return fail(1, "the ratio form takes 4 channels, got %d", channels);
+    const size_t need = rasterize_scratch_bytes(batch, channels, height, width);
+    if (scratch_bytes < need) return fail(1, "scratch too small: %zu < %zu bytes", scratch_bytes, need);
+    if ((uintptr_t)scratch & 255) return fail(1, "scratch must be 256-byte aligned");
+    HIP_TRY(launch_rasterize(coords, values, out, batch, points, channels, height, width, scratch, ratio, (hipStream_t)stream));
+    return 0;
+}
+
+int r2dm_project_points(const float* points, const float* colors, const float* view, float focal_length, int32_t size, float* uv, float* vals,
+                        int64_t total_points, void* stream) {
+    if (!points || !view || !uv || !vals) return fail(1, "null argument");
+    if (total_points < 1 || size < 1) return fail(1, "project_points: empty cloud or image");
+    HIP_TRY(launch_project_points(points, colors, view, focal_length, size, uv, vals, total_points, (hipStream_t)stream));
+    return 0;
+}
+
+size_t r2dm_render_frames_scratch_bytes(int32_t frames, int32_t size) { return frames < 1 || size < 1 ? 0 : render_frames_scratch_bytes(frames, size); }
+
+int r2dm_render_frames(const float* x, const float* trig, const float* turbo, const float* viridis, float* img, float* bev, int64_t frames,
+                       int32_t height, int32_t width, int32_t size, float min_depth, float max_depth, const float* view, float focal_length,
+                       void* scratch, size_t scratch_bytes, void* stream) {
+    if (!x || !trig || !turbo || !viridis || !img || !bev || !view || !scratch) return fail(1, "null argument");
+    if (frames < 1 || height < 1 || width < 1 || size < 1) return fail(1, "render_frames: empty batch or image");
+    if (!(max_depth > 0.f)) return fail(1, "max_depth must be > 0");
+    if (scratch_bytes < render_frames_scratch_bytes(1, size))
+        return fail(1, "scratch too small: %zu bytes hold no frame of %zu", scratch_bytes, render_frames_scratch_bytes(1, size));
+    if ((uintptr_t)scratch & 255) return fail(1, "scratch must be 256-byte aligned");
+    HIP_TRY(launch_render_frames(x, trig, turbo, viridis, img, bev, frames, height, width, size, min_depth, max_depth, view, focal_length, scratch,
+                                 scratch_bytes, (hipStream_t)stream));
+    return 0;
+}
+
+static const char* project_geometry_error(int64_t total, int32_t batch, int32_t H, int32_t W) {
+    if (batch < 1 || batch > 65535) return "project: batch must be in [1, 65535]";
+    if (H < 1 || W < 1 || (int64_t)batch * H * W >= (1LL << 31)) return "project: the grid must have 1 to 2^31 - 1 cells over the batch";
+    if (total < 0 || total >= (1LL << 31)) return "project: 0 to 2^31 - 1 points over the batch";
+    return nullptr;
+}
+
+size_t r2dm_project_scratch_bytes(int64_t total_points, int32_t batch, int32_t height, int32_t width, int32_t scan_unfolding) {
+    return project_geometry_error(total_points, batch, height, width) ? 0 : project_scratch_bytes(total_points, batch, height, width, scan_unfolding);
+}
+
+int r2dm_project_scans(const float* points, const int64_t* offsets, float* out, int32_t batch, int32_t height, int32_t width, int32_t out_width,
+                       int32_t scan_unfolding, float min_depth, float max_depth, int32_t apply_mask, int32_t layout, void* scratch,
+                       size_t scratch_bytes, void* stream) {
+    if (!offsets || !out || !scratch) return fail(1, "null argument");
+    if (batch < 1 || batch > 65535) return fail(1, "project: batch must be in [1, 65535]");
+    if (offsets[0] != 0) return fail(1, "project: offsets[0] must be 0, got %lld", (long long)offsets[0]);
+    for (int32_t b = 0; b < batch; ++b)
+        if (offsets[b + 1] < offsets[b]) return fail(1, "project: offsets decrease at scan %d (%lld after %lld)", b, (long long)offsets[b + 1], (long long)offsets[b]);
+    const int64_t total = offsets[batch];
+    if (const char* msg = project_geometry_error(total, batch, height, width)) return fail(1, "%s", msg);
+    if (total > 0 && !points) return fail(1, "null argument");
+    if ((uintptr_t)points & 15) return fail(1, "project: points must be 16-byte aligned");
+    if (out_width < 1 || out_width > width) return fail(1, "project: out_width must be in [1, width], got %d", out_width);
+    if (layout != 0 && layout != 1) return fail(1, "layout must be 0 ((B,6,H,W) xyzrdm) or 1 ((B,5,H,W) samples)");
+    if ((scan_unfolding != 0 && scan_unfolding != 1) || (apply_mask != 0 && apply_mask != 1)) return fail(1, "project: scan_unfolding and apply_mask are 0 or 1");
+    const size_t need = project_scratch_bytes(total, batch, height, width, scan_unfolding);
+    if (scratch_bytes < need) return fail(1, "scratch too small: %zu < %zu bytes", scratch_bytes, need);
+    if ((uintptr_t)scratch & 255) return fail(1, "scratch must be 256-byte aligned");
+    HIP_TRY(launch_project_scans(points, reinterpret_cast<const long long*>(offsets), out, batch, height, width, out_width, scan_unfolding, min_depth,
+                                 max_depth, apply_mask, layout, scratch, (hipStream_t)stream));
+    return 0;
+}
+
+static const char* unproject_geometry_error(int32_t batch, int32_t H, int32_t W) {
+    if (batch < 1 || batch > 65535) return "unproject: batch must be in [1, 65535]";
+    if (H < 1 || W < 1 || (int64_t)batch * H * W >= (1LL << 31)) return "unproject: the images must have 1 to 2^31 - 1 pixels over the batch";
+    return nullptr;
+}
+
+size_t r2dm_unproject_scratch_bytes(int32_t batch, int32_t height, int32_t width) {
+    return unproject_geometry_error(batch, height, width) ? 0 : unproject_scratch_bytes(batch, height, width);
+}
+
+int r2dm_unproject(const float* src, int32_t layout, const float* ray_angles, const int32_t* row_start, float* points, int32_t* index,
+                   int64_t* offsets, int32_t batch, int32_t height, int32_t width, float min_depth, float max_depth, int32_t depth_format,
+                   float keep_min, float keep_max, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!src || !points || !offsets || !scratch) return fail(1, "null argument");
+    if (layout != 0 && layout != 1) return fail(1, "layout must be 0 ((B,2,H,W) model samples) or 1 ((B,5,H,W) post-processed samples)");
+    if (layout == 0 && !ray_angles) return fail(1, "unproject: layout 0 needs ray_angles (null argument)");
+    if (depth_format < 0 || depth_format > 2) return fail(1, "depth_format must be 0 (log_depth), 1 (inverse_depth) or 2 (depth)");
+    if (const char* msg = unproject_geometry_error(batch, height, width)) return fail(1, "%s", msg);
+    if ((uintptr_t)points & 15) return fail(1, "unproject: points must be 16-byte aligned");
+    if ((uintptr_t)offsets & 7) return fail(1, "unproject: offsets must be 8-byte aligned");
+    const size_t need = unproject_scratch_bytes(batch, height, width);
+    if (scratch_bytes < need) return fail(1, "scratch too small: %zu < %zu bytes", scratch_bytes, need);
+    if ((uintptr_t)scratch & 255) return fail(1, "scratch must be 256-byte aligned");
+    HIP_TRY(launch_unproject(src, layout, ray_angles, row_start, points, index, reinterpret_cast<long long*>(offsets), batch, height, width, min_depth,
+                             max_depth, depth_format, keep_min, keep_max, scratch, (hipStream_t)stream));
+    return 0;
+}
+
+}  // extern "C"

@@ -3,7 +3,7 @@
 
 The encoding depends on the ray angles only -- not on the step, not on the sample -- so it is evaluated ONCE on the
 host when the weights are packed and enters the engine as the constant ``__cenc`` (coord_channels, H, W); its
-convolution with ``in_conv`` is folded into a per-pixel bias map there (csrc/engine.hip).  Three encodings exist
+convolution with ``in_conv`` is folded into a per-pixel bias map there (csrc/forward.hip).  Three encodings exist
 upstream; all three are tables of closed-form functions of (phi, theta):
 
     fourier_features      [sin(f_k . (phi, theta) + p_k), cos(...)]      2 * (ceil(log2 H) + ceil(log2 W)) channels

@@ -3,7 +3,7 @@
 the three down-sampling convolutions + fir_down2 launches against the three down_planes + down-sampling GEMM launches, per step, with each
 new kernel's share of its floor (bytes / 8 TB/s, FLOP / 833 TF/s).  Usage: scripts/down_gemm_trace.py OFF_kernel_trace.csv ON_kernel_trace.csv [batch]
 
-Launch positions follow the engine's fixed order (r2dm_amd/csrc/engine.hip): conv_f16x2 launches 6, 13 and 20 of the 54 of a step are the down-sampling
+Launch positions follow the engine's fixed order (r2dm_amd/csrc/forward.hip): conv_f16x2 launches 6, 13 and 20 of the 54 of a step are the down-sampling
 convolutions with the switch off (51 launches with it on)."""
 import collections
 import csv

@@ -2,7 +2,7 @@
 """Per-shape roofline table of conv_f16x2_kernel from a rocprofv3 kernel trace of bench.py (config 1: 64x1024, batch 8), plus the
 cost of the gn_finalize hops.  Usage: scripts/per_shape_table.py gpurun_out/<job>/bench_kt_kernel_trace.csv [batch] > profiles/<tag>_conv_shapes.txt
 
-The 54 launches of a reverse step come in the engine's fixed order (r2dm_amd/csrc/engine.hip: d_block1..4, u_block4..1;
+The 54 launches of a reverse step come in the engine's fixed order (r2dm_amd/csrc/forward.hip: d_block1..4, u_block4..1;
 reference efficient_unet.py:95-110,132-139,169-176); launch i of every step is averaged over all steps in the trace.
 peak = dense 16-bit MFMA 2500 TF/s / 3 products per fp32 product = 833.3 TF/s of algorithmic fp32 FLOPs."""
 import csv, sys, collections
