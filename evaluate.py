@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Drop-in for the BEV part of the reference's evaluation script (evaluate.py): scores a directory of generated
+"""Drop-in for the BEV and point-cloud parts of the reference's evaluation script (evaluate.py): scores a directory of generated
 ``samples_*.pth`` files (sample_and_save.py's (5,H,W) [depth, x, y, z, reflectance] tensors) against a real set with the
-bird's-eye-view JSD and MMD of metrics/bev.py, on the GPU (r2dm_amd.metrics).
+bird's-eye-view JSD and MMD of metrics/bev.py and, given the PointNet weights, the FPD (Frechet distance and squared MMD of
+PointNet features, metrics/distribution.py), on the GPU (r2dm_amd.metrics, r2dm_amd.pointnet).
 
 Same CLI (``--ckpt``, ``--sample_dir``, ``--dataset``, ``--batch_size``, ``--num_workers``) and the same output file,
 ``{sample_dir}_{timestamp}.json``.  The real set comes from either
@@ -11,7 +12,13 @@ Same CLI (``--ckpt``, ``--sample_dir``, ``--dataset``, ``--batch_size``, ``--num
   - ``--real_scans DIR``: a directory tree of raw Velodyne ``*.bin`` scans (KITTI-360's ``data_3d_raw``, say), projected here on the
     GPU (r2dm_amd.projection) with the checkpoint's ``cfg.data.projection`` and resized to ``cfg.data.resolution`` as the reference's
     dataset and evaluate.py do, ``--batch_size`` scans at a time.
-The HuggingFace dataset builders are not used.  FRD and FPD need the RangeNet-53 / PointNet weights and are not computed here."""
+The HuggingFace dataset builders are not used.
+
+``--pointnet_weights PATH`` (SpareNet's ``cls_model_39.pth``, the file the reference downloads; nothing is downloaded here) adds
+``pts.frechet_distance`` and ``pts.squared_mmd``: the generated features come from the batches that feed the BEV histograms, the real
+ones from the cache pickle's ``pts_feats`` or from the ``--real_dir`` / ``--real_scans`` batches; all real features are used.  The
+subsets of the squared MMD are drawn from numpy's global state as in the reference, or from ``--mmd_seed``.  FRD needs the
+RangeNet-53 weights and is not computed here."""
 import datetime
 import json
 import pickle
@@ -48,15 +55,24 @@ def load_batches(files, batch_size, num_workers):
     return torch.utils.data.DataLoader(Files(), batch_size=batch_size, num_workers=num_workers)
 
 
-def histograms_of(files, batch_size, num_workers, device):
-    """int32 (N,100,100) BEV histograms of the sample files: depth mask, then point_cloud_to_histogram (evaluate.py:22-41,145-155)."""
-    from r2dm_amd import metrics
+def _measure(imgs, extractor, hists, feats):
+    """One (B,5,H,W) batch on the GPU: its BEV histograms and, with an extractor, its PointNet features (evaluate.py:150-160)."""
+    from r2dm_amd import metrics, pointnet
 
+    hists.append(metrics.bev_histograms(imgs, image_min_depth=MIN_DEPTH, image_max_depth=MAX_DEPTH))
+    if extractor is not None:
+        feats.append(pointnet.pointnet_features(extractor, imgs))
+
+
+def histograms_of(files, batch_size, num_workers, device, extractor=None):
+    """int32 (N,100,100) BEV histograms of the sample files: depth mask, then point_cloud_to_histogram (evaluate.py:22-41,145-155);
+    with ``extractor`` also the (N,1808) PointNet features of the same batches (else None)."""
     if not files:
         raise SystemExit("no *.pth files to evaluate")
-    out = [metrics.bev_histograms(imgs.to(device, non_blocking=True), image_min_depth=MIN_DEPTH, image_max_depth=MAX_DEPTH)
-           for imgs in load_batches(files, batch_size, num_workers)]
-    return torch.cat(out)
+    hists, feats = [], []
+    for imgs in load_batches(files, batch_size, num_workers):
+        _measure(imgs.to(device, non_blocking=True), extractor, hists, feats)
+    return torch.cat(hists), (torch.cat(feats) if extractor is not None else None)
 
 
 def scan_files(root):
@@ -64,26 +80,27 @@ def scan_files(root):
     return sorted(Path(root).rglob("*.bin"))
 
 
-def histograms_of_scans(files, cfg, batch_size, device):
+def histograms_of_scans(files, cfg, batch_size, device, extractor=None):
     """int32 (N,100,100) BEV histograms of raw scans: the dataset builder's projection (64 rows, the projection's own width, masked by
-    its depth window), evaluate.py's resize to the model's resolution (nearest-exact), then the depth mask and histogram as above."""
+    its depth window), evaluate.py's resize to the model's resolution (nearest-exact), then the depth mask and histogram as above;
+    with ``extractor`` also the PointNet features of the same images (else None)."""
     import torch.nn.functional as F
 
-    from r2dm_amd import metrics, projection
+    from r2dm_amd import projection
 
     if not files:
         raise SystemExit("no *.bin files below --real_scans")
     unfolding, width = projection.parse_projection(cfg.data.projection)
     H, W = cfg.data.resolution
-    out = []
+    hists, feats = [], []
     for k in range(0, len(files), batch_size):
         points, offsets = projection.load_scans(files[k:k + batch_size])
         imgs = projection.project_scans(points, offsets, H=64, W=width, scan_unfolding=unfolding, apply_mask=True,
                                         out_width=W if W <= width else None, layout="sample", device=device)
         if tuple(imgs.shape[-2:]) != (H, W):
             imgs = F.interpolate(imgs, size=(H, W), mode="nearest-exact")
-        out.append(metrics.bev_histograms(imgs, image_min_depth=MIN_DEPTH, image_max_depth=MAX_DEPTH))
-    return torch.cat(out)
+        _measure(imgs, extractor, hists, feats)
+    return torch.cat(hists), (torch.cat(feats) if extractor is not None else None)
 
 
 def real_cache_name(cfg, split):
@@ -100,16 +117,22 @@ def evaluate(args):
     ckpt = torch.load(args.ckpt, map_location="cpu")
     cfg = Config(**ckpt["cfg"])
 
+    extractor = None
+    if getattr(args, "pointnet_weights", None) is not None:
+        from r2dm_amd import pointnet
+
+        extractor = pointnet.pretrained_pointnet(args.pointnet_weights, device=device)
+
     results = dict(img=dict(), pts=dict(), bev=dict(), info=dict())
     results["info"]["phase"] = args.dataset
     results["info"]["directory"] = args.sample_dir
 
     # real set: the reference's cache, or a directory of scans
     if args.real_scans is not None:
-        real_hists = histograms_of_scans(scan_files(args.real_scans), cfg, args.batch_size, device)
+        real_hists, real_feats = histograms_of_scans(scan_files(args.real_scans), cfg, args.batch_size, device, extractor)
         results["info"]["real"] = str(args.real_scans)
     elif args.real_dir is not None:
-        real_hists = histograms_of(sample_files(args.real_dir, limit=None), args.batch_size, args.num_workers, device)
+        real_hists, real_feats = histograms_of(sample_files(args.real_dir, limit=None), args.batch_size, args.num_workers, device, extractor)
         results["info"]["real"] = str(args.real_dir)
     else:
         path = Path(args.real_set) if args.real_set is not None else Path(real_cache_name(cfg, args.dataset))
@@ -120,11 +143,14 @@ def evaluate(args):
         with open(path, "rb") as f:
             real_set = pickle.load(f)
         real_hists = torch.from_numpy(np.ascontiguousarray(real_set["bev_hists"])).to(device)
+        real_feats = None
+        if extractor is not None:  # the reference's own PointNet features of the real set
+            real_feats = torch.from_numpy(np.ascontiguousarray(real_set["pts_feats"], dtype=np.float32)).to(device)
         results["info"]["real"] = str(path)
     results["info"]["#real"] = len(real_hists)
 
     # generated set
-    gen_hists = histograms_of(sample_files(args.sample_dir), args.batch_size, args.num_workers, device)
+    gen_hists, gen_feats = histograms_of(sample_files(args.sample_dir), args.batch_size, args.num_workers, device, extractor)
     results["info"]["#fake"] = len(gen_hists)
 
     # the real subset as the reference takes it (evaluate.py:185-187)
@@ -135,7 +161,14 @@ def evaluate(args):
 
     results["bev"]["jsd"] = metrics.compute_jsd_2d(real_sub, gen_hists)
     results["bev"]["mmd"] = metrics.compute_mmd_2d(real_sub, gen_hists)
-    results["info"]["note"] = ("img (FRD) and pts (FPD) are not computed: they need the RangeNet-53 and PointNet weights")
+    if extractor is None:
+        results["info"]["note"] = ("img (FRD) and pts (FPD) are not computed: they need the RangeNet-53 and PointNet weights")
+    else:  # all real features, as the reference (evaluate.py:182-187)
+        seed = getattr(args, "mmd_seed", None)
+        results["pts"]["frechet_distance"] = metrics.compute_frechet_distance(real_feats, gen_feats)
+        results["pts"]["squared_mmd"] = metrics.compute_squared_mmd(real_feats, gen_feats,
+                                                                    rng=None if seed is None else np.random.RandomState(seed))
+        results["info"]["note"] = "img (FRD) is not computed: it needs the RangeNet-53 weights"
 
     print(results)
     save_path = args.sample_dir + f"_{datetime.datetime.now().strftime('%Y%m%dT%H%M%S')}.json"
@@ -144,7 +177,7 @@ def evaluate(args):
     return save_path
 
 
-if __name__ == "__main__":
+def build_parser():
     parser = ArgumentParser()
     parser.add_argument("--ckpt", type=Path, required=True)
     parser.add_argument("--sample_dir", type=str, required=True)
@@ -157,4 +190,12 @@ if __name__ == "__main__":
                         help="extension: a directory of (5,H,W) real scans in the sample layout, instead of the cache")
     parser.add_argument("--real_scans", type=str, default=None,
                         help="extension: a directory tree of raw Velodyne *.bin scans, projected here with the checkpoint's projection")
-    evaluate(parser.parse_args())
+    parser.add_argument("--pointnet_weights", type=str, default=None,
+                        help="extension: SpareNet's cls_model_39.pth (the PointNet of the FPD); adds pts.frechet_distance / pts.squared_mmd")
+    parser.add_argument("--mmd_seed", type=int, default=None,
+                        help="extension: seed of the squared MMD's subset draws (default: numpy's global state, as the reference)")
+    return parser
+
+
+if __name__ == "__main__":
+    evaluate(build_parser().parse_args())

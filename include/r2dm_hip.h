@@ -180,6 +180,41 @@ size_t r2dm_bev_mmd_scratch_bytes(int32_t np, int32_t nq);
 int r2dm_bev_mmd(const float* p, const float* q, int32_t np, int32_t nq, int64_t bins, double sigma, void* scratch,
                  size_t scratch_bytes, double* out, void* stream);
 
+/* -- FPD of the evaluation script: PointNet features and their distribution metrics (metrics/extractor/pointnet.py,
+ *    metrics/distribution.py; evaluate.py:61-65,158-160,182-187) ------------------------------------------------------------------
+ * The network is PointNet1(k = 16) in eval mode with every BatchNorm folded into the layer in front of it by the caller.
+ * r2dm_pointnet_pack: w (cout, cin) fp32 -> packed (r2dm_pointnet_packed_bytes(), 16-byte aligned): the layer scaled by a power of
+ *    two (max|w| into [2^9, 2^10)) and split into an fp16 piece and an fp16 residual, in matrix-core operand order.  wscale: two
+ *    floats of device memory, [1] <- the inverse scale.  cout % 32 == 0, cin % 16 == 0.  *flag |= 4 if a weight is not finite.
+ * r2dm_pointnet_trunk: one fused pass over the points of every cloud: 3 -> 64 (fp32 FMA, ReLU), 64 -> 128 (ReLU) and 128 -> 1024 on
+ *    the fp16 matrix pipe (three products per MAC, fp32 accumulation), and the per-channel maximum over the points; only the maxima
+ *    reach memory: scratch (r2dm_pointnet_scratch_bytes()) holds them as order-preserving integer keys of W3 h2 before the last
+ *    layer's inverse scale and bias, which r2dm_pointnet_head applies.  Exact and the same bits on every call and for every order of
+ *    the points.  layout 0: src (batch,5,H,W) samples [depth, x, y, z, reflectance], xyz x (image_min_depth < depth < image_max_depth) /
+ *    divisor, points = H W, all kept; layout 1: src (batch,points,3); layout 2: src (batch,3,points).  trans: (batch,9) row-major 3 x 3
+ *    applied as point @ trans, or NULL.  w1b: (64,4) rows [w0, w1, w2, bias]; b2 (128,).
+ *    *flag |= 1 for a non-finite coordinate, |= 2 for an activation outside the fp16 operand range (65504): the results are then invalid.
+ * r2dm_pointnet_head: per cloud x1 = max * w3_inv_scale + b3 (ReLU if stn), fc1 1024 -> 512 + ReLU, fc2 512 -> 256 + ReLU,
+ *    fc3 256 -> outputs, plain fp32.  stn = 1: out (batch,9) = fc3 + identity (outputs = 9); stn = 0: out (batch,1808) =
+ *    cat(x1, x2, x3, x4), outputs = 16.
+ * r2dm_feature_moments: feats (rows,dim) fp32 -> mean (dim,) and unbiased covariance (dim,dim) in fp64, two passes, fixed order.
+ * r2dm_poly_mmd: for each of `subsets` subsets, x = rows ix[s] of X and y = rows iy[s] of Y (subset_size int64 indices each, device
+ *    memory, in range): out[s] = (sum_ij (x_i.y_j / dim + 1)^3, the same over x x x off the diagonal, over y x y off the diagonal),
+ *    fp64 throughout, no subset_size^2 matrix.  scratch: r2dm_poly_mmd_scratch_bytes(), 256-byte aligned. */
+size_t r2dm_pointnet_packed_bytes(int32_t cout, int32_t cin);
+int r2dm_pointnet_pack(const float* w, int32_t cout, int32_t cin, void* packed, float* wscale, int32_t* flag, void* stream);
+size_t r2dm_pointnet_scratch_bytes(int32_t batch);
+int r2dm_pointnet_trunk(const float* src, int32_t layout, int32_t batch, int64_t points, const float* trans, float image_min_depth,
+                        float image_max_depth, float divisor, const float* w1b, const void* w2_packed, const float* w2_inv_scale, const float* b2,
+                        const void* w3_packed, void* scratch, size_t scratch_bytes, int32_t* flag, void* stream);
+int r2dm_pointnet_head(const void* scratch, const float* w3_inv_scale, const float* b3, int32_t stn, const float* fc1_w, const float* fc1_b,
+                       const float* fc2_w, const float* fc2_b, const float* fc3_w, const float* fc3_b, int32_t outputs, float* out, int32_t batch,
+                       void* stream);
+int r2dm_feature_moments(const float* feats, int64_t rows, int32_t dim, double* mean, double* cov, void* stream);
+size_t r2dm_poly_mmd_scratch_bytes(int32_t subsets, int32_t subset_size);
+int r2dm_poly_mmd(const float* x, const float* y, const int64_t* ix, const int64_t* iy, int32_t subsets, int32_t subset_size, int32_t dim,
+                  void* scratch, size_t scratch_bytes, double* out, void* stream);
+
 /* -- rendering of generate.py (utils/render.py; generate.py:44-59) -------------------------------------------------------------
  * All arithmetic is fp32 with one rounding per operation.  The splat accumulates 64-bit fixed-point integers (scale from the
  * largest |value| of the call, taken on the device): the same bits on every call and for every order of the points.

@@ -13,11 +13,14 @@ from . import projection  # noqa: E402  (raw scans -> range images)
 from .projection import known_from_scan, load_points_as_images, load_scans, parse_projection, project_scans
 from . import pointcloud  # noqa: E402  (range images -> point clouds)
 from .pointcloud import centred_ray_angles, images_to_points, save_ply, save_scans, scan_row_start
+from . import pointnet  # noqa: E402  (PointNet features of the FPD)
+from .pointnet import pointnet_features, pretrained_pointnet
 
 __all__ = [
     "ContinuousTimeGaussianDiffusion", "DiscreteTimeGaussianDiffusion", "GaussianDiffusion", "EfficientUNet",
     "LiDARUtility", "Config", "setup_model", "setup_rng",
     "load_scans", "project_scans", "load_points_as_images", "parse_projection", "known_from_scan",
     "images_to_points", "save_scans", "save_ply", "scan_row_start", "centred_ray_angles",
+    "pretrained_pointnet", "pointnet_features",
 ]
 __version__ = "0.4.0"

@@ -284,6 +284,21 @@ hipError_t launch_bev_hist_sum(const void* hist, int is_int32, int64_t* sum, lon
 size_t mmd_scratch_bytes(int np, int nq);
 hipError_t launch_bev_mmd(const float* P, const float* Q, int np, int nq, long D, double sigma, void* scratch, double* out, hipStream_t s);
 
+// distribution metrics of feature sets (metrics.hip): fp64 mean / unbiased covariance; the polynomial-kernel MMD's three sums per subset
+hipError_t launch_feature_moments(const float* f, long n, int D, double* mean, double* cov, hipStream_t s);
+size_t poly_mmd_scratch_bytes(int subsets, int m);
+hipError_t launch_poly_mmd(const float* X, const float* Y, const long long* ix, const long long* iy, int subsets, int m, int D, void* scratch,
+                           double* out, hipStream_t s);
+
+// PointNet feature extractor of the FPD (pointnet.hip): weight packing, the fused trunk (layout 0 (B,5,H,W) samples, 1 (B,N,3), 2 (B,3,N)), the per-cloud MLPs
+hipError_t launch_pointnet_pack(const float* w, int Cout, int Cin, void* dst, float* wscale, int* flag, hipStream_t s);
+size_t pointnet_scratch_bytes(int B);
+hipError_t launch_pointnet_trunk(const float* src, int layout, int B, long n, const float* trans, float img_min, float img_max, float divisor,
+                                 const float* w1b, const void* w2p, const float* w2inv, const float* b2, const void* w3p, void* scratch, int* flag,
+                                 hipStream_t s);
+hipError_t launch_pointnet_head(const void* scratch, const float* w3inv, const float* b3, int stn, const float* w1, const float* b1, const float* w2,
+                                const float* b2, const float* w3, const float* bo, int kout, float* out, int B, hipStream_t s);
+
 // rendering of generate.py (render.hip): colour maps, the bilinear splat with 64-bit fixed-point accumulators, the fused frame renderer
 hipError_t launch_colorize(const float* x, const float* lut, uint8_t* out, long B, long hw, hipStream_t s);
 size_t rasterize_scratch_bytes(int B, int C, int H, int W);

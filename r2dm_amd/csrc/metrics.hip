@@ -310,4 +310,188 @@ hipError_t launch_bev_mmd(const float* P, const float* Q, int np, int nq, long D
     return hipGetLastError();
 }
 
+// ---- feature moments (Frechet distance) ----------------------------------------------------------
+// mean and unbiased covariance of (n, D) fp32 features in fp64, two passes (the second over centred values), every sum in a
+// fixed order: mean[d] one thread per column, cov one 64 x 64 tile per block with the rows staged 16 at a time.
+__global__ __launch_bounds__(256) void feat_mean_kernel(const float* __restrict__ f, double* __restrict__ mean, long n, int D) {
+    const int d = blockIdx.x * 256 + threadIdx.x;
+    if (d >= D) return;
+    double s = 0.0;
+    for (long r = 0; r < n; ++r) s += (double)f[r * D + d];
+    mean[d] = s / (double)n;
+}
+
+constexpr int kCovRows = 16;
+
+__global__ __launch_bounds__(256) void feat_cov_kernel(const float* __restrict__ f, const double* __restrict__ mean, double* __restrict__ cov,
+                                                       long n, int D) {
+    __shared__ double As[kCovRows][kTile], Bs[kCovRows][kTile];
+    const int i0 = blockIdx.y * kTile, j0 = blockIdx.x * kTile;
+    const int tx = threadIdx.x % 16, ty = threadIdx.x / 16;
+    const int sc = threadIdx.x % kTile, sr = threadIdx.x / kTile;  // staging: column sc, rows sr + 4 u
+    const bool va = i0 + sc < D, vb = j0 + sc < D;
+    const double ma = va ? mean[i0 + sc] : 0.0, mb = vb ? mean[j0 + sc] : 0.0;
+    double acc[kMicro][kMicro];
+#pragma unroll
+    for (int a = 0; a < kMicro; ++a)
+#pragma unroll
+        for (int c = 0; c < kMicro; ++c) acc[a][c] = 0.0;
+    for (long r0 = 0; r0 < n; r0 += kCovRows) {
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < kCovRows / 4; ++u) {
+            const long r = r0 + sr + 4 * u;
+            As[sr + 4 * u][sc] = (va && r < n) ? (double)f[r * D + i0 + sc] - ma : 0.0;
+            Bs[sr + 4 * u][sc] = (vb && r < n) ? (double)f[r * D + j0 + sc] - mb : 0.0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < kCovRows; ++k)
+#pragma unroll
+            for (int a = 0; a < kMicro; ++a)
+#pragma unroll
+                for (int c = 0; c < kMicro; ++c) acc[a][c] = fma(As[k][ty * kMicro + a], Bs[k][tx * kMicro + c], acc[a][c]);
+    }
+#pragma unroll
+    for (int a = 0; a < kMicro; ++a)
+#pragma unroll
+        for (int c = 0; c < kMicro; ++c) {
+            const int i = i0 + ty * kMicro + a, j = j0 + tx * kMicro + c;
+            if (i < D && j < D) cov[(long)i * D + j] = acc[a][c] / (double)(n - 1);
+        }
+}
+
+hipError_t launch_feature_moments(const float* f, long n, int D, double* mean, double* cov, hipStream_t s) {
+    if (n < 2 || D < 1) return hipErrorInvalidValue;
+    feat_mean_kernel<<<(D + 255) / 256, 256, 0, s>>>(f, mean, n, D);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const unsigned t = (unsigned)((D + kTile - 1) / kTile);
+    feat_cov_kernel<<<dim3(t, t), 256, 0, s>>>(f, mean, cov, n, D);
+    return hipGetLastError();
+}
+
+// ---- polynomial-kernel MMD of feature sets (metrics/distribution.py compute_squared_mmd) ---------------------------------------
+// Per subset s: x = X[ix[s]], y = Y[iy[s]] (m rows each, gathered here); the three sums of (u.v / D + 1)^3 over the pairs of
+// x x x and y x y off the diagonal and of x x y, products and sums in fp64, without an m x m matrix: a block takes a 64 x 64 tile
+// of pairs, the features stream through LDS 16 at a time; per-block partials, summed in a fixed order.
+constexpr int kPolyK = 16;
+
+__global__ __launch_bounds__(256) void poly_mmd_pairs_kernel(const float* __restrict__ X, const float* __restrict__ Y,
+                                                             const long long* __restrict__ ix, const long long* __restrict__ iy,
+                                                             double* __restrict__ partial, int m, int D) {
+    __shared__ double As[kPolyK][kTile], Bs[kPolyK][kTile];
+    __shared__ double red[256];
+    const int s = blockIdx.y;
+    const int tm = (m + kTile - 1) / kTile;
+    int t = blockIdx.x, ti, tj;
+    const float *A, *B;
+    const long long *ia, *ib;
+    bool self;
+    if (t < tm * tm) {
+        ti = t / tm, tj = t % tm;
+        A = X, B = Y, ia = ix, ib = iy, self = false;
+    } else {
+        t -= tm * tm;
+        if (t < tri_tiles(tm)) {
+            A = B = X, ia = ib = ix;
+        } else {
+            t -= tri_tiles(tm);
+            A = B = Y, ia = ib = iy;
+        }
+        self = true;
+        ti = 0;
+        while (t >= tm - ti) t -= tm - ti++;
+        tj = ti + t;
+    }
+    ia += (long)s * m, ib += (long)s * m;
+    const int i0 = ti * kTile, j0 = tj * kTile;
+    const int tx = threadIdx.x % 16, ty = threadIdx.x / 16;
+    const int sr = threadIdx.x / 4, sc = (threadIdx.x % 4) * 4;  // staging: row sr of the tile, features sc .. sc + 3 of the stage
+    const bool va = i0 + sr < m, vb = j0 + sr < m;
+    const float* ga = A + (va ? ia[i0 + sr] : 0) * (long)D;
+    const float* gb = B + (vb ? ib[j0 + sr] : 0) * (long)D;
+    double acc[kMicro][kMicro];
+#pragma unroll
+    for (int a = 0; a < kMicro; ++a)
+#pragma unroll
+        for (int c = 0; c < kMicro; ++c) acc[a][c] = 0.0;
+    for (int k0 = 0; k0 < D; k0 += kPolyK) {
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int k = k0 + sc + j;
+            As[sc + j][sr] = (va && k < D) ? (double)ga[k] : 0.0;
+            Bs[sc + j][sr] = (vb && k < D) ? (double)gb[k] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < kPolyK; ++k)
+#pragma unroll
+            for (int a = 0; a < kMicro; ++a)
+#pragma unroll
+                for (int c = 0; c < kMicro; ++c) acc[a][c] = fma(As[k][ty * kMicro + a], Bs[k][tx * kMicro + c], acc[a][c]);
+    }
+    double sum = 0.0;
+#pragma unroll
+    for (int a = 0; a < kMicro; ++a)
+#pragma unroll
+        for (int c = 0; c < kMicro; ++c) {
+            const int i = i0 + ty * kMicro + a, j = j0 + tx * kMicro + c;
+            if (i >= m || j >= m) continue;
+            double w = 1.0;
+            if (self) {  // off the diagonal only; the upper triangle counts twice
+                if (j <= i) continue;
+                w = 2.0;
+            }
+            const double v = acc[a][c] / (double)D + 1.0;
+            sum += w * (v * v * v);
+        }
+    red[threadIdx.x] = sum;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[(long)s * gridDim.x + blockIdx.x] = red[0];
+}
+
+// out[s] = (sum over x x y, over x x x off the diagonal, over y x y off the diagonal), one block per subset, fixed order
+__global__ __launch_bounds__(256) void poly_mmd_final_kernel(const double* __restrict__ partial, double* __restrict__ out, int n_xy, int n_tri) {
+    __shared__ double red[256];
+    const int s = blockIdx.x;
+    const double* ps = partial + (long)s * (n_xy + 2 * n_tri);
+    const int start[3] = {0, n_xy, n_xy + n_tri}, cnt[3] = {n_xy, n_tri, n_tri};
+    for (int c = 0; c < 3; ++c) {
+        double v = 0.0;
+        for (int i = threadIdx.x; i < cnt[c]; i += 256) v += ps[start[c] + i];
+        red[threadIdx.x] = v;
+        __syncthreads();
+        for (int w = 128; w > 0; w >>= 1) {
+            if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) out[s * 3 + c] = red[0];
+        __syncthreads();
+    }
+}
+
+size_t poly_mmd_scratch_bytes(int subsets, int m) {
+    const long tm = (m + kTile - 1) / kTile;
+    return (size_t)subsets * (size_t)(tm * tm + tm * (tm + 1)) * sizeof(double);
+}
+
+hipError_t launch_poly_mmd(const float* X, const float* Y, const long long* ix, const long long* iy, int subsets, int m, int D, void* scratch,
+                           double* out, hipStream_t s) {
+    if (subsets < 1 || subsets > 65535 || m < 1 || D < 1) return hipErrorInvalidValue;
+    const long tm = (m + kTile - 1) / kTile;
+    const long n_xy = tm * tm, n_tri = tm * (tm + 1) / 2;
+    if (n_xy + 2 * n_tri > 0x7fffffffL) return hipErrorInvalidValue;
+    poly_mmd_pairs_kernel<<<dim3((unsigned)(n_xy + 2 * n_tri), (unsigned)subsets), 256, 0, s>>>(X, Y, ix, iy, static_cast<double*>(scratch), m, D);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    poly_mmd_final_kernel<<<subsets, 256, 0, s>>>(static_cast<const double*>(scratch), out, (int)n_xy, (int)n_tri);
+    return hipGetLastError();
+}
+
 }  // namespace r2dm

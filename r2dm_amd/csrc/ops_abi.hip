@@ -74,6 +74,66 @@ int r2dm_bev_mmd(const float* p, const float* q, int32_t np, int32_t nq, int64_t
     return 0;
 }
 
+int r2dm_feature_moments(const float* feats, int64_t rows, int32_t dim, double* mean, double* cov, void* stream) {
+    if (!feats || !mean || !cov) return fail(1, "null argument");
+    if (rows < 2 || dim < 1) return fail(1, "feature_moments: at least 2 rows and 1 column");
+    HIP_TRY(launch_feature_moments(feats, rows, dim, mean, cov, (hipStream_t)stream));
+    return 0;
+}
+
+size_t r2dm_poly_mmd_scratch_bytes(int32_t subsets, int32_t subset_size) {
+    return subsets < 1 || subset_size < 1 ? 0 : poly_mmd_scratch_bytes(subsets, subset_size);
+}
+
+int r2dm_poly_mmd(const float* x, const float* y, const int64_t* ix, const int64_t* iy, int32_t subsets, int32_t subset_size, int32_t dim,
+                  void* scratch, size_t scratch_bytes, double* out, void* stream) {
+    if (!x || !y || !ix || !iy || !scratch || !out) return fail(1, "null argument");
+    if (subsets < 1 || subsets > 65535 || subset_size < 1 || dim < 1) return fail(1, "poly_mmd: 1 to 65535 subsets of at least one row");
+    if (scratch_bytes < poly_mmd_scratch_bytes(subsets, subset_size))
+        return fail(1, "scratch too small: %zu < %zu bytes", scratch_bytes, poly_mmd_scratch_bytes(subsets, subset_size));
+    if ((uintptr_t)scratch & 255) return fail(1, "scratch must be 256-byte aligned");
+    HIP_TRY(launch_poly_mmd(x, y, reinterpret_cast<const long long*>(ix), reinterpret_cast<const long long*>(iy), subsets, subset_size, dim, scratch, out,
+                            (hipStream_t)stream));
+    return 0;
+}
+
+size_t r2dm_pointnet_packed_bytes(int32_t cout, int32_t cin) {
+    return cout < 32 || cout % 32 || cin < 16 || cin % 16 ? 0 : (size_t)cout * cin * 4;
+}
+
+int r2dm_pointnet_pack(const float* w, int32_t cout, int32_t cin, void* packed, float* wscale, int32_t* flag, void* stream) {
+    if (!w || !packed || !wscale || !flag) return fail(1, "null argument");
+    if (!r2dm_pointnet_packed_bytes(cout, cin)) return fail(1, "pointnet_pack: cout must be a multiple of 32, cin of 16");
+    if ((uintptr_t)packed & 15) return fail(1, "pointnet_pack: packed must be 16-byte aligned");
+    HIP_TRY(launch_pointnet_pack(w, cout, cin, packed, wscale, flag, (hipStream_t)stream));
+    return 0;
+}
+
+size_t r2dm_pointnet_scratch_bytes(int32_t batch) { return batch < 1 || batch > 65535 ? 0 : pointnet_scratch_bytes(batch); }
+
+int r2dm_pointnet_trunk(const float* src, int32_t layout, int32_t batch, int64_t points, const float* trans, float image_min_depth,
+                        float image_max_depth, float divisor, const float* w1b, const void* w2_packed, const float* w2_inv_scale, const float* b2,
+                        const void* w3_packed, void* scratch, size_t scratch_bytes, int32_t* flag, void* stream) {
+    if (!src || !w1b || !w2_packed || !w2_inv_scale || !b2 || !w3_packed || !scratch || !flag) return fail(1, "null argument");
+    if (layout < 0 || layout > 2) return fail(1, "layout must be 0 ((B,5,H,W) samples), 1 ((B,N,3) clouds) or 2 ((B,3,N) clouds)");
+    if (batch < 1 || batch > 65535 || points < 1) return fail(1, "pointnet_trunk: batch must be in [1, 65535] and a cloud must have a point");
+    if (layout == 0 && !(divisor > 0.f)) return fail(1, "pointnet_trunk: divisor must be > 0");
+    if (scratch_bytes < pointnet_scratch_bytes(batch)) return fail(1, "scratch too small: %zu < %zu bytes", scratch_bytes, pointnet_scratch_bytes(batch));
+    if (((uintptr_t)w1b | (uintptr_t)w2_packed | (uintptr_t)w3_packed) & 15) return fail(1, "pointnet_trunk: weights must be 16-byte aligned");
+    HIP_TRY(launch_pointnet_trunk(src, layout, batch, points, trans, image_min_depth, image_max_depth, divisor, w1b, w2_packed, w2_inv_scale, b2,
+                                  w3_packed, scratch, flag, (hipStream_t)stream));
+    return 0;
+}
+
+int r2dm_pointnet_head(const void* scratch, const float* w3_inv_scale, const float* b3, int32_t stn, const float* fc1_w, const float* fc1_b,
+                       const float* fc2_w, const float* fc2_b, const float* fc3_w, const float* fc3_b, int32_t outputs, float* out, int32_t batch,
+                       void* stream) {
+    if (!scratch || !w3_inv_scale || !b3 || !fc1_w || !fc1_b || !fc2_w || !fc2_b || !fc3_w || !fc3_b || !out) return fail(1, "null argument");
+    if (batch < 1 || outputs < 1 || outputs > 16 || (stn && outputs != 9)) return fail(1, "pointnet_head: 1 to 16 outputs (9 for the transformer)");
+    HIP_TRY(launch_pointnet_head(scratch, w3_inv_scale, b3, stn, fc1_w, fc1_b, fc2_w, fc2_b, fc3_w, fc3_b, outputs, out, batch, (hipStream_t)stream));
+    return 0;
+}
+
 int r2dm_colorize(const float* x, const float* lut, uint8_t* out, int64_t batch, int64_t pixels, void* stream) {
     if (!x || !lut || !out) return fail(1, "null argument");
     if (batch < 1 || pixels < 1) return fail(1, "empty image batch");

@@ -8,6 +8,13 @@ Same names and signatures as the reference module; inputs are ROCm tensors and n
 - JSD sums the counts exactly (int64 on the GPU) and normalises them in fp64 on the host.
 - MMD sums ``1 - k = -expm1(-gamma d^2)`` in fp64 with ``d^2 = sum_k (p_k - q_k)^2`` taken directly, never as
   ``|p|^2 + |q|^2 - 2 p.q``, and never forms the N x N matrix; the result is deterministic.
+
+And the distribution metrics of feature sets (metrics/distribution.py), which evaluate.py applies to the PointNet features (FPD):
+
+- ``feature_moments``: mean and unbiased covariance in fp64 on the GPU, two passes, deterministic.
+- ``compute_frechet_distance``: those moments, then the matrix square root on the host in fp64 (scipy), as the reference.
+- ``compute_squared_mmd``: the polynomial-kernel estimator over random subsets drawn on the host as the reference draws them;
+  per subset the GPU gathers the rows and sums the three kernel matrices in fp64 without writing them.
 """
 from __future__ import annotations
 
@@ -126,3 +133,94 @@ def compute_mmd_2d(hist1: torch.Tensor, hist2: torch.Tensor) -> float:
     """BEV-based maximum mean discrepancy (metrics/bev.py): mean k_pp + mean k_qq - 2 mean k_pq, biased, sigma 0.5."""
     pq, pp, qq = mmd_terms(hist1, hist2)
     return 2.0 * pq - pp - qq
+
+
+# ---- distribution metrics of feature sets (metrics/distribution.py) ----------------------------------------------------------
+def _as_feats(feats, what: str) -> torch.Tensor:
+    """(N,D) fp32 features on the GPU; a numpy array (the reference's cache pickle) is uploaded."""
+    if isinstance(feats, np.ndarray):
+        feats = torch.from_numpy(np.ascontiguousarray(feats)).cuda()
+    _lib.require_gpu(feats, what)
+    if feats.ndim != 2:
+        raise ValueError(f"{what}: expected (N,D) features, got {tuple(feats.shape)}")
+    return _lib.f32c(feats)
+
+
+@torch.no_grad()
+def feature_moments(feats):
+    """Mean ``(D,)`` and unbiased covariance ``(D,D)`` (``np.cov(rowvar=False)``) of ``(N,D)`` features, fp64, on the GPU."""
+    f = _as_feats(feats, "feats")
+    n, d = f.shape
+    if n < 2 or d < 1:
+        raise ValueError(f"feature_moments needs at least 2 rows and 1 column, got {tuple(f.shape)}")
+    mean = torch.empty(d, dtype=torch.float64, device=f.device)
+    cov = torch.empty(d, d, dtype=torch.float64, device=f.device)
+    with torch.cuda.device(f.device):
+        _lib.check(_lib.lib().r2dm_feature_moments(_lib.ptr(f), n, d, _lib.ptr(mean), _lib.ptr(cov), _lib.stream_ptr(f.device)))
+    return mean, cov
+
+
+def compute_frechet_distance(feats1, feats2) -> float:
+    """Frechet distance between the Gaussians fitted to two feature sets (metrics/distribution.py):
+    ``|mu1 - mu2|^2 + tr(S1 + S2 - 2 sqrtm(S1 S2))``, the moments on the GPU, the rest on the host in fp64."""
+    import scipy.linalg
+
+    mu1, s1 = (t.cpu().numpy() for t in feature_moments(feats1))
+    mu2, s2 = (t.cpu().numpy() for t in feature_moments(feats2))
+    if mu1.shape != mu2.shape:
+        raise ValueError(f"features of {mu1.shape[0]} and {mu2.shape[0]} dimensions")
+    m = np.square(mu1 - mu2).sum()
+    s, _ = scipy.linalg.sqrtm(np.dot(s1, s2), disp=False)
+    return float(np.real(m + np.trace(s1 + s2 - s * 2)))
+
+
+def draw_mmd_subsets(n1: int, n2: int, num_subsets: int = 100, max_subset_size: int = 1000, rng=None):
+    """The subsets of compute_squared_mmd in the reference's order of draws: per subset first ``choice(n2, m)`` (rows of
+    feats2), then ``choice(n1, m)`` (rows of feats1), without replacement, from ``rng`` (anything with numpy's ``choice``;
+    None = numpy's global state).  Returns int64 arrays ``(idx1, idx2)`` of shape ``(num_subsets, m)``."""
+    choice = np.random.choice if rng is None else rng.choice
+    m = min(min(n1, n2), max_subset_size)
+    idx1, idx2 = np.empty((num_subsets, m), np.int64), np.empty((num_subsets, m), np.int64)
+    for s in range(num_subsets):
+        idx2[s] = choice(n2, m, replace=False)
+        idx1[s] = choice(n1, m, replace=False)
+    return idx1, idx2
+
+
+@torch.no_grad()
+def squared_mmd_from_indices(feats1, feats2, idx1, idx2) -> float:
+    """compute_squared_mmd over explicit subsets: ``idx1`` / ``idx2`` (num_subsets, m) rows of feats1 / feats2."""
+    f1, f2 = _as_feats(feats1, "feats1"), _as_feats(feats2, "feats2")
+    if f1.device != f2.device:
+        raise ValueError(f"feats1 on {f1.device}, feats2 on {f2.device}")
+    if f1.shape[1] != f2.shape[1]:
+        raise ValueError(f"features of {f1.shape[1]} and {f2.shape[1]} dimensions")
+    idx1, idx2 = np.ascontiguousarray(idx1, dtype=np.int64), np.ascontiguousarray(idx2, dtype=np.int64)
+    if idx1.ndim != 2 or idx1.shape != idx2.shape or idx1.shape[0] < 1 or idx1.shape[1] < 2:
+        raise ValueError(f"subset indices of shapes {idx1.shape} and {idx2.shape}: expected two (num_subsets, m >= 2) arrays")
+    for idx, f, what in ((idx1, f1, "idx1"), (idx2, f2, "idx2")):
+        if idx.min() < 0 or idx.max() >= f.shape[0]:
+            raise ValueError(f"{what} holds a row outside [0, {f.shape[0]})")
+    S, m = idx1.shape
+    d = f1.shape[1]
+    L = _lib.lib()
+    sums = torch.empty(S, 3, dtype=torch.float64, device=f1.device)
+    with torch.cuda.device(f1.device):
+        for k in range(0, S, 4096):  # (a launch takes up to 65535 subsets)
+            nb = min(4096, S - k)
+            ix = torch.from_numpy(idx2[k:k + nb]).to(f1.device)  # x: rows of feats2, y: rows of feats1 (the reference's naming)
+            iy = torch.from_numpy(idx1[k:k + nb]).to(f1.device)
+            scratch = torch.empty(L.r2dm_poly_mmd_scratch_bytes(nb, m) + 256, dtype=torch.uint8, device=f1.device)
+            base = (-scratch.data_ptr()) % 256
+            _lib.check(L.r2dm_poly_mmd(_lib.ptr(f2), _lib.ptr(f1), _lib.ptr(ix), _lib.ptr(iy), nb, m, d, scratch.data_ptr() + base,
+                                       scratch.numel() - base, sums[k:k + nb].data_ptr(), _lib.stream_ptr(f1.device)))
+    xy, xx, yy = sums.cpu().numpy().T
+    t = ((xx + yy) / (m - 1) - xy * 2 / m).sum()
+    return float(t / S / m)
+
+
+def compute_squared_mmd(feats1, feats2, num_subsets: int = 100, max_subset_size: int = 1000, rng=None) -> float:
+    """Squared MMD with the polynomial kernel ``(x.y / D + 1)^3`` over random subsets (metrics/distribution.py)."""
+    n1, n2 = len(feats1), len(feats2)
+    idx1, idx2 = draw_mmd_subsets(n1, n2, num_subsets, max_subset_size, rng)
+    return squared_mmd_from_indices(feats1, feats2, idx1, idx2)

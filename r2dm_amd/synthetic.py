@@ -170,3 +170,47 @@ def synthetic_checkpoint(seed: int = 0, **cfg_kwargs) -> dict:
         v4 = lambda t: t[:, None, None, None]
         sd.update(beta=v4(beta), alpha_bar=v4(ab), alpha_bar_prev=v4(abp), snr=v4(snr))
     return {"cfg": cfg, "weights": sd, "ema_weights": sd, "global_step": 0}
+
+
+def _int_uniform(key: str, seed: int, shape) -> np.ndarray:
+    """fp64 values k / 2^20 in [-1, 1) from integer PCG64 draws seeded by (CRC32 of the key, seed): the same on every platform."""
+    rs = np.random.Generator(np.random.PCG64([zlib.crc32(key.encode()), seed]))
+    return rs.integers(-2**20, 2**20, size=shape).astype(np.float64) * 2.0**-20
+
+
+def synthetic_pointnet_state(seed: int = 0) -> Dict[str, torch.Tensor]:
+    """A state dict in the layout of SpareNet's PointNet classifier (``cls_model_39.pth``: the extractor of the FPD; 64 tensors
+    and the BatchNorms' ``num_batches_tracked``), a pure function of ``seed`` built from integer draws only.
+
+    Weights are uniform with variance 1 / fan_in (activations stay O(1) through the layers); BatchNorm
+    scales have magnitudes in [0.5, 1.5) and a RANDOM SIGN -- a fold that is applied behind the maximum instead of inside the
+    weights is wrong for the negative ones --; running variances lie in [0.5, 1.5).  The feature trunk's third BatchNorm has a
+    shift in [-1.75, 0.25): more than half of the maxima over the points (``x1``) come out negative, so a maximum that starts at 0
+    cannot pass."""
+    from .pointnet import state_spec
+
+    sd: Dict[str, torch.Tensor] = {}
+    for key, shape in state_spec().items():
+        u = _int_uniform(key, seed, shape)
+        leaf = key.rsplit(".", 1)[1]
+        is_bn = ".bn" in "." + key
+        if not is_bn and leaf == "weight":
+            fan_in = int(np.prod(shape[1:]))
+            v = u * math.sqrt(3.0 / fan_in)  # (variance 1 / fan_in)
+            if key == "feat.stn.fc3.weight":
+                v = v * 0.25  # (trans stays near the identity, as in a trained network)
+        elif not is_bn:
+            v = u * 0.1
+        elif leaf == "weight":
+            sign = np.where(_int_uniform(key + "/sign", seed, shape) < 0, -1.0, 1.0)
+            v = (1.0 + 0.5 * u) * sign
+        elif leaf == "bias":
+            v = u * 1.0 - 0.75 if key == "feat.bn3.bias" else u * 0.1
+        elif leaf == "running_mean":
+            v = u * 0.1
+        else:  # running_var
+            v = 1.0 + 0.5 * u
+        sd[key] = torch.from_numpy(v.astype(np.float32))
+        if is_bn and leaf == "running_var":
+            sd[key.rsplit(".", 1)[0] + ".num_batches_tracked"] = torch.tensor(0, dtype=torch.int64)
+    return sd
