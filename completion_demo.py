@@ -10,8 +10,10 @@ HuggingFace dataset lookup, and ``--out`` names the image.  The corruption masks
 
 Written: one PNG with a column per corruption -- input image (depth over reflectance), input bird's-eye view, completed image,
 completed bird's-eye view (r2dm_amd.render; the views coloured by height) -- and, next to it, ``completion.pt`` with ``x_in``,
-``mask`` and ``x_out``.  There is no segmentation row: the reference colours its last two rows with RangeNet-53 labels, and those
-weights are not part of this package.  ``--out_scan FILE.bin`` (extension) also writes the completed scan -- the completion of
+``mask`` and ``x_out``.  ``--rangenet_weights PATH`` (the official ``darknet53-1024.tar.gz`` archive or a ``.pth`` state dict; a local
+file, nothing is downloaded) adds the reference's segmentation: RangeNet-53 labels of the completed samples (r2dm_amd.rangenet), a
+row of label-coloured images under the completed ones, the completed bird's-eye views coloured by label instead of height, and
+``labels`` in ``completion.pt``.  Without it there is no segmentation row.  ``--out_scan FILE.bin`` (extension) also writes the completed scan -- the completion of
 the full input, the first column -- as a Velodyne file in scan order (r2dm_amd.pointcloud)."""
 import math
 from argparse import ArgumentParser
@@ -54,8 +56,18 @@ def to_img(x, lidar_utils):
     return colorize(img.clamp(0, 1).flatten(1, 2), "turbo").float() / 255
 
 
-def to_bev(x, lidar_utils, size):
-    """completion_demo.py:117-133 with the height colouring: (B,2,H,W) -> (B,3,size,size)"""
+def semseg_inputs(x, lidar_utils):
+    """completion_demo.py:40-49 up to the normalisation, which the extractor's kernel applies: (B,2,H,W) in [-1,1] -> the (B,5,H,W)
+    [depth, x, y, z, reflectance] input of RangeNet and its (B,1,H,W) mask"""
+    sample = lidar_utils.denormalize(x)
+    depth = lidar_utils.revert_depth(sample[:, [0]])
+    mask = (depth > lidar_utils.min_depth).float()
+    mask *= (depth < lidar_utils.max_depth).float()
+    return torch.cat([depth, lidar_utils.to_xyz(depth), sample[:, [1]]], dim=1), mask
+
+
+def to_bev(x, lidar_utils, size, colors=None):
+    """completion_demo.py:117-133: (B,2,H,W) -> (B,3,size,size), coloured by height or by the given (B,3,H,W) colours in [0,1]"""
     from r2dm_amd.render import colorize, make_Rt, render_point_clouds
 
     R, t = make_Rt(pitch=math.pi / 4, yaw=math.pi / 4, z=0.6)
@@ -63,7 +75,8 @@ def to_bev(x, lidar_utils, size):
     xyz = lidar_utils.to_xyz(depth) / lidar_utils.max_depth
     z_min, z_max = -2 / lidar_utils.max_depth, 0.5 / lidar_utils.max_depth
     z = (xyz[:, [2]] - z_min) / (z_max - z_min)
-    colors = colorize(z.clamp(0, 1), "viridis").float() / 255
+    if colors is None:
+        colors = colorize(z.clamp(0, 1), "viridis").float() / 255
     points = xyz.flatten(2).transpose(1, 2)
     colors = 1 - colors.flatten(2).transpose(1, 2)
     return (1 - render_point_clouds(points, colors, size=size, R=R, t=t)).clamp(0, 1)
@@ -83,11 +96,23 @@ def main(args):
                          jump_length=args.jump_length, rng=r2dm_amd.setup_rng(range(BATCH), device=device)).clamp(-1, 1)
 
     W = x_in.shape[-1]
-    columns = torch.cat([to_img(x_in, lidar_utils), to_bev(x_in, lidar_utils, W), to_img(x_out, lidar_utils), to_bev(x_out, lidar_utils, W)], dim=2)
+    saved = {"x_in": x_in.cpu(), "mask": mask.cpu(), "x_out": x_out.cpu()}
+    rows = [to_img(x_in, lidar_utils), to_bev(x_in, lidar_utils, W), to_img(x_out, lidar_utils)]
+    if getattr(args, "rangenet_weights", None) is not None:  # completion_demo.py:105-106,138-140
+        from r2dm_amd.render import colorize_labels
+
+        semseg = r2dm_amd.rangenet.pretrained_rangenet(args.rangenet_weights, device=device)
+        labels = semseg.segment(*semseg_inputs(x_out, lidar_utils))
+        colors = colorize_labels(labels).float() / 255
+        rows += [colors, to_bev(x_out, lidar_utils, W, colors)]
+        saved["labels"] = labels.cpu()
+    else:
+        rows.append(to_bev(x_out, lidar_utils, W))
+    columns = torch.cat(rows, dim=2)
     args.out.parent.mkdir(parents=True, exist_ok=True)
     save_png(make_grid(columns, nrow=BATCH, pad_value=1.0), args.out)
     state = args.out.parent / "completion.pt"
-    torch.save({"x_in": x_in.cpu(), "mask": mask.cpu(), "x_out": x_out.cpu()}, state)
+    torch.save(saved, state)
     print(f'Saved to "{args.out}" and "{state}"')
     if args.out_scan is not None:
         points, offsets = r2dm_amd.images_to_points(x_out[:1], lidar_utils, layout="model", order="scan")
@@ -105,6 +130,8 @@ def parser():
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--scan", type=Path, required=True, help="a raw Velodyne scan (*.bin: float32 x, y, z, reflectance), instead of --sample_id")
     p.add_argument("--out", type=Path, default=None, help="the image (default: the reference's completion_T-..._r-..._j-....png)")
+    p.add_argument("--rangenet_weights", type=str, default=None,
+                   help="the official darknet53-1024.tar.gz archive or a .pth state dict (a local file): adds the segmentation row and label colours")
     p.add_argument("--out_scan", type=Path, default=None, help="also write the completed scan (of the full input) as a Velodyne .bin file")
     return p
 

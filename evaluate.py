@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Drop-in for the BEV and point-cloud parts of the reference's evaluation script (evaluate.py): scores a directory of generated
+"""Drop-in for the reference's evaluation script (evaluate.py): scores a directory of generated
 ``samples_*.pth`` files (sample_and_save.py's (5,H,W) [depth, x, y, z, reflectance] tensors) against a real set with the
-bird's-eye-view JSD and MMD of metrics/bev.py and, given the PointNet weights, the FPD (Frechet distance and squared MMD of
-PointNet features, metrics/distribution.py), on the GPU (r2dm_amd.metrics, r2dm_amd.pointnet).
+bird's-eye-view JSD and MMD of metrics/bev.py and, given the PointNet / RangeNet-53 weights, the FPD / FRD (Frechet distance and
+squared MMD of PointNet / RangeNet features, metrics/distribution.py), on the GPU (r2dm_amd.metrics, r2dm_amd.pointnet,
+r2dm_amd.rangenet).
 
 Same CLI (``--ckpt``, ``--sample_dir``, ``--dataset``, ``--batch_size``, ``--num_workers``) and the same output file,
 ``{sample_dir}_{timestamp}.json``.  The real set comes from either
@@ -17,8 +18,12 @@ The HuggingFace dataset builders are not used.
 ``--pointnet_weights PATH`` (SpareNet's ``cls_model_39.pth``, the file the reference downloads; nothing is downloaded here) adds
 ``pts.frechet_distance`` and ``pts.squared_mmd``: the generated features come from the batches that feed the BEV histograms, the real
 ones from the cache pickle's ``pts_feats`` or from the ``--real_dir`` / ``--real_scans`` batches; all real features are used.  The
-subsets of the squared MMD are drawn from numpy's global state as in the reference, or from ``--mmd_seed``.  FRD needs the
-RangeNet-53 weights and is not computed here."""
+subsets of the squared MMD are drawn from numpy's global state as in the reference, or from ``--mmd_seed``.
+
+``--rangenet_weights PATH`` (the official ``darknet53-1024.tar.gz`` archive the reference downloads, or a ``.pth`` state dict in its
+module layout; a local file, nothing is downloaded here) adds ``img.frechet_distance`` and ``img.squared_mmd`` when the checkpoint
+was trained with reflectance, as in the reference: the "lidargen" features of RangeNet-53 over the same batches, the real ones from
+the cache pickle's ``img_feats`` or from the ``--real_dir`` / ``--real_scans`` batches."""
 import datetime
 import json
 import pickle
@@ -55,24 +60,39 @@ def load_batches(files, batch_size, num_workers):
     return torch.utils.data.DataLoader(Files(), batch_size=batch_size, num_workers=num_workers)
 
 
-def _measure(imgs, extractor, hists, feats):
-    """One (B,5,H,W) batch on the GPU: its BEV histograms and, with an extractor, its PointNet features (evaluate.py:150-160)."""
+def _measure(imgs, extractor, hists, feats, img_extractor=None, img_feats=None):
+    """One (B,5,H,W) batch on the GPU: its BEV histograms and, with the extractors, its PointNet and RangeNet features
+    (evaluate.py:142-160)."""
     from r2dm_amd import metrics, pointnet
 
     hists.append(metrics.bev_histograms(imgs, image_min_depth=MIN_DEPTH, image_max_depth=MAX_DEPTH))
     if extractor is not None:
         feats.append(pointnet.pointnet_features(extractor, imgs))
+    if img_extractor is not None:
+        img_feats.append(img_extractor.extract(imgs, feature="lidargen", image_min_depth=MIN_DEPTH, image_max_depth=MAX_DEPTH))
 
 
-def histograms_of(files, batch_size, num_workers, device, extractor=None):
+def _measured(hists, feats, img_feats, extractor, img_extractor):
+    """(histograms, PointNet features or None), and as a third value the RangeNet features when there is an ``img_extractor``."""
+    out = (torch.cat(hists), torch.cat(feats) if extractor is not None else None)
+    return out if img_extractor is None else out + (torch.cat(img_feats),)
+
+
+def _split(measured):
+    """(histograms, PointNet features or None, RangeNet features or None) of what ``histograms_of`` / ``histograms_of_scans`` returned"""
+    return measured if len(measured) == 3 else (*measured, None)
+
+
+def histograms_of(files, batch_size, num_workers, device, extractor=None, img_extractor=None):
     """int32 (N,100,100) BEV histograms of the sample files: depth mask, then point_cloud_to_histogram (evaluate.py:22-41,145-155);
-    with ``extractor`` also the (N,1808) PointNet features of the same batches (else None)."""
+    with ``extractor`` also the (N,1808) PointNet features of the same batches (else None); with ``img_extractor`` a third value, the
+    (N,4096) RangeNet features."""
     if not files:
         raise SystemExit("no *.pth files to evaluate")
-    hists, feats = [], []
+    hists, feats, img_feats = [], [], []
     for imgs in load_batches(files, batch_size, num_workers):
-        _measure(imgs.to(device, non_blocking=True), extractor, hists, feats)
-    return torch.cat(hists), (torch.cat(feats) if extractor is not None else None)
+        _measure(imgs.to(device, non_blocking=True), extractor, hists, feats, img_extractor, img_feats)
+    return _measured(hists, feats, img_feats, extractor, img_extractor)
 
 
 def scan_files(root):
@@ -80,10 +100,11 @@ def scan_files(root):
     return sorted(Path(root).rglob("*.bin"))
 
 
-def histograms_of_scans(files, cfg, batch_size, device, extractor=None):
+def histograms_of_scans(files, cfg, batch_size, device, extractor=None, img_extractor=None):
     """int32 (N,100,100) BEV histograms of raw scans: the dataset builder's projection (64 rows, the projection's own width, masked by
     its depth window), evaluate.py's resize to the model's resolution (nearest-exact), then the depth mask and histogram as above;
-    with ``extractor`` also the PointNet features of the same images (else None)."""
+    with ``extractor`` also the PointNet features of the same images (else None); with ``img_extractor`` a third value, their RangeNet
+    features."""
     import torch.nn.functional as F
 
     from r2dm_amd import projection
@@ -92,15 +113,15 @@ def histograms_of_scans(files, cfg, batch_size, device, extractor=None):
         raise SystemExit("no *.bin files below --real_scans")
     unfolding, width = projection.parse_projection(cfg.data.projection)
     H, W = cfg.data.resolution
-    hists, feats = [], []
+    hists, feats, img_feats = [], [], []
     for k in range(0, len(files), batch_size):
         points, offsets = projection.load_scans(files[k:k + batch_size])
         imgs = projection.project_scans(points, offsets, H=64, W=width, scan_unfolding=unfolding, apply_mask=True,
                                         out_width=W if W <= width else None, layout="sample", device=device)
         if tuple(imgs.shape[-2:]) != (H, W):
             imgs = F.interpolate(imgs, size=(H, W), mode="nearest-exact")
-        _measure(imgs, extractor, hists, feats)
-    return torch.cat(hists), (torch.cat(feats) if extractor is not None else None)
+        _measure(imgs, extractor, hists, feats, img_extractor, img_feats)
+    return _measured(hists, feats, img_feats, extractor, img_extractor)
 
 
 def real_cache_name(cfg, split):
@@ -123,16 +144,26 @@ def evaluate(args):
 
         extractor = pointnet.pretrained_pointnet(args.pointnet_weights, device=device)
 
+    img_extractor = None  # (the reference computes the FRD only for a model with reflectance: evaluate.py:108,145)
+    frd_asked = getattr(args, "rangenet_weights", None) is not None
+    if frd_asked and cfg.data.train_reflectance:
+        from r2dm_amd import rangenet
+
+        img_extractor = rangenet.pretrained_rangenet(args.rangenet_weights, device=device)
+    more = () if img_extractor is None else (img_extractor,)
+    real_img = None
+
     results = dict(img=dict(), pts=dict(), bev=dict(), info=dict())
     results["info"]["phase"] = args.dataset
     results["info"]["directory"] = args.sample_dir
 
     # real set: the reference's cache, or a directory of scans
     if args.real_scans is not None:
-        real_hists, real_feats = histograms_of_scans(scan_files(args.real_scans), cfg, args.batch_size, device, extractor)
+        real_hists, real_feats, real_img = _split(histograms_of_scans(scan_files(args.real_scans), cfg, args.batch_size, device, extractor, *more))
         results["info"]["real"] = str(args.real_scans)
     elif args.real_dir is not None:
-        real_hists, real_feats = histograms_of(sample_files(args.real_dir, limit=None), args.batch_size, args.num_workers, device, extractor)
+        real_hists, real_feats, real_img = _split(histograms_of(sample_files(args.real_dir, limit=None), args.batch_size, args.num_workers, device,
+                                                                extractor, *more))
         results["info"]["real"] = str(args.real_dir)
     else:
         path = Path(args.real_set) if args.real_set is not None else Path(real_cache_name(cfg, args.dataset))
@@ -146,11 +177,13 @@ def evaluate(args):
         real_feats = None
         if extractor is not None:  # the reference's own PointNet features of the real set
             real_feats = torch.from_numpy(np.ascontiguousarray(real_set["pts_feats"], dtype=np.float32)).to(device)
+        if img_extractor is not None:  # ... and its RangeNet features
+            real_img = torch.from_numpy(np.ascontiguousarray(real_set["img_feats"], dtype=np.float32)).to(device)
         results["info"]["real"] = str(path)
     results["info"]["#real"] = len(real_hists)
 
     # generated set
-    gen_hists, gen_feats = histograms_of(sample_files(args.sample_dir), args.batch_size, args.num_workers, device, extractor)
+    gen_hists, gen_feats, gen_img = _split(histograms_of(sample_files(args.sample_dir), args.batch_size, args.num_workers, device, extractor, *more))
     results["info"]["#fake"] = len(gen_hists)
 
     # the real subset as the reference takes it (evaluate.py:185-187)
@@ -161,14 +194,23 @@ def evaluate(args):
 
     results["bev"]["jsd"] = metrics.compute_jsd_2d(real_sub, gen_hists)
     results["bev"]["mmd"] = metrics.compute_mmd_2d(real_sub, gen_hists)
-    if extractor is None:
-        results["info"]["note"] = ("img (FRD) and pts (FPD) are not computed: they need the RangeNet-53 and PointNet weights")
-    else:  # all real features, as the reference (evaluate.py:182-187)
-        seed = getattr(args, "mmd_seed", None)
+    seed = getattr(args, "mmd_seed", None)
+    rng = lambda: None if seed is None else np.random.RandomState(seed)
+    if img_extractor is not None:  # all real features, as the reference (evaluate.py:174-180)
+        results["img"]["frechet_distance"] = metrics.compute_frechet_distance(real_img, gen_img)
+        results["img"]["squared_mmd"] = metrics.compute_squared_mmd(real_img, gen_img, rng=rng())
+    if extractor is not None:  # (evaluate.py:182-187)
         results["pts"]["frechet_distance"] = metrics.compute_frechet_distance(real_feats, gen_feats)
-        results["pts"]["squared_mmd"] = metrics.compute_squared_mmd(real_feats, gen_feats,
-                                                                    rng=None if seed is None else np.random.RandomState(seed))
+        results["pts"]["squared_mmd"] = metrics.compute_squared_mmd(real_feats, gen_feats, rng=rng())
+    if frd_asked and img_extractor is None:  # (as in the reference, which skips the FRD for such a model)
+        no_frd = "img (FRD) is not computed: the checkpoint was trained without reflectance"
+        results["info"]["note"] = no_frd if extractor is not None else no_frd + "; pts (FPD) is not computed: it needs the PointNet weights"
+    elif extractor is None and img_extractor is None:
+        results["info"]["note"] = ("img (FRD) and pts (FPD) are not computed: they need the RangeNet-53 and PointNet weights")
+    elif img_extractor is None:
         results["info"]["note"] = "img (FRD) is not computed: it needs the RangeNet-53 weights"
+    elif extractor is None:
+        results["info"]["note"] = "pts (FPD) is not computed: it needs the PointNet weights"
 
     print(results)
     save_path = args.sample_dir + f"_{datetime.datetime.now().strftime('%Y%m%dT%H%M%S')}.json"
@@ -192,6 +234,9 @@ def build_parser():
                         help="extension: a directory tree of raw Velodyne *.bin scans, projected here with the checkpoint's projection")
     parser.add_argument("--pointnet_weights", type=str, default=None,
                         help="extension: SpareNet's cls_model_39.pth (the PointNet of the FPD); adds pts.frechet_distance / pts.squared_mmd")
+    parser.add_argument("--rangenet_weights", type=str, default=None,
+                        help="extension: the official darknet53-1024.tar.gz archive or a .pth state dict (the RangeNet-53 of the FRD), a local "
+                             "file; adds img.frechet_distance / img.squared_mmd for a model trained with reflectance")
     parser.add_argument("--mmd_seed", type=int, default=None,
                         help="extension: seed of the squared MMD's subset draws (default: numpy's global state, as the reference)")
     return parser

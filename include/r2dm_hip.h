@@ -215,6 +215,28 @@ size_t r2dm_poly_mmd_scratch_bytes(int32_t subsets, int32_t subset_size);
 int r2dm_poly_mmd(const float* x, const float* y, const int64_t* ix, const int64_t* iy, int32_t subsets, int32_t subset_size, int32_t dim,
                   void* scratch, size_t scratch_bytes, double* out, void* stream);
 
+/* -- FRD of the evaluation script and the segmentation of completion_demo.py: RangeNet-53 / -21 (metrics/extractor/rangenet.py) in eval
+ *    mode, every BatchNorm folded into the layer in front of it by the caller ------------------------------------------------------
+ * r2dm_rangenet_pack: w (cout, taps, cin) fp32 -> packed (r2dm_rangenet_packed_bytes(), 16-byte aligned): cout padded to 32 and cin to 16
+ *    with zeros, the layer scaled by a power of two (max|w| into [2^9, 2^10)) and split into an fp16 piece and an fp16 residual, in
+ *    matrix-core operand order.  wscale: two floats of device memory, [1] <- the inverse scale.  *flag |= 4 if a weight is not finite.
+ * r2dm_rangenet_conv: one layer as an implicit GEMM on the fp16 matrix pipe (three products per MAC, fp32 accumulation):
+ *    out = LeakyReLU_slope(conv(in) * inv_scale + bias) + add + add2 (add, add2: fp32 tensors of out's shape, or NULL; slope 1 = no
+ *    activation), fp32 NCHW.  kind 0: 1 x 1; 1: 3 x 3 pad 1 (taps row-major); 2: 3 x 3 pad 1 stride (1,2), out width = width / 2;
+ *    3 / 4: the even / odd output columns of the transposed 1 x 4, stride (1,2), pad (0,1) convolution (two taps: in[j] and in[j-1] /
+ *    in[j] and in[j+1]), out width = 2 width, the other columns are left alone; 5: the stem, in = (batch,5,height,width) samples
+ *    [depth, x, y, z, reflectance], each value (v - norm[c]) / norm[5 + c] * mask, mask (batch,1,height,width) of zeros and ones or NULL for
+ *    min_depth < depth < max_depth; the raw values of a masked pixel are not used.  cin % 16 == 0 (stem: 5).
+ *    *flag |= 1 for a non-finite value of an unmasked input pixel, |= 2 for an activation outside the fp16 operand range (65504): the
+ *    results are then invalid.  The same bits on every call; a sample's result does not depend on the rest of the batch.
+ * r2dm_rangenet_argmax: logits (batch,classes,pixels) -> labels (batch,pixels) int64, the lowest index on a tie. */
+size_t r2dm_rangenet_packed_bytes(int32_t cout, int32_t cin, int32_t taps);
+int r2dm_rangenet_pack(const float* w, int32_t cout, int32_t cin, int32_t taps, void* packed, float* wscale, int32_t* flag, void* stream);
+int r2dm_rangenet_conv(const float* in, const float* mask, const float* norm, float min_depth, float max_depth, const void* packed,
+                       const float* inv_scale, const float* bias, const float* add, const float* add2, float* out, int32_t batch, int32_t cin,
+                       int32_t height, int32_t width, int32_t cout, int32_t kind, float slope, int32_t* flag, void* stream);
+int r2dm_rangenet_argmax(const float* logits, int64_t* labels, int32_t batch, int32_t classes, int64_t pixels, void* stream);
+
 /* -- rendering of generate.py (utils/render.py; generate.py:44-59) -------------------------------------------------------------
  * All arithmetic is fp32 with one rounding per operation.  The splat accumulates 64-bit fixed-point integers (scale from the
  * largest |value| of the call, taken on the device): the same bits on every call and for every order of the points.

@@ -15,12 +15,14 @@ from . import pointcloud  # noqa: E402  (range images -> point clouds)
 from .pointcloud import centred_ray_angles, images_to_points, save_ply, save_scans, scan_row_start
 from . import pointnet  # noqa: E402  (PointNet features of the FPD)
 from .pointnet import pointnet_features, pretrained_pointnet
+from . import rangenet  # noqa: E402  (RangeNet features of the FRD, segmentation labels)
+from .rangenet import pretrained_rangenet
 
 __all__ = [
     "ContinuousTimeGaussianDiffusion", "DiscreteTimeGaussianDiffusion", "GaussianDiffusion", "EfficientUNet",
     "LiDARUtility", "Config", "setup_model", "setup_rng",
     "load_scans", "project_scans", "load_points_as_images", "parse_projection", "known_from_scan",
     "images_to_points", "save_scans", "save_ply", "scan_row_start", "centred_ray_angles",
-    "pretrained_pointnet", "pointnet_features",
+    "pretrained_pointnet", "pointnet_features", "pretrained_rangenet",
 ]
 __version__ = "0.4.0"

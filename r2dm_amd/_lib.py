@@ -107,6 +107,11 @@ SIGNATURES = {
     "r2dm_pointnet_scratch_bytes": (c_size_t, [c_int32]),
     "r2dm_pointnet_trunk": (c_int32, [_P, c_int32, c_int32, c_int64, _P, c_float, c_float, c_float, _P, _P, _P, _P, _P, _P, c_size_t, _P, _P]),
     "r2dm_pointnet_head": (c_int32, [_P, _P, _P, c_int32, _P, _P, _P, _P, _P, _P, c_int32, _P, c_int32, _P]),
+    "r2dm_rangenet_packed_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "r2dm_rangenet_pack": (c_int32, [_P, c_int32, c_int32, c_int32, _P, _P, _P, _P]),
+    "r2dm_rangenet_conv": (c_int32, [_P, _P, _P, c_float, c_float, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                     c_float, _P, _P]),
+    "r2dm_rangenet_argmax": (c_int32, [_P, _P, c_int32, c_int32, c_int64, _P]),
     "r2dm_feature_moments": (c_int32, [_P, c_int64, c_int32, _P, _P, _P]),
     "r2dm_poly_mmd_scratch_bytes": (c_size_t, [c_int32, c_int32]),
     "r2dm_poly_mmd": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, _P, c_size_t, _P, _P]),

@@ -299,6 +299,14 @@ hipError_t launch_pointnet_trunk(const float* src, int layout, int B, long n, co
 hipError_t launch_pointnet_head(const void* scratch, const float* w3inv, const float* b3, int stn, const float* w1, const float* b1, const float* w2,
                                 const float* b2, const float* w3, const float* bo, int kout, float* out, int B, hipStream_t s);
 
+// RangeNet extractor of the FRD and the segmentation (rangenet.hip): weight packing, the implicit-GEMM convolution of every layer kind, the label argmax
+size_t rangenet_packed_bytes(int Cout, int Cin, int taps);
+hipError_t launch_rangenet_pack(const float* w, int Cout, int Cin, int taps, void* dst, float* wscale, int* flag, hipStream_t s);
+hipError_t launch_rangenet_conv(const float* in, const float* mask, const float* norm, float lo, float hi, const void* wp, const float* winv,
+                                const float* bias, const float* add, const float* add2, float* out, int B, int Cin, int H, int Win, int Cout, int kind,
+                                float slope, int* flag, hipStream_t s);
+hipError_t launch_rangenet_argmax(const float* logits, long long* labels, int B, int C, long hw, hipStream_t s);
+
 // rendering of generate.py (render.hip): colour maps, the bilinear splat with 64-bit fixed-point accumulators, the fused frame renderer
 hipError_t launch_colorize(const float* x, const float* lut, uint8_t* out, long B, long hw, hipStream_t s);
 size_t rasterize_scratch_bytes(int B, int C, int H, int W);

@@ -97,6 +97,39 @@ int r2dm_poly_mmd(const float* x, const float* y, const int64_t* ix, const int64
     return 0;
 }
 
+size_t r2dm_rangenet_packed_bytes(int32_t cout, int32_t cin, int32_t taps) { return rangenet_packed_bytes(cout, cin, taps); }
+
+int r2dm_rangenet_pack(const float* w, int32_t cout, int32_t cin, int32_t taps, void* packed, float* wscale, int32_t* flag, void* stream) {
+    if (!w || !packed || !wscale || !flag) return fail(1, "null argument");
+    if (!rangenet_packed_bytes(cout, cin, taps)) return fail(1, "rangenet_pack: cout and cin must be positive, taps in [1, 9]");
+    if ((uintptr_t)packed & 15) return fail(1, "rangenet_pack: packed must be 16-byte aligned");
+    HIP_TRY(launch_rangenet_pack(w, cout, cin, taps, packed, wscale, flag, (hipStream_t)stream));
+    return 0;
+}
+
+int r2dm_rangenet_conv(const float* in, const float* mask, const float* norm, float min_depth, float max_depth, const void* packed,
+                       const float* inv_scale, const float* bias, const float* add, const float* add2, float* out, int32_t batch, int32_t cin,
+                       int32_t height, int32_t width, int32_t cout, int32_t kind, float slope, int32_t* flag, void* stream) {
+    if (!in || !packed || !inv_scale || !bias || !out || !flag) return fail(1, "null argument");
+    if (kind < 0 || kind > 5) return fail(1, "rangenet_conv: kind must be 0 (1x1), 1 (3x3), 2 (3x3 stride (1,2)), 3 / 4 (transposed 1x4, even / odd columns) or 5 (stem)");
+    if (batch < 1 || height < 1 || width < 1 || cout < 1) return fail(1, "rangenet_conv: batch, height, width and cout must be positive");
+    if (kind == 5 ? (cin != 5 || cout > 32 || !norm) : (cin < 16 || cin % 16))
+        return fail(1, "rangenet_conv: cin must be a multiple of 16 (the stem: 5 channels, at most 32 outputs, norm given)");
+    if (kind == 2 && width % 2) return fail(1, "rangenet_conv: the stride-(1,2) convolution needs an even width");
+    if (in == out || add == out || add2 == out) return fail(1, "rangenet_conv: out must not alias an input");
+    if ((uintptr_t)packed & 15) return fail(1, "rangenet_conv: packed must be 16-byte aligned");
+    HIP_TRY(launch_rangenet_conv(in, mask, norm, min_depth, max_depth, packed, inv_scale, bias, add, add2, out, batch, cin, height, width, cout, kind,
+                                 slope, flag, (hipStream_t)stream));
+    return 0;
+}
+
+int r2dm_rangenet_argmax(const float* logits, int64_t* labels, int32_t batch, int32_t classes, int64_t pixels, void* stream) {
+    if (!logits || !labels) return fail(1, "null argument");
+    if (batch < 1 || classes < 1 || pixels < 1) return fail(1, "rangenet_argmax: batch, classes and pixels must be positive");
+    HIP_TRY(launch_rangenet_argmax(logits, reinterpret_cast<long long*>(labels), batch, classes, pixels, (hipStream_t)stream));
+    return 0;
+}
+
 size_t r2dm_pointnet_packed_bytes(int32_t cout, int32_t cin) {
     return cout < 32 || cout % 32 || cin < 16 || cin % 16 ? 0 : (size_t)cout * cin * 4;
 }

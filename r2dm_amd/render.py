@@ -74,6 +74,27 @@ def colorize(tensor: torch.Tensor, cmap="turbo") -> torch.Tensor:
     return out
 
 
+# SemanticKITTI's 20 training labels in RGB (the reference's make_semantickitti_cmap; 0 unlabeled, 1 car, ... 19 traffic-sign)
+LABEL_COLORS = (
+    (0, 0, 0), (100, 150, 245), (100, 230, 245), (30, 60, 150), (80, 30, 180), (0, 0, 255), (255, 30, 30), (255, 40, 200), (150, 30, 90),
+    (255, 0, 255), (255, 150, 255), (75, 0, 75), (175, 0, 75), (255, 200, 0), (255, 120, 50), (0, 175, 0), (135, 60, 0), (150, 240, 80),
+    (255, 240, 150), (255, 0, 0))
+
+
+def label_lut() -> torch.Tensor:
+    """The (256,3) table ``colorize`` needs for ``colorize(labels / 19, label_lut())``: the reference samples its 20-colour
+    ListedColormap at ``linspace(0, 1, 256)``, entry i being colour ``floor(i / 255 * 20)`` (the last one 19)."""
+    if "labels" not in _LUTS:
+        index = np.minimum((np.linspace(0, 1, 256) * len(LABEL_COLORS)).astype(np.int64), len(LABEL_COLORS) - 1)
+        _LUTS["labels"] = torch.tensor(LABEL_COLORS, dtype=torch.float32)[torch.from_numpy(index)] / 255
+    return _LUTS["labels"]
+
+
+def colorize_labels(labels: torch.Tensor) -> torch.Tensor:
+    """completion_demo.py:138: int ``(B,1,H,W)`` labels 0 .. 19 -> uint8 ``(B,3,H,W)`` in SemanticKITTI's colours."""
+    return colorize(labels.float() / (len(LABEL_COLORS) - 1), label_lut())
+
+
 # ---- splat ---------------------------------------------------------------------------------------
 def _scratch(nbytes: int, device):
     buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)

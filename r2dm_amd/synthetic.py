@@ -214,3 +214,37 @@ def synthetic_pointnet_state(seed: int = 0) -> Dict[str, torch.Tensor]:
         if is_bn and leaf == "running_var":
             sd[key.rsplit(".", 1)[0] + ".num_batches_tracked"] = torch.tensor(0, dtype=torch.int64)
     return sd
+
+
+def synthetic_rangenet_state(seed: int = 0, backbone: int = 53) -> Dict[str, torch.Tensor]:
+    """A state dict in the module layout of the reference's RangeNet (the extractor of the FRD; ``rangenet.state_spec`` and the
+    BatchNorms' ``num_batches_tracked``), a pure function of ``seed`` built from integer draws only.
+
+    Convolution weights are uniform with variance 2 / (1.01 fan_in) -- what LeakyReLU(0.1) takes away --, the transposed ones with
+    the two taps an output column sees as fan-in; BatchNorm scales have magnitudes in [0.75, 1.25) and a RANDOM SIGN, running
+    variances lie in [0.75, 1.25).  The last BatchNorm of every residual branch is scaled by 0.15: the branches' outputs have
+    a positive mean behind the LeakyReLU, which adds up coherently over the 23 + 5 blocks (a variance-preserving branch reaches
+    |activation| ~ 2.5e5 at the decoder output); so scaled, the decoder map has an rms of about 35 and a maximum of about 200."""
+    from .rangenet import state_spec
+
+    sd: Dict[str, torch.Tensor] = {}
+    for key, shape in state_spec(backbone).items():
+        u = _int_uniform(key, seed, shape)
+        module, leaf = key.rsplit(".", 1)
+        is_bn = len(shape) == 1 and not module.endswith(".0") and module != "head.1"
+        if not is_bn and leaf == "weight":
+            fan_in = 2 * shape[0] if shape[2:] == (1, 4) else int(np.prod(shape[1:]))
+            v = u * math.sqrt(3.0 * 2.0 / (1.01 * fan_in))
+        elif not is_bn:
+            v = u * 0.1
+        elif leaf == "weight":
+            sign = np.where(_int_uniform(key + "/sign", seed, shape) < 0, -1.0, 1.0)
+            v = (1.0 + 0.25 * u) * sign * (0.15 if module.endswith(".residual.1.1") else 1.0)
+        elif leaf in ("bias", "running_mean"):
+            v = u * 0.1
+        else:  # running_var
+            v = 1.0 + 0.25 * u
+        sd[key] = torch.from_numpy(v.astype(np.float32))
+        if is_bn and leaf == "running_var":
+            sd[module + ".num_batches_tracked"] = torch.tensor(0, dtype=torch.int64)
+    return sd
