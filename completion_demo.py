@@ -13,7 +13,9 @@ completed bird's-eye view (r2dm_amd.render; the views coloured by height) -- and
 ``mask`` and ``x_out``.  ``--rangenet_weights PATH`` (the official ``darknet53-1024.tar.gz`` archive or a ``.pth`` state dict; a local
 file, nothing is downloaded) adds the reference's segmentation: RangeNet-53 labels of the completed samples (r2dm_amd.rangenet), a
 row of label-coloured images under the completed ones, the completed bird's-eye views coloured by label instead of height, and
-``labels`` in ``completion.pt``.  Without it there is no segmentation row.  ``--out_scan FILE.bin`` (extension) also writes the completed scan -- the completion of
+``labels`` in ``completion.pt``.  Without it there is no segmentation row.  ``--semseg_postprocess {none,knn,crf,crf_knn}`` refines those
+labels with the reference's post-processors at their defaults (r2dm_amd.postproc: the CRF-RNN on the logits, the kNN vote on the labels);
+the refined labels are the ones drawn and saved.  ``--out_scan FILE.bin`` (extension) also writes the completed scan -- the completion of
 the full input, the first column -- as a Velodyne file in scan order (r2dm_amd.pointcloud)."""
 import math
 from argparse import ArgumentParser
@@ -66,6 +68,16 @@ def semseg_inputs(x, lidar_utils):
     return torch.cat([depth, lidar_utils.to_xyz(depth), sample[:, [1]]], dim=1), mask
 
 
+def semseg_postprocess(name, num_classes):
+    """``--semseg_postprocess``: None, or the post-processors of ``RangeNetExtractor.segment`` at the reference's defaults"""
+    from r2dm_amd.postproc import CRFRNN, KNN
+
+    if name not in ("none", "knn", "crf", "crf_knn"):
+        raise ValueError(f"--semseg_postprocess must be none, knn, crf or crf_knn, got {name!r}")
+    steps = tuple(cls(num_classes) for key, cls in (("crf", CRFRNN), ("knn", KNN)) if key in name.split("_"))
+    return steps or None
+
+
 def to_bev(x, lidar_utils, size, colors=None):
     """completion_demo.py:117-133: (B,2,H,W) -> (B,3,size,size), coloured by height or by the given (B,3,H,W) colours in [0,1]"""
     from r2dm_amd.render import colorize, make_Rt, render_point_clouds
@@ -102,7 +114,8 @@ def main(args):
         from r2dm_amd.render import colorize_labels
 
         semseg = r2dm_amd.rangenet.pretrained_rangenet(args.rangenet_weights, device=device)
-        labels = semseg.segment(*semseg_inputs(x_out, lidar_utils))
+        labels = semseg.segment(*semseg_inputs(x_out, lidar_utils), postprocess=semseg_postprocess(getattr(args, "semseg_postprocess", "none"),
+                                                                                                  semseg.num_classes))
         colors = colorize_labels(labels).float() / 255
         rows += [colors, to_bev(x_out, lidar_utils, W, colors)]
         saved["labels"] = labels.cpu()
@@ -132,6 +145,8 @@ def parser():
     p.add_argument("--out", type=Path, default=None, help="the image (default: the reference's completion_T-..._r-..._j-....png)")
     p.add_argument("--rangenet_weights", type=str, default=None,
                    help="the official darknet53-1024.tar.gz archive or a .pth state dict (a local file): adds the segmentation row and label colours")
+    p.add_argument("--semseg_postprocess", choices=("none", "knn", "crf", "crf_knn"), default="none",
+                   help="refine the labels of --rangenet_weights: the kNN vote of RangeNet++, the CRF-RNN of SqueezeSeg, or the CRF-RNN and then the vote")
     p.add_argument("--out_scan", type=Path, default=None, help="also write the completed scan (of the full input) as a Velodyne .bin file")
     return p
 

@@ -309,6 +309,30 @@ int r2dm_unproject(const float* src, int32_t layout, const float* ray_angles, co
                    int64_t* offsets, int32_t batch, int32_t height, int32_t width, float min_depth, float max_depth,
                    int32_t depth_format, float keep_min, float keep_max, void* scratch, size_t scratch_bytes, void* stream);
 
+/* -- post-processing of the segmentation: the kNN label filter of RangeNet++ and the CRF-RNN refinement of SqueezeSeg
+ *    (metrics/extractor/rangenet.py:197-405), one launch each, zero padding at every image edge (no wrap at the azimuth seam) -----------
+ * r2dm_knn_vote: depth (batch,1,height,width) fp32, label (batch,height,width) int64 -> out (batch,height,width) int64.
+ *    A depth that is not finite is read as -1.  With the K = kh kw window offsets o in row-major order: the neighbour depth n_o(p) is the
+ *    depth at p + o, 0 outside the image and +inf where it is negative; jump_o(p) = |n_o(p) - depth(p)| inside the image, 0 outside;
+ *    dist_o(p) = sum over the window offsets q, row-major, of weight[q] * jump_o(p + q), in fp32 with one rounding per operation from an
+ *    accumulator of 0 (weight: (kh,kw) fp32 in device memory, 1 - the normalised Gaussian).  The k smallest dist_o win, ties to the lowest
+ *    o (a NaN, which only a zero weight can produce, is the largest); a winner with dist > cutoff votes for nothing (cutoff <= 0: never),
+ *    a neighbour outside the image carries label 0.  out(p) = the class with the most votes, the lowest on a tie, 0 without votes.
+ *    A label outside [0, classes) sets *flag |= 1 and votes for nothing.  The result is a function of the input bits; an image's labels
+ *    do not depend on the rest of the batch.  Limits: kh, kw odd and <= 7, 1 <= k <= min(K, 8), classes <= 32, batch <= 65535.
+ * r2dm_crf_iter: one mean-field iteration q_out = unary - compat . (ws * smooth_gamma(S) + wa * mask * appearance(S mask) * smooth_alpha(S)),
+ *    S = softmax of q_in over the classes; q_in, unary, q_out (batch,classes,height,width), xyz (batch,3,height,width), mask
+ *    (batch,1,height,width), all fp32; q_out must not alias an input.  smooth_t(S)[c](p) = sum over o != 0 of kernel_t[c][o] S[c](p + o);
+ *    appearance(X)[c](p) = sum over o != 0 of X[c](p + o) exp(-|xyz(p + o) - xyz(p)|^2 / beta[c]), everything 0 outside the image.
+ *    params, fp32 in device memory: kernel_gamma (classes,kh,kw) | kernel_alpha (classes,kh,kw) | ws (classes) | wa (classes) |
+ *    beta (classes) = 2 theta_beta^2 | compat (classes,classes), row = output class.  uniform_beta != 0: beta[0] holds for every class and
+ *    the exponentials are taken once per neighbour.  Sums run in a fixed order: the same bits on every call, independent of the batch.
+ *    Limits: kh, kw odd and <= 7, classes <= 32, batch <= 65535. */
+int r2dm_knn_vote(const float* depth, const int64_t* label, const float* weight, int64_t* out, int32_t batch, int32_t height, int32_t width,
+                  int32_t kh, int32_t kw, int32_t k, int32_t classes, float cutoff, int32_t* flag, void* stream);
+int r2dm_crf_iter(const float* q_in, const float* unary, const float* xyz, const float* mask, const float* params, float* q_out, int32_t batch,
+                  int32_t classes, int32_t height, int32_t width, int32_t kh, int32_t kw, int32_t uniform_beta, void* stream);
+
 /* -- single kernels, exported for per-op parity tests against the oracle -------------------- */
 /* ops.Conv2d(ring) 3x3 / 1x1 (models/ops.py:149-173) with optional fused GroupNorm-affine(+SiLU)
  * prologue (aff: (B,Cin,2) or NULL; prologue 0 none, 1 affine, 2 affine+SiLU) and optional

@@ -17,6 +17,8 @@ from . import pointnet  # noqa: E402  (PointNet features of the FPD)
 from .pointnet import pointnet_features, pretrained_pointnet
 from . import rangenet  # noqa: E402  (RangeNet features of the FRD, segmentation labels)
 from .rangenet import pretrained_rangenet
+from . import postproc  # noqa: E402  (kNN vote and CRF-RNN refinement of the labels)
+from .postproc import CRFRNN, KNN
 
 __all__ = [
     "ContinuousTimeGaussianDiffusion", "DiscreteTimeGaussianDiffusion", "GaussianDiffusion", "EfficientUNet",
@@ -24,5 +26,6 @@ __all__ = [
     "load_scans", "project_scans", "load_points_as_images", "parse_projection", "known_from_scan",
     "images_to_points", "save_scans", "save_ply", "scan_row_start", "centred_ray_angles",
     "pretrained_pointnet", "pointnet_features", "pretrained_rangenet",
+    "KNN", "CRFRNN",
 ]
 __version__ = "0.4.0"

@@ -128,6 +128,8 @@ SIGNATURES = {
     "r2dm_unproject_scratch_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "r2dm_unproject": (c_int32, [_P, c_int32, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_float, c_float, c_int32, c_float, c_float,
                                  _P, c_size_t, _P]),
+    "r2dm_knn_vote": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, _P, _P]),
+    "r2dm_crf_iter": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -307,6 +307,13 @@ hipError_t launch_rangenet_conv(const float* in, const float* mask, const float*
                                 float slope, int* flag, hipStream_t s);
 hipError_t launch_rangenet_argmax(const float* logits, long long* labels, int B, int C, long hw, hipStream_t s);
 
+// post-processing of the labels (postproc.hip): the kNN vote of RangeNet++ and one mean-field iteration of the CRF-RNN, each one launch
+bool postproc_window_supported(int kh, int kw);
+hipError_t launch_knn_vote(const float* depth, const long long* label, const float* weight, long long* out, int B, int H, int W, int kh, int kw, int k,
+                           int classes, float cutoff, int* flag, hipStream_t s);
+hipError_t launch_crf_iter(const float* q_in, const float* unary, const float* xyz, const float* mask, const float* params, float* q_out, int B, int N,
+                           int H, int W, int kh, int kw, int uniform_beta, hipStream_t s);
+
 // rendering of generate.py (render.hip): colour maps, the bilinear splat with 64-bit fixed-point accumulators, the fused frame renderer
 hipError_t launch_colorize(const float* x, const float* lut, uint8_t* out, long B, long hw, hipStream_t s);
 size_t rasterize_scratch_bytes(int B, int C, int H, int W);

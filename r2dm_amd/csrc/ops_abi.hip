@@ -278,4 +278,28 @@ int r2dm_unproject(const float* src, int32_t layout, const float* ray_angles, co
     return 0;
 }
 
+int r2dm_knn_vote(const float* depth, const int64_t* label, const float* weight, int64_t* out, int32_t batch, int32_t height, int32_t width,
+                  int32_t kh, int32_t kw, int32_t k, int32_t classes, float cutoff, int32_t* flag, void* stream) {
+    if (!depth || !label || !weight || !out || !flag) return fail(1, "null argument");
+    if (!postproc_window_supported(kh, kw)) return fail(1, "knn_vote: the window sides must be odd and at most 7, got %d x %d", kh, kw);
+    if (k < 1 || k > 8 || k > kh * kw) return fail(1, "knn_vote: k must be in [1, min(kh kw, 8)], got %d", k);
+    if (classes < 1 || classes > 32) return fail(1, "knn_vote: 1 to 32 classes, got %d", classes);
+    if (batch < 1 || batch > 65535 || height < 1 || width < 1 || height > 65535 * 8) return fail(1, "knn_vote: batch must be in [1, 65535], height and width positive");
+    if ((const void*)label == (const void*)out) return fail(1, "knn_vote: out must not alias label");
+    HIP_TRY(launch_knn_vote(depth, reinterpret_cast<const long long*>(label), weight, reinterpret_cast<long long*>(out), batch, height, width, kh, kw, k,
+                            classes, cutoff, flag, (hipStream_t)stream));
+    return 0;
+}
+
+int r2dm_crf_iter(const float* q_in, const float* unary, const float* xyz, const float* mask, const float* params, float* q_out, int32_t batch,
+                  int32_t classes, int32_t height, int32_t width, int32_t kh, int32_t kw, int32_t uniform_beta, void* stream) {
+    if (!q_in || !unary || !xyz || !mask || !params || !q_out) return fail(1, "null argument");
+    if (!postproc_window_supported(kh, kw)) return fail(1, "crf_iter: the window sides must be odd and at most 7, got %d x %d", kh, kw);
+    if (classes < 1 || classes > 32) return fail(1, "crf_iter: 1 to 32 classes, got %d", classes);
+    if (batch < 1 || batch > 65535 || height < 1 || width < 1 || height > 65535 * 8) return fail(1, "crf_iter: batch must be in [1, 65535], height and width positive");
+    if (q_out == q_in || q_out == unary) return fail(1, "crf_iter: q_out must not alias an input");
+    HIP_TRY(launch_crf_iter(q_in, unary, xyz, mask, params, q_out, batch, classes, height, width, kh, kw, uniform_beta, (hipStream_t)stream));
+    return 0;
+}
+
 }  // extern "C"

@@ -14,7 +14,8 @@ Every convolution but the head is followed by a BatchNorm (running statistics, e
 identity.  The BatchNorms are folded into weights and biases on the host in fp64; every layer is one launch of ONE implicit-GEMM
 kernel (csrc/rangenet.hip) on the fp16 matrix pipe with split fp32 operands (three products per multiply-add, fp32 accumulation),
 the transposed convolution two launches, one per output-column parity.  Weights are packed and split once, at construction.  There
-is no CPU or PyTorch fallback and nothing is ever downloaded: the weight file is given by the caller.
+is no CPU or PyTorch fallback.  The extractor is built from a local weight file and downloads nothing; only the reference's hub
+interface at the end of the module (``build_rangenet``) fetches a URL, through torch.hub's checkpoint cache.
 """
 from __future__ import annotations
 
@@ -358,14 +359,32 @@ class RangeNetExtractor:
 
     @torch.no_grad()
     def segment(self, samples: torch.Tensor, mask: Optional[torch.Tensor] = None, image_min_depth: float = MIN_DEPTH,
-                image_max_depth: float = MAX_DEPTH) -> torch.Tensor:
-        """int64 (B,1,H,W) labels: the argmax of the logits over the classes, the lowest index on a tie (as ``torch.argmax``)."""
+                image_max_depth: float = MAX_DEPTH, postprocess=None) -> torch.Tensor:
+        """int64 (B,1,H,W) labels: the argmax of the logits over the classes, the lowest index on a tie (as ``torch.argmax``).
+        ``postprocess``: a ``postproc.KNN``, a ``postproc.CRFRNN`` or a tuple of them, every CRFRNN before every KNN -- a CRFRNN refines the
+        logits (its ``xyz`` are the samples' ``xyz * mask``), the argmax follows, a KNN filters the labels over the depth, in which the
+        masked pixels are -1 (the reference's invalid marker)."""
+        from . import postproc
+
+        crfs, knns = postproc.split_postprocess(postprocess)
         logits = self.extract(samples, mask, None, image_min_depth, image_max_depth)
         B, C, H, W = logits.shape
+        if (crfs or knns) and B:
+            depth = samples[:, [0]].to(torch.float32)
+            m = torch.logical_and(depth > image_min_depth, depth < image_max_depth).float() if mask is None else mask.to(torch.float32)
+            if crfs:
+                xyz = samples[:, 1:4].to(torch.float32)
+                xyz = torch.where(m != 0, xyz * m, torch.zeros_like(xyz))  # (the raw values of a masked pixel take no part)
+            for crf in crfs:
+                logits = crf(logits, xyz, m)
         labels = torch.empty(B, 1, H, W, dtype=torch.int64, device=self.device)
         if B:
             with torch.cuda.device(self.device):
                 _lib.check(_lib.lib().r2dm_rangenet_argmax(_lib.ptr(logits), _lib.ptr(labels), B, C, H * W, _lib.stream_ptr(self.device)))
+            if knns:
+                depth = torch.where(m != 0, depth, torch.full_like(depth, -1.0))
+                for knn in knns:
+                    labels = knn(depth, labels)[:, None]
         return labels
 
     def __call__(self, samples: torch.Tensor) -> torch.Tensor:
@@ -378,3 +397,68 @@ def pretrained_rangenet(weights: Union[str, os.PathLike, Dict[str, torch.Tensor]
         return RangeNetExtractor(weights, device=device)
     state, mean, std, _, _ = load_weights(weights)
     return RangeNetExtractor(state, mean, std, device=device)
+
+
+# ---- the reference's hub interface: (model, preprocess) ------------------------------------------------------------------------------
+OFFICIAL_ARCHIVES = {
+    21: {"SemanticKITTI_64x2048": "darknet21"},
+    53: {"SemanticKITTI_64x2048": "darknet53", "SemanticKITTI_64x1024": "darknet53-1024", "SemanticKITTI_64x512": "darknet53-512"},
+}
+
+
+def official_url(key: str) -> str:
+    return f"http://www.ipb.uni-bonn.de/html/projects/bonnetal/lidar/semantic/models/{key}.tar.gz"
+
+
+class Preprocess:
+    """The reference's ``Preprocess``: ``preprocess(img, mask=None) = (img - mean) / std * mask`` in torch, the default mask
+    ``img[:, [0]] > 0``."""
+
+    def __init__(self, mean=None, std=None):
+        mean, std = list(DEFAULT_MEAN if mean is None else mean), list(DEFAULT_STD if std is None else std)
+        if len(mean) != len(std):
+            raise ValueError("Preprocess: mean and std must have the same length")
+        self.num_channels = len(mean)
+        self.mean, self.std = torch.tensor(mean, dtype=torch.float32), torch.tensor(std, dtype=torch.float32)
+
+    def __call__(self, img: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if img.ndim != 4 or img.shape[1] != self.num_channels:
+            raise ValueError(f"Preprocess: expected a (B,{self.num_channels},H,W) image, got {tuple(img.shape)}")
+        if mask is None:
+            mask = (img[:, [0]] > 0).float()
+        if mask.ndim != 4:
+            raise ValueError(f"Preprocess: expected a (B,1,H,W) mask, got {tuple(mask.shape)}")
+        mean, std = self.mean.to(img.device)[None, :, None, None], self.std.to(img.device)[None, :, None, None]
+        return (img - mean) / std * mask
+
+
+class PreprocessedRangeNet:
+    """``model(x, feature=None)`` of the reference's hub entries: the extractor on ALREADY preprocessed input -- the stem gets the identity
+    normalisation (mean 0, std 1) and a mask of ones -- returning the logits, the decoder map ("decoder") or the FRD feature ("lidargen")."""
+
+    def __init__(self, state: Dict[str, torch.Tensor], device="cuda"):
+        self.extractor = RangeNetExtractor(state, [0.0] * 5, [1.0] * 5, device=device)
+        self.num_classes, self.backbone = self.extractor.num_classes, self.extractor.backbone
+
+    @torch.no_grad()
+    def __call__(self, img: torch.Tensor, feature: Optional[str] = None) -> torch.Tensor:
+        _lib.require_gpu(img, "img")
+        ones = torch.ones(img.shape[0], 1, *img.shape[2:], dtype=torch.float32, device=img.device)
+        return self.extractor.extract(img, ones, feature)
+
+
+def build_rangenet(url_or_file: Union[str, os.PathLike], device="cuda", progress: bool = True) -> Tuple[PreprocessedRangeNet, Preprocess]:
+    """``(model, preprocess)`` from a local ``darknet*.tar.gz`` / ``.pth`` file, or from a URL through ``torch.hub``'s checkpoint cache (the
+    only place of this module that may download, and only for a URL)."""
+    name = os.fspath(url_or_file)
+    if "://" in name:
+        from urllib.parse import urlparse
+
+        model_dir = os.path.join(torch.hub.get_dir(), "checkpoints")
+        os.makedirs(model_dir, exist_ok=True)
+        cached = os.path.join(model_dir, os.path.basename(urlparse(name).path))
+        if not os.path.exists(cached):
+            torch.hub.download_url_to_file(name, cached, None, progress=progress)
+        name = cached
+    state, mean, std, _, _ = load_weights(name)
+    return PreprocessedRangeNet(state, device=device), Preprocess(mean, std)
