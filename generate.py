@@ -3,7 +3,8 @@
 the returned (S+1,B,2,H,W) stack, which is saved as tensors.  With ``--render_dir DIR`` the last frame is also rendered as the
 reference renders it (generate.py:44-63, r2dm_amd/render.py): ``samples_img.png``, the turbo-coloured range / reflectance
 images, and ``samples_bev.png``, the bird's-eye views; ``--render_frames`` adds ``frames/bev_%04d.png`` for every frame of the
-stack.  With ``--points_dir DIR`` the final samples are also written as Velodyne scans ``DIR/samples_%04d.bin`` (fp32 [x, y, z,
+stack, ``--render_normals`` the view of the reference's training monitor (train.py:227-239): ``samples_normal.png``, the surface normals
+as colours, and ``samples_bev_normal.png``, the bird's-eye views coloured by them.  With ``--points_dir DIR`` the final samples are also written as Velodyne scans ``DIR/samples_%04d.bin`` (fp32 [x, y, z,
 reflectance] rows in scan order, r2dm_amd.pointcloud), with ``--points_ply`` also as ``.ply`` coloured by the bird's-eye views' viridis
 height map.  Still missing from the reference's script: the mp4 (no encoder here) and the antialiased 512-pixel resize of its frames."""
 import argparse
@@ -48,13 +49,18 @@ def save_points(samples, lidar_utils, args):
 
 def render(xs, lidar_utils, args):
     """generate.py:61-63 on the last frame; with --render_frames the BEV of every frame, a few sampling steps per launch."""
-    from r2dm_amd.render import make_grid, render_frames, save_png
+    from r2dm_amd.render import make_grid, render_frames, render_normals, save_png
 
     args.render_dir.mkdir(parents=True, exist_ok=True)
     img, bev = render_frames(xs[-1], lidar_utils, size=args.bev_size)
     save_png(make_grid(img, nrow=1), args.render_dir / "samples_img.png")
     save_png(make_grid(bev, nrow=4), args.render_dir / "samples_bev.png")
     written = 2
+    if args.render_normals:
+        colors, bev = render_normals(xs[-1][:, [0]] * lidar_utils.max_depth, lidar_utils, size=args.bev_size)
+        save_png(make_grid(colors, nrow=1), args.render_dir / "samples_normal.png")
+        save_png(make_grid(bev, nrow=4), args.render_dir / "samples_bev_normal.png")
+        written += 2
     if args.render_frames:
         (args.render_dir / "frames").mkdir(exist_ok=True)
         S1, B = xs.shape[:2]
@@ -86,6 +92,8 @@ if __name__ == "__main__":
     parser.add_argument("--render_dir", type=Path, default=None, help="also write samples_img.png and samples_bev.png there")
     parser.add_argument("--bev_size", type=int, default=800, help="side of a bird's-eye view in pixels")
     parser.add_argument("--render_frames", action="store_true", help="with --render_dir: frames/bev_%%04d.png for every frame of the stack")
+    parser.add_argument("--render_normals", action="store_true",
+                        help="with --render_dir: also samples_normal.png and samples_bev_normal.png, the surface normals and the bird's-eye views coloured by them")
     parser.add_argument("--points_dir", type=Path, default=None, help="also write the final samples as Velodyne scans samples_%%04d.bin there")
     parser.add_argument("--points_ply", action="store_true", help="with --points_dir: also samples_%%04d.ply, coloured by height")
     args = parser.parse_args()

@@ -263,6 +263,40 @@ int r2dm_render_frames(const float* x, const float* trig, const float* turbo, co
                        int64_t frames, int32_t height, int32_t width, int32_t size, float min_depth, float max_depth,
                        const float* view, float focal_length, void* scratch, size_t scratch_bytes, void* stream);
 
+/* -- surface normals and the training monitor's bird's-eye view (utils/render.py:145-236; train.py:227-239) ----------------------
+ * r2dm_surface_normals: estimate_surface_normal on xyz (batch,3,height,width) fp32 -> normals (batch,3,height,width) fp32, one launch.
+ *    The neighbour of pixel (h, w) at offset (dh, dw) is the pixel (clamp(h + dh, 0, height - 1), (w + dw) mod width): rows replicate,
+ *    columns are circular (the azimuth seam is a neighbour like any other).  The eight offsets, k = 0 .. 7, are (-d,0) (-d,d) (0,d) (d,d)
+ *    (d,0) (d,-d) (0,-d) (-d,-d).  With a the pixel's own point and p_k its k-th neighbour:
+ *      V_k = p_k - a                                           (per component)
+ *      |v| = sqrt((v0 v0 + v1 v1) + v2 v2)
+ *      u x v = (u1 v2 - u2 v1, u2 v0 - u0 v2, u0 v1 - u1 v0)
+ *    mode 0 ("closest"): dist_k = |V_k| + |V_(k+2)%8|; the smallest dist_k wins, the lowest k on a tie; n = V_k x V_(k+2)%8.
+ *    mode 1 ("mean"):    c_k = V_k x V_(k+2)%8; n = (((c_0 + c_1) + c_2) + ... + c_7) / 8 (per component).
+ *    normals = n / (|n| + 1e-8f) (per component).  Everything is fp32 with one rounding per written operation (nothing contracted),
+ *    sqrt and the division correctly rounded, denormals kept: the result is a function of the input bits, the same on every call, and a
+ *    sample's normals do not depend on the rest of the batch.  A pixel whose window is all zeros gives exactly 0.  A non-finite input
+ *    makes the normals of the pixels whose window holds it unspecified and leaves every other pixel as it is.
+ *    Limits: 1 <= d <= 8, d <= width, mode 0 or 1, height, width >= 1 (height < 2 d + 1 is fine: the rows replicate); fewer than 2^31
+ *    tiles of 4 x 64 pixels over the batch.  Beyond them the call returns a status and launches nothing.  normals must not alias xyz.
+ * r2dm_normal_frames: train.py's log_images view in one pass over metric (frames,1,height,width), the depth in metres:
+ *      mask = min_depth < metric < max_depth                  (1 or 0)
+ *      xyz  = ((((metric cos_phi) cos_theta) mask) / max_depth) mask, ((((metric cos_phi) sin_theta) mask) / max_depth) mask,
+ *             (((metric sin_phi) mask) / max_depth) mask       (LiDARUtility.to_xyz, then / max_depth * mask)
+ *      n    = the normal of r2dm_surface_normals(xyz, d, mode) at the pixel
+ *      colour = (-n + 1) / 2
+ *    colors (frames,3,height,width) = colour (NULL: not written); bev (frames,3,size,size) = render_point_clouds(xyz, colour) under the
+ *    view (12 HOST floats, R row-major then t) and focal length of r2dm_project_points, splatted as r2dm_bilinear_rasterize does (64-bit
+ *    fixed point, the same bits on every call).  A point whose coordinates or colour are not finite adds nothing.  trig (4,height,width):
+ *    cos / sin of the elevation, cos / sin of the azimuth, as r2dm_render_frames takes them.  No xyz, normal or per-point tensor is written.
+ *    Frames are taken as many at a time as scratch (at least r2dm_normal_frames_scratch_bytes(1, size), 256-byte aligned) holds; a
+ *    frame's images do not depend on that number.  Limits: those of r2dm_surface_normals, max_depth > 0. */
+int r2dm_surface_normals(const float* xyz, float* normals, int32_t batch, int32_t height, int32_t width, int32_t d, int32_t mode, void* stream);
+size_t r2dm_normal_frames_scratch_bytes(int32_t frames, int32_t size);
+int r2dm_normal_frames(const float* metric, const float* trig, float* colors, float* bev, int64_t frames, int32_t height, int32_t width,
+                       int32_t size, float min_depth, float max_depth, int32_t d, int32_t mode, const float* view, float focal_length,
+                       void* scratch, size_t scratch_bytes, void* stream);
+
 /* -- raw scans to range images (data/kitti_360/kitti_360.py:34-93,164-165; the same in data/kitti_raw) -------------------------
  * r2dm_project_scans: load_points_as_images on a batch of scans held in one buffer: points (total,4) fp32 [x, y, z, reflectance]
  *    in device memory (16-byte aligned), scan b = rows offsets[b] .. offsets[b + 1] - 1; offsets = batch + 1 HOST values, offsets[0] = 0,

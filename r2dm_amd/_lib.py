@@ -122,6 +122,10 @@ SIGNATURES = {
     "r2dm_render_frames_scratch_bytes": (c_size_t, [c_int32, c_int32]),
     "r2dm_render_frames": (c_int32, [_P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_float, c_float, POINTER(c_float), c_float,
                                      _P, c_size_t, _P]),
+    "r2dm_surface_normals": (c_int32, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
+    "r2dm_normal_frames_scratch_bytes": (c_size_t, [c_int32, c_int32]),
+    "r2dm_normal_frames": (c_int32, [_P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_float, c_float, c_int32, c_int32, POINTER(c_float), c_float,
+                                     _P, c_size_t, _P]),
     "r2dm_project_scratch_bytes": (c_size_t, [c_int64, c_int32, c_int32, c_int32, c_int32]),
     "r2dm_project_scans": (c_int32, [_P, POINTER(c_int64), _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_int32, c_int32,
                                      _P, c_size_t, _P]),

@@ -327,6 +327,11 @@ size_t render_frames_scratch_bytes(int frames, int size);
 hipError_t launch_render_frames(const float* x, const float* trig, const float* turbo, const float* viridis, float* img, float* bev, long N, int H, int W,
                                 int size, float min_depth, float max_depth, const float* Rt, float focal, void* scratch, size_t scratch_bytes,
                                 hipStream_t s);
+// estimate_surface_normal and train.py's log_images view (render.hip): nullptr if (B, H, W, d, mode) can be launched, else what is wrong with them
+const char* surface_normals_error(long B, int H, int W, int d, int mode);
+hipError_t launch_surface_normals(const float* xyz, float* normals, int B, int H, int W, int d, int mode, hipStream_t s);
+hipError_t launch_normal_frames(const float* metric, const float* trig, float* colors, float* bev, long N, int H, int W, int size, float min_depth,
+                                float max_depth, int d, int mode, const float* Rt, float focal, void* scratch, size_t scratch_bytes, hipStream_t s);
 
 // raw scans -> range images (projection.hip): offsets are B + 1 HOST values (validated by the caller), Wo <= W the written width
 size_t project_scratch_bytes(long long total, int B, int H, int W, int unfold);

@@ -216,6 +216,31 @@ int r2dm_render_frames(const float* x, const float* trig, const float* turbo, co
     return 0;
 }
 
+int r2dm_surface_normals(const float* xyz, float* normals, int32_t batch, int32_t height, int32_t width, int32_t d, int32_t mode, void* stream) {
+    if (!xyz || !normals) return fail(1, "null argument");
+    if (const char* why = surface_normals_error(batch, height, width, d, mode)) return fail(1, "surface_normals: %s", why);
+    if ((const void*)xyz == (const void*)normals) return fail(1, "surface_normals: normals must not alias xyz");
+    HIP_TRY(launch_surface_normals(xyz, normals, batch, height, width, d, mode, (hipStream_t)stream));
+    return 0;
+}
+
+size_t r2dm_normal_frames_scratch_bytes(int32_t frames, int32_t size) { return r2dm_render_frames_scratch_bytes(frames, size); }
+
+int r2dm_normal_frames(const float* metric, const float* trig, float* colors, float* bev, int64_t frames, int32_t height, int32_t width, int32_t size,
+                       float min_depth, float max_depth, int32_t d, int32_t mode, const float* view, float focal_length, void* scratch,
+                       size_t scratch_bytes, void* stream) {
+    if (!metric || !trig || !bev || !view || !scratch) return fail(1, "null argument");
+    if (frames < 1 || size < 1) return fail(1, "normal_frames: empty batch or image");
+    if (const char* why = surface_normals_error(1, height, width, d, mode)) return fail(1, "normal_frames: %s", why);
+    if (!(max_depth > 0.f)) return fail(1, "max_depth must be > 0");
+    if (scratch_bytes < render_frames_scratch_bytes(1, size))
+        return fail(1, "scratch too small: %zu bytes hold no frame of %zu", scratch_bytes, render_frames_scratch_bytes(1, size));
+    if ((uintptr_t)scratch & 255) return fail(1, "scratch must be 256-byte aligned");
+    HIP_TRY(launch_normal_frames(metric, trig, colors, bev, frames, height, width, size, min_depth, max_depth, d, mode, view, focal_length, scratch,
+                                 scratch_bytes, (hipStream_t)stream));
+    return 0;
+}
+
 static const char* project_geometry_error(int64_t total, int32_t batch, int32_t H, int32_t W) {
     if (batch < 1 || batch > 65535) return "project: batch must be in [1, 65535]";
     if (H < 1 || W < 1 || (int64_t)batch * H * W >= (1LL << 31)) return "project: the grid must have 1 to 2^31 - 1 cells over the batch";

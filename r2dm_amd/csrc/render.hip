@@ -7,6 +7,8 @@
 //  frames_kernel          generate.py's render() fused: one thread per range-image pixel colours the two channels, projects the
 //                         pixel's point and splats it; no xyz / colour tensor exists.
 //  finish_kernel          accumulators -> fp32 image, or the ratio colour / (weight + 1e-8) of render_point_clouds().
+//  surface_normals_kernel estimate_surface_normal(): a 9-point stencil over an LDS tile, bit-exact to the contract of include/r2dm_hip.h.
+//  normal_frames_kernel   train.py's log_images view fused: metric depth -> xyz -> normal -> colour, projected and splatted from the same tile.
 //
 // The splat is a many-to-one sum.  Float atomics would make it depend on the arrival order; here every term is rounded ONCE to a
 // 64-bit fixed-point integer (scale 2^s, s from the largest |value| of the call, found on the device) and summed by integer vector
@@ -333,6 +335,203 @@ hipError_t launch_render_frames(const float* x, const float* trig, const float* 
                 acc + g0 * spx * 4, nullptr, bev + (f0 + g0) * 3 * spx, spx, 4, guard, scale);
             if ((e = hipGetLastError()) != hipSuccess) return e;
         }
+    }
+    return hipSuccess;
+}
+
+// ---- estimate_surface_normal (utils/render.py:145-236) and train.py:227-239 fused -----------------
+// A block owns a 4 x 64 pixel tile, one pixel per thread (a wave is one row of the tile).  The tile and its halo of d rows and d columns are
+// staged into three LDS planes, the replicate clamp of the rows and the wrap of the columns applied there, once; every thread then reads its
+// anchor and eight neighbours from LDS.  No atomics, no scratch memory: a pixel's normal is a function of its 9 input points.
+constexpr int kNormalTileH = 4, kNormalTileW = 64, kNormalMaxD = 8;
+static_assert(kNormalTileH * kNormalTileW == kRenderThreads && kNormalTileW == kWave, "one pixel per thread, one tile row per wave");
+
+struct Vec3 {
+    float x, y, z;
+};
+__device__ __forceinline__ Vec3 sub3(const Vec3& p, const Vec3& a) { return {p.x - a.x, p.y - a.y, p.z - a.z}; }
+__device__ __forceinline__ float norm3(const Vec3& v) { return sqrtf((v.x * v.x + v.y * v.y) + v.z * v.z); }
+__device__ __forceinline__ Vec3 cross3(const Vec3& u, const Vec3& v) { return {u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x}; }
+
+// The block's tile: flat block index -> (image, first row, first column)
+struct NormalTile {
+    long image;
+    int row0, col0;
+};
+__device__ __forceinline__ NormalTile normal_tile(int H, int W) {
+    const int tw = (W + kNormalTileW - 1) / kNormalTileW, th = (H + kNormalTileH - 1) / kNormalTileH;
+    const long t = blockIdx.x;
+    const long b = t / ((long)th * tw);
+    const int r = (int)(t - b * th * tw);
+    return {b, (r / tw) * kNormalTileH, (r % tw) * kNormalTileW};
+}
+
+// Stage the tile and its halo: `point(row, col)` gives the point of an image pixel; planes [3][rows][cols] with rows = 4 + 2d, cols = 64 + 2d
+template <class Point>
+__device__ __forceinline__ void stage_normal_tile(float* __restrict__ lds, const NormalTile& T, int H, int W, int d, Point point) {
+    const int rows = kNormalTileH + 2 * d, cols = kNormalTileW + 2 * d, plane = rows * cols;
+    for (int e = threadIdx.x; e < plane; e += kRenderThreads) {
+        const int i = e / cols, j = e - i * cols;
+        int row = T.row0 - d + i;
+        row = row < 0 ? 0 : (row > H - 1 ? H - 1 : row);
+        int col = (T.col0 - d + j) % W;  // (a tile may overhang the image by up to 63 columns: a full modulo)
+        col = col < 0 ? col + W : col;
+        const Vec3 p = point(row, col);
+        lds[e] = p.x;
+        lds[plane + e] = p.y;
+        lds[2 * plane + e] = p.z;
+    }
+    __syncthreads();
+}
+
+// The normal of the thread's pixel from the staged planes; `a` receives its own point
+__device__ __forceinline__ Vec3 normal_from_tile(const float* __restrict__ lds, int d, int mode, Vec3& a) {
+    const int cols = kNormalTileW + 2 * d, plane = (kNormalTileH + 2 * d) * cols;
+    const int ty = threadIdx.x / kNormalTileW, tx = threadIdx.x % kNormalTileW;
+    const int c = (ty + d) * cols + tx + d;
+    auto at = [&](int e) { return Vec3{lds[e], lds[plane + e], lds[2 * plane + e]}; };
+    a = at(c);
+    const int up = -d * cols, down = d * cols;
+    // k = 0 .. 7: (-d,0) (-d,d) (0,d) (d,d) (d,0) (d,-d) (0,-d) (-d,-d)
+    const Vec3 V[8] = {sub3(at(c + up), a),       sub3(at(c + up + d), a),   sub3(at(c + d), a), sub3(at(c + down + d), a),
+                       sub3(at(c + down), a),     sub3(at(c + down - d), a), sub3(at(c - d), a), sub3(at(c + up - d), a)};
+    Vec3 n;
+    if (mode == 0) {
+        float len[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) len[k] = norm3(V[k]);
+        float best = len[0] + len[2];
+        Vec3 u = V[0], v = V[2];
+#pragma unroll
+        for (int k = 1; k < 8; ++k) {
+            const float dist = len[k] + len[(k + 2) % 8];
+            if (dist < best) best = dist, u = V[k], v = V[(k + 2) % 8];  // (strictly smaller: the lowest k keeps a tie)
+        }
+        n = cross3(u, v);
+    } else {
+        n = cross3(V[0], V[2]);
+#pragma unroll
+        for (int k = 1; k < 8; ++k) {
+            const Vec3 ck = cross3(V[k], V[(k + 2) % 8]);
+            n = {n.x + ck.x, n.y + ck.y, n.z + ck.z};
+        }
+        n = {n.x / 8.0f, n.y / 8.0f, n.z / 8.0f};
+    }
+    const float den = norm3(n) + 1e-8f;
+    return {n.x / den, n.y / den, n.z / den};
+}
+
+__global__ __launch_bounds__(kRenderThreads) void surface_normals_kernel(const float* __restrict__ xyz, float* __restrict__ normals, int H, int W, int d,
+                                                                         int mode) {
+    extern __shared__ float normal_lds[];
+    const NormalTile T = normal_tile(H, W);
+    const long hw = (long)H * W;
+    const float* src = xyz + T.image * 3 * hw;
+    stage_normal_tile(normal_lds, T, H, W, d, [&](int row, int col) {
+        const long p = (long)row * W + col;
+        return Vec3{src[p], src[hw + p], src[2 * hw + p]};
+    });
+    const int h = T.row0 + threadIdx.x / kNormalTileW, w = T.col0 + threadIdx.x % kNormalTileW;
+    if (h >= H || w >= W) return;
+    Vec3 a;
+    const Vec3 n = normal_from_tile(normal_lds, d, mode, a);
+    float* o = normals + T.image * 3 * hw + (long)h * W + w;
+    o[0] = n.x;
+    o[hw] = n.y;
+    o[2 * hw] = n.z;
+}
+
+struct NormalFrameParams {
+    const float* metric;  // (N,1,H,W): depth in metres
+    const float* trig;    // (4,H,W)
+    float* colors;        // (N,3,H,W) or nullptr
+    int H, W, size, d, mode;
+    float min_depth, max_depth;
+    View V;
+};
+
+__global__ __launch_bounds__(kRenderThreads) void normal_frames_kernel(NormalFrameParams P, unsigned long long* __restrict__ acc, long frame0,
+                                                                       double scale) {
+    extern __shared__ float normal_lds[];
+    const NormalTile T = normal_tile(P.H, P.W);  // (image: the frame inside this launch)
+    const long hw = (long)P.H * P.W, n = frame0 + T.image;
+    const float* src = P.metric + n * hw;
+    stage_normal_tile(normal_lds, T, P.H, P.W, P.d, [&](int row, int col) {
+        const long p = (long)row * P.W + col;
+        const float metric = src[p];
+        const float m = (metric > P.min_depth && metric < P.max_depth) ? 1.0f : 0.0f;
+        const float cp = P.trig[p], sp = P.trig[hw + p], ct = P.trig[2 * hw + p], st = P.trig[3 * hw + p];
+        // LiDARUtility.to_xyz (its own mask), then / max_depth * mask
+        return Vec3{((((metric * cp) * ct) * m) / P.max_depth) * m, ((((metric * cp) * st) * m) / P.max_depth) * m,
+                    (((metric * sp) * m) / P.max_depth) * m};
+    });
+    const int h = T.row0 + threadIdx.x / kNormalTileW, w = T.col0 + threadIdx.x % kNormalTileW;
+    bool valid = h < P.H && w < P.W;
+    float u = 0.f, v = 0.f, vals[4] = {0.f, 0.f, 0.f, 0.f};
+    if (valid) {
+        Vec3 a;
+        const Vec3 nr = normal_from_tile(normal_lds, P.d, P.mode, a);
+        const float c[3] = {(-nr.x + 1.0f) / 2.0f, (-nr.y + 1.0f) / 2.0f, (-nr.z + 1.0f) / 2.0f};
+        if (P.colors) {
+            float* o = P.colors + n * 3 * hw + (long)h * P.W + w;
+            o[0] = c[0];
+            o[hw] = c[1];
+            o[2 * hw] = c[2];
+        }
+        float weight, mask;
+        project_point(P.V, a.x, a.y, a.z, u, v, weight, mask);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) vals[k] = weight * (c[k] * mask);
+        vals[3] = weight;
+        valid = isfinite(vals[0]) && isfinite(vals[1]) && isfinite(vals[2]) && isfinite(vals[3]);
+    }
+    splat_point<4>(acc + T.image * (long)P.size * P.size * 4, P.size, P.size, u, v, vals, scale, valid);
+}
+
+static long normal_tiles(int H, int W) { return (long)((H + kNormalTileH - 1) / kNormalTileH) * ((W + kNormalTileW - 1) / kNormalTileW); }
+static size_t normal_lds_bytes(int d) { return (size_t)3 * (kNormalTileH + 2 * d) * (kNormalTileW + 2 * d) * sizeof(float); }
+
+const char* surface_normals_error(long B, int H, int W, int d, int mode) {
+    if (B < 1 || H < 1 || W < 1) return "empty batch or image";
+    if (d < 1 || d > kNormalMaxD) return "the neighbour distance d must be in [1, 8]";
+    if (d > W) return "the neighbour distance d must not exceed the width";
+    if (mode != 0 && mode != 1) return "mode must be 0 (closest) or 1 (mean)";
+    if (normal_tiles(H, W) > 0x7fffffffL / B) return "2^31 or more tiles of 4 x 64 pixels over the batch";
+    return nullptr;
+}
+
+hipError_t launch_surface_normals(const float* xyz, float* normals, int B, int H, int W, int d, int mode, hipStream_t s) {
+    if (surface_normals_error(B, H, W, d, mode)) return hipErrorInvalidValue;
+    surface_normals_kernel<<<(unsigned)(normal_tiles(H, W) * B), kRenderThreads, normal_lds_bytes(d), s>>>(xyz, normals, H, W, d, mode);
+    return hipGetLastError();
+}
+
+hipError_t launch_normal_frames(const float* metric, const float* trig, float* colors, float* bev, long N, int H, int W, int size, float min_depth,
+                                float max_depth, int d, int mode, const float* Rt, float focal, void* scratch, size_t scratch_bytes, hipStream_t s) {
+    const long chunk = (long)(scratch_bytes / render_frames_scratch_bytes(1, size));
+    if (N < 1 || size < 1 || chunk < 1 || surface_normals_error(1, H, W, d, mode)) return hipErrorInvalidValue;
+    NormalFrameParams P;
+    P.metric = metric, P.trig = trig, P.colors = colors;
+    P.H = H, P.W = W, P.size = size, P.d = d, P.mode = mode;
+    P.min_depth = min_depth, P.max_depth = max_depth;
+    P.V = make_view(Rt, focal, size);
+    // every value is weight x colour x mask with weight <= 1 and colour = (1 - n) / 2 < 2: a fixed scale, no pre-pass
+    const long hw = (long)H * W, tiles = normal_tiles(H, W), spx = (long)size * size;
+    const int guard = guard_bits(hw);
+    const double scale = ldexp(1.0, 62 - guard - 1);
+    unsigned long long* acc = static_cast<unsigned long long*>(scratch);
+    long per_launch = 0x7fffffffL / tiles;  // (grid limit)
+    per_launch = per_launch < chunk ? per_launch : chunk;
+    per_launch = per_launch < 32768 ? per_launch : 32768;
+    for (long f0 = 0; f0 < N; f0 += per_launch) {
+        const long nf = N - f0 < per_launch ? N - f0 : per_launch;
+        hipError_t e = hipMemsetAsync(acc, 0, render_frames_scratch_bytes((int)nf, size), s);
+        if (e != hipSuccess) return e;
+        normal_frames_kernel<<<(unsigned)(tiles * nf), kRenderThreads, normal_lds_bytes(d), s>>>(P, acc, f0, scale);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        finish_kernel<1><<<dim3((unsigned)((spx + kRenderThreads - 1) / kRenderThreads), 1, (unsigned)nf), kRenderThreads, 0, s>>>(acc, nullptr,
+                                                                                                                                  bev + f0 * 3 * spx, spx, 4, guard, scale);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     return hipSuccess;
 }

@@ -211,8 +211,7 @@ def render_frames(x: torch.Tensor, lidar_utils, size: int = 800, scratch_frames:
     bev = torch.empty(N, 3, size, size, dtype=torch.float32, device=x.device)
     if not N:
         return img, bev
-    ang = lidar_utils.ray_angles[0].to(x.device, torch.float32)
-    trig = torch.stack([ang[0].cos(), ang[0].sin(), ang[1].cos(), ang[1].sin()]).contiguous()
+    trig = ray_trig(lidar_utils, x.device)
     turbo, viridis = _device_lut("turbo", x.device), _device_lut("viridis", x.device)
     R, t = make_Rt(pitch=math.pi / 3, yaw=math.pi / 4, z=0.8)
     per = L.r2dm_render_frames_scratch_bytes(1, size)
@@ -225,6 +224,115 @@ def render_frames(x: torch.Tensor, lidar_utils, size: int = 800, scratch_frames:
                                         float(lidar_utils.min_depth), float(lidar_utils.max_depth), _view(R, t, 1.0), 1.0, sptr, frames * per,
                                         _lib.stream_ptr(x.device)))
     return img, bev
+
+
+# ---- surface normals -----------------------------------------------------------------------------
+NORMAL_MODES = {"closest": 0, "mean": 1}
+_NORMAL_MAX_D = 8
+
+
+def _normal_args(d, mode, W):
+    if mode not in NORMAL_MODES:
+        raise NotImplementedError(mode)
+    d = int(d)
+    if not 1 <= d <= _NORMAL_MAX_D or d > W:
+        raise ValueError(f"the neighbour distance d must be in [1, min({_NORMAL_MAX_D}, width {W})], got {d}")
+    return d, NORMAL_MODES[mode]
+
+
+@torch.no_grad()
+def estimate_surface_normal(points: torch.Tensor, d: int = 2, mode: str = "closest") -> torch.Tensor:
+    """utils/render.py:145-236: coordinated points ``(B,3,H,W)`` -> unit normals ``(B,3,H,W)`` from the cross product of two
+    neighbours at distance ``d`` (rows replicate, columns wrap): the pair of the eight with the smallest summed distance to the
+    pixel (``"closest"``) or the mean over the eight pairs (``"mean"``).  One launch; the bits are those of the written-out fp32
+    contract in include/r2dm_hip.h."""
+    _lib.require_gpu(points, "points")
+    if points.ndim != 4 or points.shape[1] != 3 or points.shape[2] < 1 or points.shape[3] < 1:
+        raise ValueError(f"expected (B,3,H,W), got {tuple(points.shape)}")
+    B, _, H, W = points.shape
+    d, mode = _normal_args(d, mode, W)
+    points = _lib.f32c(points)
+    out = torch.empty_like(points)
+    if B:
+        with torch.cuda.device(points.device):
+            _lib.check(_lib.lib().r2dm_surface_normals(_lib.ptr(points), _lib.ptr(out), B, H, W, d, mode, _lib.stream_ptr(points.device)))
+    return out
+
+
+def ray_trig(lidar_utils, device) -> torch.Tensor:
+    """(4,H,W) fp32: cos / sin of the elevation, cos / sin of the azimuth of ``lidar_utils.ray_angles``, taken on ``device``."""
+    ang = lidar_utils.ray_angles[0].to(device, torch.float32)
+    return torch.stack([ang[0].cos(), ang[0].sin(), ang[1].cos(), ang[1].sin()]).contiguous()
+
+
+@torch.no_grad()
+def render_normals(metric: torch.Tensor, lidar_utils, size: int = 800, d: int = 2, mode: str = "closest", R: torch.Tensor | None = None,
+                   t=(0.0, 0.0, 1.0), focal_length: float = 1.0, scratch_frames: int | None = None, trig: torch.Tensor | None = None,
+                   with_colors: bool = True):
+    """train.py:227-239 in one pass.  ``metric`` (B,1,H,W), the depth in metres -> ``colors`` (B,3,H,W), the surface normals of
+    ``to_xyz(metric) / max_depth * mask`` as ``(-n + 1) / 2``, and ``bev`` (B,3,size,size), that cloud in those colours under the view
+    ``R`` / ``t`` (default: train.py's, no rotation and t = [0, 0, 1]).  ``trig`` replaces ``ray_trig(lidar_utils)``;
+    ``scratch_frames`` bounds the frames accumulated at a time; ``with_colors=False`` returns ``(None, bev)``."""
+    _lib.require_gpu(metric, "metric")
+    if metric.ndim != 4 or metric.shape[1] != 1 or tuple(metric.shape[2:]) != tuple(lidar_utils.ray_angles.shape[2:]):
+        raise ValueError(f"expected (B,1,{','.join(map(str, lidar_utils.ray_angles.shape[2:]))}) depths, got {tuple(metric.shape)}")
+    size = int(size)
+    if size < 1:
+        raise ValueError(f"size {size}")
+    L = _lib.lib()
+    metric = _lib.f32c(metric)
+    B, _, H, W = metric.shape
+    d, mode = _normal_args(d, mode, W)
+    if trig is None:
+        trig = ray_trig(lidar_utils, metric.device)
+    else:
+        _lib.require_gpu(trig, "trig")
+        if tuple(trig.shape) != (4, H, W):
+            raise ValueError(f"expected trig (4,{H},{W}), got {tuple(trig.shape)}")
+        trig = _lib.f32c(trig)
+    colors = torch.empty(B, 3, H, W, dtype=torch.float32, device=metric.device) if with_colors else None
+    bev = torch.empty(B, 3, size, size, dtype=torch.float32, device=metric.device)
+    if not B:
+        return colors, bev
+    if t is not None and not isinstance(t, torch.Tensor):
+        t = torch.tensor(t, dtype=torch.float32)
+    per = L.r2dm_normal_frames_scratch_bytes(1, size)
+    frames = max(1, min(B, _SCRATCH_CAP // per)) if scratch_frames is None else int(scratch_frames)
+    if frames < 1:
+        raise ValueError(f"scratch_frames {scratch_frames}")
+    buf, sptr, _ = _scratch(frames * per, metric.device)
+    with torch.cuda.device(metric.device):
+        _lib.check(L.r2dm_normal_frames(_lib.ptr(metric), _lib.ptr(trig), _lib.ptr(colors), _lib.ptr(bev), B, H, W, size,
+                                        float(lidar_utils.min_depth), float(lidar_utils.max_depth), d, mode, _view(R, t, focal_length),
+                                        float(focal_length), sptr, frames * per, _lib.stream_ptr(metric.device)))
+    return colors, bev
+
+
+@torch.no_grad()
+def log_images(image: torch.Tensor, lidar_utils, channels=(1, 1), tag: str = "name", size: int = 800) -> dict:
+    """train.py:221-245: the panels the reference's training monitor logs for a normalised ``(B,C,H,W)`` batch in [-1,1], ``channels``
+    = (depth channels, reflectance channels), as uint8 ``(B,3,.,.)`` images: ``{tag}/depth`` (turbo), ``{tag}/depth/orig`` (turbo of the
+    metric depth / max_depth), ``{tag}/bev`` (the bird's-eye view coloured by surface normal), ``{tag}/mask`` (binary_r) and
+    ``{tag}/reflectance`` (plasma).  A key is present only when its channel is."""
+    _lib.require_gpu(image, "image")
+    channels = tuple(int(c) for c in channels)
+    if image.ndim != 4 or len(channels) != 2 or min(channels) < 0 or max(channels) > 1 or image.shape[1] != sum(channels):
+        raise ValueError(f"expected (B,{sum(channels)},H,W) for channels {channels} (0 or 1 each), got {tuple(image.shape)}")
+    image = lidar_utils.denormalize(image)
+    depth, rflct = torch.split(image, channels, dim=1)
+    out = {}
+    if depth.numel() > 0:
+        out[f"{tag}/depth"] = colorize(depth)
+        metric = lidar_utils.revert_depth(depth)
+        mask = (metric > lidar_utils.min_depth) & (metric < lidar_utils.max_depth)
+        out[f"{tag}/depth/orig"] = colorize(metric / lidar_utils.max_depth)
+        _, bev = render_normals(metric, lidar_utils, size=size, with_colors=False)
+        out[f"{tag}/bev"] = bev.mul(255).clamp(0, 255).byte()
+    if rflct.numel() > 0:
+        out[f"{tag}/reflectance"] = colorize(rflct, "plasma")
+    if depth.numel() > 0:
+        out[f"{tag}/mask"] = colorize(mask.float(), "binary_r")
+    return out
 
 
 # ---- image files ---------------------------------------------------------------------------------
