@@ -376,6 +376,24 @@ int64_t r2dm_conv_packed_elems(int32_t cout, int32_t cin, int32_t ksize, int32_t
 int r2dm_conv2d_ring(const float* x, const float* w, const float* bias, float* w_packed, const float* aff,
                      int32_t prologue, const float* residual, const float* scale, float* y, int32_t batch,
                      int32_t cin, int32_t cout, int32_t height, int32_t width, int32_t ksize, void* stream);
+/* The same launch (same selection, packing and test hooks) with the fields that otherwise only the engine's walk sets:
+ *   x1, c1         second input allocation holding the LAST c1 of the cin channels (x then holds the first cin - c1): the up path's concat without
+ *                  a copy; c1 = 0 and x1 = NULL: one source
+ *   res_broadcast  1: residual is ONE (cout, H, W) map added to every sample
+ *   stat           fused GroupNorm statistics of y: (batch, stat_groups, r2dm_conv_stat_slots(height, width), 2) doubles [sum, sum of squares];
+ *                  this launch writes groups [stat_goff, stat_goff + cout / stat_cpg) of stat_cpg = 8 | 16 | 32 | 64 channels; NULL: none
+ *   range          device int[2]: [1] takes the running maximum of a bound on |y| as float bits -- the exact max|y|, except from conv_f16x2.hip,
+ *                  which records sqrt(largest four-pixel energy) (1 + 1e-6): max|y| <= bound <= 2 max|y|; NULL: no record
+ *   reverse        1: descending tile walk (conv_f16x2.hip, proj_f16x2.hip)
+ *   chosen         HOST int32[3] (or NULL) <- algorithm (ConvAlgo), output channels per tile, image rows per tile of the selected kernel
+ * Returns 1 -- before anything is launched or written -- for every combination the selected kernel would refuse, ignore, or that would leave the
+ * sink: statistics from a kernel that emits none (the 32-channel fp32 tile, the few-output direct kernel) or for groups that do not fit; x1 / range
+ * on the direct kernels; a concat seam off the kernel's chunk boundary; reverse on a kernel without the descending walk; c1 outside [0, cin). */
+int32_t r2dm_conv_stat_slots(int32_t height, int32_t width);
+int r2dm_conv2d_ring_ex(const float* x, const float* x1, int32_t c1, const float* w, const float* bias, float* w_packed, const float* aff,
+                        int32_t prologue, const float* residual, int32_t res_broadcast, const float* scale, float* y, double* stat,
+                        int32_t stat_groups, int32_t stat_goff, int32_t stat_cpg, int32_t* range, int32_t reverse, int32_t* chosen, int32_t batch,
+                        int32_t cin, int32_t cout, int32_t height, int32_t width, int32_t ksize, void* stream);
 /* nn.GroupNorm / AdaGN statistics folded to y = x*a + d (models/efficient_unet.py:72; ops.py:176-200).
  * gamma/beta (C,) or NULL; ada (B,2C) [scale|shift] or NULL; partial: scratch of
  * r2dm_group_norm_scratch_bytes(); aff out (B,C,2); stats out (B,G,2) mean/rstd or NULL. */

@@ -84,6 +84,9 @@ SIGNATURES = {
     "r2dm_conv_packed_elems": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
     "r2dm_conv2d_ring": (c_int32, [_P, _P, _P, _P, _P, c_int32, _P, _P, _P, c_int32, c_int32, c_int32, c_int32,
                                    c_int32, c_int32, _P]),
+    "r2dm_conv_stat_slots": (c_int32, [c_int32, c_int32]),
+    "r2dm_conv2d_ring_ex": (c_int32, [_P, _P, c_int32, _P, _P, _P, _P, c_int32, _P, c_int32, _P, _P, _P, c_int32, c_int32, c_int32, _P, c_int32,
+                                      _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
     "r2dm_group_norm_scratch_bytes": (c_size_t, [c_int32, c_int32]),
     "r2dm_group_norm_affine": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32,
                                          c_float, _P]),

@@ -26,9 +26,24 @@ static int test_io16() {
     return e ? atoi(e) : 0;
 }
 
-int r2dm_conv2d_ring(const float* x, const float* w, const float* bias, float* w_packed, const float* aff,
-                     int32_t prologue, const float* residual, const float* scale, float* y, int32_t B, int32_t cin,
-                     int32_t cout, int32_t H, int32_t W, int32_t ksize, void* stream) {
+// what r2dm_conv2d_ring_ex sets beyond r2dm_conv2d_ring: the ConvParams fields that otherwise only forward.hip fills
+struct ConvExtras {
+    const float* x1 = nullptr;  // second input allocation: the last c1 of the cin channels (Src::p1)
+    int c1 = 0;
+    int res_broadcast = 0;      // the residual is one (cout, H, W) map for the whole batch (res_bs = 0)
+    double* stat = nullptr;     // fused statistics sink [B][stat_G][conv_stat_slots(H, W)][2]
+    int stat_G = 0, stat_goff = 0, stat_cpg = 0;
+    int* range = nullptr;       // device int[2]: [1] takes the running maximum
+    int reverse = 0;
+    int32_t* chosen = nullptr;  // HOST int32[3] <- algo, co_tile, px_rows
+};
+
+// One convolution launch on caller-provided tensors: the algorithm and tile selection, the packing, and the IO16 / pre-pass test hooks of the
+// single-kernel entries.  Every combination a launcher would refuse, ignore or run past the caller's buffers is refused HERE, before the first
+// launch: nothing is written then.
+static int conv2d_ring_impl(const float* x, const float* w, const float* bias, float* w_packed, const float* aff, int32_t prologue, const float* residual,
+                            const float* scale, float* y, int32_t B, int32_t cin, int32_t cout, int32_t H, int32_t W, int32_t ksize, void* stream,
+                            const ConvExtras& ex) {
     if (!x || !w || !bias || !w_packed || !y) return fail(1, "null argument");
     if (ksize != 1 && ksize != 3) return fail(1, "kernel size must be 1 or 3");
     hipStream_t st = (hipStream_t)stream;
@@ -49,6 +64,35 @@ int r2dm_conv2d_ring(const float* x, const float* w, const float* bias, float* w
     if (algo == ALGO_F16X2 || algo == ALGO_P1F16) pieces = g_single_kernel_pieces;
     const int co_tile = algo == ALGO_F16X2 ? conv_f16x2_pick_co_tile(cin, cout, H, W, (long)B * H * W, &px_rows) : algo == ALGO_P1F16 ? 64 : algo == ALGO_BF16X3 ? conv_bf16x3_co_tile(cin, cout, (long)B * H * W) : conv_pick_co_tile(cout, taps, (long)B * H * W);
     const int cin_pad = algo != ALGO_F32 ? cin : conv_cin_pad(cin, taps, co_tile);
+    if (ex.chosen) {
+        ex.chosen[0] = algo;
+        ex.chosen[1] = co_tile;
+        ex.chosen[2] = px_rows;
+    }
+    // ---- the extended entry's fields: what the launchers refuse (conv_direct / conv_bf16x3 / conv_f16x2 / proj_f16x2 .hip), what they would silently ignore,
+    // and what would send a kernel past the caller's sink
+    if ((ex.res_broadcast | ex.reverse) & ~1) return fail(1, "conv2d_ring_ex: res_broadcast and reverse are 0 or 1");
+    if (ex.res_broadcast && !residual) return fail(1, "conv2d_ring_ex: res_broadcast without a residual");
+    if (ex.c1 < 0 || ex.c1 >= cin) return fail(1, "conv2d_ring_ex: c1 = %d outside [0, cin = %d)", ex.c1, cin);
+    if ((ex.x1 != nullptr) != (ex.c1 > 0)) return fail(1, "conv2d_ring_ex: x1 and c1 go together");
+    if (ex.x1) {
+        const int c0 = cin - ex.c1;
+        if (algo == ALGO_DIRECT) return fail(1, "conv2d_ring_ex: the direct kernels take one input allocation");  // (launch_conv_direct; the engine's in / out convolutions)
+        if ((algo == ALGO_BF16X3 || algo == ALGO_F16X2) && c0 % 16) return fail(1, "conv2d_ring_ex: the concat seam (%d) must lie on a 16-channel chunk boundary", c0);
+        if (algo == ALGO_P1F16 && c0 % 8) return fail(1, "conv2d_ring_ex: the concat seam (%d) must lie on an 8-channel boundary", c0);
+    }
+    if (ex.range && algo == ALGO_DIRECT) return fail(1, "conv2d_ring_ex: the direct kernels record no range");
+    if (ex.reverse && algo != ALGO_F16X2 && algo != ALGO_P1F16) return fail(1, "conv2d_ring_ex: this kernel has no descending tile walk");
+    if (ex.stat) {
+        // (forward.hip emits_stats: not the 32-channel fp32 tile, not the few-output direct kernel)
+        const bool emits = algo == ALGO_BF16X3 || algo == ALGO_F16X2 || algo == ALGO_P1F16 || (algo == ALGO_F32 && co_tile >= 64) || (algo == ALGO_DIRECT && cout > 4);
+        if (!emits) return fail(1, "conv2d_ring_ex: this kernel (algo %d, tile %d) emits no statistics", algo, co_tile);
+        const int cpg = ex.stat_cpg;
+        if (cpg != 8 && cpg != 16 && cpg != 32 && cpg != 64) return fail(1, "conv2d_ring_ex: stat_cpg = %d (8, 16, 32 or 64 channels per group)", cpg);
+        if (cout % cpg) return fail(1, "conv2d_ring_ex: %d output channels do not split into groups of %d", cout, cpg);
+        if (ex.stat_goff < 0 || ex.stat_goff + cout / cpg > ex.stat_G) return fail(1, "conv2d_ring_ex: groups [%d, %d) outside a sink of %d", ex.stat_goff, ex.stat_goff + cout / cpg, ex.stat_G);
+        if (test_io16() & 3) return fail(1, "conv2d_ring_ex: no statistics together with the fp16 storage hook");
+    }
     const float* wscale = nullptr;
     if (algo == ALGO_F16X2) {  // the range flag and the weight scale: behind the packed weights (r2dm_conv_packed_elems reserves 64 floats)
         float* tail = w_packed + conv_f16x2_packed_floats(cin, cout);
@@ -63,14 +107,25 @@ int r2dm_conv2d_ring(const float* x, const float* w, const float* bias, float* w
     } else {
         HIP_TRY(launch_pack_conv(w, w_packed, cout, cin, taps, co_tile, cin_pad, st, algo));
     }
-    ConvParams p = conv_params(Src{x, nullptr, cin, 0, (long)cin * H * W, 0}, w_packed, bias, y, (long)cout * H * W, B, H, W, cin, cin_pad, cout, taps, co_tile, algo, prologue);
+    const long hw = (long)H * W;
+    const Src src = ex.x1 ? Src{x, ex.x1, cin - ex.c1, ex.c1, (cin - ex.c1) * hw, ex.c1 * hw} : Src{x, nullptr, cin, 0, cin * hw, 0};
+    ConvParams p = conv_params(src, w_packed, bias, y, (long)cout * H * W, B, H, W, cin, cin_pad, cout, taps, co_tile, algo, prologue);
     p.px_rows = px_rows;
     p.pieces = pieces;
     p.wscale = wscale;
     p.aff = (const float2*)aff;
     p.res = residual;
-    p.res_bs = (long)cout * H * W;
+    p.res_bs = ex.res_broadcast ? 0 : (long)cout * H * W;
     p.scale = scale;
+    p.range = ex.range;
+    p.reverse = ex.reverse;
+    if (ex.stat) {
+        p.stat = ex.stat;
+        p.stat_G = ex.stat_G;
+        p.stat_goff = ex.stat_goff;
+        p.stat_cpg = ex.stat_cpg;
+        p.stat_slots = conv_stat_slots(H, W);
+    }
     // per-kernel tests of the fp16 activation storage (conv_f16x2.hip, one-plane mode): R2DM_TEST_IO16 = 1 (x holds fp16), 2 (y and the
     // residual hold fp16) or 3 -- the caller passes tensors of that type behind the float pointers
     if (const char* e = getenv("R2DM_TEST_IO16"); e && (atoi(e) & 3)) {  // (bit 2 alone: only the kernel selection above -- the fp32 twin of a storage test)
@@ -101,6 +156,32 @@ int r2dm_conv2d_ring(const float* x, const float* w, const float* bias, float* w
     }
     HIP_TRY(launch_conv(p, st));
     return 0;
+}
+
+int r2dm_conv2d_ring(const float* x, const float* w, const float* bias, float* w_packed, const float* aff,
+                     int32_t prologue, const float* residual, const float* scale, float* y, int32_t B, int32_t cin,
+                     int32_t cout, int32_t H, int32_t W, int32_t ksize, void* stream) {
+    return conv2d_ring_impl(x, w, bias, w_packed, aff, prologue, residual, scale, y, B, cin, cout, H, W, ksize, stream, ConvExtras{});
+}
+
+int32_t r2dm_conv_stat_slots(int32_t H, int32_t W) { return conv_stat_slots(H, W); }
+
+int r2dm_conv2d_ring_ex(const float* x, const float* x1, int32_t c1, const float* w, const float* bias, float* w_packed, const float* aff, int32_t prologue,
+                        const float* residual, int32_t res_broadcast, const float* scale, float* y, double* stat, int32_t stat_G, int32_t stat_goff,
+                        int32_t stat_cpg, int32_t* range, int32_t reverse, int32_t* chosen, int32_t B, int32_t cin, int32_t cout, int32_t H, int32_t W,
+                        int32_t ksize, void* stream) {
+    ConvExtras ex;
+    ex.x1 = x1;
+    ex.c1 = c1;
+    ex.res_broadcast = res_broadcast;
+    ex.stat = stat;
+    ex.stat_G = stat_G;
+    ex.stat_goff = stat_goff;
+    ex.stat_cpg = stat_cpg;
+    ex.range = range;
+    ex.reverse = reverse;
+    ex.chosen = chosen;
+    return conv2d_ring_impl(x, w, bias, w_packed, aff, prologue, residual, scale, y, B, cin, cout, H, W, ksize, stream, ex);
 }
 
 size_t r2dm_group_norm_scratch_bytes(int32_t B, int32_t groups) { return (size_t)B * groups * 256 * (2 * sizeof(double) + sizeof(float)); }

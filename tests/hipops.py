@@ -1,4 +1,6 @@
 """Test-side wrappers around the single-kernel C-ABI entry points of libr2dm_hip.so."""
+import ctypes
+
 import torch
 
 from r2dm_amd import _lib
@@ -30,6 +32,72 @@ def conv2d_ring(x, w, b, aff=None, prologue=0, residual=None, scale=None, io16=0
                                   _lib.ptr(residual), _lib.ptr(sc), y.data_ptr(), B, cin, cout, H, W, k, _st(x)))
     torch.cuda.synchronize()
     return y
+
+
+def guarded(shape, dtype, guard, device, fill=float("nan")):
+    """(whole, view): a `fill`-filled flat buffer and the contiguous view of `shape` in its middle, `guard` elements from either end."""
+    n = 1
+    for s in shape:
+        n *= s
+    whole = torch.full((guard + n + guard,), fill, device=device, dtype=dtype)
+    return whole, whole[guard:guard + n].view(*shape)
+
+
+def guard_intact(whole, guard):
+    """The two bands around a guarded() view still hold their NaN fill."""
+    return bool(torch.isnan(whole[:guard]).all() and torch.isnan(whole[-guard:]).all())
+
+
+class ConvExResult:
+    """y; stat (B, groups, slots, 2) float64 or None; range: the int32[2] record after the call (CPU) or None; chosen: (algo, co_tile, px_rows)."""
+
+    def __init__(self, y, stat, range_, chosen):
+        self.y, self.stat, self.range, self.chosen = y, stat, range_, chosen
+
+
+ALGO_F32, ALGO_BF16X3, ALGO_DIRECT, ALGO_F16X2, ALGO_P1F16 = range(5)  # ConvAlgo (csrc/common.h), as r2dm_conv2d_ring_ex reports it
+
+
+def conv2d_ring_ex(x, w, b, x1=None, aff=None, prologue=0, residual=None, res_broadcast=False, scale=None, stat_groups=0, stat_goff=0, stat_cpg=0,
+                   range_init=None, reverse=0, c1=None):
+    """r2dm_conv2d_ring_ex: x1 -- the last channels of the input in a second allocation (x holds the first ones; c1 overrides x1's channel
+    count, for the refusal tests); stat_groups > 0 -- a statistics sink of that many groups; range_init -- the two int32 the range record
+    starts from (None: no record).  y and the sink start NaN-filled inside NaN guard bands (one plane / 64 doubles) that must survive the
+    call; if the entry refuses, y and the sink must still hold nothing but the fill, and the error is raised on."""
+    L = _lib.lib()
+    B, c0, H, W = x.shape
+    dev = x.device
+    cout, k = w.shape[0], w.shape[-1]
+    w, b, x = _lib.f32c(w), _lib.f32c(b), _lib.f32c(x)
+    if x1 is not None:
+        x1 = _lib.f32c(x1)
+    cin = w.shape[1]
+    if c1 is None:
+        c1 = 0 if x1 is None else x1.shape[1]
+        assert c0 + c1 == cin
+    if residual is not None:
+        residual = _lib.f32c(residual)
+        assert residual.shape == ((cout, H, W) if res_broadcast else (B, cout, H, W))
+    packed = torch.empty(L.r2dm_conv_packed_elems(cout, cin, k, B, H, W), device=dev)
+    yg = (H * W + 63) // 64 * 64  # one plane, in whole 256-byte lines (the kernels store 16-byte vectors)
+    y_all, y = guarded((B, cout, H, W), torch.float32, yg, dev)
+    st_all = stat = None
+    if stat_groups:
+        st_all, stat = guarded((B, stat_groups, L.r2dm_conv_stat_slots(H, W), 2), torch.float64, 64, dev)
+    rng = None if range_init is None else torch.tensor(list(range_init), device=dev, dtype=torch.int32)
+    sc = None if scale is None else torch.tensor([scale], device=dev, dtype=torch.float32)
+    chosen = (ctypes.c_int32 * 3)(-1, -1, -1)
+    rc = L.r2dm_conv2d_ring_ex(x.data_ptr(), _lib.ptr(x1), c1, w.data_ptr(), b.data_ptr(), packed.data_ptr(), _lib.ptr(aff), prologue, _lib.ptr(residual),
+                               int(res_broadcast), _lib.ptr(sc), y.data_ptr(), _lib.ptr(stat), stat_groups, stat_goff, stat_cpg, _lib.ptr(rng), reverse,
+                               ctypes.addressof(chosen), B, cin, cout, H, W, k, _st(x))
+    torch.cuda.synchronize()
+    if rc != 0:
+        assert torch.isnan(y_all).all() and (st_all is None or torch.isnan(st_all).all()), "a refused launch wrote to y or to the sink"
+        assert rng is None or rng.tolist() == list(range_init), "a refused launch wrote to the range record"
+        _lib.check(rc)
+    assert guard_intact(y_all, yg), "write outside y"
+    assert st_all is None or guard_intact(st_all, 64), "write outside the statistics sink"
+    return ConvExResult(y, stat, None if rng is None else rng.cpu(), tuple(chosen))
 
 
 def group_norm_affine(x, groups, eps, gamma=None, beta=None, ada=None):

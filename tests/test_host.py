@@ -570,3 +570,15 @@ def test_out_conv_keeps_its_loads_in_flight(tmp_path):
                 found = int(re.search(r"\.vgpr_count:\s+(\d+)", rec).group(1))
     assert found is not None, "conv_direct_rows_kernel<2, false> not found in the library's code objects"
     assert found >= 100, f"out_conv allocates {found} registers: its loads are no longer four channels deep"
+
+
+def test_conv_statistics_slot_count_and_extended_entry_null_argument():
+    """r2dm_conv_stat_slots (what a caller sizes the fused-statistics sink of r2dm_conv2d_ring_ex with): 4-row x 64-pixel tiles x 4 rows x 2
+    halves, for the geometries of tests/test_hip_conv_engine_paths.py; and the extended entry checks its pointers before it touches a GPU."""
+    from r2dm_amd import _lib
+
+    L = _lib.lib()
+    for h, w in ((4, 64), (8, 128), (8, 64), (12, 128), (32, 256), (6, 96), (64, 256), (64, 1024)):
+        assert L.r2dm_conv_stat_slots(h, w) == ((h + 3) // 4) * ((w + 63) // 64) * 8, (h, w)
+    rc = L.r2dm_conv2d_ring_ex(None, None, 0, None, None, None, None, 0, None, 0, None, None, None, 0, 0, 0, None, 0, None, 2, 64, 64, 8, 64, 3, None)
+    assert rc == 1 and b"null argument" in L.r2dm_last_error()
