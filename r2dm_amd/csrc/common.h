@@ -145,7 +145,6 @@ struct ConvParams {
     // fp16 STORAGE of activations (conv_f16x2.hip, the one-plane mode: round 5): x16 -- the input tensor(s) hold fp16; y16 -- the output and
     // the residual do.  Pointers stay typed float*, batch strides stay in ELEMENTS.
     int x16 = 0, y16 = 0;
-    int stagger = 0;  // experiment (R2DM_F2_STAGGER, conv_f16x2.hip): every other block of an XCD starts so many clock ticks late -- de-phases the blocks' tile ends
     unsigned long long* prof = nullptr;  // optional [nblk][4] s_memtime stamps (perf probe; nullptr in production)
 };
 int conv_pick_algo(int Cin, int Cout, int taps);  // env R2DM_CONV_ALGO=f32 forces ALGO_F32 everywhere

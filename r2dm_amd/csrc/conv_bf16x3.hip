@@ -302,13 +302,9 @@ __global__ __launch_bounds__(256, 1) void conv_bf16x3_stream_kernel(const ConvPa
         if (tx == 1) {
             // B_sigma: everybody is past tap (sigma, 0).  Before it: this wave's pieces of stage sigma+1 have landed
             // (only stage sigma+2's PPW may still be in flight) and its x-tile writes are done.
-#ifndef X3S_NO_BARRIER  // (X3S_NO_*: ablation switches for scripts/build_variant.sh -- timing experiments, wrong results)
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW) : "memory");
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
-#else
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
             asm volatile("" ::: "memory");
             if (ky == 0) {
                 // hipcc waits for the raw pixels (its own loads) at their first use with a vmcnt that knows nothing
@@ -362,14 +358,11 @@ __global__ __launch_bounds__(256, 1) void conv_bf16x3_stream_kernel(const ConvPa
                 if (i == 10) fr(ic<10>{});
                 if (i == 11) fr(ic<11>{});
             }
-#ifndef X3S_NO_DMA
             if (tx == 1) {  // PPW pieces spread over the tap, into the ring slot of stage sigma-1
 #pragma unroll
                 for (int kp = 0; kp < PPW; ++kp)
                     if (i == (kp * UNITS) / PPW) dma_piece(sdma, kp);
             }
-#endif
-#ifndef X3S_NO_XF
             if (t >= 1 && t <= 6) {  // transform of chunk c+1: 144 slots; stream X pairs 0..7, stream Y pairs 8..15,
 #pragma unroll
                 for (int sub = 0; sub < XSL; ++sub) {
@@ -383,7 +376,6 @@ __global__ __launch_bounds__(256, 1) void conv_bf16x3_stream_kernel(const ConvPa
                     }
                 }
             }
-#endif
             if (t == 7) {  // raw pixels of the chunk after next: 12 loads over the last units of the tap
 #pragma unroll
                 for (int jl = 0; jl < LPU; ++jl) {
@@ -398,7 +390,6 @@ __global__ __launch_bounds__(256, 1) void conv_bf16x3_stream_kernel(const ConvPa
         tap(c, ic<0>{}, PAR); tap(c, ic<1>{}, PAR); tap(c, ic<2>{}, PAR);
         tap(c, ic<3>{}, PAR); tap(c, ic<4>{}, PAR); tap(c, ic<5>{}, PAR);
         tap(c, ic<6>{}, PAR); tap(c, ic<7>{}, PAR); tap(c, ic<8>{}, PAR);
-#ifndef X3S_NO_FLIP
         if ((c & bmask) == bmask) {  // flush (acc restarts from C = 0 in the next chunk: no zeroing pass)
             if (c & (bmask + 1)) {
 #pragma unroll
@@ -416,7 +407,6 @@ __global__ __launch_bounds__(256, 1) void conv_bf16x3_stream_kernel(const ConvPa
                         for (int r = 0; r < 16; ++r) acc2[m][n][r] += acc[m][n][r];
             }
         }
-#endif
 #pragma unroll
         for (int n = 0; n < NR; ++n) {
             const unsigned tswap = xcur[n];
@@ -439,11 +429,7 @@ __global__ __launch_bounds__(256, 1) void conv_bf16x3_stream_kernel(const ConvPa
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.f;  // everything was flushed (Cin % 64 == 0)
     // whole tiles (every shape of the network): the wide epilogue through this wave's 1 KiB patch behind the weight ring
-#ifndef R2DM_NO_WIDE_EPILOGUE
     if (H % TH == 0 && W % TW == 0)
-#else
-    if (false)
-#endif
         conv_epilogue_wide<TH, TW, MR, NR, true>(p, acc, acc2, b, th, tw, nTw, cot * CO_T, wave, lane,
                                                  reinterpret_cast<float*>(smem + WB0 + RING * WBYTES) + wave * 256);
     else
@@ -787,9 +773,7 @@ __global__ __launch_bounds__(256, 2) void conv_bf16x3_pair_kernel(const ConvPara
             // chunk boundary: the single x tile is rewritten while the other block of this CU owns the matrix pipe
             __builtin_amdgcn_s_barrier();  // every wave has its last fragments of this chunk in registers
             asm volatile("" ::: "memory");
-#ifndef X3P_NO_XF
             transform_all();
-#endif
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
@@ -808,11 +792,7 @@ __global__ __launch_bounds__(256, 2) void conv_bf16x3_pair_kernel(const ConvPara
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // surplus DMA pieces / prefetched fragments must not outlive the block
     if (p.prof) t2 = __builtin_amdgcn_s_memtime();
 
-#ifndef R2DM_NO_WIDE_EPILOGUE
     if (H % TH == 0 && W % TW == 0)  // whole tiles: wide epilogue, this wave's 1 KiB patch behind the weight ring
-#else
-    if (false)
-#endif
         conv_epilogue_wide<TH, TW, MR, NR, false>(p, acc, accd, b, th, tw, nTw, cot * CO_T, wave, lane,
                                                   reinterpret_cast<float*>(smem + WB1 + RING2 * WBYTES) + wave * 256);
     else

@@ -31,9 +31,7 @@ constexpr int TH = 4, TW = 64, XR = TH + 2, XS = TW + 2, CK = 8, MAXCO = 4;
 // Round 5, tried and reverted: channel batches of 4 double-buffered by hand (inline-assembly loads, counted vmcnt, one batch of 48 loads
 // always in flight; 416 registers, one wave per SIMD as before): 52.5 -> 65.7 us at batch 8 (scripts/jobs/j340.sh) -- three 1 KiB-span
 // load instructions per (channel, row) keep the CU's address pipeline busy either way; more in flight only queues there.
-#ifndef DC_ROWS
-#define DC_ROWS 2
-#endif
+constexpr int DC_ROWS = 2;
 template <int CO, bool X16 = false>  // X16 (round 6): the input tensor is stored as fp16 (the one-plane mode's activation storage)
 __global__ __launch_bounds__(256) void conv_direct_rows_kernel(const ConvParams p) {
     using gcf = const float __attribute__((address_space(1)))*;
@@ -71,9 +69,7 @@ __global__ __launch_bounds__(256) void conv_direct_rows_kernel(const ConvParams 
     const float* xb1 = !p.x.p1 ? xb0 : X16 ? reinterpret_cast<const float*>(reinterpret_cast<const unsigned short*>(p.x.p1) + b * p.x.bs1) : p.x.p1 + b * p.x.bs1;
     const int c0 = p.x.p1 ? p.x.c0 : p.Cin;
     const gcf wg = (gcf)p.w;
-#ifndef DC_UNROLL
-#define DC_UNROLL 4  // (one wave per SIMD: the loads in flight hide the latency -- 2: 65.6 us, 4: 52.8 us, 8: 64.0 us at batch 8)
-#endif
+    constexpr int DC_UNROLL = 4;  // (one wave per SIMD: the loads in flight hide the latency -- 2: 65.6 us, 4: 52.8 us, 8: 64.0 us at batch 8)
     if constexpr (X16) {
         // fp16 input (the one-plane mode's out_conv), a loop of its own since round 6: through the shared body below the compiler converted every row behind a full wait --
         // ~8 serial round trips per channel, 133 us per launch at batch 8 for HALF the bytes of the fp32 launch (52 us); read in the ISA, profiles/r06_tile_end_diet.txt.
@@ -82,10 +78,7 @@ __global__ __launch_bounds__(256) void conv_direct_rows_kernel(const ConvParams 
         using gch = const unsigned short __attribute__((address_space(1)))*;
         const unsigned short* h0 = reinterpret_cast<const unsigned short*>(xb0);
         const unsigned short* h1 = reinterpret_cast<const unsigned short*>(xb1);
-#ifndef DC16_BATCH
-#define DC16_BATCH 2  // (channels per load batch at batch 8: 1: 53.0 us, 2: 52.3 us, 4: 70.8 us, 8: 68.4 us -- more registers, fewer waves; scripts/jobs/j446.sh)
-#endif
-        constexpr int NB = DC16_BATCH;
+        constexpr int NB = 2;  // (channels per load batch at batch 8: 1: 53.0 us, 2: 52.3 us, 4: 70.8 us, 8: 68.4 us -- more registers, fewer waves; scripts/jobs/j446.sh)
         for (int cb = 0; cb < p.Cin; cb += NB) {  // (Cin % 2 == 0: launcher)
             unsigned long long rv[NB][R + 2];
             unsigned short rl[NB][R + 2], rr[NB][R + 2];

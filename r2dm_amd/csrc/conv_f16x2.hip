@@ -120,17 +120,12 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(const ConvParams p, 
     constexpr int COT = GEO::COT, WSTAGE = GEO::WSTAGE, RING = GEO::RING, WB0 = GEO::WB0, PATCH0 = GEO::PATCH0, RESQ = GEO::RESQ,
                   RES0 = GEO::RES0, ADTAB0 = GEO::ADTAB0, BIAS0 = GEO::BIAS0;
     constexpr bool ONEACC = GEO::ONEACC;
-    // Round 5, the tile end of the one-accumulator tiles (-DF2_EPI_V1: round 4's, for A/B): biases wait in an LDS table the stagers fill
+    // Round 5, the tile end of the one-accumulator tiles: biases wait in an LDS table the stagers fill
     // three chunks ahead (requested at the tile's end they cost its first quarter ~1.9 k cycles), the residual of the first two quarters is
     // prefetched by LDS-DMA during the tile's last chunk (no registers: requested at the tile's end the first quarters waited for HBM, 10 k
     // cycles per tile of the eight-row tile), and all eight quarters are finished at the tile's end (no row block waits in LDS: the
     // multipliers bound a chunk of these tiles, a deferred quarter costs what it takes wherever it runs).
-#ifdef F2_EPI_V1
-    constexpr bool EPI2 = false;
-#else
-    constexpr bool EPI2 = ONEACC;
-#endif
-    // Round 6, the tile end of the one-accumulator tiles SHARED between the two wave groups (-DF2_NO_EPI3: round 5's, for A/B).  In-kernel timelines
+    // Round 6, the tile end of the one-accumulator tiles SHARED between the two wave groups.  In-kernel timelines
     // (profiles/r06_level1_timeline.txt): a tile end is 7 k cycles of the four multiplying waves' own instruction stream (8 quarters x ~0.85 k: turn, bias /
     // residual / scale, store, statistics) -- 11-14 k with a residual, whose loads a wave can only keep four quarters of in flight -- while the four staging
     // waves, a tile ahead, sleep at their next barrier (16 k cycles per tile end in the level-1 residual launches).  Now a multiplying wave turns its last
@@ -138,11 +133,7 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(const ConvParams p, 
     // residual loads, stores, statistics -- while the multiplier finishes the first NQ - NSQ; a second barrier ends the tile.  LDS: the wave's two waiting
     // slots (their DMA-prefetched residual is in registers by then) and, for the eight-row tile's third and fourth quarter, x buffer 1, which is dead from
     // the tile's last barrier until the stagers' next transform -- behind the second barrier; the multipliers' 1 KiB turn patches move there too.
-#ifdef F2_NO_EPI3
-    constexpr bool EPI3 = false;
-#else
-    constexpr bool EPI3 = EPI2 && IOM == 0 && PRO != PRO_PRESPLIT;
-#endif
+    constexpr bool EPI3 = ONEACC && IOM == 0 && PRO != PRO_PRESPLIT;
     constexpr int NSQ = !EPI3 ? 0 : NR == 4 ? 4 : 2;  // quarters (the last ones: whole statistics pairs) the staging partner finishes
     constexpr int XDUMP = NSQ > 2 ? NSQ - 2 : 0;      // ... of which so many wait in x buffer 1: [4 x 1 KiB patches][4 waves x XDUMP x 4 KiB]
     static_assert(4096 + 4 * XDUMP * 4096 <= XBYTES, "tile-end scratch inside x buffer 1");
@@ -169,10 +160,8 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(const ConvParams p, 
     // per CU either way) and the launcher pads the LDS request to >= 156 KiB, so no wave of any other kernel or process is ever resident on
     // the same CU.  Why: next to ANOTHER PROCESS's waves on its CU the one-plane 32-channel tile (181 registers) ended 12-17 of 20 runs of
     // 600 forwards in a GPU memory fault at a wild address (never a wrong result); with the CU to itself 0 of 70, all modes
-    // (profiles/r05_coresidency.txt: what was ruled out, and that the cause is NOT identified).  -DF2_SHARE_CU: the allocation hipcc computes.
-#ifndef F2_SHARE_CU
+    // (profiles/r05_coresidency.txt: what was ruled out, and that the cause is NOT identified).
     asm volatile("" ::: "v255");
-#endif
     const int tid = threadIdx.x;
     const int lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
     const int wave8 = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -188,10 +177,6 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(const ConvParams p, 
     const int nIt = (total_tiles - (int)blockIdx.x + G - 1) / G;  // tiles of this block (grid <= total_tiles)
     const int Q = nIt * nchunks;
     const int c0 = p.x.c0;
-    if (p.stagger > 0 && nIt >= 3 && ((blockIdx.x >> 3) & 1)) {  // (experiment: half of the blocks out of phase with the other half)
-        const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-        while (__builtin_amdgcn_s_memtime() - t0 < (unsigned long long)p.stagger) __builtin_amdgcn_s_sleep(32);
-    }
 
     // tile `it` of this block -> output channel tile, sample, tile row / column (all wave-uniform: scalar ALU, F2Div)
     auto udiv = [&](unsigned x, int d, unsigned m) __attribute__((always_inline)) { return d == 1 ? x : __umulhi(x, m); };
@@ -256,9 +241,6 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(const ConvParams p, 
                 d_s = 0;
                 set_dma_item(++d_item);
             }
-#ifdef F2_NO_DMA  // timing ablation (wrong results)
-            if (slot >= 0) return;
-#endif
             // one M0 set-up per group of pieces, the instruction offset advances the global and the LDS address together
             if constexpr (PPW == 3) {  // pieces 3w, 3w+1, 3w+2 (64-channel tiles: the whole stage; 128-channel tiles, one plane: the h plane)
                 const unsigned char* s3 = src + wv * (PPW * 1024);
@@ -479,15 +461,6 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(const ConvParams p, 
             asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(d) : "v"(voff), "s"(base) : "memory");
         };
         auto gload_px = [&](RAW& d, const unsigned char* base, unsigned voff) __attribute__((always_inline)) {
-#ifdef F2_NO_PXLOAD  // fault bisection (wrong results): no pixel load is issued
-            asm volatile("" : "=v"(d) : "v"(voff), "s"(base));
-            return;
-#endif
-#ifdef F2_NT_XLOAD  // experiment (round 5): the input pixels as streaming loads
-            if constexpr (X16) asm volatile("global_load_dwordx2 %0, %1, %2 nt" : "=v"(d) : "v"(voff), "s"(base) : "memory");
-            else asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "=v"(d) : "v"(voff), "s"(base) : "memory");
-            return;
-#endif
             if constexpr (X16) asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(d) : "v"(voff), "s"(base) : "memory");
             else asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(d) : "v"(voff), "s"(base) : "memory");
         };
@@ -544,7 +517,7 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(const ConvParams p, 
             asm volatile("" : "+v"(tab_v));
             if (tab_lane) *reinterpret_cast<f32x4*>(smem + ADTAB0 + t4 * 16) = tab_v;
         };
-        // ---- the tile's biases (EPI2): fetched while its chunk 1 is staged (three or more chunks before the multipliers want them), one float
+        // ---- the tile's biases (one-accumulator tiles): fetched while its chunk 1 is staged (three or more chunks before the multipliers want them), one float
         // per thread, into the slot of the tile's parity -- read last at the end of the tile two back
         float bias_v = 0.f;
         auto bias_fetch = [&]() __attribute__((always_inline)) {  // one VMEM operation, counted by hand like the others
@@ -608,9 +581,6 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(const ConvParams p, 
                     qv1 = r.ok[u] ? qv1 : 0.f;
                 }
             } else if (sl == 7) {
-#ifdef F2_NO_XF  // timing ablation (wrong results)
-                xpk[eo][0][i2] = xpk[eo][NPLK - 1][i2] = __float_as_uint(qv0);
-#else
                 if constexpr (NPLK == 2) {
                     if constexpr (LSCALED) split_f16x2(qv0, qv1, xpk[eo][0][i2], xpk[eo][1][i2]);
                     else split_f16x2_true(qv0, qv1, xpk[eo][0][i2], xpk[eo][1][i2]);
@@ -618,7 +588,6 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(const ConvParams p, 
                     using f32x2 = __attribute__((ext_vector_type(2))) float;
                     xpk[eo][0][i2] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{qv0, qv1}, f16x2));  // v_cvt_pk_f16_f32 (RNE)
                 }
-#endif
             }
         };
         // pixels 2*half, 2*half+1 of the quads of units 0 .. NUR - 1 into x buffer `buf`
@@ -631,9 +600,6 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(const ConvParams p, 
                 // SIMD with a multiplier and cannot afford to wait for its own results (exp2 / rcp are quarter rate)
 #pragma unroll
                 for (int sl = 0; sl < 8; ++sl) {
-#ifdef F2_NO_XF
-                    if (sl != 0 && sl != 7) continue;
-#endif
 #pragma unroll
                     for (int eo = 0; eo < 2; ++eo)
 #pragma unroll
@@ -956,7 +922,7 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(const ConvParams p, 
                 unsigned char* nbuf = smem + ((q + 1) & 1) * XBYTES;  // x buffer of chunk q+1 (read by nobody during chunk q)
                 const bool tile_ends = x_c == 0;  // this iteration stages the NEXT tile's chunk 0: the multipliers are in their tile's last chunk
                 const bool fetch = x_c == nchunks - 2, last_of_tile = x_c == nchunks - 1;
-                const bool bias_now = EPI2 && x_c == 1;  // (nchunks >= 4: never the iteration of the table fetch or store)
+                const bool bias_now = ONEACC && x_c == 1;  // (nchunks >= 4: never the iteration of the table fetch or store)
                 if (fetch && !fold) table_fetch(t_item + 1);  // (one more operation in the queue: the counted waits below only get stricter)
                 if (bias_now) bias_fetch();          // (likewise)
                 dma_stage(3 * q, ic<RING - 1>{});    // D0
@@ -1052,18 +1018,7 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(const ConvParams p, 
             asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(xb[NXB == 1 ? 0 : n]), "i"(pl * (XPL * 16) + ky * (XS * 16) + tx * 16 + seg));
         }
     };
-    // all fragments of a tap (0, 0) at once, in the order the taps read them: plane 0 (into h buffer NB), then plane 1
-    auto frag_all = [&](const unsigned (&xb)[NXB], unsigned wb, auto NB) __attribute__((always_inline)) {
-        auto f = [&](auto PL, auto WW) __attribute__((always_inline)) { frag_rd(xb, wb, ic<0>{}, ic<0>{}, PL, WW, NB); };
-        f(ic<0>{}, ic<0>{}); f(ic<0>{}, ic<1>{}); f(ic<0>{}, ic<2>{});
-        if constexpr (NOPS >= 4) f(ic<0>{}, ic<3>{});
-        if constexpr (NOPS == 6) { f(ic<0>{}, ic<4>{}); f(ic<0>{}, ic<5>{}); }
-        if constexpr (NPLK == 2) {
-            f(ic<1>{}, ic<0>{}); f(ic<1>{}, ic<1>{}); f(ic<1>{}, ic<2>{});
-            if constexpr (NOPS >= 4) f(ic<1>{}, ic<3>{});
-            if constexpr (NOPS == 6) { f(ic<1>{}, ic<4>{}); f(ic<1>{}, ic<5>{}); }
-        }
-    };
+    // all fragments of tap (0, 0) of x buffer 0 at once, in the order the taps read them: plane 0 (into h buffer 0), then plane 1
     auto frag_first = [&](unsigned wb) __attribute__((always_inline)) {
         auto f = [&](auto PL, auto WW) __attribute__((always_inline)) { frag_rd(xb0, wb, ic<0>{}, ic<0>{}, PL, WW, ic<0>{}); };
         f(ic<0>{}, ic<0>{}); f(ic<0>{}, ic<1>{}); f(ic<0>{}, ic<2>{});
@@ -1118,10 +1073,6 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(const ConvParams p, 
             const u32x4& ub = qq == 1 ? fb1[n] : fb0[cur][n];
             // (unit order: xh(B) wl(A) | xl(B) wh(A) | xh wh -- the A/B roles of "x" and "w" are spelled out in the reads above)
             const f16x8 fra = __builtin_bit_cast(f16x8, ua), frb = __builtin_bit_cast(f16x8, ub);
-#ifdef F2_NO_MFMA  // timing ablation (wrong results): how fast are the stagers without a multiplier on their SIMD?
-            if (i == 0) asm volatile("" :: "v"(fra), "v"(frb), "v"(ac));
-            else
-#endif
             if (t == 0 && c == 0 && (ACC2 ? (qq == 0 || qq == 2) : i < MR * NR)) {  // first product into each accumulator of a tile: start from zero
                 const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
                 ac = __builtin_amdgcn_mfma_f32_32x32x16_f16(fra, frb, zero, 0, 0, 0);
@@ -1227,11 +1178,7 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(const ConvParams p, 
         const gcrv ru = (gcrv)(reinterpret_cast<const unsigned char*>(p.res) + ((long)b * p.res_bs + (long)(cot * COT) * HW) * YE);
 #pragma unroll
         for (int k8 = 0; k8 < 4; ++k8) {
-#ifdef F2_NT_RES  // experiment (round 5): the residual is read once
-            rv[k8] = __builtin_nontemporal_load(ru + (long)(m * 32 + k8 * 8) * (HW >> 2) + off);
-#else
             rv[k8] = (ru + (long)(m * 32 + k8 * 8) * (HW >> 2))[off];
-#endif
         }
     };
     auto res_request = [&](auto QD, int b, int th, int tw, int cot, int ln) __attribute__((always_inline)) { res_request_to(rv_e, QD, b, th, tw, cot, ln); };
@@ -1270,9 +1217,6 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(const ConvParams p, 
             f32x4 v = t[k8] * wsc + bias_e[m * 4 + k8];
             v = rv_f32(rv[k8]) + v;  // (without a residual the buffers stay zero -- res_request_to returns before it writes them: no select per element)
             v *= sc_blk;             // (1.0f without p.scale: exact)
-#ifdef F2_NO_STORE  // fault bisection (wrong results): nothing is stored
-            if (ln >= 0) { ps[k8] = v[0]; pq[k8] = v[1]; continue; }
-#endif
             if constexpr (Y16) {     // stored as fp16 (RNE); the statistics and the range maximum are those of the stored values
                 using f32x2 = __attribute__((ext_vector_type(2))) float;
                 const RV pk = (RV)__builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{v[0], v[1]}, f16x2)) |
@@ -1280,11 +1224,7 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(const ConvParams p, 
                 (yu + (long)(m * 32 + k8 * 8) * (HW >> 2))[off] = pk;
                 v = rv_f32(pk);
             } else {
-#ifdef F2_NT_STORE  // experiment (round 5): the output as a streaming store -- it is not read again before the launch ends
-                __builtin_nontemporal_store(v, yu + (long)(m * 32 + k8 * 8) * (HW >> 2) + off);
-#else
                 (yu + (long)(m * 32 + k8 * 8) * (HW >> 2))[off] = v;
-#endif
             }
 #ifdef F2_RANGE_ELEMENTWISE
             if (p.range) amax_e = fmaxf(fmaxf(amax_e, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
@@ -1303,9 +1243,6 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(const ConvParams p, 
     auto half_stats = [&](auto M, const float (&s0)[4], const float (&q0)[4], const float (&s1)[4], const float (&q1)[4], int b, int th,
                           int tw, int cot, int ln) __attribute__((always_inline)) {
         if (!p.stat) return;
-#ifdef F2_NO_STORE
-        if (ln >= 0) return;
-#endif
 #ifndef F2_STATS_F64
         float st_s[4], st_q[4];
 #pragma unroll
@@ -1375,7 +1312,7 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(const ConvParams p, 
                 }
                 // (the eight-row tile cannot hold 16 residual registers through a chunk -- as loads here they were spilled one by one behind
                 // vmcnt(0): its first quarter's residual is requested at the tile's end, in front of the biases that quarter waits for anyway)
-                if constexpr (EPI2) {
+                if constexpr (ONEACC) {
                     // the residual of quarters 0 and 1 by LDS-DMA into the wave's two waiting slots (4 KiB each: block k8 at 1 KiB k8, lane L's
                     // four pixels at 16 L -- the turned layout, read back with one ds_read_b128 per block); no register is written
                     if constexpr (!Y16) {
@@ -1384,14 +1321,14 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(const ConvParams p, 
                             res_dma(ic<1>{}, e_b, e_th, e_tw, e_cot, ln);
                         }
                     }
-                } else if constexpr (NR != 4) res_request(ic<0>{}, e_b, e_th, e_tw, e_cot, ln);
+                } else res_request(ic<0>{}, e_b, e_th, e_tw, e_cot, ln);
             }
         }
         tap(q, ic<0>{}, PAR); tap(q, ic<1>{}, PAR); tap(q, ic<2>{}, PAR);
         tap(q, ic<3>{}, PAR); tap(q, ic<4>{}, PAR); tap(q, ic<5>{}, PAR);
         tap(q, ic<6>{}, PAR); tap(q, ic<7>{}, PAR); tap(q, ic<8>{}, PAR);
         ++e_c;
-        if constexpr (EPI2) {
+        if constexpr (ONEACC) {
             // ---- one-accumulator tiles, round 5: eight quarters (m, n) per wave, numbered qd = m NR + n, in pairs (2 M, 2 M + 1) that share a
             // statistics slot, ALL finished at the tile's end.  Biases: LDS table (stagers).  Residual: quarters 0 and 1 from the wave's two
             // waiting slots (LDS-DMA, requested a chunk ago), quarters 2 .. 7 through four register buffers -- 2, 3 requested here (they have
@@ -1527,144 +1464,7 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(const ConvParams p, 
                     frag_first(lds_w0);  // (stage 3 (q + 1): ring slot 0)
                 }
             }
-        } else if constexpr (ONEACC) {
-            // ---- 128-channel tile and eight-row tile (round 4's tile end, -DF2_EPI_V1): ONE accumulator per MFMA tile, eight quarters (m, n) per wave, numbered qd = m NR + n, in pairs
-            // (2 M, 2 M + 1) that share a statistics slot (128 channels: row block M, both 32-pixel segments of the wave's row; eight rows: row
-            // block M / 2, the wave's row M % 2).  Six are finished at the tile's end, the
-            // last row block's two (6, 7) wait, turned, in 32 KiB of LDS and are finished behind the next tile's first two chunks (the
-            // multipliers bound a chunk of this tile -- 24 MFMAs per tap -- so a deferred quarter costs what it takes; at the tile's end all
-            // four stagers and the matrix pipe wait).  Biases are requested at the tile's end, one row block ahead (the loop has no
-            // registers for sixteen of them: as 16 loads in the last chunk they were spilled one by one behind vmcnt(0) -- 4.5 k cycles);
-            // the residual of quarters 1 .. 3 (HBM: ~2 k cycles) is requested up front and a quarter's buffer takes the quarter four
-            // further on as soon as it is free -- with one quarter of lead every quarter waited for its residual (17.7 k cycles per tile end).
-            // the waiting row block (quarters 6, 7): both behind the next tile's FIRST chunk -- quarter 6's residual was requested at the
-            // tile's end, quarter 7's is requested here and has quarter 6's ~1.5 k cycles to arrive; nothing but that residual and four
-            // biases stays alive through a chunk (a statistics carry between two slices was spilled and re-read behind vmcnt(0))
-            auto slice_w = [&](const RV (&rv6)[4], RV (&rv7)[4], auto REQ) __attribute__((always_inline)) {
-                const int ln = fresh_lane();
-                if constexpr (decltype(REQ)::value) res_request_to(rv7, ic<7>{}, pe_b, pe_th, pe_tw, pe_cot, ln);
-                float ps0[4], pq0[4], ps1[4], pq1[4];
-                {
-                    f32x4 t[4];
-#pragma unroll
-                    for (int k8 = 0; k8 < 4; ++k8) t[k8] = *reinterpret_cast<const f32x4*>(dump + k8 * 256 + (ln >> 3) * 32 + (ln & 7) * 4);
-                    quarter(ic<6>{}, t, rv6, pe_b, pe_th, pe_tw, pe_cot, ln, ps0, pq0);
-                }
-                {
-                    f32x4 t[4];
-#pragma unroll
-                    for (int k8 = 0; k8 < 4; ++k8) t[k8] = *reinterpret_cast<const f32x4*>(dump + 1024 + k8 * 256 + (ln >> 3) * 32 + (ln & 7) * 4);
-                    quarter(ic<7>{}, t, rv7, pe_b, pe_th, pe_tw, pe_cot, ln, ps1, pq1);
-                }
-                half_stats(ic<3>{}, ps0, pq0, ps1, pq1, pe_b, pe_th, pe_tw, pe_cot, ln);
-                range_flush(ln);
-                pending = false;
-            };
-            // The eight-row tile finishes all eight quarters at the tile's end: with a residual held for a waiting row block through the next
-            // tile's first chunk it spilled twelve of those registers, each behind vmcnt(0); the multipliers bound a chunk of these tiles, so
-            // a deferred quarter costs what it takes wherever it runs.
-            constexpr bool DEFER_ROWBLOCK = NR != 4;
-            if constexpr (decltype(PAR)::value == 0) {
-                if (DEFER_ROWBLOCK && pending && e_c == 1) {
-                    // the next chunk's first fragments (72 registers, prefetched by tap 8) are dropped for the slice and read again behind
-                    // it: with them alive the slice spilled fragments around itself
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    if constexpr (MR == 4) {
-                        asm volatile("" : "=v"(fa0[1][0]), "=v"(fa0[1][1]), "=v"(fa0[1][2]), "=v"(fa0[1][3]), "=v"(fb0[1][0]), "=v"(fb0[1][1]));
-                        asm volatile("" : "=v"(fa1[0]), "=v"(fa1[1]), "=v"(fa1[2]), "=v"(fa1[3]), "=v"(fb1[0]), "=v"(fb1[1]));
-                    } else {
-                        asm volatile("" : "=v"(fa0[1][0]), "=v"(fa0[1][1]), "=v"(fb0[1][0]), "=v"(fb0[1][1]), "=v"(fb0[1][2]), "=v"(fb0[1][3]));
-                        asm volatile("" : "=v"(fa1[0]), "=v"(fa1[1]), "=v"(fb1[0]), "=v"(fb1[1]), "=v"(fb1[2]), "=v"(fb1[3]));
-                    }
-                    RV rv7[4] = {};
-                    slice_w(rv_e, rv7, ic<1>{});
-                    frag_all(xb1, lds_w0, ic<1>{});  // (chunk q + 1: x buffer 1, stage 3 (q + 1) in ring slot 0, h buffer 1)
-                }
-            } else {
-                if (e_c == nchunks) {
-                    e_c = 0;
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // no fragment read may land in a register the epilogue reuses
-                    stamp(7);
-                    const int ln = fresh_lane();
-                    const int l31e = ln & 31, hie = ln >> 5;
-                    const bool last_tile = !DEFER_ROWBLOCK || e_item + 1 == nIt;
-                    auto bias_request = [&](auto M) __attribute__((always_inline)) {
-                        constexpr int m = decltype(M)::value;
-#pragma unroll
-                        for (int k8 = 0; k8 < 4; ++k8) bias_e[m * 4 + k8] = ((gcf)p.bias)[e_cot * COT + m * 32 + k8 * 8 + (ln >> 3)];
-                    };
-                    // (eight-row tile: nothing of the epilogue lives through the MFMA loop -- its first residual buffer is local to the tile's end;
-                    // rv_e, which must keep its zeros for launches without a residual, costs the other tiles 16 registers all along)
-                    RV rv0l[4] = {};
-                    auto& rvA = [&]() -> RV (&)[4] { if constexpr (NR == 4) return rv0l; else return rv_e; }();
-                    if constexpr (NR == 4) res_request_to(rvA, ic<0>{}, e_b, e_th, e_tw, e_cot, ln);
-                    bias_request(ic<0>{});
-                    bias_request(ic<1>{});  // (the eight-row tile has two row blocks: all of its biases)
-                    RV rv1[4] = {}, rv2[4] = {}, rv3[4] = {};
-                    res_request_to(rv1, ic<1>{}, e_b, e_th, e_tw, e_cot, ln);
-                    res_request_to(rv2, ic<2>{}, e_b, e_th, e_tw, e_cot, ln);
-                    // (eight-row tile: the fourth buffer is requested behind quarter 0, whose accumulator registers it takes -- requested here it
-                    // was spilled behind vmcnt(0))
-                    if constexpr (NR != 4) res_request_to(rv3, ic<3>{}, e_b, e_th, e_tw, e_cot, ln);
-                    auto do_q = [&](auto QD, RV (&rv)[4], float (&ps)[4], float (&pq)[4]) __attribute__((always_inline)) {
-                        constexpr int qd = decltype(QD)::value, m = qd / NR, n = qd % NR;
-                        f32x4 t[4];
-#pragma unroll
-                        for (int k8 = 0; k8 < 4; ++k8) {
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) patch[(j + 4 * hie) * 32 + l31e] = acc[m][n][4 * k8 + j];
-                            t[k8] = *reinterpret_cast<const f32x4*>(patch + (ln >> 3) * 32 + (ln & 7) * 4);
-                        }
-                        quarter(QD, t, rv, e_b, e_th, e_tw, e_cot, ln, ps, pq);
-                    };
-                    float ps0[4], pq0[4], ps1[4], pq1[4];
-                    stamp(20);
-                    do_q(ic<0>{}, rvA, ps0, pq0);
-                    stamp(21);
-                    if constexpr (NR == 4) res_request_to(rv3, ic<3>{}, e_b, e_th, e_tw, e_cot, ln);
-                    res_request_to(rvA, ic<4>{}, e_b, e_th, e_tw, e_cot, ln);
-                    do_q(ic<1>{}, rv1, ps1, pq1);
-                    stamp(22);
-                    res_request_to(rv1, ic<5>{}, e_b, e_th, e_tw, e_cot, ln);
-                    half_stats(ic<0>{}, ps0, pq0, ps1, pq1, e_b, e_th, e_tw, e_cot, ln);
-                    stamp(23);
-                    if constexpr (MR == 4) bias_request(ic<2>{});
-                    do_q(ic<2>{}, rv2, ps0, pq0);
-                    stamp(24);
-                    if (last_tile) res_request_to(rv2, ic<6>{}, e_b, e_th, e_tw, e_cot, ln);  // (nothing left to hide the waiting quarters behind)
-                    do_q(ic<3>{}, rv3, ps1, pq1);
-                    if (last_tile) res_request_to(rv3, ic<7>{}, e_b, e_th, e_tw, e_cot, ln);
-                    half_stats(ic<1>{}, ps0, pq0, ps1, pq1, e_b, e_th, e_tw, e_cot, ln);
-                    if constexpr (MR == 4) bias_request(ic<3>{});
-                    do_q(ic<4>{}, rvA, ps0, pq0);
-                    do_q(ic<5>{}, rv1, ps1, pq1);
-                    half_stats(ic<2>{}, ps0, pq0, ps1, pq1, e_b, e_th, e_tw, e_cot, ln);
-                    // the last row block waits in LDS (the patch -- the first KiB of slot 0 -- is free now: LDS operations of a wave are in order)
-                    turn_write(ic<6>{}, dump, ln);
-                    turn_write(ic<7>{}, dump + 1024, ln);
-                    pe_b = e_b; pe_th = e_th; pe_tw = e_tw; pe_cot = e_cot;
-                    pending = true;
-                    stamp(8);
-                    if (last_tile) {
-                        slice_w(rv2, rv3, ic<0>{});  // (clears `pending`)
-                        stamp(43);
-                    } else {
-                        res_request(ic<6>{}, e_b, e_th, e_tw, e_cot, ln);
-                    }
-                    // (the accumulators restart from C = 0 in the next tile's first products: end the old values' lives)
-                    if constexpr (MR == 4) {
-                        asm volatile("" : "=v"(acc[0][0]), "=v"(acc[0][1]), "=v"(acc[1][0]), "=v"(acc[1][1]));
-                        asm volatile("" : "=v"(acc[2][0]), "=v"(acc[2][1]), "=v"(acc[3][0]), "=v"(acc[3][1]));
-                    } else {
-                        asm volatile("" : "=v"(acc[0][0]), "=v"(acc[0][1]), "=v"(acc[0][2]), "=v"(acc[0][3]));
-                        asm volatile("" : "=v"(acc[1][0]), "=v"(acc[1][1]), "=v"(acc[1][2]), "=v"(acc[1][3]));
-                    }
-                    if (++e_item < nIt) decode(e_item, e_cot, e_b, e_th, e_tw);
-                    frag_first(lds_w0);  // (stage 3 (q + 1): ring slot 0)
-                }
-            }
-        } else {
-        if constexpr (decltype(PAR)::value == 0) {
+        } else if constexpr (decltype(PAR)::value == 0) {
             if (pending && e_c == 1) slice(ic<1>{});
             if constexpr (NQ == 4) {
                 if (pending && e_c == 3) slice(ic<3>{});
@@ -1742,7 +1542,6 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(const ConvParams p, 
                 // this chunk's last barrier); also after the last tile -- harmless, keeps the registers plainly defined
                 frag_first(lds_w0 + (unsigned)(((3 * (q + 1)) & (RING - 1)) * WSTAGE));
             }
-        }
         }
     };
 
@@ -1838,10 +1637,9 @@ int conv_f16x2_pick_co_tile(int Cin, int Cout, int H, int W, long pixels_times_b
     // The one-accumulator tiles take three truncating accumulator updates per tap where the 64 x 4 tile takes one.  Measured per layer
     // against fp64 (tests/test_hip_kernels.py::test_conv3x3_both_operand_splits): their rms error is 0.4-0.6x a plain fp32 fmaf chain's (the
     // fp32-MFMA kernel with one accumulator) at every depth, 0.66-0.70x the library's fp32 kernel at Cin <= 128, 1.2x at Cin = 256 and 1.7x at
-    // Cin = 512, where that kernel accumulates on two levels.  Used up to Cin = 256 (R2DM_F2_WIDE_MAX_CIN: experiments), where the launch
-    // still has a tile per CU at the planned batch: 128 x 4 for layers with >= 128 output channels, else 64 x 8 (R2DM_F2_TALL=0: never).
-    static const int max_cin = getenv("R2DM_F2_WIDE_MAX_CIN") ? atoi(getenv("R2DM_F2_WIDE_MAX_CIN")) : 256;
-    static const bool tall_on = !getenv("R2DM_F2_TALL") || atoi(getenv("R2DM_F2_TALL")) != 0;
+    // Cin = 512, where that kernel accumulates on two levels.  Used up to Cin = 256, where the launch
+    // still has a tile per CU at the planned batch: 128 x 4 for layers with >= 128 output channels, else 64 x 8.
+    constexpr int max_cin = 256;
     const long px_tiles = pixels_times_batch / (4 * f2::TW);
     if (wide_ok && Cin <= max_cin && px_tiles * (Cout / 128) >= f2_cu_count()) return 128;
     // (the eight-row tile pays where a block has enough chunks to amortise its longer tile end: measured per launch at batch 8, profiles/r05_tall_tile.txt --
@@ -1849,7 +1647,7 @@ int conv_f16x2_pick_co_tile(int Cin, int Cout, int H, int W, long pixels_times_b
     // fewer 64-channel tiles than CUs (u_block4 at batch 8: 128): 32-channel tiles, so that every CU has one (R2DM_F2_NARROW=0: never)
     static const bool narrow_on = !getenv("R2DM_F2_NARROW") || atoi(getenv("R2DM_F2_NARROW")) != 0;
     if (narrow_ok && narrow_on && px_tiles * (Cout / 64) < f2_cu_count() && px_tiles * (Cout / 32) >= px_tiles * (Cout / 64) * 2) return 32;
-    if (tall_ok && tall_on && px_rows && Cin <= max_cin && (px_tiles / 2) * (Cout / 64) * (long)(Cin / f2::CK) >= 16L * f2_cu_count()) rows = 8;
+    if (tall_ok && px_rows && Cin <= max_cin && (px_tiles / 2) * (Cout / 64) * (long)(Cin / f2::CK) >= 16L * f2_cu_count()) rows = 8;
     return 64;
 }
 
@@ -1895,34 +1693,27 @@ static hipError_t launch_f2(const ConvParams& p, long tiles, hipStream_t s) {
     // workgroup of ANOTHER process.  Next to a neighbour process whose workgroups hold LDS, the 32-channel tile -- the only tile that left
     // room for them -- ended in a GPU memory fault (scripts/jobs/j314.sh .. j316.sh: not without the neighbour, not with R2DM_F2_NARROW=0);
     // the same signature as round 2's "wrong results next to a second process" of a 17 KiB-LDS kernel (LABNOTES.md section 6): whatever the
-    // platform does there, a block that owns the CU's LDS is not exposed to it.  R2DM_F2_LDS_EXACT=1: experiments.
-    static const bool lds_exact = getenv("R2DM_F2_LDS_EXACT") != nullptr;
-    const int LDS_TOTAL = GEO::LDS_TOTAL >= 156 * 1024 || lds_exact ? GEO::LDS_TOTAL : 156 * 1024;
+    // platform does there, a block that owns the CU's LDS is not exposed to it.
+    const int LDS_TOTAL = GEO::LDS_TOTAL >= 156 * 1024 ? GEO::LDS_TOTAL : 156 * 1024;
     constexpr int COT = GEO::COT;
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
         if (e != hipSuccess) return e;
-#ifndef F2_SHARE_CU
         // "a block owns its CU" is what fences the open co-residency defect (root cause NOT identified) -- so it
         // is checked, once per instantiation, instead of assumed: with this launch's LDS request and the kernel's register allocation exactly ONE
-        // block must fit a CU.  A later drop in register or LDS use (or -DF2_SHARE_CU / R2DM_F2_LDS_EXACT=1 builds, which skip this on purpose)
-        // would otherwise re-expose the fault silently.
-        if (!lds_exact) {
-            int nb = 0;
-            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(kern), 512, (size_t)LDS_TOTAL);
-            if (e != hipSuccess) return e;
-            if (nb != 1) {
-                fprintf(stderr, "r2dm: conv_f16x2_kernel<%d,%d,%d,%d,%d>: %d blocks would fit one CU (must be exactly 1: a block owns its CU)\n", PRO, NPLK, MRK, NRK, IOM, nb);
-                return hipErrorLaunchFailure;
-            }
+        // block must fit a CU.  A later drop in register or LDS use would otherwise re-expose the fault silently.
+        int nb = 0;
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(kern), 512, (size_t)LDS_TOTAL);
+        if (e != hipSuccess) return e;
+        if (nb != 1) {
+            fprintf(stderr, "r2dm: conv_f16x2_kernel<%d,%d,%d,%d,%d>: %d blocks would fit one CU (must be exactly 1: a block owns its CU)\n", PRO, NPLK, MRK, NRK, IOM, nb);
+            return hipErrorLaunchFailure;
         }
-#endif
         attr_set = true;
     }
-    static const bool one_tile_blocks = getenv("R2DM_F2_NONPERSISTENT") != nullptr;  // experiments: one tile per block
     const int n_cu = f2_cu_count();
-    const unsigned grid = (unsigned)(tiles < n_cu || one_tile_blocks ? tiles : n_cu);
+    const unsigned grid = (unsigned)(tiles < n_cu ? tiles : n_cu);
     const int nCoT = p.Cout / COT, nTw = p.W / f2::TW, nTh = p.H / GEO::TH;
     const int dmax = nCoT > nTw ? (nCoT > nTh ? nCoT : nTh) : (nTw > nTh ? nTw : nTh);
     if (tiles * dmax >= (1ll << 32)) return hipErrorInvalidValue;  // (F2Div is exact below that)
@@ -1941,7 +1732,6 @@ static hipError_t launch_f2_tile(const ConvParams& p, hipStream_t s) {
     if constexpr (MRK == 1) {
         if (p.prologue == PRO_PRESPLIT) return p.pieces == 1 ? hipErrorInvalidValue : launch_f2<PRO_PRESPLIT, 2, 1, 2>(p, tiles, s);
     }
-    {
     if (p.pieces == 1) {  // one fp16 product per MAC (the reduced-precision bulk mode)
         const int iom = (p.x16 ? 1 : 0) | (p.y16 ? 2 : 0);  // fp16 storage of the input / of the output and residual
         if (iom) {  // (the residual blocks' convolutions -- GroupNorm + SiLU input -- and the plain-input down- / up-sampling convolutions)
@@ -1965,7 +1755,6 @@ static hipError_t launch_f2_tile(const ConvParams& p, hipStream_t s) {
         case PRO_AFFINE_SILU: return launch_f2<PRO_AFFINE_SILU, 2, MRK, NRK>(p, tiles, s);
     }
     return hipErrorInvalidValue;
-    }
 }
 
 // GroupNorm folded into this launch?  8 groups of 8 .. 64 channels over exactly the input channels, at most 4 x 256 statistics slots per
@@ -1982,7 +1771,6 @@ bool conv_f16x2_fold_supported(const ConvParams& p, int groups, int slots) {
     const long tps = (long)(p.Cout / p.co_tile) * (p.W / f2::TW) * (p.H / p.px_rows), tiles = tps * p.B;
     const int n_cu = f2_cu_count();
     if (tiles <= n_cu) return true;  // one tile per block
-    if (getenv("R2DM_F2_NONPERSISTENT")) return true;
     const int G = n_cu;
     for (int blk = 0; blk < G; ++blk) {
         const long nIt = (tiles - blk + G - 1) / G;
@@ -1993,10 +1781,7 @@ bool conv_f16x2_fold_supported(const ConvParams& p, int groups, int slots) {
     return true;
 }
 
-hipError_t launch_conv_f16x2(const ConvParams& p_in, hipStream_t s) {
-    ConvParams p = p_in;
-    static const int stagger = getenv("R2DM_F2_STAGGER") ? atoi(getenv("R2DM_F2_STAGGER")) : 0;
-    p.stagger = stagger;
+hipError_t launch_conv_f16x2(const ConvParams& p, hipStream_t s) {
     if (!conv_f16x2_supported(p.Cin, p.Cout, p.taps, p.H, p.W, p.co_tile, p.px_rows)) return hipErrorInvalidValue;
     if (p.x.p1 && p.x.c0 % f2::CK) return hipErrorInvalidValue;  // a chunk must not straddle the concat seam
     if (p.prologue != PRO_NONE && p.prologue != PRO_PRESPLIT && p.aff == nullptr && p.gn_partial == nullptr) return hipErrorInvalidValue;

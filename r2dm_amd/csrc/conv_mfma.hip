@@ -611,9 +611,6 @@ hipError_t launch_conv(const ConvParams& p, hipStream_t s) {
         if (p.co_tile == 128) return launch_pro<9, 128, 2, 2, kCK3_128, false, 2>(p, s);
         if (p.co_tile == 64) {
             // long reductions (K = 9*Cin > 1152) get the two-level accumulator
-#ifdef R2DM_ACC2_ALL
-            if (true) return launch_pro<9, 64, 1, 4, kCK3_64_DEEP, true, 2>(p, s);
-#endif
             // (pieces == 5: per-kernel test hook -- ONE accumulator at any depth, i.e. the plain fmaf chain the split kernels are measured against)
             return p.Cin > 128 && p.pieces != 5 ? launch_pro<9, 64, 1, 4, kCK3_64_DEEP, true, 2>(p, s)
                                                 : launch_pro<9, 64, 1, 4, kCK3_64, false, 3>(p, s);

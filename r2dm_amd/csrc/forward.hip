@@ -28,8 +28,7 @@ struct Ctx {
     int n_sites = 0;
     std::string ctx;
     int* range_site(const char* what) {
-        static const bool shared = getenv("R2DM_RANGE_SHARED") != nullptr;  // (probe: one slot for the whole forward, as until round 5 -- profiles/r06_range_slots.txt)
-        const int k = shared ? 0 : n_sites + 1 < r2dm_handle::RANGE_SITES ? ++n_sites : 0;  // (beyond the table: the shared slot 0 -- still guarded, just not named)
+        const int k = n_sites + 1 < r2dm_handle::RANGE_SITES ? ++n_sites : 0;  // (beyond the table: the shared slot 0 -- still guarded, just not named)
         if ((int)h->site_names.size() <= k) h->site_names.resize(k + 1);
         h->site_names[k] = ctx.empty() ? std::string(what) : ctx + ": " + what;
         return (int*)blob(h->range_flag) + 2 * k;
@@ -213,17 +212,9 @@ struct Ctx {
         // allocation sequence, which must be the same in both walks)
         const bool fused_stats = o.sink && o.sink->p && emits_stats(L);
         if (o.sink && o.sink->p && !fused_stats) const_cast<Sink*>(o.sink)->incomplete = true;
-        // The operand pre-pass (presplit.hip) is an EXPERIMENT, off by default: R2DM_F2_PRESPLIT_MIN_COUT=256 sends the layers with >= 256
-        // output channels through it.  Round-4 A/B (profiles/r04_presplit.txt): bit-identical outputs, conv_f16x2's own roofline fraction
-        // 0.387 -> 0.403, the STEP 1.7 % slower (6.19 -> 6.30 ms): the pass costs more than the staging waves' transform did -- with the
-        // stagers idle a chunk still takes 4.5 k cycles (multipliers + three barriers; 5.2 k before), prologue / tile ends / tail are unchanged.
-        // (decided in both walks: the allocation sequence must be the same)
-        static const int presplit_min_cout = getenv("R2DM_F2_PRESPLIT_MIN_COUT") ? atoi(getenv("R2DM_F2_PRESPLIT_MIN_COUT")) : 0;  // (0: never)
         const bool f2_launch = L.f2 && h->f16_path() && (pro != PRO_NONE || o.input_bounded);
-        float* xs = nullptr;
-        if (f2_launch && !fold && L.f2_cot == 64 && L.f2_rows == 4 && presplit_min_cout > 0 && L.cout >= presplit_min_cout && presplit_supported(x, L.cin, H, W))
-            xs = (float*)ar->alloc((size_t)presplit_floats(B, L.cin, H, W) * sizeof(float));
-        if (f2_launch && pre_fold && !xs) xs = (float*)ar->alloc((size_t)presplit_floats(B, L.cin, H, W) * sizeof(float));
+        // the operand pre-pass's planes (decided in both walks: the allocation sequence must be the same)
+        float* xs = f2_launch && pre_fold ? (float*)ar->alloc((size_t)presplit_floats(B, L.cin, H, W) * sizeof(float)) : nullptr;
         if (!dry()) {
             ConvParams p = conv_params(x, blob(L.w), blob(L.b), y.p, y.bs(), B, H, W, L.cin, L.cin_pad, L.cout, L.taps, L.co_tile, L.algo, pro);
             p.aff = aff;
@@ -235,8 +226,7 @@ struct Ctx {
             // the fp16 split where the input's range is guarded: GroupNorm-normalised (gn_finalize's bound) or tracked by its
             // producer (fir_up2's running maximum)
             if (f2_launch) {
-                static const int rev_mode = getenv("R2DM_TILE_ORDER") ? atoi(getenv("R2DM_TILE_ORDER")) : 1;  // 0: always ascending (experiments)
-                p.reverse = rev_mode ? (f2_launches++ & 1) : 0;
+                p.reverse = f2_launches++ & 1;
                 last_reverse = p.reverse;
                 p.algo = ALGO_F16X2;
                 p.w = blob(L.w_f2);
@@ -258,23 +248,19 @@ struct Ctx {
                     p.gn_range = range_site("GroupNorm output bound |a| M + |d| (folded into the convolution)");
                 }
             }
-            // deep layers (many 64-channel output tiles): the input transform once, by the pre-pass (presplit.hip)
+            // many output-channel tiles per x tile: the input transform once, by the pre-pass with the GroupNorm folded in (presplit.hip)
             if (xs) {
-                if (pre_fold) {
-                    const Sink& k = *ns->stats;
-                    note(launch_presplit_fold(x, pro, xs, B, L.cin, H, W, k.p, k.slots, k.cpg < 64 ? k.slots / 2 : k.slots, k.cpg, h->cfg.gn_eps, ns->gamma, ns->beta, ns->ada,
-                                              (long)h->ada_rows, range_site("GroupNorm output bound |a| M + |d| (folded into the operand pre-pass)"), st), "presplit_fold");
-                } else
-                    note(launch_presplit(x, aff, pro, xs, B, L.cin, H, W, st), "presplit");
+                const Sink& k = *ns->stats;
+                note(launch_presplit_fold(x, pro, xs, B, L.cin, H, W, k.p, k.slots, k.cpg < 64 ? k.slots / 2 : k.slots, k.cpg, h->cfg.gn_eps, ns->gamma, ns->beta, ns->ada,
+                                          (long)h->ada_rows, range_site("GroupNorm output bound |a| M + |d| (folded into the operand pre-pass)"), st), "presplit_fold");
                 p.x = Src{xs, nullptr, L.cin, 0, presplit_floats(1, L.cin, H, W), 0};
                 p.prologue = PRO_PRESPLIT;
                 p.aff = nullptr;
             }
             if (L.p1 && h->f16_path() && pro != PRO_AFFINE_SILU && (pro != PRO_NONE || o.input_bounded)) {
                 p.algo = ALGO_P1F16;
-                // (a skip convolution reads the tensor its block's conv1 has just read: start where that walk ended.  R2DM_PROJ_ORDER=0: always forwards)
-                static const bool proj_rev = !getenv("R2DM_PROJ_ORDER") || atoi(getenv("R2DM_PROJ_ORDER")) != 0;
-                p.reverse = proj_rev && last_reverse == 0 ? 1 : 0;
+                // (a skip convolution reads the tensor its block's conv1 has just read: start where that walk ended)
+                p.reverse = last_reverse == 0;
                 p.w = blob(L.w_p1);
                 p.wscale = blob(L.ws_p1) + 1;
                 p.co_tile = 64;

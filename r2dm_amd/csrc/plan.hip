@@ -48,10 +48,7 @@ ConvLayer r2dm_handle::conv(const std::string& wkey, const std::string& bkey, in
     L.cin_pad = L.algo != ALGO_F32 ? cin : conv_cin_pad(cin, L.taps, L.co_tile);
     L.w = take(L.packed_elems());
     // (at least half a wave of tiles per CU at the planned batch: below that the persistent kernel leaves CUs idle)
-    static const long f2_min_tiles = [] {  // (R2DM_F2_MIN_TILES: experiments)
-        const char* e = getenv("R2DM_F2_MIN_TILES");
-        return e ? atol(e) : 128L;
-    }();
+    constexpr long f2_min_tiles = 128;
     if (L.algo == ALGO_BF16X3 && H > 0 && conv_f16x2_supported(cin, cout, L.taps, H, W) && (px_batch / 256) * (cout / 64) >= f2_min_tiles) {
         L.f2 = true;
         L.f2_cot = conv_f16x2_pick_co_tile(cin, cout, H, W, px_batch, &L.f2_rows);

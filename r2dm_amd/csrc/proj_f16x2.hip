@@ -403,12 +403,11 @@ hipError_t launch_proj_f16x2(const ConvParams& p, hipStream_t s, bool bias_rowfa
         if (!(p.x16 && p.y16) || p.pieces != 1 || p.prologue != PRO_NONE || p.res || p.stat) return hipErrorInvalidValue;
         return launch_p1<PRO_NONE, 1, 3>(p, s);
     }
-    static const bool tall_on = getenv("R2DM_PROJ_TALL") == nullptr || atoi(getenv("R2DM_PROJ_TALL")) != 0;  // (0: experiments)
     if (bias_rowfac) {  // the down-sampling GEMM: plain input, the split arithmetic, no residual
         if (p.pieces == 1 || p.prologue != PRO_NONE || p.res || p.x16 || p.y16) return hipErrorInvalidValue;
-        return tall_on && p.Cout % p1::COB == 0 ? launch_p1_tall<PRO_NONE, 2, true>(p, s) : launch_p1<PRO_NONE, 2, 0, true>(p, s);
+        return p.Cout % p1::COB == 0 ? launch_p1_tall<PRO_NONE, 2, true>(p, s) : launch_p1<PRO_NONE, 2, 0, true>(p, s);
     }
-    if (tall_on && p.Cout % p1::COB == 0) {  // 256-channel blocks: every pixel staged Cout / 256 times instead of Cout / 64
+    if (p.Cout % p1::COB == 0) {  // 256-channel blocks: every pixel staged Cout / 256 times instead of Cout / 64
         if (p.pieces == 1) return p.prologue == PRO_NONE ? launch_p1_tall<PRO_NONE, 1>(p, s) : launch_p1_tall<PRO_AFFINE, 1>(p, s);
         return p.prologue == PRO_NONE ? launch_p1_tall<PRO_NONE, 2>(p, s) : launch_p1_tall<PRO_AFFINE, 2>(p, s);
     }

@@ -1,5 +1,7 @@
 """Test-side wrappers around the single-kernel C-ABI entry points of libr2dm_hip.so."""
+import contextlib
 import ctypes
+import os
 
 import torch
 
@@ -8,6 +10,23 @@ from r2dm_amd import _lib
 
 def _st(t):
     return _lib.stream_ptr(t.device)
+
+
+@contextlib.contextmanager
+def env(**kv):
+    """Environment switches for the duration of a block (the library reads most of them per call); a value of None leaves its name alone.
+    On exit every name is what it was before: its previous value, or unset."""
+    kv = {k: str(v) for k, v in kv.items() if v is not None}
+    saved = {k: os.environ.get(k) for k in kv}
+    os.environ.update(kv)
+    try:
+        yield
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
 
 
 def set_conv_pieces(n):

@@ -96,18 +96,13 @@ class selected:
         self.env = {"R2DM_F2_CO_TILE": tile, "R2DM_TEST_IO16": "4" if variant == "few-input direct" else None}
 
     def __enter__(self):
-        self.saved = {k: os.environ.get(k) for k in self.env}
         self.H.set_conv_pieces(self.pieces)
-        for k, v in self.env.items():
-            if v is not None:
-                os.environ[k] = v
+        self.cm = self.H.env(**self.env)
+        self.cm.__enter__()
 
     def __exit__(self, *exc):
         self.H.set_conv_pieces(2)
-        for k, v in self.saved.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
+        return self.cm.__exit__(*exc)
 
 
 def epilogue_scale(variant):

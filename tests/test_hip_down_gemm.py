@@ -6,7 +6,6 @@ proj_f16x2.hip) -- kernel by kernel against fp64, and through the engine with th
     FIR(conv(x) + b)[co][i][j] = sum_{ky,kx,ci} w[co][ci][ky][kx] A[ky][kx][ci][i][j] + b[co] rowfac[i]
 """
 import math
-import os
 
 import pytest
 import torch
@@ -149,17 +148,12 @@ def test_down_gemm_statistics_slots(B, cin, cout, h, w):
 # ---- engine --------------------------------------------------------------------------------------------------------------------
 def _model(switch, resolution):
     """A model whose engine was created with R2DM_DOWN_GEMM = switch (the library reads it once, at r2dm_create)."""
+    import hipops
     import r2dm_amd
 
-    saved = os.environ.get("R2DM_DOWN_GEMM")
-    os.environ["R2DM_DOWN_GEMM"] = switch
-    try:
+    with hipops.env(R2DM_DOWN_GEMM=switch):
         ddpm, _, _ = r2dm_amd.setup_model(synthetic_ckpt(resolution=resolution), device=DEV, show_info=False)
         ddpm.model(torch.zeros(1, 2, *resolution, device=DEV), torch.zeros(1, device=DEV))  # (the engine exists now)
-    finally:
-        os.environ.pop("R2DM_DOWN_GEMM", None)
-        if saved is not None:
-            os.environ["R2DM_DOWN_GEMM"] = saved
     return ddpm.model
 
 

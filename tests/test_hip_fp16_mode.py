@@ -70,23 +70,17 @@ def test_conv_one_product_tiles_are_bit_identical(H, cin, cout, h, w):
     """Round 5: every tile of conv_f16x2 in the one-product mode -- 64 x 4, 128 x 4, 64 x 8 and the 32-channel tile u_block4 runs on at batch 8
     (whose one-plane weight stage is three DMA pieces for four staging waves) -- computes one product per MAC into one accumulator in the same
     order: bit-identical outputs, with GroupNorm + SiLU prologue, residual and scale."""
-    import os
-
     x, wt, b = rnd(1, 3, cin, h, w), rnd(2, cout, cin, 3, 3) / math.sqrt(9 * cin), rnd(3, cout)
     res = rnd(4, 3, cout, h, w)
     aff = torch.stack([torch.rand(3, cin) + 0.5, torch.randn(3, cin) * 0.3], -1).contiguous()
     outs = {}
-    saved = os.environ.get("R2DM_F2_CO_TILE")
     H.set_conv_pieces(1)
     try:
         for tile in ("64", "32", "128", "64x8"):
-            os.environ["R2DM_F2_CO_TILE"] = tile
-            outs[tile] = H.conv2d_ring(x.to(DEV), wt.to(DEV), b.to(DEV), aff=aff.to(DEV), prologue=2, residual=res.to(DEV), scale=0.70710678).cpu()
+            with H.env(R2DM_F2_CO_TILE=tile):
+                outs[tile] = H.conv2d_ring(x.to(DEV), wt.to(DEV), b.to(DEV), aff=aff.to(DEV), prologue=2, residual=res.to(DEV), scale=0.70710678).cpu()
     finally:
         H.set_conv_pieces(2)
-        os.environ.pop("R2DM_F2_CO_TILE", None)
-        if saved is not None:
-            os.environ["R2DM_F2_CO_TILE"] = saved
     for tile in ("32", "128", "64x8"):
         assert torch.equal(outs[tile], outs["64"]), tile
 
@@ -98,47 +92,28 @@ def test_conv_fp16_storage_is_exact(H, cin, cout, h, w, tile):
     outputs.  Storage is the ONLY change: on fp16-representable inputs a launch reading fp16 gives bit for bit what the same launch reading the
     same values as fp32 gives, and a launch writing fp16 gives exactly RNE_f16 of the fp32 launch's output -- every tile, with GroupNorm +
     SiLU prologue, fp16 residual and scale."""
-    import os
-
     B = 3
     x, wt, b = rnd(1, B, cin, h, w).half().float(), rnd(2, cout, cin, 3, 3) / math.sqrt(9 * cin), rnd(3, cout)
     res = rnd(4, B, cout, h, w).half().float()
     aff = torch.stack([torch.rand(B, cin) + 0.5, torch.randn(B, cin) * 0.3], -1).contiguous()
-    saved = {k: os.environ.get(k) for k in ("R2DM_F2_CO_TILE", "R2DM_TEST_IO16")}
     H.set_conv_pieces(1)
     out = {}
     try:
-        os.environ["R2DM_F2_CO_TILE"] = tile
         for io in (0, 1, 2, 3):
-            os.environ["R2DM_TEST_IO16"] = str(io)
-            out[io] = H.conv2d_ring(x.to(DEV), wt.to(DEV), b.to(DEV), aff=aff.to(DEV), prologue=2, residual=res.to(DEV), scale=0.70710678, io16=io).cpu()
+            with H.env(R2DM_F2_CO_TILE=tile, R2DM_TEST_IO16=io):
+                out[io] = H.conv2d_ring(x.to(DEV), wt.to(DEV), b.to(DEV), aff=aff.to(DEV), prologue=2, residual=res.to(DEV), scale=0.70710678, io16=io).cpu()
     finally:
         H.set_conv_pieces(2)
-        for k, v in saved.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
     assert out[0].dtype == torch.float32 and out[3].dtype == torch.float16
     assert torch.equal(out[1], out[0])                       # fp16 input: the same values, the same arithmetic
     assert torch.equal(out[2], out[0].half()) and torch.equal(out[3], out[0].half())  # fp16 output: the fp32 result, rounded once
 
 
-class _io16:
+def _io16(v):
     """R2DM_TEST_IO16 for the duration of a block (the single-kernel C entries read it per call)."""
+    import hipops
 
-    def __init__(self, v):
-        self.v = str(v)
-
-    def __enter__(self):
-        import os
-        self.saved = os.environ.get("R2DM_TEST_IO16")
-        os.environ["R2DM_TEST_IO16"] = self.v
-
-    def __exit__(self, *a):
-        import os
-        os.environ.pop("R2DM_TEST_IO16", None)
-        if self.saved is not None:
-            os.environ["R2DM_TEST_IO16"] = self.saved
+    return hipops.env(R2DM_TEST_IO16=v)
 
 
 @pytest.mark.parametrize("C,h,w,groups", [(128, 64, 1024, 8), (256, 32, 512, 8), (16, 8, 64, 0)])
@@ -203,27 +178,20 @@ def test_unet_fp16_storage_levels(O):
     """The whole denoiser with every activation of levels 1 and 2 stored as fp16 (default in the one-plane mode) against the same mode storing fp16 only
     between a residual block's two convolutions (R2DM_FP16_STORAGE=1, round 5) and fp32 everywhere (0): all three inside the mode's tolerance class against
     the fp64 oracle, and within a few fp16 roundings of each other."""
-    import os
-
+    import hipops
     import r2dm_amd
 
     ck = synthetic_ckpt()
     x, c = rnd(70, 2, 2, 64, 1024).to(DEV), torch.tensor([-3.0, 2.0], device=DEV)
     sd = {k: v.double().to(DEV) for k, v in O.strip_prefix(ck["ema_weights"]).items()}
     truth = O.unet_forward(sd, O.UNetConfig(), x.double(), c.double()).cpu()
-    saved = os.environ.get("R2DM_FP16_STORAGE")
     ys = {}
-    try:
-        for lvl in ("2", "1", "0"):
-            os.environ["R2DM_FP16_STORAGE"] = lvl
+    for lvl in ("2", "1", "0"):
+        with hipops.env(R2DM_FP16_STORAGE=lvl):
             m, _, _ = r2dm_amd.setup_model(ck, device=DEV, show_info=False, max_batch=2, precision="fp16")
             ys[lvl] = m.model(x, c).cpu()
             assert torch.equal(ys[lvl], m.model(x, c).cpu())
             del m
-    finally:
-        os.environ.pop("R2DM_FP16_STORAGE", None)
-        if saved is not None:
-            os.environ["R2DM_FP16_STORAGE"] = saved
     e = {k: rel_rms(v, truth) for k, v in ys.items()}
     print(f"fp16 mode vs fp64, storage levels 2 / 1 / 0: rel rms {e['2']:.2e} {e['1']:.2e} {e['0']:.2e}; level 2 vs level 0: {rel_rms(ys['2'], ys['0'].double()):.2e}")
     assert all(2e-4 < v < 3e-3 for v in e.values())

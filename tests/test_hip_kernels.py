@@ -106,19 +106,14 @@ def test_conv3x3_both_operand_splits(O, H, cin, cout, h, w, pro):
     variants = ([("f16x2/64", 2, "64"), ("bf16x3", 3, None), ("f32 mfma", 4, None), ("f32 chain", 5, None)] + ([("f16x2/128", 2, "128")] if cout % 128 == 0 else [])
                 + ([("f16x2/64x8", 2, "64x8")] if h % 8 == 0 else [])  # (round 5: the one-accumulator tile of 64 channels x 8 rows)
                 + [("f16x2/32", 2, "32")])                              # (round 5: 32-channel tiles for launches with fewer 64-channel tiles than CUs)
-    saved = os.environ.get("R2DM_F2_CO_TILE")
     for name, pieces, tile in variants:
         H.set_conv_pieces(pieces)
-        if tile:
-            os.environ["R2DM_F2_CO_TILE"] = tile
         try:
-            out[name] = H.conv2d_ring(x.to(DEV), wt.to(DEV), b.to(DEV), aff=None if aff is None else aff.to(DEV), prologue=pro,
-                                      residual=res.to(DEV), scale=0.70710678).cpu()
+            with H.env(R2DM_F2_CO_TILE=tile):
+                out[name] = H.conv2d_ring(x.to(DEV), wt.to(DEV), b.to(DEV), aff=None if aff is None else aff.to(DEV), prologue=pro,
+                                          residual=res.to(DEV), scale=0.70710678).cpu()
         finally:
             H.set_conv_pieces(2)
-            os.environ.pop("R2DM_F2_CO_TILE", None)
-            if saved is not None:
-                os.environ["R2DM_F2_CO_TILE"] = saved
     e = {k: (max_abs(v, ref), (v.double() - ref).pow(2).mean().sqrt().item()) for k, v in out.items()}
     print(f"conv {cin}->{cout} pro={pro}: " + " | ".join(f"{k} max {v[0]:.2e} rms {v[1]:.2e}" for k, v in e.items()))
     assert not torch.equal(out["f16x2/64"], out["bf16x3"]) and not torch.equal(out["f16x2/64"], out["f32 mfma"])  # the mode switches took effect
@@ -151,22 +146,16 @@ def test_conv3x3_operand_prepass_is_bit_identical(H, cin, cout, h, w, pro):
     x, wt, b = rnd(11, B, cin, h, w).to(DEV), (rnd(12, cout, cin, 3, 3) / math.sqrt(9 * cin)).to(DEV), rnd(13, cout).to(DEV)
     res = rnd(14, B, cout, h, w).to(DEV)
     aff = torch.stack([torch.rand(B, cin) + 0.5, torch.randn(B, cin) * 0.3], -1).contiguous().to(DEV) if pro else None
-    saved = {k: os.environ.get(k) for k in ("R2DM_F2_PRESPLIT", "R2DM_F2_CO_TILE")}
     try:
-        os.environ["R2DM_F2_CO_TILE"] = "64"
         for pieces in (2, 1):
             H.set_conv_pieces(pieces)
             out = {}
             for pre in ("0", "1"):
-                os.environ["R2DM_F2_PRESPLIT"] = pre
-                out[pre] = H.conv2d_ring(x, wt, b, aff=aff, prologue=pro, residual=res, scale=0.70710678)
+                with H.env(R2DM_F2_CO_TILE="64", R2DM_F2_PRESPLIT=pre):
+                    out[pre] = H.conv2d_ring(x, wt, b, aff=aff, prologue=pro, residual=res, scale=0.70710678)
             assert torch.isfinite(out["1"]).all() and torch.equal(out["0"], out["1"]), (pieces, (out["0"] - out["1"]).abs().max().item())
     finally:
         H.set_conv_pieces(2)
-        for k, v in saved.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
 
 
 def test_conv3x3_batch_tiling_variants(O, H):
@@ -268,20 +257,13 @@ def test_fir_resamplers(O, H, shape):
     x = rnd(30, *shape)
     d = H.fir_down2(x.to(DEV))
     assert max_abs(d.cpu(), O.fir_down2(x.double())) < 1e-6
-    os.environ["R2DM_FIR_SHFL"] = "0"
-    try:
+    with H.env(R2DM_FIR_SHFL="0"):
         assert torch.equal(d, H.fir_down2(x.to(DEV)))
-    finally:
-        del os.environ["R2DM_FIR_SHFL"]
     want, got = O.fir_up2(x.double()), []
     for mode in ("0", "2", None):  # the two-column kernel | the 2 x 8 kernel at any size | what the launcher picks
-        if mode is not None:
-            os.environ["R2DM_FIR_UP_WIDE"] = mode
-        try:
+        with H.env(R2DM_FIR_UP_WIDE=mode):
             got.append(H.fir_up2(x.to(DEV)))
             assert max_abs(got[-1].cpu(), want) < 1e-6, mode
-        finally:
-            os.environ.pop("R2DM_FIR_UP_WIDE", None)
     assert torch.equal(got[0], got[1]) and torch.equal(got[0], got[2])  # one spelled-out chain (up1) in both kernels
 
 
@@ -297,11 +279,8 @@ def test_fir_down_with_fused_group_norm_statistics(H, B, C, Hh, Ww):
     assert r is not None
     y, stat = r
     assert torch.equal(y, H.fir_down2(x))
-    os.environ["R2DM_FIR_NARROW"] = "1"  # (the generic two-outputs-per-thread kernel: one spelled-out FMA chain in all three, resample.hip fir4)
-    try:
+    with H.env(R2DM_FIR_NARROW="1"):  # (the generic two-outputs-per-thread kernel: one spelled-out FMA chain in all three, resample.hip fir4)
         assert torch.equal(y, H.fir_down2(x))
-    finally:
-        del os.environ["R2DM_FIR_NARROW"]
     assert torch.isfinite(stat).all()
     cpg = C // 8
     yd = y.double().reshape(B, 8, -1)

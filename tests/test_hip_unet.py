@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN_RES, max_abs, rnd, synthetic_ckpt
+from hipops import env
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -412,17 +413,11 @@ def test_group_norm_folded_into_its_consumer_is_bit_identical(res, batch):
     ck = synthetic_ckpt(resolution=res)
     x, c = rnd(7, batch, 2, *res).to(DEV), torch.linspace(-4.0, 6.0, batch).to(DEV)
     outs = {}
-    saved = os.environ.get("R2DM_GN_FOLD")
     for mode in ("1", "0"):
-        os.environ["R2DM_GN_FOLD"] = mode
-        try:
+        with env(R2DM_GN_FOLD=mode):
             m, _, _ = r2dm_amd.setup_model(ck, device=DEV, show_info=False, max_batch=batch)
             outs[mode] = (m.model(x, c).clone(), m.model(x, c).clone())
             del m
-        finally:
-            os.environ.pop("R2DM_GN_FOLD", None)
-            if saved is not None:
-                os.environ["R2DM_GN_FOLD"] = saved
     assert torch.equal(outs["1"][0], outs["1"][1]) and torch.equal(outs["0"][0], outs["0"][1])
     assert torch.equal(outs["1"][0], outs["0"][0])
 
@@ -438,20 +433,14 @@ def test_operand_prepass_with_folded_group_norm_is_bit_identical(res, batch):
     ck = synthetic_ckpt(resolution=res)
     x, c = rnd(9, batch, 2, *res).to(DEV), torch.linspace(-5.0, 7.0, batch).to(DEV)
     outs = {}
-    saved = os.environ.get("R2DM_F2_PRESPLIT_NARROW")
     for mode in ("2", "1", "0"):  # (2: the 512 -> 512 launches of level 4 as well)
-        os.environ["R2DM_F2_PRESPLIT_NARROW"] = mode
-        try:
+        with env(R2DM_F2_PRESPLIT_NARROW=mode):
             m, _, _ = r2dm_amd.setup_model(ck, device=DEV, show_info=False, max_batch=batch)
             outs[mode] = (m.model(x, c).clone(), m.model(x, c).clone())
             sites = [n for n, _ in m.model.range_report()]
             if mode == "1" and res == (64, 1024) and batch == 8:
                 assert any("operand pre-pass" in n for n in sites), sites[:5]  # (the path under test really ran)
             del m
-        finally:
-            os.environ.pop("R2DM_F2_PRESPLIT_NARROW", None)
-            if saved is not None:
-                os.environ["R2DM_F2_PRESPLIT_NARROW"] = saved
     assert torch.equal(outs["1"][0], outs["1"][1]) and torch.equal(outs["0"][0], outs["0"][1]) and torch.equal(outs["2"][0], outs["2"][1])
     assert torch.equal(outs["1"][0], outs["0"][0]) and torch.equal(outs["2"][0], outs["0"][0])
 
@@ -467,17 +456,11 @@ def test_fir_down_statistics_match_the_streaming_pass(res, batch):
     ck = synthetic_ckpt(resolution=res)
     x, c = rnd(11, batch, 2, *res).to(DEV), torch.linspace(-3.0, 5.0, batch).to(DEV)
     outs = {}
-    saved = os.environ.get("R2DM_FIR_STATS")
     for mode in ("1", "0"):
-        os.environ["R2DM_FIR_STATS"] = mode
-        try:
+        with env(R2DM_FIR_STATS=mode):
             m, _, _ = r2dm_amd.setup_model(ck, device=DEV, show_info=False, max_batch=batch)
             outs[mode] = (m.model(x, c).clone(), m.model(x, c).clone())
             del m
-        finally:
-            os.environ.pop("R2DM_FIR_STATS", None)
-            if saved is not None:
-                os.environ["R2DM_FIR_STATS"] = saved
     assert torch.equal(outs["1"][0], outs["1"][1]) and torch.equal(outs["0"][0], outs["0"][1])
     assert max_abs(outs["1"][0], outs["0"][0]) < 2e-6 and rms(outs["1"][0], outs["0"][0]) < 2e-7
 
@@ -492,15 +475,9 @@ def test_in_conv_channel_shares_are_bit_identical(res, batch):
     m, _, _ = r2dm_amd.setup_model(synthetic_ckpt(resolution=res), device=DEV, show_info=False, max_batch=batch)
     x, c = rnd(13, batch, 2, *res).to(DEV), torch.linspace(-2.0, 4.0, batch).to(DEV)
     outs = []
-    saved = os.environ.get("R2DM_FEW_IN_SPLIT")
-    try:
-        for split in ("1", "2", "4"):
-            os.environ["R2DM_FEW_IN_SPLIT"] = split
+    for split in ("1", "2", "4"):
+        with env(R2DM_FEW_IN_SPLIT=split):
             outs.append(m.model(x, c).clone())
-    finally:
-        os.environ.pop("R2DM_FEW_IN_SPLIT", None)
-        if saved is not None:
-            os.environ["R2DM_FEW_IN_SPLIT"] = saved
     assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
     assert torch.equal(outs[1], m.model(x, c))  # (the default: two shares)
 

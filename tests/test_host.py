@@ -28,6 +28,7 @@ def test_fir_down_statistics_geometry_host_logic():
     it must refuse, so that the engine falls back to the streaming pass: too few patches per slot, channels that do not split into 8 groups of
     8 / 16 / 32 / 64, widths / heights the wide kernel does not take.  The slot count is the convolution epilogues' (conv_stat_slots of the
     OUTPUT geometry: 4-row x 64-pixel tiles x 4 rows x 2 halves)."""
+    from hipops import env
     from r2dm_amd import _lib
 
     f = _lib.lib().r2dm_fir_down2_stat_slots
@@ -40,11 +41,8 @@ def test_fir_down_statistics_geometry_host_logic():
         for level, c in enumerate((128, 256, 512)):
             hh, ww = h >> level, w >> level  # the down-sampler's INPUT geometry at this level
             assert f(c, 8, hh, ww) == epi_slots(hh // 2, ww // 2), (res, level)
-    os.environ["R2DM_FIR_STATS"] = "0"
-    try:
+    with env(R2DM_FIR_STATS="0"):
         assert f(128, 8, 64, 1024) == 0  # (the A/B switch)
-    finally:
-        del os.environ["R2DM_FIR_STATS"]
     assert f(512, 8, 4, 32) == 0      # 16x128 golden network, level 3: 32 patches per slot (< one wave's 64)
     assert f(64, 8, 8, 64) == 0       # fewer than 64 patches per slot
     assert f(128, 8, 64, 1020) == 0   # width not a multiple of 8
@@ -487,7 +485,33 @@ def test_conv_f16x2_blocks_own_their_cu(tmp_path):
     assert len(counts) >= 30, "conv_f16x2_kernel instantiations not found in the library's code objects"
     assert all(v + a == 256 for _, v, a in counts), [c for c in counts if c[1] + c[2] != 256][:4]
     src = open(os.path.join(ROOT, "r2dm_amd", "csrc", "conv_f16x2.hip")).read()
-    assert re.search(r"LDS_TOTAL >= 156 \* 1024 \|\| lds_exact \? GEO::LDS_TOTAL : 156 \* 1024", src), "the launcher's LDS padding"
+    assert re.search(r"LDS_TOTAL = GEO::LDS_TOTAL >= 156 \* 1024 \? GEO::LDS_TOTAL : 156 \* 1024;", src), "the launcher's LDS padding"
+    assert "lds_exact" not in src and "F2_SHARE_CU" not in src  # (no switch takes the padding or the register clobber away)
+
+
+def test_environment_switches_are_the_documented_set():
+    """INTEGRATION.md, "Environment switches and build macros", lists every R2DM_* name the shipped code reads -- no more, no fewer: the names in
+    the built library's strings and those the Python side looks up in os.environ equal the table's two groups.  A switch added later is
+    documented or this fails; the experiment switches removed from the library stay out."""
+    import glob
+
+    lib = os.path.join(ROOT, "r2dm_amd", "libr2dm_hip.so")
+    if not os.path.exists(lib):
+        pytest.skip("libr2dm_hip.so not built")
+    in_lib = {m.decode() for m in re.findall(rb"R2DM_[A-Z0-9_]+", open(lib, "rb").read())}
+    scripts = glob.glob(os.path.join(ROOT, "r2dm_amd", "*.py")) + glob.glob(os.path.join(ROOT, "*.py"))
+    assert any(f.endswith("bench.py") for f in scripts) and any(f.endswith("sample_and_save.py") for f in scripts)
+    in_python = set()
+    for f in scripts:
+        in_python |= set(re.findall(r"""os\.environ(?:\.get\(|\[)\s*["'](R2DM_[A-Z0-9_]+)["']""", open(f).read()))
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read().split("## Environment switches and build macros")[1]
+    rows = re.findall(r"^\| `(R2DM_[A-Z0-9_]+)` \| (library|Python) \|", doc, re.M)
+    assert len(rows) == len({n for n, _ in rows})  # (one row per name)
+    assert in_lib == {n for n, who in rows if who == "library"}, sorted(in_lib ^ {n for n, who in rows if who == "library"})
+    assert in_python == {n for n, who in rows if who == "Python"}, sorted(in_python ^ {n for n, who in rows if who == "Python"})
+    removed = {"R2DM_RANGE_SHARED", "R2DM_F2_PRESPLIT_MIN_COUT", "R2DM_TILE_ORDER", "R2DM_PROJ_ORDER", "R2DM_F2_WIDE_MAX_CIN", "R2DM_F2_TALL",
+               "R2DM_F2_LDS_EXACT", "R2DM_F2_NONPERSISTENT", "R2DM_F2_STAGGER", "R2DM_PROJ_TALL", "R2DM_F2_MIN_TILES", "R2DM_DEBUG_FIXED_NOISE"}
+    assert not removed & (in_lib | in_python)
 
 
 def test_bench_dump_outputs_is_float32_and_capped(tmp_path):
