@@ -421,8 +421,18 @@ int r2dm_fir_down2_stats(const float* x, float* y, double* stat, int32_t batch, 
  * and last output row): y (B, Cout, H/2, W/2) = Resample(down=2)(Conv2d(x, w, bias)).  w is OIHW; w_packed: caller scratch of 9 cin cout + 64 floats;
  * planes: caller scratch of B 9 cin (H/2) (W/2) floats; cin % 32 == 0, cout % 64 == 0, height % 8 == 0, width % 128 == 0.  stat (optional): the
  * GroupNorm statistics of y in the convolution epilogues' slot grid, (B, groups, r2dm_down_gemm_stat_slots(), 2) doubles (0 slots: not available).
- * The engine takes this pair in the default precision unless R2DM_DOWN_GEMM=0 (read at r2dm_create). */
+ * More than half of the nine planes are copies of each other (kx = 0 is kx = 2 one column to the left; V[2][i] = V[0][i + 1] away from the border rows):
+ * r2dm_down_phase_planes writes every distinct plane once -- planes: (B, 2 phases [kx = 2 | kx = 1], C, H + 3 rows, W/2 + 4), r2dm_down_phase_planes_floats(C, H, W)
+ * floats per sample; a channel's rows are V[0][0 .. H/2), V[1][0 .. H/2), V[2][0], V[2][H/2 - 2], V[2][H/2 - 1]; a row's column j is at float 4 + j and float 3 of a
+ * phase-0 row holds column W/2 - 1 -- and r2dm_down_gemm runs that pass and maps the nine taps onto it in its loader.  r2dm_down_gemm_nine runs the product over all
+ * nine planes (r2dm_down_planes' pass): the same bits.  Both take `planes` sized for nine.
+ * The engine takes the pair in the default precision; R2DM_DOWN_GEMM (read at r2dm_create): 1 (default) = the phase planes, 9 = all nine planes, 0 = Conv3x3 +
+ * fir_down2. */
 int r2dm_down_planes(const float* x, float* planes, int32_t batch, int32_t channels, int32_t height, int32_t width, void* stream);
+int r2dm_down_phase_planes(const float* x, float* planes, int32_t batch, int32_t channels, int32_t height, int32_t width, void* stream);
+int64_t r2dm_down_phase_planes_floats(int32_t channels, int32_t height, int32_t width); /* per sample; 0: geometry not supported */
+int r2dm_down_gemm_nine(const float* x, const float* w, const float* bias, float* w_packed, float* planes, float* y, double* stat,
+                        int32_t batch, int32_t cin, int32_t cout, int32_t groups, int32_t height, int32_t width, void* stream);
 int32_t r2dm_down_gemm_stat_slots(int32_t cin, int32_t cout, int32_t groups, int32_t height, int32_t width);
 int r2dm_down_gemm(const float* x, const float* w, const float* bias, float* w_packed, float* planes, float* y, double* stat,
                    int32_t batch, int32_t cin, int32_t cout, int32_t groups, int32_t height, int32_t width, void* stream);

@@ -191,8 +191,10 @@ bool proj_f16x2_supported(int Cin, int Cout, int taps, int H, int W);
 long proj_f16x2_packed_floats(int Cin, int Cout);
 // taps = 9: w is the OIHW tensor of a 3x3 convolution over Cin / 9 channels, packed as the (Cout, Cin) matrix of the down-sampling GEMM (column = tap * Cin / 9 + ci)
 hipError_t launch_pack_proj_f16x2(const float* w_oi, float* dst, int Cout, int Cin, int* range_flag, hipStream_t s, float* wscale = nullptr, int taps = 1);
-// bias_rowfac: the bias is scaled by the FIR's row factor (7/8 on the first and last row) -- the down-sampling GEMM over launch_down_planes' output
-hipError_t launch_proj_f16x2(const ConvParams& p, hipStream_t s, bool bias_rowfac = false);
+// down != DOWN_NONE: the down-sampling GEMM -- the bias is scaled by the FIR's row factor (7/8 on the first and last row); DOWN_NINE: x is launch_down_planes'
+// output, DOWN_PHASE: launch_down_phase_planes' (x.bs0 = down_phase_planes_floats; Cin stays 9 x the convolution's input channels: the K order is the same)
+enum DownOperand { DOWN_NONE = 0, DOWN_NINE = 1, DOWN_PHASE = 2 };
+hipError_t launch_proj_f16x2(const ConvParams& p, hipStream_t s, int down = DOWN_NONE);
 
 struct GNParams {
     Src x;
@@ -229,6 +231,15 @@ int fir_down2_stat_slots(int C, int G, int H, int W);
 // range (optional): range[1] takes the running maximum of |a| as float bits.  Needs H % 4 == 0, W % 8 == 0.
 bool down_planes_supported(int H, int W);
 hipError_t launch_down_planes(const float* x, long xbs, float* a, long abs_, int B, int C, int H, int W, hipStream_t s, int* range = nullptr);
+// ... the same operand with every distinct plane stored once (resample.hip down_planes_phase_kernel): a <- [B][phase E, O][C][H + 3 rows][W/2 + 4], per sample
+// down_phase_planes_floats(C, H, W) floats -- 0.47 .. 0.53 of the nine planes; launch_proj_f16x2(p, s, DOWN_PHASE) maps the nine taps onto it
+bool down_phase_planes_supported(int H, int W);
+long down_phase_planes_floats(int C, int H, int W);
+hipError_t launch_down_phase_planes(const float* x, long xbs, float* a, long abs_, int B, int C, int H, int W, hipStream_t s, int* range = nullptr);
+// row of a channel's (Ho + Ho + 3)-row block that holds V[ky][i]: V[0] | V[1] | V[2][0], V[2][Ho - 2], V[2][Ho - 1]; every other V[2][i] is V[0][i + 1]
+__host__ __device__ inline int down_phase_row(int ky, int i, int Ho) {
+    return ky == 0 ? i : ky == 1 ? Ho + i : i == 0 ? 2 * Ho : i == Ho - 1 ? 2 * Ho + 2 : i == Ho - 2 ? 2 * Ho + 1 : i + 1;
+}
 hipError_t launch_fir_up2(const float* x, long xbs, float* y, long ybs, int B, int C, int H, int W,
                           hipStream_t s, int* range = nullptr, int x16 = 0, int y16 = 0);  // range[1]: running max |output| as float bits (may be nullptr)
 

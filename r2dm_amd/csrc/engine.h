@@ -46,7 +46,7 @@ struct ConvLayer {
     bool p1 = false;
     size_t w_p1 = 0, ws_p1 = 0;
     // ... and, for a stage's down-sampling 3x3 convolution, the (Cout, 9 Cin) matrix of the down-sampling GEMM (FIR first, then a 1x1 convolution over the nine
-    // filtered planes at the output resolution: resample.hip down_planes_kernel + proj_f16x2.hip), columns (ky, kx, ci)
+    // filtered planes at the output resolution: resample.hip down_planes_phase_kernel / down_planes_kernel + proj_f16x2.hip), columns (ky, kx, ci)
     bool dg = false;
     size_t w_dg = 0, ws_dg = 0;
     size_t packed_elems() const { return (size_t)conv_packed_floats(algo, cin, cout, taps, co_tile, cin_pad); }
@@ -109,8 +109,10 @@ struct r2dm_handle {
     // residual (ALGO_F16X2 / ALGO_P1F16) wherever a second packing exists, three bf16 pieces elsewhere; 3 = three bf16 pieces
     // everywhere; 1 = the kernels of mode 2 with the fp16 piece alone (one product per MAC: reduced precision, bulk sampling)
     int conv_pieces = 2;
-    // R2DM_DOWN_GEMM=0 (read once, at r2dm_create): the down stages keep Conv3x3 at the finer resolution + fir_down2, as until round 6 (A/B, the parity test)
-    bool down_gemm = true;
+    // R2DM_DOWN_GEMM (read once, at r2dm_create): 1 (default) = FIR first, then the GEMM over the phase planes (every distinct plane stored once: resample.hip
+    // down_planes_phase_kernel); 9 = the same GEMM over all nine planes (down_planes_kernel: the A/B twin, bit-identical); 0 = the down stages keep Conv3x3 at the
+    // finer resolution + fir_down2, as until round 6 (A/B, the parity test)
+    int down_gemm = 1;
     bool f16_path() const { return conv_pieces != 3; }  // operands go through fp16: their range is guarded
     bool flags_fresh = false;  // the blob's range flags have been cleared since the last r2dm_bind_blob (first load does it)
     size_t range_flag = 0;  // blob slot (RANGE_SITES pairs of ints, ALGO_F16X2): [0] != 0: a weight outside the fp16 range; [2 k + 1]: float
@@ -244,12 +246,13 @@ inline ConvParams conv_params(const Src& x, const float* w, const float* bias, f
     return p;
 }
 
-// the down-sampling GEMM over launch_down_planes' output (B, 9 cin, Ho, Wo): w / wscale its packed matrix and weight scale; stat (may be null): GroupNorm
-// statistics of y for G groups in the convolution epilogues' slot grid
+// the down-sampling GEMM over launch_down_planes' output (B, 9 cin, Ho, Wo) or, `phase`, launch_down_phase_planes' (B, 2, cin, 2 Ho + 3, Wo + 4: launch it with
+// DOWN_PHASE): w / wscale its packed matrix and weight scale; stat (may be null): GroupNorm statistics of y for G groups in the convolution epilogues' slot grid
 inline ConvParams down_gemm_params(const float* planes, const float* w, const float* bias, const float* wscale, float* y, int B, int cin, int cout, int Ho,
-                                   int Wo, double* stat, int G) {
+                                   int Wo, double* stat, int G, bool phase) {
     const int K = 9 * cin;  // a 1x1 convolution over the nine filtered planes of every channel, at the output resolution
-    ConvParams p = conv_params(Src{planes, nullptr, K, 0, (long)K * Ho * Wo, 0}, w, bias, y, (long)cout * Ho * Wo, B, Ho, Wo, K, K, cout, 1, 64, ALGO_P1F16, PRO_NONE);
+    const long bs = phase ? down_phase_planes_floats(cin, 2 * Ho, 2 * Wo) : (long)K * Ho * Wo;
+    ConvParams p = conv_params(Src{planes, nullptr, K, 0, bs, 0}, w, bias, y, (long)cout * Ho * Wo, B, Ho, Wo, K, K, cout, 1, 64, ALGO_P1F16, PRO_NONE);
     p.pieces = 2;
     p.wscale = wscale;
     if (stat) {

@@ -35,7 +35,7 @@ int r2dm_create(r2dm_handle** out, const r2dm_config* cfg) {
     if (int rc = check_config(*cfg)) return rc;
     r2dm_handle* h = new r2dm_handle();
     h->cfg = *cfg;
-    if (const char* e = getenv("R2DM_DOWN_GEMM")) h->down_gemm = atoi(e) != 0;
+    if (const char* e = getenv("R2DM_DOWN_GEMM")) h->down_gemm = atoi(e) == 0 ? 0 : atoi(e) == 9 ? 9 : 1;
     (void)hipGetDevice(&h->device);
     build_plan(h);
     *out = h;

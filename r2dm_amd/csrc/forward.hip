@@ -417,15 +417,18 @@ struct Ctx {
         bool c16 = si.f16;  // the current tensor (stage input or `cur`) is stored as fp16
         Sink carry = in_stats;  // statistics of the current tensor, owned elsewhere for the stage input
         bool carry_owned = false;
-        // FIR first, then the stride-2 convolution as a GEMM over the nine filtered planes (resample.hip down_planes_kernel): a quarter of the MACs of
-        // conv + fir_down2.  Taken where the plan packed the matrix (geometry, R2DM_DOWN_GEMM), the precision is the default three-product split and
+        // FIR first, then the stride-2 convolution as a GEMM over the nine filtered planes (resample.hip): a quarter of the MACs of conv + fir_down2.  The
+        // planes are stored once each (down_planes_phase_kernel: two column phases x 2 Ho + 3 rows, about 1.0 x the input instead of 2.25 x) unless
+        // R2DM_DOWN_GEMM=9 asks for all nine (down_planes_kernel); the GEMM's loader maps the taps, the product is the same bits.  Taken where the plan packed the matrix (geometry, R2DM_DOWN_GEMM), the precision is the default three-product split and
         // the input's producer tracks max|x|; everything else -- fp32-bf16x3, the one-plane mode with its fp16 storage, a tripped guard's fallback --
         // keeps conv + FIR.  Leaves what the FIR launch leaves: the tensor and, where fir_down2 would, the statistics of the first block's norm.
         // (a two-source input never reaches a down stage today; if one does it keeps conv + FIR: the pre-pass reads one tensor)
         if (s.down && s.dconv.dg && h->conv_pieces == 2 && si.tracked && !si.f16 && !in.p1) {
             ctx = s.name + ".downsample";
             const ConvLayer& L = s.dconv;
-            Tensor a = make(9 * L.cin, H / 2, W / 2);
+            const bool phase = h->down_gemm != 9;
+            // (phase planes: 2 cin channels of (H + 3) x (W / 2 + 4))
+            Tensor a = phase ? make(2 * L.cin, H + 3, W / 2 + 4) : make(9 * L.cin, H / 2, W / 2);
             cur = make(s.cout, H / 2, W / 2);
             Sink fs;
             if (fir_down2_stat_slots(s.cout, h->cfg.gn_num_groups, H, W)) fs = make_sink(s.cout, H / 2, W / 2);
@@ -433,14 +436,17 @@ struct Ctx {
                 // Range: the FIR weights are non-negative and sum to at most 1 per axis, so max|a| <= max|x|, which the producer has recorded at its own site;
                 // the pass records max|a| itself all the same (one guarded atomic per wave), so the report names the GEMM's operand.
                 // (profiling: both launches in class 2, "1x1 / in / out convolutions" -- the pass with no FLOPs of its own, the GEMM with those it executes)
-                int* site = range_site("max|FIR planes| (operand of the down-sampling GEMM)");
+                // (the name tells the two layouts apart: tests/test_hip_down_phase.py reads from it which pair an engine took)
+                int* site = range_site(phase ? "max|FIR planes| (operand of the down-sampling GEMM, every distinct plane once)"
+                                             : "max|FIR planes| (operand of the down-sampling GEMM, all nine)");
                 hipEvent_t e0 = prof_begin(2, 0.0);
-                note(launch_down_planes(in.p0, in.bs0, a.p, a.bs(), B, L.cin, H, W, st, site), "down_planes");
+                if (phase) note(launch_down_phase_planes(in.p0, in.bs0, a.p, a.bs(), B, L.cin, H, W, st, site), "down_phase_planes");
+                else note(launch_down_planes(in.p0, in.bs0, a.p, a.bs(), B, L.cin, H, W, st, site), "down_planes");
                 if (e0) (void)hipEventRecord(e0, st);
-                const ConvParams p = down_gemm_params(a.p, blob(L.w_dg), blob(L.b), blob(L.ws_dg) + 1, cur.p, B, L.cin, L.cout, H / 2, W / 2, fs.p, h->cfg.gn_num_groups);
+                const ConvParams p = down_gemm_params(a.p, blob(L.w_dg), blob(L.b), blob(L.ws_dg) + 1, cur.p, B, L.cin, L.cout, H / 2, W / 2, fs.p, h->cfg.gn_num_groups, phase);
                 last_reverse = -1;
                 hipEvent_t e1 = prof_begin(2, 2.0 * B * (double)L.cout * 9 * L.cin * (H / 2) * (W / 2));
-                note(launch_proj_f16x2(p, st, /*bias_rowfac=*/true), "down_gemm");
+                note(launch_proj_f16x2(p, st, phase ? DOWN_PHASE : DOWN_NINE), "down_gemm");
                 if (e1) (void)hipEventRecord(e1, st);
             }
             drop(a);

@@ -231,8 +231,20 @@ int32_t r2dm_down_gemm_stat_slots(int32_t cin, int32_t cout, int32_t G, int32_t 
     return cpg >= 8 && cpg <= 64 && !(cpg & (cpg - 1)) ? conv_stat_slots(H / 2, W / 2) : 0;
 }
 
-int r2dm_down_gemm(const float* x, const float* w, const float* bias, float* w_packed, float* planes, float* y, double* stat, int32_t B, int32_t cin,
-                   int32_t cout, int32_t G, int32_t H, int32_t W, void* stream) {
+int r2dm_down_phase_planes(const float* x, float* planes, int32_t B, int32_t C, int32_t H, int32_t W, void* stream) {
+    if (!x || !planes) return fail(1, "null argument");
+    if (B < 1 || C < 1 || !down_phase_planes_supported(H, W)) return fail(1, "down_phase_planes: needs height %% 4 == 0 and width %% 8 == 0 (>= 16)");
+    HIP_TRY(launch_down_phase_planes(x, (long)C * H * W, planes, down_phase_planes_floats(C, H, W), B, C, H, W, (hipStream_t)stream));
+    return 0;
+}
+
+int64_t r2dm_down_phase_planes_floats(int32_t C, int32_t H, int32_t W) {
+    return C < 1 || !down_phase_planes_supported(H, W) ? 0 : down_phase_planes_floats(C, H, W);
+}
+
+// phase: the operand with every distinct plane stored once (r2dm_down_gemm) | all nine planes (r2dm_down_gemm_nine); `planes` is sized for nine either way
+static int down_gemm_entry(const float* x, const float* w, const float* bias, float* w_packed, float* planes, float* y, double* stat, int32_t B, int32_t cin,
+                           int32_t cout, int32_t G, int32_t H, int32_t W, void* stream, bool phase) {
     if (!x || !w || !bias || !w_packed || !planes || !y) return fail(1, "null argument");
     if (B < 1 || H < 4 || W < 16 || !down_planes_supported(H, W) || !proj_f16x2_supported(9 * cin, cout, 1, H / 2, W / 2))
         return fail(1, "down_gemm: needs cin %% 32 == 0, cout %% 64 == 0, height %% 8 == 0, width %% 128 == 0");
@@ -243,10 +255,21 @@ int r2dm_down_gemm(const float* x, const float* w, const float* bias, float* w_p
     HIP_TRY(hipMemsetAsync(tail, 0, sizeof(int), st));
     HIP_TRY(launch_pack_proj_f16x2(w, w_packed, cout, 9 * cin, (int*)tail, st, tail + 2, 9));
     const int Ho = H / 2, Wo = W / 2;
-    HIP_TRY(launch_down_planes(x, (long)cin * H * W, planes, 9L * cin * Ho * Wo, B, cin, H, W, st));
-    const ConvParams p = down_gemm_params(planes, w_packed, bias, tail + 3, y, B, cin, cout, Ho, Wo, stat, G);
-    HIP_TRY(launch_proj_f16x2(p, st, /*bias_rowfac=*/true));
+    if (phase) HIP_TRY(launch_down_phase_planes(x, (long)cin * H * W, planes, down_phase_planes_floats(cin, H, W), B, cin, H, W, st));
+    else HIP_TRY(launch_down_planes(x, (long)cin * H * W, planes, 9L * cin * Ho * Wo, B, cin, H, W, st));
+    const ConvParams p = down_gemm_params(planes, w_packed, bias, tail + 3, y, B, cin, cout, Ho, Wo, stat, G, phase);
+    HIP_TRY(launch_proj_f16x2(p, st, phase ? DOWN_PHASE : DOWN_NINE));
     return 0;
+}
+
+int r2dm_down_gemm(const float* x, const float* w, const float* bias, float* w_packed, float* planes, float* y, double* stat, int32_t B, int32_t cin,
+                   int32_t cout, int32_t G, int32_t H, int32_t W, void* stream) {
+    return down_gemm_entry(x, w, bias, w_packed, planes, y, stat, B, cin, cout, G, H, W, stream, true);
+}
+
+int r2dm_down_gemm_nine(const float* x, const float* w, const float* bias, float* w_packed, float* planes, float* y, double* stat, int32_t B, int32_t cin,
+                        int32_t cout, int32_t G, int32_t H, int32_t W, void* stream) {
+    return down_gemm_entry(x, w, bias, w_packed, planes, y, stat, B, cin, cout, G, H, W, stream, false);
 }
 
 int r2dm_fir_up2(const float* x, float* y, int32_t B, int32_t C, int32_t H, int32_t W, void* stream) {

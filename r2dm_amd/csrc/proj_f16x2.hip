@@ -37,12 +37,17 @@ constexpr int LDS_TOTAL = PATCH0 + 4 * 1024;  // 55 296
 // NPLK = operand planes in use: 2 = the split arithmetic (parity path), 1 = the h plane alone: one fp16 product per MAC, the
 // reduced-precision bulk mode (conv_f16x2.hip); the l planes are then neither written nor read.
 // FIRB: the bias takes the FIR's row factor (conv_epilogue.h) -- the down-sampling GEMM over the nine filtered planes of resample.hip's down_planes_kernel
-template <int PRO, int NPLK, int IOM = 0, bool FIRB = false>
+// PHP (with FIRB): x is the phase layout of down_planes_phase_kernel -- [phase E, O][Cin / 9][2 H + 3 rows][W + 4].  A 32-value chunk lies inside one tap (ky, kx)
+// (Cin / 9 is a multiple of 32), so per chunk the loader picks the phase (kx = 1: O), the row (down_phase_row) and the column shift (kx = 0: one to the left,
+// 4-byte aligned quads); same values in the same K order as the nine planes: bit-identical output.
+using f32x4u = float __attribute__((ext_vector_type(4), aligned(4)));
+template <int PRO, int NPLK, int IOM = 0, bool FIRB = false, bool PHP = false>
 __global__ __launch_bounds__(256, 2) void proj_f16x2_kernel(const ConvParams p) {
     constexpr bool X16 = (IOM & 1) != 0, Y16 = (IOM & 2) != 0;  // (round 6) fp16 storage of the input tensor(s) / of the output (+ residual): the one-plane mode's skip convolutions
     using namespace p1;
     using gcf4 = const f32x4 __attribute__((address_space(1)))*;
     using gcu4 = const u32x4 __attribute__((address_space(1)))*;
+    using gcf4u = const f32x4u __attribute__((address_space(1)))*;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     f16_saturate_mode();
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
@@ -66,12 +71,26 @@ __global__ __launch_bounds__(256, 2) void proj_f16x2_kernel(const ConvParams p) 
     const int c0 = p.x.p1 ? p.x.c0 : p.Cin;  // (a chunk group of 8 never straddles the seam: launcher)
     const float* affb = PRO != PRO_NONE ? reinterpret_cast<const float*>(p.aff) + (size_t)b * p.Cin * 2 : nullptr;
     const unsigned char* wsrc = reinterpret_cast<const unsigned char*>(p.w) + (size_t)cot * nchunks * (2 * CO_T * CKP * 2);
+    // (PHP) this thread's quad in the rows holding V[ky][its image row], the channel stride, and the tap / first channel of the next chunk to load
+    const int cin1 = p.Cin / 9, pchan = (2 * H + 3) * (W + 4);
+    const int pcol = 4 + tw * TW + (q & 15) * 4, irow = th * TH + (q >> 4);
+    int tap_n = 0, ci_n = 0;
 
     f32x4 raw[8], ad4[4];
     u32x4 wv[2];
     auto load_chunk = [&](int c) __attribute__((always_inline)) {
         const int ch = c * CKP + cg * 8;
-        if constexpr (X16) {  // (element offsets: load4 addresses halves)
+        if constexpr (PHP) {  // (chunks are loaded in order)
+            const int ky = tap_n / 3, kx = tap_n - 3 * ky;
+            const float* pl = xb0 + (kx == 1 ? (long)cin1 * pchan : 0L) + (long)(ci_n + cg * 8) * pchan + (down_phase_row(ky, irow, H) * (W + 4) + pcol) - (kx == 0);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) raw[i] = *(gcf4u)(pl + (long)i * pchan);
+            ci_n += CKP;
+            if (ci_n == cin1) {
+                ci_n = 0;
+                ++tap_n;
+            }
+        } else if constexpr (X16) {  // (element offsets: load4 addresses halves)
             const float* px = ch < c0 ? p.x.p0 : p.x.p1;
             const long e0 = (ch < c0 ? b * p.x.bs0 + (long)ch * HW : b * p.x.bs1 + (long)(ch - c0) * HW) + poff;
 #pragma unroll
@@ -188,7 +207,7 @@ constexpr int PATCH0T = 2 * XPLT + 2 * WPLT;  // 51 200
 constexpr int LDS_TALL = PATCH0T + 4 * 1024;  // 55 296: two blocks per CU
 }  // namespace p1
 
-template <int PRO, int NPLK, bool FIRB = false>
+template <int PRO, int NPLK, bool FIRB = false, bool PHP = false>  // PHP: as proj_f16x2_kernel; one pixel per thread, so the column shift of kx = 0 is free
 __global__ __launch_bounds__(256, 2) void proj_tall_f16x2_kernel(const ConvParams p) {
     using namespace p1;
     using gcf = const float __attribute__((address_space(1)))*;
@@ -220,15 +239,31 @@ __global__ __launch_bounds__(256, 2) void proj_tall_f16x2_kernel(const ConvParam
     const float* affb = PRO != PRO_NONE ? reinterpret_cast<const float*>(p.aff) + (size_t)b * p.Cin * 2 : nullptr;
     constexpr int WCH = 2 * CO_T * CKP * 2;  // bytes of one (co tile, chunk) in the packed weights: planes h, l
     const unsigned char* wsrc = reinterpret_cast<const unsigned char*>(p.w) + (size_t)(cob * 4) * nchunks * WCH;
+    // (PHP) this thread's pixel in the rows holding V[ky][the block's image row], the channel stride, and the tap / first channel of the next chunk to load
+    const int cin1 = p.Cin / 9, pchan = (2 * H + 3) * (W + 4);
+    const int pcol = 4 + tw * TW + px, irow = th * TH + row;
+    int tap_n = 0, ci_n = 0;
 
     float raw[8];
     f32x4 ad4[4];
     u32x4 wv[4][2];
     auto load_chunk = [&](int c) __attribute__((always_inline)) {
         const int ch = c * CKP + cg * 8;
+        if constexpr (PHP) {  // (chunks are loaded in order)
+            const int ky = tap_n / 3, kx = tap_n - 3 * ky;
+            const float* pl = xb0 + (kx == 1 ? (long)cin1 * pchan : 0L) + (long)(ci_n + cg * 8) * pchan + (down_phase_row(ky, irow, H) * (W + 4) + pcol) - (kx == 0);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) raw[i] = ((gcf)pl)[(long)i * pchan];
+            ci_n += CKP;
+            if (ci_n == cin1) {
+                ci_n = 0;
+                ++tap_n;
+            }
+        } else {
         const float* pl = ch < c0 ? xb0 + (long)ch * HW : xb1 + (long)(ch - c0) * HW;
 #pragma unroll
         for (int i = 0; i < 8; ++i) raw[i] = ((gcf)pl)[(long)i * HW + poff];
+        }
         if (PRO != PRO_NONE) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) ad4[j] = *(gcf4)(affb + (size_t)(ch + 2 * j) * 2);
@@ -366,9 +401,9 @@ hipError_t launch_pack_proj_f16x2(const float* w, float* dst, int Cout, int Cin,
     return hipGetLastError();
 }
 
-template <int PRO, int NPLK, bool FIRB = false>
+template <int PRO, int NPLK, bool FIRB = false, bool PHP = false>
 static hipError_t launch_p1_tall(const ConvParams& p, hipStream_t s) {
-    auto kern = proj_tall_f16x2_kernel<PRO, NPLK, FIRB>;
+    auto kern = proj_tall_f16x2_kernel<PRO, NPLK, FIRB, PHP>;
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, p1::LDS_TALL);
@@ -380,9 +415,9 @@ static hipError_t launch_p1_tall(const ConvParams& p, hipStream_t s) {
     return hipGetLastError();
 }
 
-template <int PRO, int NPLK, int IOM = 0, bool FIRB = false>
+template <int PRO, int NPLK, int IOM = 0, bool FIRB = false, bool PHP = false>
 static hipError_t launch_p1(const ConvParams& p, hipStream_t s) {
-    auto kern = proj_f16x2_kernel<PRO, NPLK, IOM, FIRB>;
+    auto kern = proj_f16x2_kernel<PRO, NPLK, IOM, FIRB, PHP>;
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, p1::LDS_TOTAL);
@@ -394,7 +429,7 @@ static hipError_t launch_p1(const ConvParams& p, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_proj_f16x2(const ConvParams& p, hipStream_t s, bool bias_rowfac) {
+hipError_t launch_proj_f16x2(const ConvParams& p, hipStream_t s, int down) {
     if (!proj_f16x2_supported(p.Cin, p.Cout, p.taps, p.H, p.W)) return hipErrorInvalidValue;
     if (p.x.p1 && p.x.c0 % 8) return hipErrorInvalidValue;  // a thread's 8 channels must not straddle the concat seam
     if (p.prologue == PRO_AFFINE_SILU || (p.prologue != PRO_NONE && p.aff == nullptr)) return hipErrorInvalidValue;
@@ -403,8 +438,12 @@ hipError_t launch_proj_f16x2(const ConvParams& p, hipStream_t s, bool bias_rowfa
         if (!(p.x16 && p.y16) || p.pieces != 1 || p.prologue != PRO_NONE || p.res || p.stat) return hipErrorInvalidValue;
         return launch_p1<PRO_NONE, 1, 3>(p, s);
     }
-    if (bias_rowfac) {  // the down-sampling GEMM: plain input, the split arithmetic, no residual
+    if (down != DOWN_NONE) {  // the down-sampling GEMM: plain input, the split arithmetic, no residual
         if (p.pieces == 1 || p.prologue != PRO_NONE || p.res || p.x16 || p.y16) return hipErrorInvalidValue;
+        if (down == DOWN_PHASE) {  // one source, whole chunks inside a tap
+            if (p.x.p1 || p.Cin % (9 * p1::CKP)) return hipErrorInvalidValue;
+            return p.Cout % p1::COB == 0 ? launch_p1_tall<PRO_NONE, 2, true, true>(p, s) : launch_p1<PRO_NONE, 2, 0, true, true>(p, s);
+        }
         return p.Cout % p1::COB == 0 ? launch_p1_tall<PRO_NONE, 2, true>(p, s) : launch_p1<PRO_NONE, 2, 0, true>(p, s);
     }
     if (p.Cout % p1::COB == 0) {  // 256-channel blocks: every pixel staged Cout / 256 times instead of Cout / 64

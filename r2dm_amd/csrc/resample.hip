@@ -318,6 +318,103 @@ hipError_t launch_down_planes(const float* x, long xbs, float* a, long abs_, int
     return hipGetLastError();
 }
 
+// ---- down_planes, phase layout: only the planes that differ ---------------------------------------------------------------------
+// More than half of the nine planes are copies of each other.  Columns: A[ky][0][i][j] and A[ky][2][i][(j - 1) mod Wo] are the fir4 chain over the same four V values,
+// so two column phases exist -- E = the kx = 2 plane (kx = 0 reads it one column to the left, circularly), O = the kx = 1 plane.  Rows: V[2][i] and V[0][i + 1] read
+// the same four input rows with every tap indicator on for 1 <= i <= Ho - 3; only V[2][0], V[2][Ho - 2] and V[2][Ho - 1] are values of their own (the FIR zero-pads
+// the convolution's OUTPUT).  Same fir4 chains on the same operands as down_planes_kernel: every value is the bits of the nine-plane value it stands for.
+//   a: [B][phase E, O][C][2 Ho + 3 rows][Wo + 4] fp32; rows [0, Ho) = V[0], [Ho, 2 Ho) = V[1], then V[2][0], V[2][Ho - 2], V[2][Ho - 1] (down_phase_row);
+//   a row's data starts at float 4 (16-byte stores); float 3 of an E row holds column Wo - 1, so that column j - 1 of kx = 0 is a plain address at j = 0.
+// One thread -> a 2 x 4 patch of one channel: input rows 4 i2 - 2 .. 4 i2 + 5, columns 8t - 1 .. 8t + 9; eight 16-byte stores instead of eighteen (ten for the
+// first row pair, which adds V[2][0], twelve for the last, which adds V[2][Ho - 2] and V[2][Ho - 1]; fourteen at Ho = 2, where one pair is both).  range: max |a| over the distinct planes = the maximum over all nine.
+__global__ __launch_bounds__(256) void down_planes_phase_kernel(const float* __restrict__ x, long xbs, float* __restrict__ a, long abs_, int C, int H, int W,
+                                                                int* __restrict__ range) {
+    using f32x2 = __attribute__((ext_vector_type(2))) float;
+    const int Ho = H >> 1, Wo = W >> 1, Wq = Wo >> 2, Hq = Ho >> 1;
+    const int P = Wo + 4;
+    const long per_plane = (long)Hq * Wq, total = per_plane * C, chan = (long)(2 * Ho + 3) * P, phase = chan * C;
+    const int b = blockIdx.y;
+    float amax = 0.f;
+    for (long idx = blockIdx.x * 256L + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const int c = idx / per_plane;
+        const long rem = idx % per_plane;
+        const int i2 = rem / Wq, t = rem % Wq;
+        const float* xp = x + b * xbs + (long)c * H * W;
+        float* ac = a + b * abs_ + c * chan + 4 + 4 * t;  // phase E, row 0, this thread's quad
+        const int cl = t == 0 ? W - 1 : 8 * t - 1, cr = t == Wq - 1 ? 0 : 8 * t + 8;
+        float v[8][11];  // input rows 4 i2 - 2 + a, columns 8t - 1 .. 8t + 9; rows outside the image are zero
+#pragma unroll
+        for (int r8 = 0; r8 < 8; ++r8) {
+            const int r = 4 * i2 - 2 + r8;
+            const bool in = r >= 0 && r < H;
+            const float* row = xp + (long)(r < 0 ? 0 : r >= H ? H - 1 : r) * W;
+            const float l = row[cl];
+            const f32x2 rr = *reinterpret_cast<const f32x2*>(row + cr);
+            const f32x4 m0 = *reinterpret_cast<const f32x4*>(row + 8 * t), m1 = *reinterpret_cast<const f32x4*>(row + 8 * t + 4);
+            v[r8][0] = in ? l : 0.f;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                v[r8][1 + e] = in ? m0[e] : 0.f;
+                v[r8][5 + e] = in ? m1[e] : 0.f;
+            }
+            v[r8][9] = in ? rr[0] : 0.f;
+            v[r8][10] = in ? rr[1] : 0.f;
+        }
+#pragma unroll
+        for (int o = 0; o < 2; ++o) {
+            const int i = 2 * i2 + o;
+            bool on[4];  // FIR tap t falls on a real row of the convolution's output
+#pragma unroll
+            for (int tt = 0; tt < 4; ++tt) on[tt] = 2 * i - 1 + tt >= 0 && 2 * i - 1 + tt < H;
+#pragma unroll
+            for (int ky = 0; ky < 3; ++ky) {
+                if (ky == 2 && i != 0 && i < Ho - 2) continue;  // V[2][i] is V[0][i + 1]
+                float vv[11];  // V[ky][i] at the eleven columns: input row 2i - 2 + tt + ky = v[2 o + tt + ky]
+#pragma unroll
+                for (int e = 0; e < 11; ++e)
+                    vv[e] = fir4(on[0] ? v[2 * o + ky][e] : 0.f, on[1] ? v[2 * o + ky + 1][e] : 0.f, on[2] ? v[2 * o + ky + 2][e] : 0.f,
+                                 on[3] ? v[2 * o + ky + 3][e] : 0.f);
+                f32x4 oe, oo;  // output column 4t + j of tap column kx: input columns 2 (4t + j) + tt + kx - 2 = vv[2 j + kx - 1 + tt]
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    oe[j] = fir4(vv[2 * j + 1], vv[2 * j + 2], vv[2 * j + 3], vv[2 * j + 4]);
+                    oo[j] = fir4(vv[2 * j], vv[2 * j + 1], vv[2 * j + 2], vv[2 * j + 3]);
+                    amax = fmaxf(amax, fmaxf(fabsf(oe[j]), fabsf(oo[j])));
+                }
+                auto put = [&](int slot) __attribute__((always_inline)) {
+                    float* d = ac + (long)slot * P;
+                    *reinterpret_cast<f32x4*>(d) = oe;
+                    *reinterpret_cast<f32x4*>(d + phase) = oo;
+                    if (t == Wq - 1) d[-4 * t - 1] = oe[3];  // column Wo - 1 in front of column 0
+                };
+                if (ky < 2) put(ky * Ho + i);
+                else {  // (Ho = 2: row 0 is also row Ho - 2)
+                    if (i == 0) put(2 * Ho);
+                    if (i == Ho - 2) put(2 * Ho + 1);
+                    if (i == Ho - 1) put(2 * Ho + 2);
+                }
+            }
+        }
+    }
+    if (range) {
+        amax = wave_max_f32(amax);
+        if ((threadIdx.x & 63) == 0) {
+            const int bits = __float_as_int(amax);
+            if (bits > __atomic_load_n(range + 1, __ATOMIC_RELAXED)) atomicMax(range + 1, bits);
+        }
+    }
+}
+
+bool down_phase_planes_supported(int H, int W) { return down_planes_supported(H, W); }  // (H = 4 shares no row and is stored all the same: 7 rows for 6)
+
+long down_phase_planes_floats(int C, int H, int W) { return 2L * C * (H + 3) * (W / 2 + 4); }
+
+hipError_t launch_down_phase_planes(const float* x, long xbs, float* a, long abs_, int B, int C, int H, int W, hipStream_t s, int* range) {
+    if (!down_phase_planes_supported(H, W)) return hipErrorInvalidValue;
+    down_planes_phase_kernel<<<dim3(grid_for((long)C * (H / 4) * (W / 8)), B), 256, 0, s>>>(x, xbs, a, abs_, C, H, W, range);
+    return hipGetLastError();
+}
+
 // The bilinear weights of the up-sampler as ONE spelled-out chain, shared by its two kernels (round 6; as fir4 for the down-samplers): which kernel a map
 // takes depends on its size, and a sample must come out the same bits whatever batch it is part of (tests/test_hip_configs.py).
 __device__ __forceinline__ float up1(float far, float near) { return __builtin_fmaf(0.75f, near, 0.25f * far); }  // 3/4 of the nearer sample + 1/4 of the farther one
