@@ -67,6 +67,12 @@ void r2dm_destroy(r2dm_handle* h);
 int64_t r2dm_num_tensors(const r2dm_handle* h);
 int r2dm_tensor_at(const r2dm_handle* h, int64_t index, r2dm_tensor_info* out);
 size_t r2dm_blob_bytes(const r2dm_handle* h);
+/* The blob's parts that are STATE, not weights (byte offset and size; a checksum of "the weights" leaves them out -- distributed.py):
+ * the range-guard slots -- int32[2 * 256]: [0] the packers' "weight not finite" flag, which travels with the blob; [2 k + 1] site k's bound as
+ * float bits, a running maximum raised by every forward: whoever adopts a blob clears [1 ..] on its own stream -- and the constant
+ * coordinate map of in_conv (0 bytes without a coordinate encoding), which the first forward after a bind computes from the weights. */
+int r2dm_blob_flag_region(const r2dm_handle* h, size_t* offset, size_t* bytes);
+int r2dm_blob_cmap_region(const r2dm_handle* h, size_t* offset, size_t* bytes);
 
 /* Fingerprint of the blob's LAYOUT as this handle planned it: every slot's key, offset and packing (algorithm, channel / pixel tile of
  * each convolution's packings -- they depend on max_batch, the device's CU count and experiment switches, not only on the
@@ -403,6 +409,11 @@ int r2dm_group_norm_affine(const float* x, const float* gamma, const float* beta
                            int32_t width, int32_t groups, float eps, void* stream);
 int r2dm_affine_act(const float* x, const float* aff, float* y, int32_t batch, int32_t channels, int64_t hw,
                     int32_t silu, void* stream);
+/* The same fold from a statistics sink the producers' epilogues filled -- stat: (B, groups, slots, 2) doubles [sum, sum of squares], every slot written --
+ * i.e. the finalize kernel of the engine's walk alone (the consumer-side fold of conv_f16x2.hip repeats its arithmetic bit for bit); no range flag.
+ * Kernel-level test hook, like r2dm_affine_act. */
+int r2dm_group_norm_from_stats(const double* stat, int32_t slots, const float* gamma, const float* beta, const float* ada, float* aff, float* stats,
+                               int32_t batch, int32_t channels, int32_t height, int32_t width, int32_t groups, float eps, void* stream);
 /* ops.Resample(down=2) / (up=2) (models/ops.py:52-146) */
 int r2dm_fir_down2(const float* x, float* y, int32_t batch, int32_t channels, int32_t height, int32_t width,
                    void* stream);

@@ -62,6 +62,8 @@ SIGNATURES = {
     "r2dm_num_tensors": (c_int64, [_P]),
     "r2dm_tensor_at": (c_int32, [_P, c_int64, POINTER(TensorInfo)]),
     "r2dm_blob_bytes": (c_size_t, [_P]),
+    "r2dm_blob_flag_region": (c_int32, [_P, POINTER(c_size_t), POINTER(c_size_t)]),
+    "r2dm_blob_cmap_region": (c_int32, [_P, POINTER(c_size_t), POINTER(c_size_t)]),
     "r2dm_blob_layout_hash": (ctypes.c_uint64, [_P]),
     "r2dm_bind_blob": (c_int32, [_P, _P, c_size_t]),
     "r2dm_load_tensor": (c_int32, [_P, c_int64, _P, c_int64, _P]),
@@ -91,6 +93,7 @@ SIGNATURES = {
     "r2dm_group_norm_affine": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32,
                                          c_float, _P]),
     "r2dm_affine_act": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int64, c_int32, _P]),
+    "r2dm_group_norm_from_stats": (c_int32, [_P, c_int32, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, _P]),
     "r2dm_fir_down2": (c_int32, [_P, _P, c_int32, c_int32, c_int32, c_int32, _P]),
     "r2dm_fir_down2_stat_slots": (c_int32, [c_int32, c_int32, c_int32, c_int32]),
     "r2dm_fir_down2_stats": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),

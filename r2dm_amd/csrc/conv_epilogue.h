@@ -118,10 +118,11 @@ __device__ __forceinline__ void epi_stat_write_bfly8(const ConvParams& p, double
     }
 }
 
-// conv_f16x2.hip's tile ends (round 6): the wave's share of a statistics slot -- 2 quarters x 64 lanes x 4 pixels of an 8-channel block, 512 values -- is summed in
-// fp32 (pairwise: 2 + 1 + 6 butterfly levels, ~1e-7 relative, unbiased and independent from slot to slot: a group's >= 128 slots average it down to ~1e-8), fp64 from
-// the slot on (gn_finalize / the folded GroupNorm).  One instruction per exchange instead of two plus a half-rate add and sixteen conversions: with the range maximum
-// taken from the sums of squares, -0.9 % on the step (profiles/r06_tile_end_diet.txt); -DF2_STATS_F64 restores the fp64 butterfly above.
+// conv_f16x2.hip's ONE-plane instance (the fp16 bulk mode): the wave's share of a statistics slot -- 2 quarters x 64 lanes x 4 pixels of an 8-channel block, 512 values -- is
+// summed in fp32 (pairwise: 2 + 1 + 6 butterfly levels, ~1e-7 relative), fp64 from the slot on (gn_finalize / the folded GroupNorm).  One instruction per exchange instead of
+// two plus a half-rate add and sixteen conversions (profiles/r06_tile_end_diet.txt).  NOT for the parity modes: gn_moments forms var = E[x^2] - mean^2, which multiplies the
+// sums' relative error by (mean / sigma)^2 -- at |mean| / sigma = 16 the normalised tensor was 8 ... 30 times further from fp64 than an fp32 GroupNorm on groups of 4 ... 32
+// slots (tests/test_hip_gn_dc_offset.py, profiles/gn_dc_offset.txt).  The two-plane instances take the fp64 butterfly above: four pixels in fp32, fp64 beyond.
 __device__ __forceinline__ void epi_stat_write_bfly8(const ConvParams& p, float (&st_s)[4], float (&st_q)[4], int b, int th,
                                                      int tw, int nTw, int co_half, int wave_px, int lane) {
     using gdouble = double __attribute__((address_space(1)))*;

@@ -111,6 +111,7 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(const ConvParams p, 
     static_assert(NPLK == 1 || NPLK == 2, "planes");
     static_assert(IOM == 0 || (NPLK == 1 && PRO != PRO_PRESPLIT), "fp16 storage: the one-plane mode");
     constexpr bool X16 = (IOM & 1) != 0, Y16 = (IOM & 2) != 0;
+    using StatT = std::conditional_t<NPLK == 2, double, float>;  // a statistics slot's sums beyond four pixels (half_stats)
     constexpr int XE = X16 ? 2 : 4, YE = Y16 ? 2 : 4;  // bytes per stored element
     using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
     static_assert((MRK == 2 && (NRK == 2 || NRK == 4)) || (MRK == 4 && NRK == 2) || (MRK == 1 && NRK == 2), "tile family");
@@ -870,21 +871,12 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(const ConvParams p, 
 #endif
                     }
                     if ((k & 1) && p.stat) {  // a pair of quarters = one image row of one 32-channel half = one statistics slot: the multipliers' half_stats
-#ifndef F2_STATS_F64
-                        float st_s[4], st_q[4];
+                        StatT st_s[4], st_q[4];  // (two planes: four pixels in fp32, fp64 beyond; one plane: fp32 to the slot -- half_stats)
 #pragma unroll
                         for (int k8 = 0; k8 < 4; ++k8) {
-                            st_s[k8] = ps[0][k8] + ps[1][k8];
-                            st_q[k8] = pq[0][k8] + pq[1][k8];
+                            st_s[k8] = (StatT)ps[0][k8] + (StatT)ps[1][k8];
+                            st_q[k8] = (StatT)pq[0][k8] + (StatT)pq[1][k8];
                         }
-#else
-                        double st_s[4], st_q[4];
-#pragma unroll
-                        for (int k8 = 0; k8 < 4; ++k8) {
-                            st_s[k8] = (double)ps[0][k8] + (double)ps[1][k8];
-                            st_q[k8] = (double)pq[0][k8] + (double)pq[1][k8];
-                        }
-#endif
                         const int mm = qd >> 1;
                         if constexpr (NR == 4) epi_stat_write_bfly8(p, st_s, st_q, b, 2 * th + (wave >> 1), tw, nTw, cot * COT + (mm >> 1) * 32, 2 * (wave & 1) + (mm & 1), ln);
                         else epi_stat_write_bfly8(p, st_s, st_q, b, th, tw, nTw, cot * COT + mm * 32, wave, ln);
@@ -1243,21 +1235,15 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(const ConvParams p, 
     auto half_stats = [&](auto M, const float (&s0)[4], const float (&q0)[4], const float (&s1)[4], const float (&q1)[4], int b, int th,
                           int tw, int cot, int ln) __attribute__((always_inline)) {
         if (!p.stat) return;
-#ifndef F2_STATS_F64
-        float st_s[4], st_q[4];
+        // The parity path (two planes) is cancellation-safe: four pixels in fp32, fp64 beyond, as conv_epilogue_wide -- var = E[x^2] - mean^2 multiplies the
+        // relative error of the sums by (mean / sigma)^2, and a residual stream with a DC component has |mean| / sigma of 16 and more
+        // (tests/test_hip_gn_dc_offset.py, profiles/gn_dc_offset.txt).  The one-plane bulk mode keeps the slot's 512 values in fp32 (conv_epilogue.h).
+        StatT st_s[4], st_q[4];
 #pragma unroll
         for (int k8 = 0; k8 < 4; ++k8) {
-            st_s[k8] = s0[k8] + s1[k8];
-            st_q[k8] = q0[k8] + q1[k8];
+            st_s[k8] = (StatT)s0[k8] + (StatT)s1[k8];
+            st_q[k8] = (StatT)q0[k8] + (StatT)q1[k8];
         }
-#else
-        double st_s[4], st_q[4];
-#pragma unroll
-        for (int k8 = 0; k8 < 4; ++k8) {  // (four pixels in fp32, fp64 beyond: conv_epilogue.h)
-            st_s[k8] = (double)s0[k8] + (double)s1[k8];
-            st_q[k8] = (double)q0[k8] + (double)q1[k8];
-        }
-#endif
         // M = index of a pair of quarters (2 M, 2 M + 1): one image row of one 32-channel half -- a statistics slot.  Four-row tiles: the
         // half is M, the slot (tile, wave).  The eight-row tile's wave owns rows 2 wave, 2 wave + 1: half M / 2, and the slot is the one the
         // four-row tiling gives that row -- tile row 2 th + wave / 2, "wave" 2 (wave % 2) + M % 2: same slots, same sums, same order.

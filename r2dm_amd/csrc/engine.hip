@@ -58,6 +58,21 @@ int r2dm_tensor_at(const r2dm_handle* h, int64_t i, r2dm_tensor_info* out) {
 }
 
 size_t r2dm_blob_bytes(const r2dm_handle* h) { return h ? h->blob_floats * sizeof(float) : 0; }
+// The two parts of the blob that are not weights: the range-guard slots -- int[2 RANGE_SITES]: [0] the packers' weight flag, [2 k + 1] the running maximum of
+// site k, raised by every forward -- and in_conv's constant coordinate map, which the first forward after a bind computes from the weights.
+int r2dm_blob_flag_region(const r2dm_handle* h, size_t* offset, size_t* bytes) {
+    if (!h || !offset || !bytes) return fail(1, "null argument");
+    *offset = h->range_flag * sizeof(float);
+    *bytes = 2 * r2dm_handle::RANGE_SITES * sizeof(int);
+    return 0;
+}
+int r2dm_blob_cmap_region(const r2dm_handle* h, size_t* offset, size_t* bytes) {
+    if (!h || !offset || !bytes) return fail(1, "null argument");
+    const r2dm_config& c = h->cfg;
+    *offset = c.coord_channels > 0 ? h->cmap * sizeof(float) : 0;
+    *bytes = c.coord_channels > 0 ? (size_t)c.base_channels * c.height * c.width * sizeof(float) : 0;
+    return 0;
+}
 int r2dm_bind_blob(r2dm_handle* h, void* blob, size_t bytes) {
     if (!h || !blob) return fail(1, "null argument");
     if (bytes < r2dm_blob_bytes(h)) return fail(1, "blob too small: %zu < %zu", bytes, r2dm_blob_bytes(h));
@@ -66,7 +81,9 @@ int r2dm_bind_blob(r2dm_handle* h, void* blob, size_t bytes) {
     h->cmap_ready = false;
     // The range flags travel WITH the blob: [0] (a weight outside the fp16 range, raised by the packers) must survive a bind
     // on another rank, and nothing here may touch device memory behind the caller's streams.  A blob that is filled through
-    // r2dm_load_tensor gets both flags cleared by the first load after this bind, on the packing stream.
+    // r2dm_load_tensor gets both flags cleared by the first load after this bind, on the packing stream.  The site bounds [1..] of an
+    // adopted blob are the SOURCE's running maxima, not this handle's: the caller clears them on its own stream (r2dm_blob_flag_region;
+    // unet.py adopt_packed_weights) -- not here, for the same reason.
     h->flags_fresh = false;
     return 0;
 }

@@ -197,6 +197,15 @@ int r2dm_group_norm_affine(const float* x, const float* gamma, const float* beta
     return 0;
 }
 
+int r2dm_group_norm_from_stats(const double* stat, int32_t slots, const float* gamma, const float* beta, const float* ada, float* aff, float* stats,
+                               int32_t B, int32_t C, int32_t H, int32_t W, int32_t groups, float eps, void* stream) {
+    if (!stat || !aff) return fail(1, "null argument");
+    if (B < 1 || slots < 1 || groups < 1 || C % groups) return fail(1, "group_norm_from_stats: %d slots, %d channels in %d groups", slots, C, groups);
+    GNParams g{Src{nullptr, nullptr, C, 0, (long)C * H * W, 0}, B, H, W, groups, eps, gamma, beta, ada, 2L * C, const_cast<double*>(stat), (float2*)aff, stats};
+    HIP_TRY(launch_group_norm_finalize(g, C, slots, (hipStream_t)stream));  // (no partial_max, no range flag: the finalize kernel reads the sink alone)
+    return 0;
+}
+
 int r2dm_affine_act(const float* x, const float* aff, float* y, int32_t B, int32_t C, int64_t hw, int32_t silu,
                     void* stream) {
     HIP_TRY(launch_gn_apply(x, (const float2*)aff, y, B, C, hw, silu, (hipStream_t)stream));

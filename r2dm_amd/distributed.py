@@ -59,9 +59,11 @@ def broadcast_packed_weights(model, device, src: int = 0) -> None:
         model.adopt_packed_weights(wire.to(device) if on_host else wire, layout_hash=meta[0])
 
 
-def blob_checksum(blob: torch.Tensor) -> int:
+def blob_checksum(blob: torch.Tensor, skip=()) -> int:
     """A 63-bit checksum of a packed weight blob, computed where the blob lives: the wrapping sum of its 8-byte words, each multiplied by an
-    odd weight that depends on its position (word i times 2 i + 1) -- a plain sum would not notice two words changing places."""
+    odd weight that depends on its position (word i times 2 i + 1) -- a plain sum would not notice two words changing places.
+    ``skip``: ``[(byte offset, bytes)]``, multiples of 8, that count as zeros -- the blob's state regions (``packed_state_regions()``: the range
+    guard's running maxima change with every forward and differ from rank to rank although the weights are the same)."""
     blob = blob.reshape(-1)
     if blob.dtype != torch.uint8:
         blob = blob.view(torch.uint8)
@@ -71,7 +73,12 @@ def blob_checksum(blob: torch.Tensor) -> int:
     words = blob[:n].view(torch.int64)
     weight = torch.arange(words.numel(), dtype=torch.int64, device=words.device) * 2 + 1
     tail = int((blob[n:].to(torch.int64) * torch.arange(1, blob.numel() - n + 1, dtype=torch.int64, device=blob.device)).sum().item()) if n < blob.numel() else 0
-    return (int((words * weight).sum().item()) + tail) & 0x7FFFFFFFFFFFFFFF
+    total = (words * weight).sum()  # (int64 arithmetic wraps: sums and differences of it are exact modulo 2^64)
+    for off, size in skip:
+        if off % 8 or size % 8 or off < 0 or off + size > n:
+            raise ValueError(f"skipped region ({off}, {size}) is not a run of whole 8-byte words inside the blob's {blob.numel()} bytes")
+        total = total - (words[off // 8:(off + size) // 8] * weight[off // 8:(off + size) // 8]).sum()
+    return (int(total.item()) + tail) & 0x7FFFFFFFFFFFFFFF
 
 
 def collective_report(model=None, device=None) -> dict:
@@ -81,7 +88,10 @@ def collective_report(model=None, device=None) -> dict:
     td = _dist()
     if td is None or td.get_world_size() == 1:
         return {"backend": None, "world_size": 1, "blob_crc_equal_on_all_ranks": None}
-    crc = blob_checksum(model.packed_weights(device)) if model is not None else 0
+    # (the weights alone: the blob also carries the range guard's running maxima, which every forward raises -- ranks that have sampled different seeds hold
+    # different ones -- and the constant map of in_conv, zero until a rank's first forward)
+    skip = model.packed_state_regions() if hasattr(model, "packed_state_regions") else ()
+    crc = blob_checksum(model.packed_weights(device), skip) if model is not None else 0
     on_host = td.get_backend() != "nccl"
     t = torch.tensor([crc, -crc], dtype=torch.int64, device="cpu" if on_host else device)
     td.all_reduce(t, op=td.ReduceOp.MIN)  # (min(crc), min(-crc) = -max(crc))

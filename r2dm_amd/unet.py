@@ -105,6 +105,16 @@ class _Engine:
     def layout_hash(self) -> int:
         return int(_lib.lib().r2dm_blob_layout_hash(self.h))
 
+    def state_regions(self):
+        """``[(byte offset, bytes)]`` of the blob's parts that are not weights: the range-guard slots and in_conv's constant map."""
+        L, out = _lib.lib(), []
+        for fn in (L.r2dm_blob_flag_region, L.r2dm_blob_cmap_region):
+            off, n = ctypes.c_size_t(0), ctypes.c_size_t(0)
+            _lib.check(fn(self.h, ctypes.byref(off), ctypes.byref(n)))
+            if n.value:
+                out.append((int(off.value), int(n.value)))
+        return out
+
     def bind(self, blob: torch.Tensor):
         _lib.require_gpu(blob, "weight blob")
         assert blob.dtype == torch.uint8 and blob.is_contiguous()
@@ -248,6 +258,15 @@ class EfficientUNet(nn.Module):
         self._ensure_packed(device)
         return self._engine.blob
 
+    def packed_state_regions(self):
+        """``[(byte offset, bytes)]`` of the packed blob that hold STATE rather than weights -- the range guard's slots (running maxima that every
+        forward raises) and the constant coordinate map the first forward computes: what a checksum of the weights leaves out
+        (``distributed.blob_checksum(blob, skip=...)``)."""
+        if self._engine is None:
+            self._engine = _Engine(self.geometry, self.max_batch)
+            self.set_precision(self.precision)
+        return self._engine.state_regions()
+
     def packed_layout_hash(self) -> int:
         """Fingerprint of the blob layout THIS model's engine plans (r2dm_blob_layout_hash): the packings depend on ``max_batch``, the
         device's CU count and experiment switches, not only on the configuration -- a blob may only be adopted between equal layouts."""
@@ -272,6 +291,12 @@ class EfficientUNet(nn.Module):
         if blob.numel() != self._engine.blob_bytes():
             raise _lib.R2DMError(f"blob has {blob.numel()} bytes, engine expects {self._engine.blob_bytes()}")
         self._engine.bind(blob)
+        # The guard slots travel inside the blob: [0], the packers' weight flag, belongs to the weights and stays; the site bounds behind it are
+        # the SOURCE model's running maxima -- this model has run nothing yet.  Cleared here, on this model's stream (r2dm_bind_blob must not
+        # touch device memory behind the caller's streams).
+        off, n = self._engine.state_regions()[0]
+        with torch.cuda.device(blob.device):
+            blob[off + 4:off + n].zero_()
         self._packed_for = (blob.device.type, blob.device.index)
 
     def packed_weight_bytes(self) -> int:

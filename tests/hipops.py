@@ -132,6 +132,18 @@ def group_norm_affine(x, groups, eps, gamma=None, beta=None, ada=None):
     return aff, stats
 
 
+def group_norm_from_stats(stat, C, H, W, eps, gamma=None, beta=None, ada=None):
+    """(aff, stats) of gn_finalize_kernel over a statistics sink (B, groups, slots, 2) float64 as a producer's epilogue left it."""
+    B, groups, slots, two = stat.shape
+    assert two == 2 and stat.dtype == torch.float64 and stat.is_contiguous()
+    aff = torch.empty(B, C, 2, device=stat.device)
+    stats = torch.empty(B, groups, 2, device=stat.device)
+    _lib.check(_lib.lib().r2dm_group_norm_from_stats(stat.data_ptr(), slots, _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(ada), aff.data_ptr(), stats.data_ptr(),
+                                                     B, C, H, W, groups, eps, _st(stat)))
+    torch.cuda.synchronize()
+    return aff, stats
+
+
 def affine_act(x, aff, silu):
     L = _lib.lib()
     B, C, H, W = x.shape

@@ -368,3 +368,67 @@ def test_checkpoint_preflight_on_both_sides_of_the_trip_point(capsys):
     # ... and a discrete-time checkpoint (the sampler walks integer timesteps: /root/reference/models/diffusion/discrete_time.py:182-201)
     disc = check.preflight(synthetic_ckpt(timestep_type="discrete", num_training_steps=1000, noise_schedule="linear"), num_steps=4, batch=1, device=DEV)
     assert disc["condition"] == "timestep" and disc["trips"] == [] and len(disc["sites"]) > 40
+
+
+def test_weight_checksum_is_stable_across_a_forward():
+    """ADVICE round 6, finding 3: the 256 range-site slots live inside the weight blob and are running maxima, so a checksum of the whole
+    blob changed with every forward and collective_report called equal weights different.  The checksum of the weights (the blob without
+    packed_state_regions(): the guard slots and in_conv's constant map, which the first forward computes) is the same before the first
+    forward and after a forward plus check_range(); the whole blob's is not (the forward did raise bounds); and a changed weight still
+    shows."""
+    import r2dm_amd
+    from r2dm_amd import distributed as D
+
+    ddpm, _, _ = r2dm_amd.setup_model(synthetic_ckpt(resolution=GOLDEN_RES), device=DEV, show_info=False, max_batch=2)
+    m = ddpm.model
+    blob = m.packed_weights()  # (on the device the model was set up on: naming another spelling of it packs afresh)
+    skip = m.packed_state_regions()
+    assert skip and skip[0][1] == 2 * 256 * 4, skip
+    before, before_all = D.blob_checksum(blob, skip), D.blob_checksum(blob)
+    m(rnd(97, 2, 2, *GOLDEN_RES).to(DEV), torch.zeros(2, device=DEV))
+    m.check_range()
+    assert any(b > 0 for _, b in m.range_report()), "the forward raised no site bound: nothing tested"
+    assert m.packed_weights().data_ptr() == blob.data_ptr()
+    assert D.blob_checksum(blob, skip) == before
+    assert D.blob_checksum(blob) != before_all
+    off = sum(skip[0])  # (the first word behind the guard slots: a constant or a weight)
+    word = blob[off:off + 4].clone()
+    blob[off:off + 4] = word ^ 1
+    assert D.blob_checksum(blob, skip) != before
+    blob[off:off + 4] = word
+    assert D.blob_checksum(blob, skip) == before
+
+
+def test_adopted_blob_does_not_import_the_source_models_site_bounds():
+    """Same finding: adopt_packed_weights took the source rank's running maxima with the blob.  A model that adopts the blob of a model
+    that has sampled reports no site bound after its own first check_range() with nothing run (slot [0], the packers' weight flag, is
+    still carried: test_weight_flag_survives_blob_adoption)."""
+    import r2dm_amd
+
+    ck = synthetic_ckpt(resolution=GOLDEN_RES)
+    a, _, _ = r2dm_amd.setup_model(ck, device=DEV, show_info=False, max_batch=2)
+    a.sample(batch_size=2, num_steps=2, progress=False, rng=r2dm_amd.setup_rng([1, 2], DEV))
+    a.model.check_range()
+    assert any(b > 0 for _, b in a.model.range_report())
+    blob = a.model.packed_weights().clone()
+    b, _, _ = r2dm_amd.setup_model(ck, device="cpu", show_info=False, max_batch=2)
+    b.to(DEV)
+    b.model.adopt_packed_weights(blob, layout_hash=a.model.packed_layout_hash())
+    b.model.check_range()
+    assert all(bound == 0 for _, bound in b.model.range_report()), [r for r in b.model.range_report() if r[1] != 0][:4]
+    off, n = b.model.packed_state_regions()[0]
+    assert not blob[off + 4:off + n].any(), "site bounds of the source model in the adopter's blob"
+    # (range_report names the sites of a walk: with nothing run yet it has none to show.)  What the adopter reports after its OWN first forward --
+    # a quiet input, far below what the source sampled -- is what a freshly loaded model reports after the same forward, site by site.
+    x, c = 0.01 * rnd(96, 2, 2, *GOLDEN_RES).to(DEV), torch.zeros(2, device=DEV)
+    fresh, _, _ = r2dm_amd.setup_model(ck, device=DEV, show_info=False, max_batch=2)
+    want = fresh.model(x, c)
+    fresh.model.check_range()
+    got = b.model(x, c)
+    b.model.check_range()
+    assert torch.equal(got, want)
+    rep = b.model.range_report()
+    assert rep and any(bound > 0 for _, bound in rep) and rep == fresh.model.range_report()
+    a.model(x, c)
+    a.model.check_range()
+    assert rep != a.model.range_report(), "the source's larger maxima do not show: the comparison above proves nothing"
