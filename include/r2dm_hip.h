@@ -88,6 +88,11 @@ int r2dm_load_tensor(r2dm_handle* h, int64_t index, const float* dev_src, int64_
 size_t r2dm_workspace_bytes(const r2dm_handle* h, int32_t batch);
 int r2dm_unet_forward(r2dm_handle* h, const float* x, const float* cond, float* out, int32_t batch,
                       void* workspace, size_t workspace_bytes, void* stream);
+/* What a forward at this batch in the handle's precision mode enqueues, from the sizing walk (host only: no GPU, no weights, the handle unchanged): one
+ * text line per launch in enqueue order -- "layer | launch | out=<workspace offset, or dst> [| a convolution's kernel, tile, shape and fusions]
+ * [| range sites it hands out, profiling class]".  Writes at most cap - 1 characters and a NUL to buf (may be NULL); *need = the size that holds all of it.
+ * The dispatch tests compare it with tests/golden/forward_listing.json. */
+int r2dm_forward_listing(const r2dm_handle* h, int32_t batch, char* buf, size_t cap, size_t* need);
 
 /* -- arithmetic of the convolutions / attention core on the 16-bit matrix pipe (tensors and accumulation are fp32 in every mode):
  *      pieces = 2 (default, parity mode): every fp32 operand v is split to 22 bits, v = h + 2^-11 l with h = RNE_f16(v),

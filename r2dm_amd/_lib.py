@@ -69,6 +69,7 @@ SIGNATURES = {
     "r2dm_load_tensor": (c_int32, [_P, c_int64, _P, c_int64, _P]),
     "r2dm_workspace_bytes": (c_size_t, [_P, c_int32]),
     "r2dm_unet_forward": (c_int32, [_P, _P, _P, _P, c_int32, _P, c_size_t, _P]),
+    "r2dm_forward_listing": (c_int32, [_P, c_int32, _P, c_size_t, POINTER(c_size_t)]),
     "r2dm_set_conv_pieces": (c_int32, [_P, c_int32]),
     "r2dm_check_range": (c_int32, [_P, _P]),
     "r2dm_test_raise_range_bound": (c_int32, [_P, c_float, _P]),

@@ -113,6 +113,7 @@ struct r2dm_handle {
     // down_planes_phase_kernel); 9 = the same GEMM over all nine planes (down_planes_kernel: the A/B twin, bit-identical); 0 = the down stages keep Conv3x3 at the
     // finer resolution + fir_down2, as until round 6 (A/B, the parity test)
     int down_gemm = 1;
+    bool plan_fits16 = false;  // every layer of levels 1 and 2 got a packing whose kernel has fp16 activation storage (build_plan; the mode's part: run_forward)
     bool f16_path() const { return conv_pieces != 3; }  // operands go through fp16: their range is guarded
     bool flags_fresh = false;  // the blob's range flags have been cleared since the last r2dm_bind_blob (first load does it)
     size_t range_flag = 0;  // blob slot (RANGE_SITES pairs of ints, ALGO_F16X2): [0] != 0: a weight outside the fp16 range; [2 k + 1]: float
@@ -155,6 +156,10 @@ namespace r2dm {
 extern int g_single_kernel_pieces;  // precision mode of the single-kernel entries (r2dm_set_conv_pieces(NULL, ...); kernel_abi.hip)
 
 void build_plan(r2dm_handle* h);
+// a layer's own packing (plan.hip): the tile and the input-channel padding of the kernel `algo` names, and whether that kernel writes fused statistics
+int conv_base_co_tile(int algo, int cin, int cout, int taps, long px_batch);
+int conv_base_cin_pad(int algo, int cin, int taps, int co_tile);
+bool conv_emits_stats(int algo, int co_tile, int cout);
 int check_config(const r2dm_config& c);
 
 // ---- workspace arena -------------------------------------------------------------------------
@@ -217,8 +222,9 @@ struct Tensor {
     size_t bytes(int B) const { return (size_t)B * C * H * W * (f16 ? 2 : sizeof(float)); }
 };
 
-// one forward over the arena: dry (Arena::dry) it only measures the workspace, else it enqueues every kernel on `st` (forward.hip)
-int run_forward(r2dm_handle* h, Arena& ar, const float* x, const float* cond, float* out, int B, hipStream_t st);
+// one forward over the arena: dry (Arena::dry) it only measures the workspace, else it enqueues every kernel on `st` (forward.hip);
+// dry with a `listing`: one line per launch it would enqueue, the handle untouched (r2dm_forward_listing)
+int run_forward(r2dm_handle* h, Arena& ar, const float* x, const float* cond, float* out, int B, hipStream_t st, std::string* listing = nullptr);
 
 // ConvParams with the fields every launch sets, in the struct's order; aff / res / scale are null, everything else keeps its default
 inline ConvParams conv_params(const Src& x, const float* w, const float* bias, float* y, long y_bs, int B, int H, int W, int Cin, int CinPad, int Cout, int taps,
@@ -246,6 +252,15 @@ inline ConvParams conv_params(const Src& x, const float* w, const float* bias, f
     return p;
 }
 
+// where a convolution's epilogue leaves the GroupNorm statistics of its output: groups [goff, ...) of a sink of G groups, `slots` slots each
+inline void conv_stat_sink(ConvParams& p, double* stat, int G, int goff, int cpg, int slots) {
+    p.stat = stat;
+    p.stat_G = G;
+    p.stat_goff = goff;
+    p.stat_cpg = cpg;
+    p.stat_slots = slots;
+}
+
 // the down-sampling GEMM over launch_down_planes' output (B, 9 cin, Ho, Wo) or, `phase`, launch_down_phase_planes' (B, 2, cin, 2 Ho + 3, Wo + 4: launch it with
 // DOWN_PHASE): w / wscale its packed matrix and weight scale; stat (may be null): GroupNorm statistics of y for G groups in the convolution epilogues' slot grid
 inline ConvParams down_gemm_params(const float* planes, const float* w, const float* bias, const float* wscale, float* y, int B, int cin, int cout, int Ho,
@@ -255,13 +270,7 @@ inline ConvParams down_gemm_params(const float* planes, const float* w, const fl
     ConvParams p = conv_params(Src{planes, nullptr, K, 0, bs, 0}, w, bias, y, (long)cout * Ho * Wo, B, Ho, Wo, K, K, cout, 1, 64, ALGO_P1F16, PRO_NONE);
     p.pieces = 2;
     p.wscale = wscale;
-    if (stat) {
-        p.stat = stat;
-        p.stat_G = G;
-        p.stat_goff = 0;
-        p.stat_cpg = cout / G;
-        p.stat_slots = conv_stat_slots(Ho, Wo);
-    }
+    if (stat) conv_stat_sink(p, stat, G, 0, cout / G, conv_stat_slots(Ho, Wo));
     return p;
 }
 

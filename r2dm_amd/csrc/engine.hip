@@ -190,6 +190,21 @@ size_t r2dm_workspace_bytes(const r2dm_handle* hc, int32_t B) {
     return bytes;
 }
 
+int r2dm_forward_listing(const r2dm_handle* h, int32_t B, char* buf, size_t cap, size_t* need) {
+    if (!h || B < 1 || !need) return fail(1, "forward_listing: a handle, a batch >= 1 and `need`");
+    std::string s;
+    Arena ar{(char*)kAlign, 0, true};
+    // (the caller's output: any address the arena never hands out; the walk with a listing changes nothing in the handle)
+    if (int rc = run_forward(const_cast<r2dm_handle*>(h), ar, (const float*)kAlign, (const float*)kAlign, (float*)sizeof(float), B, nullptr, &s)) return rc;
+    *need = s.size() + 1;
+    if (buf && cap) {
+        const size_t n = std::min(s.size(), cap - 1);
+        memcpy(buf, s.data(), n);
+        buf[n] = 0;
+    }
+    return 0;
+}
+
 int r2dm_unet_forward(r2dm_handle* h, const float* x, const float* cond, float* out, int32_t B, void* ws,
                       size_t ws_bytes, void* stream) {
     if (!h || !x || !cond || !out || !ws) return fail(1, "null argument");

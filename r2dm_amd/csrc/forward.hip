@@ -29,17 +29,65 @@ struct Ctx {
     std::string ctx;
     int* range_site(const char* what) {
         const int k = n_sites + 1 < r2dm_handle::RANGE_SITES ? ++n_sites : 0;  // (beyond the table: the shared slot 0 -- still guarded, just not named)
-        if ((int)h->site_names.size() <= k) h->site_names.resize(k + 1);
-        h->site_names[k] = ctx.empty() ? std::string(what) : ctx + ": " + what;
+        if (lst) {  // (the line already names the layer)
+            pend += " site=" + std::to_string(k) + ":\"" + what + "\"";
+        } else {
+            if ((int)h->site_names.size() <= k) h->site_names.resize(k + 1);
+            h->site_names[k] = ctx.empty() ? std::string(what) : ctx + ": " + what;
+        }
         return (int*)blob(h->range_flag) + 2 * k;
     }
+
+    // ---- [listing> the listing (r2dm_forward_listing): with `lst` set the walk is dry, but builds every launch's parameters and writes a line where it would
+    // enqueue; the handle stays as it was (site names, profiling state, cmap_ready)
+    std::string* lst = nullptr;
+    const void* user_out = nullptr;  // the caller's output tensor ("dst" in the listing)
+    std::string pend;                // range sites, profiling class and refusals noted since the last line
+    bool skip() const { return dry() && !lst; }  // nothing to launch and nothing to list: only the allocations count
+    // "layer | launch | out=<arena offset> [| a convolution's ConvParams: what fixes the kernel instantiation and its side effects; flags only where set] [| notes]"
+    void list_line(const char* name, const void* out, const char* tag, const ConvParams* p) {
+        static const char* const algos[] = {"F32", "BF16X3", "DIRECT", "F16X2", "P1F16"};
+        char b[256];
+        std::string& s = *lst;
+        s += (ctx.empty() ? std::string("-") : ctx) + " | " + name + " | out=";
+        if (tag) s += tag;
+        else if (out == user_out) s += "dst";
+        else s += std::to_string((size_t)((const char*)out - ar->base));
+        if (p) {
+            snprintf(b, sizeof(b), " | algo=%s tile=%dx%d pieces=%d pro=%d cin=%d/%d cout=%d taps=%d hw=%dx%d", algos[p->algo], p->co_tile, p->px_rows, p->pieces, p->prologue, p->Cin,
+                     p->CinPad, p->Cout, p->taps, p->H, p->W);
+            s += b;
+            if (p->aff) s += " aff";
+            if (p->gn_partial) s += " fold=" + std::to_string(p->gn_slots) + "/" + std::to_string(p->gn_stride);  // (slots read / slot stride)
+            if (p->stat) s += " stat=" + std::to_string(p->stat_goff) + "/" + std::to_string(p->stat_cpg);        // (first group / channels per group)
+            if (p->res) s += p->res_bs ? " res" : " res=bcast";
+            if (p->scale) s += " scale";
+            if (p->x16) s += " x16";
+            if (p->y16) s += " y16";
+            if (p->reverse) s += " rev";
+            if (p->range) s += " range";
+        }
+        s += pend.empty() ? "" : " |" + pend;
+        s += "\n";
+        pend.clear();
+    }
+    // one launch: enqueued and noted, or (listing) written down; `out`: what it writes, `p`: a convolution's parameters
+    template <class F>
+    void run(const char* name, const void* out, F&& launch, const ConvParams* p = nullptr, const char* tag = nullptr) {
+        if (lst) list_line(name, out, tag, p);
+        else note(launch(), name);
+    }
+    // <listing] ----
 
     // (once the arena has handed out a pointer beyond the caller's workspace NOTHING more is launched -- the walk goes on
     // dry, so `peak` still comes out right for the error message -- instead of enqueueing kernels that write outside the workspace)
     bool dry() const { return ar->dry || ar->overflow; }
     void note(hipError_t e, const char* w) {
-        const bool debug_sync = g_debug_sync;  // fault hunting: wait for and name every launch
-        if (debug_sync && e == hipSuccess && !dry()) {
+        if (lst) {  // (a refusal: it surfaces from a real forward only; the listing shows it on the launch's line)
+            if (e != hipSuccess) pend += std::string(" refused=\"") + w + "\"";
+            return;
+        }
+        if (g_debug_sync && e == hipSuccess && !dry()) {  // fault hunting: wait for and name every launch
             fprintf(stderr, "[r2dm] %s ...", w);
             fflush(stderr);
             e = hipStreamSynchronize(st);
@@ -53,11 +101,7 @@ struct Ctx {
     const float* blob(size_t off) const { return h->blob + off; }
 
     Tensor make(int C, int H, int W, bool f16 = false) {
-        Tensor t;
-        t.C = C;
-        t.H = H;
-        t.W = W;
-        t.f16 = f16;
+        Tensor t{nullptr, C, H, W, f16};
         t.p = (float*)ar->alloc(t.bytes(B));
         return t;
     }
@@ -75,6 +119,7 @@ struct Ctx {
         int C = 0, cpg = 0, slots = 0;  // C: channels of the normalised (possibly concatenated) tensor
         bool incomplete = false;        // a producer could not emit its share: the consumer runs the streaming pass instead
         explicit operator bool() const { return p != nullptr && !incomplete; }
+        int read_slots() const { return cpg < 64 ? slots / 2 : slots; }  // (groups of fewer than 64 channels leave the second half of their slots zero)
     };
     Sink make_sink(int C_total, int H, int W) {
         Sink k;
@@ -93,19 +138,14 @@ struct Ctx {
         if (k.p) ar->release(k.p);
         k.p = nullptr;
     }
-    // which convolution kernels write fused statistics: the split-bf16 kernels and the fp32-MFMA kernel with >= 64-channel
-    // tiles; the 32-channel fp32 tile (Cout <= 32) and the direct kernel do not
-    static bool emits_stats(const ConvLayer& L) {
-        return L.algo == ALGO_BF16X3 || (L.algo == ALGO_F32 && L.co_tile >= 64) || (L.algo == ALGO_DIRECT && L.cout > 4);
-    }  // (and ALGO_F16X2, a second packing of a BF16X3 layer)
     float2* finalize(const Sink& k, int H, int W, const float* gamma, const float* beta, const float* ada) {
         float2* aff = (float2*)ar->alloc((size_t)B * k.C * sizeof(float2));
-        if (!dry()) {
+        if (!skip()) {
             GNParams g{Src{}, B, H, W, h->cfg.gn_num_groups, h->cfg.gn_eps, gamma, beta, ada, (long)h->ada_rows, k.p, aff,
                        nullptr};
             // (range guard of the fp16 consumers: the slot energies bound max|x| -- norm.hip; no separate maximum is recorded)
             if (h->f16_path()) g.range_flag = range_site("GroupNorm output bound |a| M + |d| (gn_finalize)");  // (only the fp16 operand paths have a range to guard)
-            note(launch_group_norm_finalize(g, k.C, k.slots, st), "group_norm_finalize");
+            run("group_norm_finalize", aff, [&] { return launch_group_norm_finalize(g, k.C, k.slots, st); });
         }
         return aff;
     }
@@ -117,12 +157,12 @@ struct Ctx {
     float2* group_norm(const Src& x, int H, int W, const float* gamma, const float* beta, const float* ada) {
         const int C = x.c0 + x.c1;
         float2* aff = (float2*)ar->alloc((size_t)B * C * sizeof(float2));
-        if (!dry()) {
+        if (!skip()) {
             GNParams g{x, B, H, W, h->cfg.gn_num_groups, h->cfg.gn_eps, gamma, beta, ada, (long)h->ada_rows,
                        gn_partial, aff, nullptr};
             g.partial_max = (float*)(gn_partial + (size_t)B * h->cfg.gn_num_groups * 256 * 2);
             if (h->f16_path()) g.range_flag = range_site("GroupNorm output bound |a| max|x| + |d| (streaming statistics)");  // (only the fp16 operand paths have a range to guard)
-            note(launch_group_norm(g, st), "group_norm");
+            run("group_norm", aff, [&] { return launch_group_norm(g, st); });
         }
         return aff;
     }
@@ -137,6 +177,10 @@ struct Ctx {
 
     // in-stream timing of a launch: records the opening event and returns the closing one (nullptr: profiling off)
     hipEvent_t prof_begin(int cls, double flop) {
+        if (lst) {
+            pend += " class=" + std::to_string(cls);
+            return nullptr;
+        }
         if (!h->prof_on) return nullptr;
         if (h->prof_used + 2 > h->prof_ev.size()) {
             hipEvent_t a, c;
@@ -171,120 +215,125 @@ struct Ctx {
         bool x16 = false, y16 = false;   // fp16 storage of the input / of the output (+ residual): act16(L) launches only
     };
 
-    Tensor conv(const ConvLayer& L, const Src& x, int H, int W, const ConvOpts& o) {
-        const int pro = o.prologue;
-        const NormSpec* ns = o.norm;
-        const float2* aff = o.aff;
-        // (decided in the dry walk as well, from shapes and the batch alone: the allocation sequence must be the same in both walks)
-        bool fold = false, pre_fold = false;
-        float2* own_aff = nullptr;
-        if (ns) {
+    // What one convolution launch runs on and what it fuses.  choose() decides it from the layer's packings, the precision mode, the prologue, the guard on
+    // the input's range, the incoming statistics, the batch and the resolution -- nothing the sizing walk does not know --, so both walks allocate alike;
+    // conv() only carries it out.
+    enum NormKind { NORM_NONE, NORM_FOLDED, NORM_PRE_FOLD, NORM_FINALIZE, NORM_STREAMING };
+    struct ConvChoice {
+        int algo = ALGO_F32, co_tile = 0, px_rows = 4, pieces = 3;  // the kernel, its tile and its operand pieces
+        // the GroupNorm in front: folded into the convolution's staging waves | into the operand pre-pass | the finalize launch over fused statistics | the
+        // streaming statistics pass (the last two leave `aff` for the prologue)
+        NormKind norm = NORM_NONE;
+        bool fused_stats = false;      // the epilogue writes the output's statistics into ConvOpts::sink ...
+        bool sink_incomplete = false;  // ... or cannot: the sink's consumer runs the streaming pass
+        // range sites, in the order they are handed out: the folded GroupNorm's output bound (NORM_FOLDED, NORM_PRE_FOLD), then ...
+        bool track_out = false;        // ... max|output|
+        const char* refused = nullptr;  // x16 / y16 asked of a launch that cannot take them: what a real forward reports
+    };
+    ConvChoice choose(const ConvLayer& L, const Src& x, int H, int W, const ConvOpts& o) const {
+        ConvChoice c;
+        // the fp16 split where the input's range is guarded: GroupNorm-normalised (gn_finalize's bound) or tracked by its producer (fir_up2's running maximum)
+        const bool guarded = h->f16_path() && (o.prologue != PRO_NONE || o.input_bounded);
+        c.algo = L.f2 && guarded ? ALGO_F16X2 : L.p1 && guarded && o.prologue != PRO_AFFINE_SILU ? ALGO_P1F16 : L.algo;
+        c.co_tile = c.algo == ALGO_F16X2 ? L.f2_cot : c.algo == ALGO_P1F16 ? 64 : L.co_tile;
+        if (c.algo == ALGO_F16X2) c.px_rows = L.f2_rows;
+        if (c.algo == ALGO_F16X2 || c.algo == ALGO_P1F16) c.pieces = (c.algo == ALGO_F16X2 && L.f2_cot == 32 && narrow_split()) ? 2 : h->conv_pieces;
+        if (const NormSpec* ns = o.norm) {
             const Sink& k = *ns->stats;
             const int G = h->cfg.gn_num_groups;
-            if (k && L.f2 && h->f16_path() && k.C == L.cin && G == 8) {
+            c.norm = k ? NORM_FINALIZE : NORM_STREAMING;
+            if (k && c.algo == ALGO_F16X2 && k.C == L.cin && G == 8) {
                 ConvParams q;
-                q.Cin = L.cin; q.Cout = L.cout; q.taps = L.taps; q.H = H; q.W = W; q.co_tile = L.f2_cot; q.px_rows = L.f2_rows; q.B = B; q.prologue = pro;
-                const int slots = k.cpg < 64 ? k.slots / 2 : k.slots;  // (groups of fewer than 64 channels leave the second half of their slots zero)
-                q.reverse = 0;
-                fold = conv_f16x2_fold_supported(q, G, slots);
-                q.reverse = 1;  // (whichever direction this launch will walk its tiles in)
-                fold = fold && conv_f16x2_fold_supported(q, G, slots);
+                q.Cin = L.cin; q.Cout = L.cout; q.taps = L.taps; q.H = H; q.W = W; q.co_tile = L.f2_cot; q.px_rows = L.f2_rows; q.B = B; q.prologue = o.prologue;
+                bool fold = true;  // (whichever direction this launch will walk its tiles in: that is the walk's state, not the choice's)
+                for (q.reverse = 0; q.reverse < 2; ++q.reverse) fold = fold && conv_f16x2_fold_supported(q, G, k.read_slots());
+                if (fold) c.norm = NORM_FOLDED;
+                // Round 6 EXPERIMENT, off by default (R2DM_F2_PRESPLIT_NARROW=1): the launches on 32-channel tiles (u_block4: eight output-channel tiles stage the
+                // same x tile, the stagers bound a chunk at 4.5 k cycles for 1.7 k of MFMAs) take their input through the operand pre-pass with the GroupNorm
+                // folded into THAT pass (presplit_fold_kernel): bit-identical; the convolutions go 43.8 -> 28.7 us and 78.3 -> 51.7 us, and the six 12.4 us passes
+                // (a launch + three dependent round trips over an 8 MB tensor) take it all back: step 5.894 | 5.895 ms (profiles/r06_narrow_presplit.txt).
+                // (=2: also the 512 -> 512 launches of level 4 on 64-channel tiles, eight output-channel tiles per x tile as well)
+                const bool narrow_tile = L.f2_cot == 32 || (narrow_presplit() >= 2 && L.f2_cot == 64 && L.cout >= 512);
+                if (narrow_presplit() && narrow_tile && L.f2_rows == 4 && h->conv_pieces == 2 && presplit_supported(x, L.cin, H, W)) c.norm = NORM_PRE_FOLD;
             }
-            // Round 6 EXPERIMENT, off by default (R2DM_F2_PRESPLIT_NARROW=1): the launches on 32-channel tiles (u_block4: eight output-channel tiles stage the
-            // same x tile, the stagers bound a chunk at 4.5 k cycles for 1.7 k of MFMAs) take their input through the operand pre-pass with the GroupNorm
-            // folded into THAT pass (presplit_fold_kernel): bit-identical; the convolutions go 43.8 -> 28.7 us and 78.3 -> 51.7 us, and the six 12.4 us passes
-            // (a launch + three dependent round trips over an 8 MB tensor) take it all back: step 5.894 | 5.895 ms (profiles/r06_narrow_presplit.txt).
-            // (=2: also the 512 -> 512 launches of level 4 on 64-channel tiles, eight output-channel tiles per x tile as well)
-            const bool narrow_tile = L.f2_cot == 32 || (narrow_presplit() >= 2 && L.f2_cot == 64 && L.cout >= 512);
-            if (k && narrow_presplit() && L.f2 && narrow_tile && L.f2_rows == 4 && h->conv_pieces == 2 && G == 8 && k.C == L.cin && presplit_supported(x, L.cin, H, W)) {
-                fold = false;
-                pre_fold = true;
-            }
-            if (!fold && !pre_fold) aff = own_aff = norm(k, x, H, W, ns->gamma, ns->beta, ns->ada);
         }
-        Tensor y;
-        y.C = L.cout;
-        y.H = H;
-        y.W = W;
-        y.f16 = o.y16;
-        y.p = o.dst ? o.dst : (float*)ar->alloc(y.bytes(B));
-        // (decided in the dry walk as well: the consumer's choice between finalize and the streaming pass changes the
-        // allocation sequence, which must be the same in both walks)
-        const bool fused_stats = o.sink && o.sink->p && emits_stats(L);
-        if (o.sink && o.sink->p && !fused_stats) const_cast<Sink*>(o.sink)->incomplete = true;
-        const bool f2_launch = L.f2 && h->f16_path() && (pro != PRO_NONE || o.input_bounded);
-        // the operand pre-pass's planes (decided in both walks: the allocation sequence must be the same)
-        float* xs = f2_launch && pre_fold ? (float*)ar->alloc((size_t)presplit_floats(B, L.cin, H, W) * sizeof(float)) : nullptr;
-        if (!dry()) {
-            ConvParams p = conv_params(x, blob(L.w), blob(L.b), y.p, y.bs(), B, H, W, L.cin, L.cin_pad, L.cout, L.taps, L.co_tile, L.algo, pro);
+        // (the layer's own kernel decides, whichever packing runs: conv_f16x2 and proj_f16x2 write what the kernel they stand in for writes)
+        c.fused_stats = o.sink && o.sink->p && conv_emits_stats(L.algo, L.co_tile, L.cout);
+        c.sink_incomplete = o.sink && o.sink->p && !c.fused_stats;
+        // (every MFMA kernel records the maximum; the direct kernels' outputs never feed an fp16 operand unnormalised)
+        c.track_out = o.track_out && h->f16_path() && c.algo != ALGO_DIRECT;
+        // (conv_f16x2 launches, the direct in / out convolutions and the fp16-operand skip convolutions take fp16 storage; the streaming statistics pass reads fp32)
+        if ((o.x16 || o.y16) && c.algo != ALGO_F16X2 && c.algo != ALGO_DIRECT && c.algo != ALGO_P1F16) c.refused = "fp16 storage on a kernel without it";
+        else if (o.x16 && c.norm == NORM_STREAMING) c.refused = "fp16 storage behind a streaming GroupNorm";
+        return c;
+    }
+
+    Tensor conv(const ConvLayer& L, const Src& x, int H, int W, const ConvOpts& o) {
+        const ConvChoice c = choose(L, x, H, W, o);
+        const NormSpec* ns = o.norm;
+        const float2* aff = o.aff;
+        float2* own_aff = nullptr;
+        if (c.norm == NORM_FINALIZE) aff = own_aff = finalize(*ns->stats, H, W, ns->gamma, ns->beta, ns->ada);
+        if (c.norm == NORM_STREAMING) aff = own_aff = group_norm(x, H, W, ns->gamma, ns->beta, ns->ada);
+        Tensor y{o.dst, L.cout, H, W, o.y16};
+        if (!y.p) y.p = (float*)ar->alloc(y.bytes(B));
+        if (c.sink_incomplete) const_cast<Sink*>(o.sink)->incomplete = true;
+        // many output-channel tiles per x tile: the input transform once, by the pre-pass with the GroupNorm folded in (presplit.hip)
+        float* xs = c.norm == NORM_PRE_FOLD ? (float*)ar->alloc((size_t)presplit_floats(B, L.cin, H, W) * sizeof(float)) : nullptr;
+        if (!skip()) {
+            ConvParams p = conv_params(x, blob(L.w), blob(L.b), y.p, y.bs(), B, H, W, L.cin, L.cin_pad, L.cout, L.taps, c.co_tile, c.algo, o.prologue);
+            p.px_rows = c.px_rows;
+            p.pieces = c.pieces;
             p.aff = aff;
             p.res = o.res ? o.res->p : nullptr;
             p.res_bs = o.res && !o.res_broadcast ? o.res->bs() : 0;
             p.scale = o.scale;
-            p.x16 = o.x16;  // (conv_f16x2 launches, the direct in / out convolutions and the fp16-operand skip convolutions take them; checked below)
+            p.x16 = o.x16;
             p.y16 = o.y16;
-            // the fp16 split where the input's range is guarded: GroupNorm-normalised (gn_finalize's bound) or tracked by its
-            // producer (fir_up2's running maximum)
-            if (f2_launch) {
+            if (c.algo == ALGO_F16X2) {
                 p.reverse = f2_launches++ & 1;
                 last_reverse = p.reverse;
-                p.algo = ALGO_F16X2;
                 p.w = blob(L.w_f2);
                 p.wscale = blob(L.ws_f2) + 1;
-                p.co_tile = L.f2_cot;
-                p.px_rows = L.f2_rows;
-                p.pieces = (L.f2_cot == 32 && narrow_split()) ? 2 : h->conv_pieces;
-                if (fold) {
-                    const Sink& k = *ns->stats;
+            } else if (c.algo == ALGO_P1F16) {
+                // (a skip convolution reads the tensor its block's conv1 has just read: start where that walk ended)
+                p.reverse = last_reverse == 0;
+                p.w = blob(L.w_p1);
+                p.wscale = blob(L.ws_p1) + 1;
+            }
+            if (c.norm == NORM_FOLDED || c.norm == NORM_PRE_FOLD) {
+                const Sink& k = *ns->stats;
+                int* site = range_site(xs ? "GroupNorm output bound |a| M + |d| (folded into the operand pre-pass)" : "GroupNorm output bound |a| M + |d| (folded into the convolution)");
+                if (xs) {
+                    run("presplit_fold", xs, [&] {
+                        return launch_presplit_fold(x, o.prologue, xs, B, L.cin, H, W, k.p, k.slots, k.read_slots(), k.cpg, h->cfg.gn_eps, ns->gamma, ns->beta, ns->ada, (long)h->ada_rows, site, st);
+                    });
+                    p.x = Src{xs, nullptr, L.cin, 0, presplit_floats(1, L.cin, H, W), 0};
+                    p.prologue = PRO_PRESPLIT;
+                } else {
                     p.gn_partial = k.p;
                     p.gn_stride = k.slots;
-                    p.gn_slots = k.cpg < 64 ? k.slots / 2 : k.slots;
+                    p.gn_slots = k.read_slots();
                     p.gn_cpg = k.cpg;
                     p.gn_eps = h->cfg.gn_eps;
                     p.gn_gamma = ns->gamma;
                     p.gn_beta = ns->beta;
                     p.gn_ada = ns->ada;
                     p.gn_ada_stride = (long)h->ada_rows;
-                    p.gn_range = range_site("GroupNorm output bound |a| M + |d| (folded into the convolution)");
+                    p.gn_range = site;
                 }
             }
-            // many output-channel tiles per x tile: the input transform once, by the pre-pass with the GroupNorm folded in (presplit.hip)
-            if (xs) {
-                const Sink& k = *ns->stats;
-                note(launch_presplit_fold(x, pro, xs, B, L.cin, H, W, k.p, k.slots, k.cpg < 64 ? k.slots / 2 : k.slots, k.cpg, h->cfg.gn_eps, ns->gamma, ns->beta, ns->ada,
-                                          (long)h->ada_rows, range_site("GroupNorm output bound |a| M + |d| (folded into the operand pre-pass)"), st), "presplit_fold");
-                p.x = Src{xs, nullptr, L.cin, 0, presplit_floats(1, L.cin, H, W), 0};
-                p.prologue = PRO_PRESPLIT;
-                p.aff = nullptr;
-            }
-            if (L.p1 && h->f16_path() && pro != PRO_AFFINE_SILU && (pro != PRO_NONE || o.input_bounded)) {
-                p.algo = ALGO_P1F16;
-                // (a skip convolution reads the tensor its block's conv1 has just read: start where that walk ended)
-                p.reverse = last_reverse == 0;
-                p.w = blob(L.w_p1);
-                p.wscale = blob(L.ws_p1) + 1;
-                p.co_tile = 64;
-                p.pieces = h->conv_pieces;
-            }
-            // (every MFMA kernel records the maximum; the direct kernels' outputs never feed an fp16 operand unnormalised)
-            if (o.track_out && h->f16_path() && p.algo != ALGO_DIRECT) p.range = range_site("max|output| (raw input of the next fp16-operand kernel)");
-            if (fused_stats) {
-                p.stat = o.sink->p;
-                p.stat_G = h->cfg.gn_num_groups;
-                p.stat_goff = o.goff;
-                p.stat_cpg = o.sink->cpg;
-                p.stat_slots = o.sink->slots;
-            }
-            if ((o.x16 || o.y16) && p.algo != ALGO_F16X2 && p.algo != ALGO_DIRECT && p.algo != ALGO_P1F16) note(hipErrorInvalidValue, "fp16 storage on a kernel without it");
-            if (o.x16 && !fold && !pre_fold && own_aff && !(ns && *ns->stats)) note(hipErrorInvalidValue, "fp16 storage behind a streaming GroupNorm");
+            if (c.track_out) p.range = range_site("max|output| (raw input of the next fp16-operand kernel)");
+            if (c.fused_stats) conv_stat_sink(p, o.sink->p, h->cfg.gn_num_groups, o.goff, o.sink->cpg, o.sink->slots);
+            if (c.refused) note(hipErrorInvalidValue, c.refused);
             // ALGORITHMIC flops of the reference's convolution (in_conv: all 34 input channels, although the
             // constant Fourier half is folded into a bias map here)
             hipEvent_t e1 = prof_begin(p.algo == ALGO_F16X2 ? 0 : p.algo == ALGO_BF16X3 ? 1 : 2, 2.0 * B * (double)L.cout * (L.src_cin ? L.src_cin : L.cin) * L.taps * H * W);
-            if (g_debug_sync)
+            if (g_debug_sync && !lst)
                 fprintf(stderr, "[r2dm] conv algo %d %d->%d taps %d co_tile %d %dx%d B %d pro %d w %p bias %p gn %p blob [%p, +%zu) x %p/%p (c0 %d) y %p res %p aff %p stat %p ws [%p, +%zu)\n", p.algo, p.Cin,
-                        p.Cout, p.taps, p.co_tile, H, W, B, pro, (const void*)p.w, (const void*)p.bias, (const void*)p.gn_partial, (void*)h->blob, h->blob_floats * 4, (const void*)p.x.p0, (const void*)p.x.p1, p.x.c0, (void*)p.y, (const void*)p.res, (const void*)p.aff,
+                        p.Cout, p.taps, p.co_tile, H, W, B, o.prologue, (const void*)p.w, (const void*)p.bias, (const void*)p.gn_partial, (void*)h->blob, h->blob_floats * 4, (const void*)p.x.p0, (const void*)p.x.p1, p.x.c0, (void*)p.y, (const void*)p.res, (const void*)p.aff,
                         (void*)p.stat, (void*)ar->base, ar->cap);
-            note(launch_conv(p, st), "conv");
+            run("conv", y.p, [&] { return launch_conv(p, st); }, &p);
             if (e1) (void)hipEventRecord(e1, st);
         }
         if (xs) ar->release(xs);  // (stream-ordered: the next user of that memory is enqueued behind this convolution)
@@ -332,8 +381,8 @@ struct Ctx {
         Tensor t1 = conv(r.conv1, x, H, W, c1);
         const NormSpec n2{&s1, nullptr, nullptr, proj + r.ada_row};
         Tensor skip;
-        const Tensor* res;
-        Tensor ident;
+        const Tensor ident{const_cast<float*>(x.p0), x.c0, H, W};  // identity skip: the block input is single-source then
+        const Tensor* res = &ident;
         if (r.has_skip) {
             ctx = blk + ".skip";
             ConvOpts cs;
@@ -342,12 +391,6 @@ struct Ctx {
             cs.y16 = out16;
             skip = conv(r.skip, x, H, W, cs);
             res = &skip;
-        } else {
-            ident.p = const_cast<float*>(x.p0);  // identity skip: block input is single-source here
-            ident.C = x.c0;
-            ident.H = H;
-            ident.W = W;
-            res = &ident;
         }
         ctx = blk + ".conv2";
         ConvOpts c2;
@@ -387,7 +430,7 @@ struct Ctx {
         Tensor qkv = conv(a.qkv, src1(x), x.H, x.W, cq);
         ar->release(aff);
         Tensor o = make(a.C, x.H, x.W);
-        if (!dry()) note(launch_attention(qkv.p, o.p, B, a.C, h->cfg.attn_num_heads, x.H * x.W, st, f2 ? h->conv_pieces : 0), "attention");
+        if (!skip()) run("attention", o.p, [&] { return launch_attention(qkv.p, o.p, B, a.C, h->cfg.attn_num_heads, x.H * x.W, st, f2 ? h->conv_pieces : 0); });
         drop(qkv);
         // (the core's output is a convex combination of v: |o| <= max|qkv|, which the qkv epilogue has recorded)
         ctx = blk + ".out_proj";
@@ -423,51 +466,43 @@ struct Ctx {
         // the input's producer tracks max|x|; everything else -- fp32-bf16x3, the one-plane mode with its fp16 storage, a tripped guard's fallback --
         // keeps conv + FIR.  Leaves what the FIR launch leaves: the tensor and, where fir_down2 would, the statistics of the first block's norm.
         // (a two-source input never reaches a down stage today; if one does it keeps conv + FIR: the pre-pass reads one tensor)
-        if (s.down && s.dconv.dg && h->conv_pieces == 2 && si.tracked && !si.f16 && !in.p1) {
+        if (s.down) {
             ctx = s.name + ".downsample";
             const ConvLayer& L = s.dconv;
-            const bool phase = h->down_gemm != 9;
-            // (phase planes: 2 cin channels of (H + 3) x (W / 2 + 4))
-            Tensor a = phase ? make(2 * L.cin, H + 3, W / 2 + 4) : make(9 * L.cin, H / 2, W / 2);
-            cur = make(s.cout, H / 2, W / 2);
-            Sink fs;
-            if (fir_down2_stat_slots(s.cout, h->cfg.gn_num_groups, H, W)) fs = make_sink(s.cout, H / 2, W / 2);
-            if (!dry()) {
-                // Range: the FIR weights are non-negative and sum to at most 1 per axis, so max|a| <= max|x|, which the producer has recorded at its own site;
-                // the pass records max|a| itself all the same (one guarded atomic per wave), so the report names the GEMM's operand.
-                // (profiling: both launches in class 2, "1x1 / in / out convolutions" -- the pass with no FLOPs of its own, the GEMM with those it executes)
-                // (the name tells the two layouts apart: tests/test_hip_down_phase.py reads from it which pair an engine took)
-                int* site = range_site(phase ? "max|FIR planes| (operand of the down-sampling GEMM, every distinct plane once)"
-                                             : "max|FIR planes| (operand of the down-sampling GEMM, all nine)");
-                hipEvent_t e0 = prof_begin(2, 0.0);
-                if (phase) note(launch_down_phase_planes(in.p0, in.bs0, a.p, a.bs(), B, L.cin, H, W, st, site), "down_phase_planes");
-                else note(launch_down_planes(in.p0, in.bs0, a.p, a.bs(), B, L.cin, H, W, st, site), "down_planes");
-                if (e0) (void)hipEventRecord(e0, st);
-                const ConvParams p = down_gemm_params(a.p, blob(L.w_dg), blob(L.b), blob(L.ws_dg) + 1, cur.p, B, L.cin, L.cout, H / 2, W / 2, fs.p, h->cfg.gn_num_groups, phase);
-                last_reverse = -1;
-                hipEvent_t e1 = prof_begin(2, 2.0 * B * (double)L.cout * 9 * L.cin * (H / 2) * (W / 2));
-                note(launch_proj_f16x2(p, st, phase ? DOWN_PHASE : DOWN_NINE), "down_gemm");
-                if (e1) (void)hipEventRecord(e1, st);
+            const bool gemm = L.dg && h->conv_pieces == 2 && si.tracked && !si.f16 && !in.p1, phase = h->down_gemm != 9;
+            Tensor t;  // what the stage's second launch reads: the FIR planes (phase planes: 2 cin channels of (H + 3) x (W / 2 + 4)) | the convolution's output
+            if (gemm) {
+                t = phase ? make(2 * L.cin, H + 3, W / 2 + 4) : make(9 * L.cin, H / 2, W / 2);
+            } else {
+                ConvOpts cd;
+                cd.input_bounded = si.tracked;
+                cd.x16 = si.f16;
+                cd.y16 = si.f16 && lvl16(H);
+                t = conv(L, in, H, W, cd);
             }
-            drop(a);
-            H /= 2;
-            W /= 2;
-            have = true;
-            carry = fs;
-            carry_owned = fs.p != nullptr;
-        } else if (s.down) {
-            ctx = s.name + ".downsample";
-            ConvOpts cd;
-            cd.input_bounded = si.tracked;
-            cd.x16 = si.f16;
-            cd.y16 = si.f16 && lvl16(H);
-            Tensor t = conv(s.dconv, in, H, W, cd);
             cur = make(s.cout, H / 2, W / 2, t.f16 && lvl16(H / 2));
-            // the FIR pass leaves the statistics of its output for the first residual block's norm (resample.hip; where its geometry
+            // the FIR pass / the GEMM leaves the statistics of its output for the first residual block's norm (resample.hip; where the geometry
             // does not fit the slot grid: no fused statistics, the streaming pass)
             Sink fs;
             if (fir_down2_stat_slots(s.cout, h->cfg.gn_num_groups, H, W)) fs = make_sink(s.cout, H / 2, W / 2);
-            if (!dry()) note(launch_fir_down2(t.p, t.bs(), cur.p, cur.bs(), B, s.cout, H, W, st, fs.p, h->cfg.gn_num_groups, t.f16, cur.f16), "fir_down2");
+            if (gemm && !skip()) {
+                // Range: the FIR weights are non-negative and sum to at most 1 per axis, so max|a| <= max|x|, which the producer has recorded at its own site;
+                // the pass records max|a| itself all the same (one guarded atomic per wave), so the report names the GEMM's operand.
+                // (profiling: both launches in class 2, "1x1 / in / out convolutions" -- the pass with no FLOPs of its own, the GEMM with those it executes)
+                int* site = range_site(phase ? "max|FIR planes| (operand of the down-sampling GEMM, every distinct plane once)"
+                                             : "max|FIR planes| (operand of the down-sampling GEMM, all nine)");
+                hipEvent_t e0 = prof_begin(2, 0.0);
+                if (phase) run("down_phase_planes", t.p, [&] { return launch_down_phase_planes(in.p0, in.bs0, t.p, t.bs(), B, L.cin, H, W, st, site); });
+                else run("down_planes", t.p, [&] { return launch_down_planes(in.p0, in.bs0, t.p, t.bs(), B, L.cin, H, W, st, site); });
+                if (e0) (void)hipEventRecord(e0, st);
+                const ConvParams p = down_gemm_params(t.p, blob(L.w_dg), blob(L.b), blob(L.ws_dg) + 1, cur.p, B, L.cin, L.cout, H / 2, W / 2, fs.p, h->cfg.gn_num_groups, phase);
+                last_reverse = -1;
+                hipEvent_t e1 = prof_begin(2, 2.0 * B * (double)L.cout * 9 * L.cin * (H / 2) * (W / 2));
+                run("down_gemm", cur.p, [&] { return launch_proj_f16x2(p, st, phase ? DOWN_PHASE : DOWN_NINE); }, &p);
+                if (e1) (void)hipEventRecord(e1, st);
+            } else if (!skip()) {
+                run("fir_down2", cur.p, [&] { return launch_fir_down2(t.p, t.bs(), cur.p, cur.bs(), B, s.cout, H, W, st, fs.p, h->cfg.gn_num_groups, t.f16, cur.f16); });
+            }
             c16 = cur.f16;
             drop(t);
             H /= 2;
@@ -519,7 +554,10 @@ struct Ctx {
             Tensor u = make(s.cout, 2 * H, 2 * W, lvl16(2 * H) && s.uconv.f2);
             const bool track = s.uconv.f2 && h->f16_path();  // the fp16-operand convolution below needs max|u| < 65504
             ctx = s.name + ".upsample";
-            if (!dry()) note(launch_fir_up2(cur.p, cur.bs(), u.p, u.bs(), B, s.cout, H, W, st, track ? range_site("max|FIR output| (raw input of the up-sampling convolution)") : nullptr, cur.f16, u.f16), "fir_up2");
+            if (!skip()) {
+                int* site = track ? range_site("max|FIR output| (raw input of the up-sampling convolution)") : nullptr;
+                run("fir_up2", u.p, [&] { return launch_fir_up2(cur.p, cur.bs(), u.p, u.bs(), B, s.cout, H, W, st, site, cur.f16, u.f16); });
+            }
             drop(cur);
             ConvOpts cu;
             cu.sink = out;
@@ -536,36 +574,34 @@ struct Ctx {
 
 }  // namespace
 
-int r2dm::run_forward(r2dm_handle* h, Arena& ar, const float* x, const float* cond, float* out, int B, hipStream_t st) {
+int r2dm::run_forward(r2dm_handle* h, Arena& ar, const float* x, const float* cond, float* out, int B, hipStream_t st, std::string* listing) {
     const r2dm_config& c = h->cfg;
     Ctx k{h, &ar, st, B, nullptr, nullptr};
+    k.lst = listing;
+    k.user_out = out;
     const int H = c.height, W = c.width, T = c.temb_channels;
     float* act = (float*)ar.alloc((size_t)2 * B * T * sizeof(float));  // [SiLU(temb) | hidden scratch]
     float* proj = (float*)ar.alloc((size_t)B * h->ada_rows * sizeof(float));
     k.gn_partial = (double*)ar.alloc((size_t)B * c.gn_num_groups * 256 * (2 * sizeof(double) + sizeof(float)));  // sums | maxima
     k.proj = proj;
-    if (!k.dry()) {
+    if (!k.skip()) {
         EmbedParams e{cond, k.blob(h->freqs), k.blob(h->w1), k.blob(h->b1), k.blob(h->w2), k.blob(h->b2), act,
                       act + (size_t)B * T, B, c.base_channels, T};
-        k.note(launch_time_embedding(e, st), "time_embedding");
-        k.note(launch_ada_proj(act, k.blob(h->ada_w), k.blob(h->ada_b), proj, B, T, h->ada_rows, st), "ada_proj");
+        k.run("time_embedding", act, [&] { return launch_time_embedding(e, st); });
+        k.run("ada_proj", proj, [&] { return launch_ada_proj(act, k.blob(h->ada_w), k.blob(h->ada_b), proj, B, T, h->ada_rows, st); });
     }
     // input = cat([x, cenc]) (efficient_unet.py:278-281), never materialised: the constant cenc half of in_conv is the
     // per-pixel bias map `cmap`, the per-step convolution runs over the in_channels data channels only
     Src in{x, nullptr, c.in_channels, 0, (long)c.in_channels * H * W, 0};
-    if (c.coord_channels && !h->cmap_ready && !k.dry()) {
+    if (c.coord_channels && (listing || (!h->cmap_ready && !k.dry()))) {  // (the listing shows it whether or not this handle has run it yet)
         const ConvLayer& L = h->in_conv_c;
         const ConvParams q = conv_params(Src{k.blob(h->cenc), nullptr, c.coord_channels, 0, 0, 0}, k.blob(L.w), k.blob(L.b), h->blob + h->cmap, 0, 1, H, W, L.cin, L.cin_pad, L.cout, 9,
                                          L.co_tile, ALGO_F32, PRO_NONE);
-        k.note(hipMemsetAsync(h->blob + h->zero_bias, 0, h->in_conv.cout * sizeof(float), st), "zero bias");
-        k.note(launch_conv(q, st), "in_conv constant map");
-        h->cmap_ready = true;
+        if (!listing) k.note(hipMemsetAsync(h->blob + h->zero_bias, 0, h->in_conv.cout * sizeof(float), st), "zero bias");
+        k.run("in_conv constant map", nullptr, [&] { return launch_conv(q, st); }, &q, "cmap (first forward after a bind only)");
+        if (!listing) h->cmap_ready = true;
     }
-    Tensor cmap_t;
-    cmap_t.p = h->blob + h->cmap;
-    cmap_t.C = h->in_conv.cout;
-    cmap_t.H = H;
-    cmap_t.W = W;
+    const Tensor cmap_t{h->blob + h->cmap, h->in_conv.cout, H, W};
     const int G = c.gn_num_groups;
     const Stage* S = h->stages;
     // GroupNorm sinks that outlive a stage: the first norm of d_block1 (input = in_conv output) and the first norm of
@@ -583,18 +619,8 @@ int r2dm::run_forward(r2dm_handle* h, Arena& ar, const float* x, const float* co
         // model per setting).
         const char* e = getenv("R2DM_FP16_STORAGE");
         const int level = e ? atoi(e) : 2;
-        // ... and every convolution of those levels on a kernel that has the second I/O type (at small batches some layers have too few tiles for conv_f16x2
-        // and run the bf16 kernels: then nothing changes)
-        auto blocks_ok = [](const Stage& st) {
-            for (const ResLayer& r : st.res)
-                if (!r.conv1.f2 || !r.conv2.f2 || (r.has_skip && !r.skip.p1)) return false;
-            return true;
-        };
-        k.all16 = level >= 2 && h->conv_pieces == 1 && G == 8 && c.base_channels % 64 == 0 && h->in_conv.algo == ALGO_DIRECT && h->in_conv.cout > 4 &&
-                  h->out_conv.algo == ALGO_DIRECT && W % 4 == 0 && S[1].down && S[2].down && S[1].dconv.f2 && S[2].dconv.f2 && S[5].up && S[6].up &&
-                  S[5].uconv.f2 && S[6].uconv.f2 && !S[0].attn && !S[1].attn && !S[6].attn && !S[7].attn && blocks_ok(S[0]) && blocks_ok(S[1]) && blocks_ok(S[6]) &&
-                  blocks_ok(S[7]) && S[6].skip_in_bounded && S[7].skip_in_bounded &&
-                  fir_down2_stat_slots(S[1].cout, G, H, W) != 0 && fir_down2_stat_slots(S[2].cout, G, H / 2, W / 2) != 0;
+        // ... and a plan whose levels 1 and 2 can all store it (r2dm_handle::plan_fits16, build_plan), FIR statistics at both levels (R2DM_FIR_STATS: read per call)
+        k.all16 = level >= 2 && h->conv_pieces == 1 && h->plan_fits16 && fir_down2_stat_slots(S[1].cout, G, H, W) != 0 && fir_down2_stat_slots(S[2].cout, G, H / 2, W / 2) != 0;
     }
     k.ctx = "in_conv";
     Ctx::ConvOpts ci;

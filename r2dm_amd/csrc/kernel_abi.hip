@@ -13,8 +13,8 @@ int64_t r2dm_conv_packed_elems(int32_t cout, int32_t cin, int32_t ksize, int32_t
     const int taps = ksize * ksize;
     int algo = conv_pick_algo(cin, cout, taps);
     if (algo == ALGO_DIRECT) algo = ALGO_F32;  // scratch sized for the larger (fp32-MFMA) packing: either may be chosen
-    const int ct = algo == ALGO_BF16X3 ? conv_bf16x3_co_tile(cin, cout, (long)B * H * W) : conv_pick_co_tile(cout, taps, (long)B * H * W);
-    int64_t n = (int64_t)conv_packed_floats(algo, cin, cout, taps, ct, algo != ALGO_F32 ? cin : conv_cin_pad(cin, taps, ct));
+    const int ct = conv_base_co_tile(algo, cin, cout, taps, (long)B * H * W);
+    int64_t n = (int64_t)conv_packed_floats(algo, cin, cout, taps, ct, conv_base_cin_pad(algo, cin, taps, ct));
     if (algo == ALGO_BF16X3 && conv_f16x2_supported(cin, cout, taps, H, W)) n = std::max<int64_t>(n, conv_f16x2_packed_floats(cin, cout) + 64);
     if (proj_f16x2_supported(cin, cout, taps, H, W)) n = std::max<int64_t>(n, proj_f16x2_packed_floats(cin, cout) + 64);
     return n;
@@ -62,8 +62,8 @@ static int conv2d_ring_impl(const float* x, const float* w, const float* bias, f
     if (algo == ALGO_BF16X3 && g_single_kernel_pieces != 3 && conv_f16x2_supported(cin, cout, taps, H, W)) algo = ALGO_F16X2;
     if (algo == ALGO_F32 && g_single_kernel_pieces < 3 && prologue != PRO_AFFINE_SILU && proj_f16x2_supported(cin, cout, taps, H, W)) algo = ALGO_P1F16;
     if (algo == ALGO_F16X2 || algo == ALGO_P1F16) pieces = g_single_kernel_pieces;
-    const int co_tile = algo == ALGO_F16X2 ? conv_f16x2_pick_co_tile(cin, cout, H, W, (long)B * H * W, &px_rows) : algo == ALGO_P1F16 ? 64 : algo == ALGO_BF16X3 ? conv_bf16x3_co_tile(cin, cout, (long)B * H * W) : conv_pick_co_tile(cout, taps, (long)B * H * W);
-    const int cin_pad = algo != ALGO_F32 ? cin : conv_cin_pad(cin, taps, co_tile);
+    const int co_tile = algo == ALGO_F16X2 ? conv_f16x2_pick_co_tile(cin, cout, H, W, (long)B * H * W, &px_rows) : algo == ALGO_P1F16 ? 64 : conv_base_co_tile(algo, cin, cout, taps, (long)B * H * W);
+    const int cin_pad = conv_base_cin_pad(algo, cin, taps, co_tile);
     if (ex.chosen) {
         ex.chosen[0] = algo;
         ex.chosen[1] = co_tile;
@@ -84,8 +84,8 @@ static int conv2d_ring_impl(const float* x, const float* w, const float* bias, f
     if (ex.range && algo == ALGO_DIRECT) return fail(1, "conv2d_ring_ex: the direct kernels record no range");
     if (ex.reverse && algo != ALGO_F16X2 && algo != ALGO_P1F16) return fail(1, "conv2d_ring_ex: this kernel has no descending tile walk");
     if (ex.stat) {
-        // (forward.hip emits_stats: not the 32-channel fp32 tile, not the few-output direct kernel)
-        const bool emits = algo == ALGO_BF16X3 || algo == ALGO_F16X2 || algo == ALGO_P1F16 || (algo == ALGO_F32 && co_tile >= 64) || (algo == ALGO_DIRECT && cout > 4);
+        // (this entry knows the kernel it launches; the engine asks about the layer's own kernel, whichever packing runs: forward.hip choose)
+        const bool emits = algo == ALGO_F16X2 || algo == ALGO_P1F16 || conv_emits_stats(algo, co_tile, cout);
         if (!emits) return fail(1, "conv2d_ring_ex: this kernel (algo %d, tile %d) emits no statistics", algo, co_tile);
         const int cpg = ex.stat_cpg;
         if (cpg != 8 && cpg != 16 && cpg != 32 && cpg != 64) return fail(1, "conv2d_ring_ex: stat_cpg = %d (8, 16, 32 or 64 channels per group)", cpg);
@@ -119,13 +119,7 @@ static int conv2d_ring_impl(const float* x, const float* w, const float* bias, f
     p.scale = scale;
     p.range = ex.range;
     p.reverse = ex.reverse;
-    if (ex.stat) {
-        p.stat = ex.stat;
-        p.stat_G = ex.stat_G;
-        p.stat_goff = ex.stat_goff;
-        p.stat_cpg = ex.stat_cpg;
-        p.stat_slots = conv_stat_slots(H, W);
-    }
+    if (ex.stat) conv_stat_sink(p, ex.stat, ex.stat_G, ex.stat_goff, ex.stat_cpg, conv_stat_slots(H, W));
     // per-kernel tests of the fp16 activation storage (conv_f16x2.hip, one-plane mode): R2DM_TEST_IO16 = 1 (x holds fp16), 2 (y and the
     // residual hold fp16) or 3 -- the caller passes tensors of that type behind the float pointers
     if (const char* e = getenv("R2DM_TEST_IO16"); e && (atoi(e) & 3)) {  // (bit 2 alone: only the kernel selection above -- the fp32 twin of a storage test)
@@ -170,17 +164,7 @@ int r2dm_conv2d_ring_ex(const float* x, const float* x1, int32_t c1, const float
                         const float* residual, int32_t res_broadcast, const float* scale, float* y, double* stat, int32_t stat_G, int32_t stat_goff,
                         int32_t stat_cpg, int32_t* range, int32_t reverse, int32_t* chosen, int32_t B, int32_t cin, int32_t cout, int32_t H, int32_t W,
                         int32_t ksize, void* stream) {
-    ConvExtras ex;
-    ex.x1 = x1;
-    ex.c1 = c1;
-    ex.res_broadcast = res_broadcast;
-    ex.stat = stat;
-    ex.stat_G = stat_G;
-    ex.stat_goff = stat_goff;
-    ex.stat_cpg = stat_cpg;
-    ex.range = range;
-    ex.reverse = reverse;
-    ex.chosen = chosen;
+    const ConvExtras ex{x1, c1, res_broadcast, stat, stat_G, stat_goff, stat_cpg, range, reverse, chosen};  // (the struct's order)
     return conv2d_ring_impl(x, w, bias, w_packed, aff, prologue, residual, scale, y, B, cin, cout, H, W, ksize, stream, ex);
 }
 

@@ -28,8 +28,8 @@ ConvLayer r2dm_handle::conv_slice(const std::string& wkey, int src_cin, int src_
         return e && e[0] == 'f';
     }();
     L.algo = (!force_f32 && H > 0 && conv_few_in_supported(cin, cout, L.taps, H, W)) ? ALGO_DIRECT : ALGO_F32;
-    L.co_tile = conv_pick_co_tile(cout, L.taps, px_batch);
-    L.cin_pad = L.algo == ALGO_DIRECT ? cin : conv_cin_pad(cin, L.taps, L.co_tile);
+    L.co_tile = conv_base_co_tile(L.algo, cin, cout, L.taps, px_batch);
+    L.cin_pad = conv_base_cin_pad(L.algo, cin, L.taps, L.co_tile);
     L.src_cin = src_cin;
     L.src_off = src_off;
     L.w = take(L.packed_elems());
@@ -44,8 +44,8 @@ ConvLayer r2dm_handle::conv(const std::string& wkey, const std::string& bkey, in
     L.cout = cout;
     L.taps = ksize * ksize;
     L.algo = conv_pick_algo(cin, cout, L.taps);
-    L.co_tile = L.algo == ALGO_BF16X3 ? conv_bf16x3_co_tile(cin, cout, px_batch) : conv_pick_co_tile(cout, L.taps, px_batch);
-    L.cin_pad = L.algo != ALGO_F32 ? cin : conv_cin_pad(cin, L.taps, L.co_tile);
+    L.co_tile = conv_base_co_tile(L.algo, cin, cout, L.taps, px_batch);
+    L.cin_pad = conv_base_cin_pad(L.algo, cin, L.taps, L.co_tile);
     L.w = take(L.packed_elems());
     // (at least half a wave of tiles per CU at the planned batch: below that the persistent kernel leaves CUs idle)
     constexpr long f2_min_tiles = 128;
@@ -71,6 +71,17 @@ ConvLayer r2dm_handle::conv(const std::string& wkey, const std::string& bkey, in
     return L;
 }
 namespace r2dm {
+
+// The mechanical part of a layer's own (first) packing, shared by the plan and the single-kernel entries: the output-channel tile of the kernel `algo` names, the
+// input-channel padding only the fp32-MFMA packing has, and which of those kernels write fused statistics -- the split-bf16 kernels, the fp32-MFMA kernel
+// with >= 64-channel tiles and the few-input direct kernel; the 32-channel fp32 tile (Cout <= 32) and the few-output direct kernel do not.
+int conv_base_co_tile(int algo, int cin, int cout, int taps, long px_batch) {
+    return algo == ALGO_BF16X3 ? conv_bf16x3_co_tile(cin, cout, px_batch) : conv_pick_co_tile(cout, taps, px_batch);
+}
+int conv_base_cin_pad(int algo, int cin, int taps, int co_tile) { return algo != ALGO_F32 ? cin : conv_cin_pad(cin, taps, co_tile); }
+bool conv_emits_stats(int algo, int co_tile, int cout) {
+    return algo == ALGO_BF16X3 || (algo == ALGO_F32 && co_tile >= 64) || (algo == ALGO_DIRECT && cout > 4);
+}
 
 void build_plan(r2dm_handle* h) {
     const r2dm_config& c = h->cfg;
@@ -177,6 +188,18 @@ void build_plan(r2dm_handle* h) {
         h->stages[s - 1].track_final = true;
         if (s > 4) h->stages[7 - s].track_final = true;
     }
+    // fp16 storage of the two full-resolution levels (forward.hip Ctx::lvl16), as far as the plan decides it: the default network family (every GroupNorm of
+    // levels 1 and 2 on fused statistics -- the streaming pass reads fp32 --, in_conv on the few-input kernel) and every convolution of those levels on a kernel
+    // that has the second I/O type (at small batches some layers have too few tiles for conv_f16x2 and run the bf16 kernels: then nothing changes)
+    auto blocks_ok = [](const Stage& st) {
+        for (const ResLayer& r : st.res)
+            if (!r.conv1.f2 || !r.conv2.f2 || (r.has_skip && !r.skip.p1)) return false;
+        return true;
+    };
+    const Stage* S = h->stages;
+    h->plan_fits16 = c.gn_num_groups == 8 && C0 % 64 == 0 && h->in_conv.algo == ALGO_DIRECT && h->in_conv.cout > 4 && h->out_conv.algo == ALGO_DIRECT && c.width % 4 == 0 &&
+                     S[1].down && S[2].down && S[1].dconv.f2 && S[2].dconv.f2 && S[5].up && S[6].up && S[5].uconv.f2 && S[6].uconv.f2 && !S[0].attn && !S[1].attn && !S[6].attn &&
+                     !S[7].attn && blocks_ok(S[0]) && blocks_ok(S[1]) && blocks_ok(S[6]) && blocks_ok(S[7]) && S[6].skip_in_bounded && S[7].skip_in_bounded;
 }
 
 int check_config(const r2dm_config& c) {

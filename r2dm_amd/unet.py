@@ -137,6 +137,14 @@ class _Engine:
             torch.cuda.current_stream(device).synchronize()  # sources may be freed after this
 
     # -- forward -----------------------------------------------------------------------------
+    def listing(self, B: int) -> str:
+        """One line per launch of a forward at batch ``B`` in the current precision mode (r2dm_forward_listing: host only)."""
+        L, need = _lib.lib(), ctypes.c_size_t(0)
+        _lib.check(L.r2dm_forward_listing(self.h, B, None, 0, ctypes.byref(need)))
+        buf = ctypes.create_string_buffer(need.value)
+        _lib.check(L.r2dm_forward_listing(self.h, B, buf, need.value, ctypes.byref(need)))
+        return buf.value.decode()
+
     def forward(self, x: torch.Tensor, cond: torch.Tensor) -> torch.Tensor:
         L = _lib.lib()
         B = x.shape[0]

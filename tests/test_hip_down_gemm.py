@@ -207,19 +207,19 @@ def test_engine_precision_switch_both_directions(engines, truth):
     assert torch.equal(y3["1"], y3["0"])
 
 
-def _range_sites(net):
-    """Names of the range-guard sites of the engine's last forward."""
-    from r2dm_amd import _lib
-
-    L = _lib.lib()
-    return [L.r2dm_range_site_name(net._engine.h, k).decode() for k in range(256)]
+def _down_stages_on_the_gemm(net, B):
+    """How many down stages of a forward at batch B run the FIR pre-pass + GEMM pair (the engine's listing of its launches)."""
+    launches = [ln.split(" | ")[1] for ln in net._engine.listing(B).splitlines()]
+    assert launches.count("down_phase_planes") == launches.count("down_gemm") and "down_planes" not in launches
+    assert launches.count("down_gemm") + launches.count("fir_down2") == 3
+    return launches.count("down_gemm")
 
 
 def test_all_three_down_stages_take_the_gemm_at_32x512(engines, truth):
     x, c, _ = truth
     for s, want in (("1", 3), ("0", 0)):
         engines[s](x[:1].to(DEV), c[:1].to(DEV))
-        assert sum("FIR planes" in n for n in _range_sites(engines[s])) == want, s
+        assert _down_stages_on_the_gemm(engines[s], 1) == want, s
 
 
 def test_golden_resolution_keeps_conv_and_fir(golden):
@@ -232,6 +232,6 @@ def test_golden_resolution_keeps_conv_and_fir(golden):
     for i, c in enumerate(g["conds"].tolist()):
         cond = torch.full((2,), c, device=DEV)
         y = on(x, cond)
-        assert not any("FIR planes" in n for n in _range_sites(on))
+        assert _down_stages_on_the_gemm(on, 2) == 0
         assert torch.equal(y, off(x, cond))
         assert max_abs(y.cpu(), g["y"][i]) < 2e-5, c

@@ -135,18 +135,16 @@ def engines():
 
 @pytest.mark.parametrize("B", [1, 3])
 def test_engine_phase_planes_and_nine_planes_agree(engines, B):
-    """32 x 512: all three down stages take the GEMM.  The two settings give the same bits, each repeats bit for bit, and both ran the pre-pass three times."""
-    from r2dm_amd import _lib
-
+    """32 x 512: all three down stages take the GEMM.  The two settings give the same bits, each repeats bit for bit, and both run the pre-pass three times."""
     x, c = rnd(94, 3, 2, 32, 512)[:B].to(DEV), torch.tensor([-9.0, 0.5, 6.0])[:B].to(DEV)
     out = {}
     for s, net in engines.items():
         out[s] = net(x, c)
         assert torch.equal(out[s], net(x, c)), s
-        names = [_lib.lib().r2dm_range_site_name(net._engine.h, k).decode() for k in range(256)]
-        assert sum("FIR planes" in n for n in names) == 3, s
-        # ... and each its own: the site's name says which layout the engine wrote (forward.hip), so a switch that was ignored cannot pass as agreement
-        assert sum("every distinct plane once" in n for n in names) == (3 if s == "1" else 0), s
-        assert sum("all nine" in n for n in names) == (3 if s == "9" else 0), s
+        launches = [ln.split(" | ")[1] for ln in net._engine.listing(B).splitlines()]
+        assert launches.count("down_gemm") == 3, s
+        # ... and each its own: the forward's listing says which layout the engine writes, so a switch that was ignored cannot pass as agreement
+        assert launches.count("down_phase_planes") == (3 if s == "1" else 0), s
+        assert launches.count("down_planes") == (3 if s == "9" else 0), s
     assert torch.isfinite(out["9"]).all()
     assert torch.equal(out["1"], out["9"])
