@@ -163,6 +163,21 @@ int r2dm_repaint_blend(const float* known, const float* noise, const float* unkn
 int r2dm_q_step(const float* x_s, const float* noise, const float* coef, float* x_t, int32_t batch, int64_t per_sample,
                 void* stream);
 
+/* -- denoising loss: the value of GaussianDiffusion.p_loss between the denoiser call and the loss weight
+ *    (models/diffusion/base.py:133-137), one pass over prediction, x_0, noise (batch, channels, plane) fp32 and the mask.
+ *    objective: 0 eps (target = noise), 1 v (alpha * noise - sigma * x_0, coef (B,2) = (alpha, sigma) host-computed scalars; coef is read
+ *    for this objective only), 2 x_0.  criterion: 0 l2, 1 l1, 2 huber (SmoothL1Loss, beta = 1).  mask: NULL (all ones) or
+ *    (batch, mask_channels, plane) with mask_channels 1 (broadcast over the channels) or `channels`.
+ *    num (batch, channels) fp64 = sum of loss * mask per plane; den (batch) fp64 = the sum of the mask over its own elements
+ *    (channels * plane with no mask).  Sums are float64 in a fixed order (no atomics): bit-reproducible, and a sample's sums do not
+ *    depend on the rest of the batch.  scratch: r2dm_diffusion_loss_scratch_bytes(batch, channels, plane) bytes (0 for an empty or
+ *    oversized problem), 8-byte aligned.  The fp32 pointers must be 16-byte aligned when plane is a multiple of 4 (read as quads), else
+ *    4-byte aligned; num and den 8-byte aligned. */
+size_t r2dm_diffusion_loss_scratch_bytes(int32_t batch, int32_t channels, int64_t plane);
+int r2dm_diffusion_loss(const float* prediction, const float* x_0, const float* noise, const float* mask, int32_t mask_channels,
+                        const float* coef, int32_t objective, int32_t criterion, int32_t batch, int32_t channels, int64_t plane,
+                        void* scratch, double* num, double* den, void* stream);
+
 /* -- sample post-processing: LiDARUtility.denormalize/revert_depth/to_xyz + concat
  *    (utils/lidar.py:49-61,98-120; sample_and_save.py:52-57).  x (B,2,H,W) in [-1,1],
  *    ray_angles (2,H,W) [elevation, azimuth] in rad, out (B,5,H,W) = depth,x,y,z,reflectance. */

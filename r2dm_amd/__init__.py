@@ -19,6 +19,8 @@ from . import rangenet  # noqa: E402  (RangeNet features of the FRD, segmentatio
 from .rangenet import pretrained_rangenet
 from . import postproc  # noqa: E402  (kNN vote and CRF-RNN refinement of the labels)
 from .postproc import CRFRNN, KNN
+from . import loss  # noqa: E402  (the denoising loss over noise levels)
+from .loss import loss_curve
 
 __all__ = [
     "ContinuousTimeGaussianDiffusion", "DiscreteTimeGaussianDiffusion", "GaussianDiffusion", "EfficientUNet",
@@ -26,6 +28,6 @@ __all__ = [
     "load_scans", "project_scans", "load_points_as_images", "parse_projection", "known_from_scan",
     "images_to_points", "save_scans", "save_ply", "scan_row_start", "centred_ray_angles",
     "pretrained_pointnet", "pointnet_features", "pretrained_rangenet",
-    "KNN", "CRFRNN",
+    "KNN", "CRFRNN", "loss_curve",
 ]
 __version__ = "0.4.0"

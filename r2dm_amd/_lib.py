@@ -82,6 +82,8 @@ SIGNATURES = {
     "r2dm_posterior_step": (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int64, c_int32, c_int32, c_float, _P]),
     "r2dm_repaint_blend": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int64, c_int32, c_int32, _P]),
     "r2dm_q_step": (c_int32, [_P, _P, _P, _P, c_int32, c_int64, _P]),
+    "r2dm_diffusion_loss_scratch_bytes": (c_size_t, [c_int32, c_int32, c_int64]),
+    "r2dm_diffusion_loss": (c_int32, [_P, _P, _P, _P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, c_int64, _P, _P, _P, _P]),
     "r2dm_lidar_postprocess": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_float, c_float, _P]),
     "r2dm_lidar_postprocess_fmt": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_float, c_float, c_int32, _P]),
     "r2dm_conv_packed_elems": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
@@ -226,6 +228,45 @@ def q_step(x_s, noise, coef) -> torch.Tensor:
     with torch.cuda.device(x_s.device):
         check(lib().r2dm_q_step(ptr(x_s), ptr(noise), ptr(coef), ptr(out), B, x_s.numel() // B, stream_ptr(x_s.device)))
     return out
+
+
+LOSS_OBJECTIVES = {"eps": 0, "v": 1, "x_0": 2}
+LOSS_CRITERIA = {"l2": 0, "l1": 1, "huber": 2}
+
+
+def diffusion_loss(prediction, x_0, noise, mask, coef, objective: str, criterion: str):
+    """``(num (B,C), den (B,))`` in float64: per sample and channel the sum of ``criterion(prediction - target) * mask``, and the sum of
+    the mask over its own elements (``C*H*W`` for ``mask=None``) -- base.py:133-136 in one pass.  ``mask``: None, (B,1,H,W) or (B,C,H,W);
+    ``coef`` (B,2) = (alpha, sigma), read for the ``v`` objective only."""
+    require_gpu(prediction, "prediction")
+    if objective not in LOSS_OBJECTIVES:
+        raise ValueError(f"invalid objective {objective}")
+    if criterion not in LOSS_CRITERIA:
+        raise ValueError(f"invalid criterion: {criterion}")
+    if prediction.dim() < 2 or x_0.shape != prediction.shape or noise.shape != prediction.shape:
+        raise ValueError(f"prediction {tuple(prediction.shape)}, x_0 {tuple(x_0.shape)} and noise {tuple(noise.shape)} must have one (B,C,...) shape")
+    dev = prediction.device
+    prediction, x_0, noise = f32c(prediction), f32c(x_0.to(dev)), f32c(noise.to(dev))
+    B, C = prediction.shape[:2]
+    plane = prediction.numel() // max(B * C, 1)
+    mask_c = 0
+    if mask is not None:
+        if mask.dim() != prediction.dim() or mask.shape[0] != B or mask.shape[1] not in (1, C) or mask.shape[2:] != prediction.shape[2:]:
+            raise ValueError(f"loss_mask {tuple(mask.shape)} must be (B,1,...) or (B,C,...) of prediction {tuple(prediction.shape)}")
+        mask, mask_c = f32c(mask.to(dev)), mask.shape[1]
+    coef = None if coef is None else f32c(coef.to(dev))
+    if objective == "v" and (coef is None or coef.shape != (B, 2)):
+        raise ValueError("the v objective needs coef (B,2) = (alpha, sigma)")
+    nbytes = lib().r2dm_diffusion_loss_scratch_bytes(B, C, plane)
+    if nbytes == 0:
+        raise R2DMError(f"diffusion_loss: empty or oversized problem (B={B}, C={C}, plane={plane})")
+    scratch = torch.empty(nbytes // 8, device=dev, dtype=torch.float64)
+    num = torch.empty(B, C, device=dev, dtype=torch.float64)
+    den = torch.empty(B, device=dev, dtype=torch.float64)
+    with torch.cuda.device(dev):
+        check(lib().r2dm_diffusion_loss(ptr(prediction), ptr(x_0), ptr(noise), ptr(mask), mask_c, ptr(coef), LOSS_OBJECTIVES[objective],
+                                        LOSS_CRITERIA[criterion], B, C, plane, ptr(scratch), ptr(num), ptr(den), stream_ptr(dev)))
+    return num, den
 
 
 DEPTH_FORMATS = {"log_depth": 0, "inverse_depth": 1, "depth": 2}

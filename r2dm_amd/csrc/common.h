@@ -282,6 +282,10 @@ hipError_t launch_repaint_blend(const float* known, const float* noise, const fl
                                 hipStream_t s);
 hipError_t launch_q_step(const float* x, const float* noise, const float* coef, float* out, int B, long per_sample,
                          hipStream_t s);
+// denoising loss (reference base.py:122-139): per-(sample, channel) sums of criterion(prediction - target) * mask and the mask's own sum, in float64
+size_t diffusion_loss_scratch_bytes(int B, int C, long plane);
+hipError_t launch_diffusion_loss(const float* pred, const float* x_0, const float* noise, const float* mask, int mask_c, const float* coef,
+                                 int objective, int criterion, int B, int C, long plane, void* scratch, double* num, double* den, hipStream_t s);
 
 // (B,2,H,W) in [-1,1] -> (B,5,H,W) [depth, x, y, z, reflectance]  (reference sample_and_save.py:52-57)
 hipError_t launch_lidar_postprocess(const float* x, const float* angles, float* y, int B, int H, int W,

@@ -29,6 +29,33 @@ int r2dm_q_step(const float* x_s, const float* noise, const float* coef, float* 
     return 0;
 }
 
+static bool loss_geometry_ok(int32_t B, int32_t C, int64_t plane) {
+    return B >= 1 && B <= 65535 && C >= 1 && C <= 65535 && plane >= 1 && plane <= (1LL << 40) / C / B;
+}
+
+size_t r2dm_diffusion_loss_scratch_bytes(int32_t B, int32_t C, int64_t plane) {
+    return loss_geometry_ok(B, C, plane) ? diffusion_loss_scratch_bytes(B, C, plane) : 0;
+}
+
+int r2dm_diffusion_loss(const float* prediction, const float* x_0, const float* noise, const float* mask, int32_t mask_channels,
+                        const float* coef, int32_t objective, int32_t criterion, int32_t B, int32_t C, int64_t plane, void* scratch,
+                        double* num, double* den, void* stream) {
+    if (!prediction || !x_0 || !noise || !scratch || !num || !den) return fail(1, "null argument");
+    if (objective < 0 || objective > 2) return fail(1, "diffusion_loss: objective must be 0 (eps), 1 (v) or 2 (x_0), got %d", objective);
+    if (criterion < 0 || criterion > 2) return fail(1, "diffusion_loss: criterion must be 0 (l2), 1 (l1) or 2 (huber), got %d", criterion);
+    if (objective == 1 && !coef) return fail(1, "diffusion_loss: the v objective needs coef (null argument)");
+    if (!loss_geometry_ok(B, C, plane)) return fail(1, "diffusion_loss: batch and channels must be in [1, 65535], the tensors 1 to 2^40 elements");
+    if (mask && mask_channels != 1 && mask_channels != C) return fail(1, "diffusion_loss: mask_channels must be 1 or %d, got %d", C, mask_channels);
+    const uintptr_t a = plane % 4 == 0 ? 15 : 3;  // a plane that is a multiple of 4 is read as quads
+    if (((uintptr_t)prediction | (uintptr_t)x_0 | (uintptr_t)noise | (uintptr_t)mask) & a)
+        return fail(1, "diffusion_loss: prediction, x_0, noise and mask must be %d-byte aligned for a plane of %lld elements", (int)a + 1, (long long)plane);
+    if (((uintptr_t)coef & 3) || (((uintptr_t)scratch | (uintptr_t)num | (uintptr_t)den) & 7))
+        return fail(1, "diffusion_loss: coef must be 4-byte aligned; scratch, num and den 8-byte aligned");
+    HIP_TRY(launch_diffusion_loss(prediction, x_0, noise, mask, mask_channels, coef, objective, criterion, B, C, plane, scratch, num, den,
+                                  (hipStream_t)stream));
+    return 0;
+}
+
 int r2dm_lidar_postprocess(const float* x, const float* ang, float* out, int32_t B, int32_t H, int32_t W,
                            float min_depth, float max_depth, void* stream) {
     return r2dm_lidar_postprocess_fmt(x, ang, out, B, H, W, min_depth, max_depth, 0, stream);

@@ -8,6 +8,7 @@
 //
 // also: K12 LiDAR post-processing of finished samples (reference sample_and_save.py:52-57).
 #include "common.h"
+#include "wave_ops.h"
 
 namespace r2dm {
 
@@ -212,6 +213,139 @@ hipError_t launch_q_step(const float* x, const float* noise, const float* coef, 
     long bx = (per_sample / 4 + 255) / 256;
     if (bx > 256) bx = 256;
     q_step_kernel<<<dim3((unsigned)bx, B), 256, 0, s>>>(x, noise, coef, out, per_sample);
+    return hipGetLastError();
+}
+
+// ---- denoising loss (reference base.py:122-139 p_loss: target, criterion, mask, the two sums) -----------------------------
+// One pass over prediction, x_0, noise and the mask.  Per element, float32 in the reference's operation order:
+//   target  eps: noise | x_0: x_0 | v: alpha * noise - sigma * x_0          (continuous_time.py:140-151, discrete_time.py:93-102)
+//   d = prediction - target;  l2: d * d | l1: |d| | huber: |d| < 1 ? 0.5 d d : |d| - 0.5   (base.py:39-44, SmoothL1Loss with beta = 1)
+//   ... times the mask value (base.py:135).
+// Sums in float64 and in a fixed order: thread (grid-stride over ONE (sample, channel) plane) -> wave -> the block's four waves ->
+// part[b][c][block] = (sum of loss * mask, sum of mask); loss_finalize_kernel then adds a plane's blocks in index order.  The
+// number of blocks per plane depends on `plane` alone, so a sample's sums do not depend on the batch it is in; no atomics.
+// A plane that is a multiple of 4 is read as 16-byte quads (every plane then starts on a quad); any other plane element by element.
+enum { CRIT_L2 = 0, CRIT_L1 = 1, CRIT_HUBER = 2 };
+constexpr int kLossMaxBlocks = 16;  // blocks per plane: 16 x 1024 elements per pass
+static int loss_blocks(long plane) {
+    const long n = (plane + 1023) / 1024;
+    return n < 1 ? 1 : n > kLossMaxBlocks ? kLossMaxBlocks : (int)n;
+}
+size_t diffusion_loss_scratch_bytes(int B, int C, long plane) { return (size_t)B * C * loss_blocks(plane) * 2 * sizeof(double); }
+
+#pragma clang fp contract(off)
+template <int OBJ, int CRIT>
+__device__ __forceinline__ float loss_elem(float pr, float x0, float z, float alpha, float sigma) {
+    float target;
+    if (OBJ == OBJ_EPS) target = z;
+    else if (OBJ == OBJ_X0) target = x0;
+    else target = alpha * z - sigma * x0;
+    const float d = pr - target;
+    if (CRIT == CRIT_L2) return d * d;
+    const float ad = fabsf(d);
+    if (CRIT == CRIT_L1) return ad;
+    return ad < 1.0f ? 0.5f * ad * ad : ad - 0.5f;
+}
+
+template <int OBJ, int CRIT>
+__global__ __launch_bounds__(256) void diffusion_loss_kernel(const float* __restrict__ pred, const float* __restrict__ x_0,
+                                                             const float* __restrict__ noise, const float* __restrict__ mask,
+                                                             const float* __restrict__ coef, double* __restrict__ part, long plane,
+                                                             int mask_c) {
+    const int c = blockIdx.y, b = blockIdx.z, C = gridDim.y;
+    float alpha = 0.f, sigma = 0.f;
+    if (OBJ == OBJ_V) alpha = coef[2 * b], sigma = coef[2 * b + 1];
+    const long base = ((long)b * C + c) * plane;
+    const float *pp = pred + base, *xp = x_0 + base, *zp = noise + base;
+    const float* mp = mask ? mask + (mask_c == 1 ? (long)b * plane : base) : nullptr;
+    double num = 0.0, den = 0.0;
+    if ((plane & 3) == 0) {
+        const long n4 = plane >> 2;
+        for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+            const f32x4 p = reinterpret_cast<const f32x4*>(pp)[i], x = reinterpret_cast<const f32x4*>(xp)[i];
+            const f32x4 z = reinterpret_cast<const f32x4*>(zp)[i];
+            f32x4 m = {1.f, 1.f, 1.f, 1.f};
+            if (mp) m = reinterpret_cast<const f32x4*>(mp)[i];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float l = loss_elem<OBJ, CRIT>(p[e], x[e], z[e], alpha, sigma);
+                if (mp) l = l * m[e];
+                num += (double)l;
+                den += (double)m[e];
+            }
+        }
+    } else {
+        for (long i = blockIdx.x * 256L + threadIdx.x; i < plane; i += (long)gridDim.x * 256) {
+            const float m = mp ? mp[i] : 1.f;
+            float l = loss_elem<OBJ, CRIT>(pp[i], xp[i], zp[i], alpha, sigma);
+            if (mp) l = l * m;
+            num += (double)l;
+            den += (double)m;
+        }
+    }
+    num = wave_sum_f64(num);
+    den = wave_sum_f64(den);
+    __shared__ double sh[2][4];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) sh[0][wave] = num, sh[1][wave] = den;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double* o = part + (((long)b * C + c) * gridDim.x + blockIdx.x) * 2;
+        o[0] = ((sh[0][0] + sh[0][1]) + sh[0][2]) + sh[0][3];
+        o[1] = ((sh[1][0] + sh[1][1]) + sh[1][2]) + sh[1][3];
+    }
+}
+#pragma clang fp contract(fast)
+
+// num[b][c] = a plane's block sums in index order; den[b] = the mask's own elements: its `den_c` planes (1 or C) in channel order, or, with
+// no mask, C * plane exactly
+__global__ __launch_bounds__(64) void loss_finalize_kernel(const double* __restrict__ part, double* __restrict__ num, double* __restrict__ den,
+                                                           int C, int blocks, int den_c, double den_all) {
+    const int b = blockIdx.x;
+    for (int c = threadIdx.x; c < C; c += 64) {
+        const double* p = part + ((long)b * C + c) * blocks * 2;
+        double s = 0.0;
+        for (int j = 0; j < blocks; ++j) s += p[2 * j];
+        num[(long)b * C + c] = s;
+    }
+    if (threadIdx.x == 0) {
+        double s = den_all;
+        if (den_c > 0) {
+            s = 0.0;
+            for (int c = 0; c < den_c; ++c)
+                for (int j = 0; j < blocks; ++j) s += part[(((long)b * C + c) * blocks + j) * 2 + 1];
+        }
+        den[b] = s;
+    }
+}
+
+template <int OBJ>
+static hipError_t launch_loss_crit(int crit, dim3 g, hipStream_t s, const float* pred, const float* x_0, const float* noise, const float* mask,
+                                   const float* coef, double* part, long plane, int mask_c) {
+    switch (crit) {
+        case CRIT_L2: diffusion_loss_kernel<OBJ, CRIT_L2><<<g, 256, 0, s>>>(pred, x_0, noise, mask, coef, part, plane, mask_c); break;
+        case CRIT_L1: diffusion_loss_kernel<OBJ, CRIT_L1><<<g, 256, 0, s>>>(pred, x_0, noise, mask, coef, part, plane, mask_c); break;
+        case CRIT_HUBER: diffusion_loss_kernel<OBJ, CRIT_HUBER><<<g, 256, 0, s>>>(pred, x_0, noise, mask, coef, part, plane, mask_c); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// (arguments validated by r2dm_diffusion_loss: 1 <= B, C <= 65535, plane >= 1, mask_c in {1, C}, alignment)
+hipError_t launch_diffusion_loss(const float* pred, const float* x_0, const float* noise, const float* mask, int mask_c, const float* coef,
+                                 int objective, int criterion, int B, int C, long plane, void* scratch, double* num, double* den, hipStream_t s) {
+    const int blocks = loss_blocks(plane);
+    const dim3 g((unsigned)blocks, (unsigned)C, (unsigned)B);
+    double* part = static_cast<double*>(scratch);
+    hipError_t e;
+    switch (objective) {
+        case OBJ_EPS: e = launch_loss_crit<OBJ_EPS>(criterion, g, s, pred, x_0, noise, mask, coef, part, plane, mask_c); break;
+        case OBJ_V: e = launch_loss_crit<OBJ_V>(criterion, g, s, pred, x_0, noise, mask, coef, part, plane, mask_c); break;
+        case OBJ_X0: e = launch_loss_crit<OBJ_X0>(criterion, g, s, pred, x_0, noise, mask, coef, part, plane, mask_c); break;
+        default: return hipErrorInvalidValue;
+    }
+    if (e != hipSuccess) return e;
+    loss_finalize_kernel<<<B, 64, 0, s>>>(part, num, den, C, blocks, mask ? mask_c : 0, (double)C * (double)plane);
     return hipGetLastError();
 }
 

@@ -15,7 +15,8 @@ MI355X design, not a translation:
   * Noise stays in ``torch.randn(generator=...)`` so that seeds mean what they mean in the
     reference (base.py:71-94).
 
-Training-side members (loss, timestep sampling) are out of scope.
+The denoising loss ``ddpm(x_0, loss_mask)`` (base.py:122-149) is evaluated forward-only: one noising (``r2dm_q_step``), one denoiser
+call and one fused HIP reduction (``r2dm_diffusion_loss``); there is no autograd and no optimizer here.
 """
 from __future__ import annotations
 
@@ -42,6 +43,12 @@ _OBJECTIVES = {"eps": 0, "v": 1, "x_0": 2}
 # posterior kernel modes (csrc/posterior.hip)
 _M_CT_DDPM, _M_CT_DDIM, _M_DT_DDPM, _M_DT_DDIM, _M_DT_DDIM_NOISE = 0, 1, 2, 3, 4
 _NCOEF = 8
+_CRITERIA = ("l2", "l1", "huber")  # base.py:39-44
+
+
+class NoCPUFallback(_lib.R2DMError, NotImplementedError):
+    """The denoising loss was asked of a model or an image batch that is not on a GPU: an ``R2DMError`` like every other entry point's
+    refusal, and a ``NotImplementedError`` for callers of the earlier sampling-only package, whose ``forward`` raised that."""
 
 
 # --------------------------------------------------------------------------------------
@@ -311,13 +318,101 @@ class GaussianDiffusion(nn.Module):
     def _on_device(self, dev) -> bool:
         return self.schedule_on == "device" and torch.device(dev).type == "cuda"
 
-    # -- training side: out of scope ------------------------------------------------------
-    def forward(self, *args, **kwargs):
-        raise NotImplementedError(
-            "r2dm_amd builds the sampling path only; the training loss "
-            "(reference base.py:122-149) is out of scope -- see DESIGN.md")
+    # -- the denoising loss (base.py:99-149), forward only ------------------------------------
+    def sample_timesteps(self, batch_size: int, device) -> torch.Tensor:
+        raise NotImplementedError
 
-    p_loss = forward
+    def get_network_condition(self, steps):
+        raise NotImplementedError
+
+    def get_target(self, x_0, steps, noise):
+        raise NotImplementedError
+
+    def get_loss_weight(self, steps):
+        raise NotImplementedError
+
+    def _log_snr_of_steps(self, steps) -> torch.Tensor:
+        """(B,) log-SNR of per-sample steps, evaluated where ``schedule_on`` says."""
+        raise NotImplementedError
+
+    def _loss_coef(self, steps) -> torch.Tensor:
+        """(B,2) = (alpha, sigma) of q(x_t | x_0) at per-sample steps: the rows of ``r2dm_q_step`` and of the ``v`` target."""
+        raise NotImplementedError
+
+    def _loss_weight_of_snr(self, snr: torch.Tensor) -> torch.Tensor:
+        """Min-SNR weighting (continuous_time.py:155-167, discrete_time.py:105-117), the reference's ops on ``snr``."""
+        clipped_snr = snr.clone()
+        if self.min_snr_loss_weight:
+            clipped_snr.clamp_(max=self.min_snr_gamma)
+        if self.objective == "eps":
+            return clipped_snr / snr
+        if self.objective == "x_0":
+            return clipped_snr
+        if self.objective == "v":
+            return clipped_snr / (snr + 1)
+        raise ValueError(f"invalid objective {self.objective}")
+
+    def _criterion_name(self) -> str:
+        if self.loss_type not in _CRITERIA:  # (base.py:45 also takes an nn.Module: autograd-side code, no HIP kernel for it)
+            raise ValueError(f"invalid criterion: {self.loss_type}")
+        return self.loss_type
+
+    @torch.inference_mode()
+    def loss_terms(self, x_0, steps, loss_mask=None, rng=None, noise=None) -> dict:
+        """The value of ``p_loss`` (base.py:122-139) with its pieces; forward only, under ``torch.inference_mode()``: nothing returned
+        carries a gradient.  One noising (``r2dm_q_step``), one denoiser call, one fused reduction (``r2dm_diffusion_loss``: target,
+        criterion, mask and the float64 sums in one pass).
+
+        ``noise`` (extension): explicit noise instead of a draw; else ``randn_like(x_0, rng)``, ``rng`` as everywhere in this class
+        (None: the global generator of ``x_0``'s device, as the reference's ``q_step_from_x_0(x_0, steps)``).
+        ``loss_mask``: None (all ones), ``(B,1,H,W)`` or ``(B,C,H,W)``.
+
+        -> ``per_channel`` (B,C): the channel's masked loss sum over the mask's sum (the channels add up to ``per_sample``);
+        ``per_sample`` (B,): base.py:135-137, ``float32(sum) / (float32(mask sum) + 1e-8)``; ``weight`` (B,): ``get_loss_weight``;
+        ``weighted`` (B,): ``per_sample * weight``; ``log_snr`` (B,); ``loss`` (0-d): base.py:138 as the reference evaluates it.  There
+        the (B,1) losses meet the (B,1,1,1) weights, so the product is (B,1,B,1) -- every loss with every weight -- and its mean is
+        ``mean(weight) * mean(per_sample)`` up to rounding, not ``mean(weighted)``; the two agree when all steps are equal
+        (``r2dm_amd.loss.loss_curve`` evaluates one level at a time).  A sample's entries do not depend on the rest of the batch."""
+        if self.device.type != "cuda" or not x_0.is_cuda:
+            raise NoCPUFallback(f"the denoising loss runs as HIP kernels on an MI355X (model on {self.device}, x_0 on {x_0.device}): "
+                                "r2dm_amd has no CPU fallback")
+        objective, criterion = self.objective, self._criterion_name()
+        self._objective_id()
+        dev = x_0.device
+        x_0 = _lib.f32c(x_0)
+        B = x_0.shape[0]
+        steps = steps.reshape(-1)
+        if steps.numel() != B:
+            raise ValueError(f"steps must have shape ({B},), got {tuple(steps.shape)}")
+        if noise is None:
+            noise = self.randn_like(x_0, rng=rng)
+        coef = self._loss_coef(steps).to(dev)
+        x_t = _lib.q_step(x_0, noise, coef)
+        prediction = self.model(x_t, self.get_network_condition(steps).to(dev))  # (a range-guard trip: handled inside EfficientUNet.forward)
+        num, den = _lib.diffusion_loss(prediction, x_0, noise, loss_mask, coef, objective, criterion)
+        total = num[:, 0].clone()
+        for c in range(1, num.shape[1]):  # channel order, whatever the batch
+            total += num[:, c]
+        den32 = den.float().add(1e-8)
+        per_sample = total.float() / den32
+        weight = self.get_loss_weight(steps).reshape(B).to(dev)
+        loss = (per_sample[:, None] * weight[:, None, None, None]).mean()
+        return {"per_channel": num.float() / den32[:, None], "per_sample": per_sample, "weight": weight, "weighted": per_sample * weight,
+                "log_snr": self._log_snr_of_steps(steps).reshape(B).to(dev), "loss": loss}
+
+    def p_loss(self, x_0, steps, loss_mask=None, rng=None):
+        """base.py:122-139 -> 0-d float32 on the device; ``loss_terms(...)["loss"]``.  Forward only: evaluated under
+        ``torch.inference_mode()``, the result carries no gradient (there is no training here)."""
+        return self.loss_terms(x_0, steps, loss_mask, rng=rng)["loss"]
+
+    def forward(self, x_0, loss_mask=None, rng=None):
+        """base.py:141-149: the denoising loss at freshly drawn steps -- the steps first, then the noise.  Forward only, no gradient
+        (see ``p_loss``).  On a model or a batch that is not on a GPU: ``NoCPUFallback``."""
+        if self.device.type != "cuda" or not x_0.is_cuda:
+            raise NoCPUFallback(f"the denoising loss runs as HIP kernels on an MI355X (model on {self.device}, x_0 on {x_0.device}): "
+                                "r2dm_amd has no CPU fallback")
+        steps = self.sample_timesteps(x_0.shape[0], x_0.device)
+        return self.p_loss(x_0, steps, loss_mask, rng=rng)
 
     def _objective_id(self) -> int:
         if self.objective not in _OBJECTIVES:
@@ -387,7 +482,43 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
         return self._log_snr_1d(t)[:, None, None, None]
 
     def get_network_condition(self, steps):
+        """(B,) per-sample steps -> (B,) log-SNR (continuous_time.py:137-138), with the schedule's torch ops on ``steps`` as they are."""
         return self._log_snr_1d(steps)
+
+    # -- the denoising loss's pieces (continuous_time.py:133-167) --------------------------
+    def sample_timesteps(self, batch_size: int, device) -> torch.Tensor:
+        return torch.rand(batch_size, device=device, dtype=torch.float32)
+
+    def _log_snr_of_steps(self, steps) -> torch.Tensor:
+        """(B,) log-SNR where ``schedule_on`` says: on the host row by row on 1-element tensors (see ``_coefficients``: the values of the
+        reference's CPU run, and a row does not depend on the batch), or with the same ops on the device."""
+        if self._on_device(steps.device):
+            return self._log_snr_1d(steps.detach().float().reshape(-1))
+        steps = steps.detach().to("cpu", torch.float32).reshape(-1)
+        return torch.cat([self._log_snr_1d(steps[i:i + 1]) for i in range(steps.numel())])
+
+    def _loss_coef(self, steps) -> torch.Tensor:
+        return self._alpha_sigma_rows(steps)
+
+    def get_target(self, x_0, step_t, noise):
+        """continuous_time.py:140-151, in torch (the fused loss kernel does not call this; the tests compare it with that kernel)."""
+        if self.objective == "eps":
+            return noise
+        if self.objective == "x_0":
+            return x_0
+        if self.objective == "v":
+            coef = self._alpha_sigma_rows(step_t).to(x_0.device)
+            alpha, sigma = coef[:, 0][:, None, None, None], coef[:, 1][:, None, None, None]
+            return alpha * noise - sigma * x_0
+        raise ValueError(f"invalid objective {self.objective}")
+
+    def get_loss_weight(self, steps):
+        """(B,1,1,1) min-SNR loss weights (continuous_time.py:153-167), on ``steps``' device."""
+        log_snr = self._log_snr_of_steps(steps)
+        if self._on_device(steps.device):
+            return self._loss_weight_of_snr(log_snr.exp())[:, None, None, None]
+        rows = [self._loss_weight_of_snr(log_snr[i:i + 1].exp()) for i in range(log_snr.numel())]  # (host: row by row, as the log-SNR)
+        return torch.cat(rows)[:, None, None, None].to(steps.device)
 
     # -- host-side coefficient table -------------------------------------------------------
     def _coefficient_row(self, t: torch.Tensor, s: torch.Tensor, mode: str, ddim_eta: float):
@@ -650,6 +781,46 @@ class DiscreteTimeGaussianDiffusion(GaussianDiffusion):
 
     def get_network_condition(self, steps):
         return steps
+
+    # -- the denoising loss's pieces (discrete_time.py:80-124) -----------------------------
+    def sample_timesteps(self, batch_size: int, device) -> torch.Tensor:
+        return torch.randint(low=0, high=self.num_training_steps, size=(batch_size,), device=device, dtype=torch.long)
+
+    def _log_snr_of_steps(self, steps) -> torch.Tensor:
+        """(B,) ``log(snr[steps])`` where ``schedule_on`` says: on the host row by row (a row does not depend on the batch), or on the device."""
+        if self._on_device(steps.device):
+            return self.snr[steps.to(self.snr.device).long().reshape(-1), 0, 0, 0].log()
+        snr = self.snr.detach().cpu()[steps.detach().to("cpu", torch.long).reshape(-1), 0, 0, 0]
+        return torch.cat([snr[i:i + 1].log() for i in range(snr.numel())])
+
+    def _loss_coef(self, steps) -> torch.Tensor:
+        """(sqrt(alpha_bar), sqrt(1 - alpha_bar)) rows on the host (discrete_time.py:122-123).  The roots are taken in float64 and rounded
+        to float32 -- the correctly rounded float32 root, which a GPU's float32 sqrt also gives: torch's float32 sqrt on a CPU is not
+        correctly rounded on every host (measured: 9 of the 1000 steps' roots one ulp off on one host, 213 on another)."""
+        ab = self.alpha_bar.detach().cpu()[steps.detach().to("cpu", torch.long).reshape(-1), 0, 0, 0]
+        return torch.stack([ab.double().sqrt().float(), (1 - ab).double().sqrt().float()], dim=-1).contiguous()
+
+    def get_target(self, x_0, steps, noise):
+        """discrete_time.py:93-102, in torch (the fused loss kernel does not call this; the tests compare it with that kernel)."""
+        if self.objective == "eps":
+            return noise
+        if self.objective == "x_0":
+            return x_0
+        if self.objective == "v":
+            alpha_bar = self.alpha_bar.to(x_0.device)[steps.to(x_0.device)]
+            return alpha_bar.sqrt() * noise - (1 - alpha_bar).sqrt() * x_0
+        raise ValueError(f"invalid objective {self.objective}")
+
+    def get_loss_weight(self, timesteps):
+        """(B,1,1,1) min-SNR loss weights (discrete_time.py:104-117): a table lookup, a clamp and one division -- the same bits on
+        the host and on the device."""
+        return self._loss_weight_of_snr(self.snr[timesteps.to(self.snr.device)])
+
+    def q_step_from_x_0(self, x_0, steps, rng=None):
+        """Forward process q(x_t | x_0) (discrete_time.py:119-124); HIP kernel r2dm_q_step, which replays the reference's operation
+        order (two products, one sum): the same bits as the reference's expression."""
+        noise = self.randn_like(x_0, rng=rng)
+        return _lib.q_step(x_0, noise, self._loss_coef(steps).to(x_0.device)), noise
 
     def _coefficients(self, steps: torch.Tensor, mode: str, eta: float):
         """Row scalars of discrete_time.py:135-177 on the host (float32, same op order)."""
