@@ -1,0 +1,140 @@
+#!/usr/bin/env python3
+"""Scores scan completion on held-out scans, on the GPU: every scan is corrupted (``--corruption``: ``full``, ``beams:K``,
+``random_beams:P``, ``random_points:P``; repeatable), completed by RePaint and / or by nearest / linear interpolation of the known beams
+(``--methods``), and compared with the scan itself -- mean absolute and root-mean-square error of range and reflectance over the pixels
+that had to be filled in, the recall of returns, the rate of false returns and, with ``--rangenet_weights``, the IoU of the RangeNet-53
+labels of the completed image against the labels of the real scan (r2dm_amd.completion.evaluate_completion; DESIGN.md section 4,
+"Completion metrics").
+
+The scans come from either
+  - ``--real_scans DIR``: a directory tree of raw Velodyne ``*.bin`` scans, projected here with the checkpoint's ``cfg.data.projection``
+    (64 rows, the projection's width, masked by the depth window) and resized to ``cfg.data.resolution`` (nearest-exact); or
+  - ``--real_dir DIR``: a directory of ``*.pth`` files with (5,H,W) [depth, x, y, z, reflectance] scans at the model's resolution, what
+    ``evaluate.py --real_dir`` reads.
+``--rangenet_weights PATH`` is the official ``darknet53-1024.tar.gz`` archive or a ``.pth`` state dict (a local file; nothing is
+downloaded); ``--semseg_postprocess`` refines the labels of both images with the reference's post-processors.  Scan i draws its masks and
+its RePaint noise from generators seeded from ``(--seed, i)`` (r2dm_amd.completion.scan_seed), whatever ``--batch_size``.
+
+Writes one JSON document to ``--out``: ``info`` (checkpoint, number of scans, settings) and ``results[kind][method]`` (counts, error
+sums, micro and macro averages, per-class IoU and mIoU, or ``skipped``); an undefined value is ``null``.  ``--save_dir DIR`` also writes
+the tensors behind the numbers, one ``.pt`` file per corruption."""
+import json
+from argparse import ArgumentParser
+from pathlib import Path
+
+import torch
+import torch.nn.functional as F
+
+from evaluate import sample_files, scan_files
+
+
+def planes_of_scans(files, cfg, lidar_utils, batch_size, device):
+    """(N,6,H,W) masked [x, y, z, reflectance, depth, mask] planes of raw scans at ``cfg.data.resolution``"""
+    from r2dm_amd import projection
+
+    unfolding, width = projection.parse_projection(cfg.data.projection)
+    out = []
+    for k in range(0, len(files), batch_size):
+        points, offsets = projection.load_scans(files[k:k + batch_size])
+        xyzrdm = projection.project_scans(points, offsets, H=64, W=width, scan_unfolding=unfolding, min_depth=lidar_utils.min_depth,
+                                          max_depth=lidar_utils.max_depth, apply_mask=True, device=device)
+        out.append(F.interpolate(xyzrdm, size=tuple(cfg.data.resolution), mode="nearest-exact"))
+    return torch.cat(out)
+
+
+def planes_of_samples(files, cfg, lidar_utils, device):
+    """The same planes from (5,H,W) [depth, x, y, z, reflectance] files: a pixel counts as measured when its depth lies inside the
+    checkpoint's depth window."""
+    imgs = torch.stack([torch.load(f, map_location="cpu").float() for f in files]).to(device)
+    if imgs.dim() != 4 or imgs.shape[1] != 5:
+        raise SystemExit(f"--real_dir: expected (5,H,W) scans, got {tuple(imgs.shape[1:])}")
+    if tuple(imgs.shape[-2:]) != tuple(cfg.data.resolution):
+        imgs = F.interpolate(imgs, size=tuple(cfg.data.resolution), mode="nearest-exact")
+    depth = imgs[:, [0]]
+    mask = ((depth > lidar_utils.min_depth) & (depth < lidar_utils.max_depth)).float()
+    planes = torch.cat([imgs[:, 1:4], imgs[:, [4]], depth, mask], dim=1)
+    return torch.where(mask != 0, planes, torch.zeros_like(planes))
+
+
+@torch.no_grad()
+def main(argv=None):
+    import r2dm_amd
+    from completion_demo import semseg_postprocess
+    from r2dm_amd import completion
+
+    args = build_parser().parse_args(argv)
+    if (args.real_scans is None) == (args.real_dir is None):
+        raise SystemExit("give one of --real_scans DIR / --real_dir DIR")
+    kinds = list(dict.fromkeys(args.corruption or ["beams:4"]))
+    for kind in kinds:
+        completion.parse_kind(kind)
+    device = torch.device("cuda")
+    ddpm, lidar_utils, cfg = r2dm_amd.setup_model(args.ckpt, device=device, show_info=False, max_batch=args.batch_size)
+    if args.real_scans is not None:
+        files = scan_files(args.real_scans)[:args.limit]
+        if not files:
+            raise SystemExit("no *.bin files below --real_scans")
+        planes = planes_of_scans(files, cfg, lidar_utils, args.batch_size, device)
+    else:
+        files = sample_files(args.real_dir, limit=args.limit)
+        if not files:
+            raise SystemExit("no *.pth files in --real_dir")
+        planes = planes_of_samples(files, cfg, lidar_utils, device)
+    semseg, post = None, None
+    if args.rangenet_weights is not None:
+        semseg = r2dm_amd.rangenet.pretrained_rangenet(args.rangenet_weights, device=device)
+        post = semseg_postprocess(args.semseg_postprocess, semseg.num_classes)
+    out = completion.evaluate_completion(ddpm, lidar_utils, planes, kinds, methods=tuple(args.methods), num_steps=args.num_steps,
+                                         num_resample_steps=args.num_resample_steps, jump_length=args.jump_length, seed=args.seed,
+                                         batch_size=args.batch_size, semseg=semseg, semseg_postprocess=post, keep=args.save_dir is not None)
+    results, kept = out if args.save_dir is not None else (out, None)
+    info = {"ckpt": str(args.ckpt), "source": str(args.real_scans if args.real_scans is not None else args.real_dir), "num_scans": len(files),
+            "resolution": list(cfg.data.resolution), "corruptions": kinds, "methods": list(args.methods), "num_steps": args.num_steps,
+            "num_resample_steps": args.num_resample_steps, "jump_length": args.jump_length, "batch_size": args.batch_size, "seed": args.seed,
+            "lo": float(lidar_utils.min_depth), "hi": float(lidar_utils.max_depth), "rangenet_weights": args.rangenet_weights,
+            "semseg_postprocess": args.semseg_postprocess if semseg is not None else None}
+    doc = completion.jsonable({"info": info, "results": results})
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(doc, f, indent=4, allow_nan=False)
+    if kept is not None:
+        args.save_dir.mkdir(parents=True, exist_ok=True)
+        for kind, tensors in kept.items():
+            torch.save(tensors, args.save_dir / (kind.replace(":", "_") + ".pt"))
+    for kind in kinds:
+        for method, entry in results[kind].items():
+            if "skipped" in entry:
+                print(f"{kind:>20} {method:>8}: skipped")
+                continue
+            m, iou = entry["micro"], entry.get("iou", {}).get("miou")
+            print(f"{kind:>20} {method:>8}: MAE depth {m['mae_depth']:.4f} m, reflectance {m['mae_reflectance']:.4f}, recall {m['return_recall']:.4f}"
+                  + ("" if iou is None else f", mIoU {iou:.4f}"))
+    print(f"{len(files)} scans -> {args.out}")
+    return doc
+
+
+def build_parser():
+    parser = ArgumentParser()
+    parser.add_argument("--ckpt", type=Path, required=True)
+    parser.add_argument("--real_scans", type=str, default=None, help="a directory tree of raw Velodyne *.bin scans, projected here")
+    parser.add_argument("--real_dir", type=str, default=None, help="a directory of (5,H,W) scans in the sample layout (*.pth)")
+    parser.add_argument("--limit", type=int, default=None, help="the first so many scans (sorted)")
+    parser.add_argument("--corruption", action="append", default=None, metavar="KIND",
+                        help="full, beams:K, random_beams:P or random_points:P; repeatable (default: beams:4)")
+    parser.add_argument("--methods", nargs="+", choices=["repaint", "nearest", "linear"], default=["repaint"])
+    parser.add_argument("--num_steps", type=int, default=32)
+    parser.add_argument("--num_resample_steps", type=int, default=10)
+    parser.add_argument("--jump_length", type=int, default=1)
+    parser.add_argument("--batch_size", type=int, default=8, help="scans per RePaint call")
+    parser.add_argument("--seed", type=int, default=0, help="scan i draws its masks and its noise from generators seeded from (seed, i)")
+    parser.add_argument("--rangenet_weights", type=str, default=None,
+                        help="the official darknet53-1024.tar.gz archive or a .pth state dict (a local file): adds per-class IoU and mIoU")
+    parser.add_argument("--semseg_postprocess", choices=("none", "knn", "crf", "crf_knn"), default="none",
+                        help="refine the labels of both images: the kNN vote of RangeNet++, the CRF-RNN of SqueezeSeg, or the CRF-RNN and then the vote")
+    parser.add_argument("--save_dir", type=Path, default=None, help="also write the tensors behind the numbers, one .pt file per corruption")
+    parser.add_argument("--out", type=str, default="completion.json")
+    return parser
+
+
+if __name__ == "__main__":
+    main()

@@ -393,6 +393,34 @@ int r2dm_knn_vote(const float* depth, const int64_t* label, const float* weight,
 int r2dm_crf_iter(const float* q_in, const float* unary, const float* xyz, const float* mask, const float* params, float* q_out, int32_t batch,
                   int32_t classes, int32_t height, int32_t width, int32_t kh, int32_t kw, int32_t uniform_beta, void* stream);
 
+/* -- completion metrics: how good an inpainted scan is (beam-level upsampling of held-out scans, the second results table of the R2DM
+ *    paper; the reference has no code for it) ---------------------------------------------------------------------------------------------
+ * r2dm_completion_error: pred, target (batch,5,plane) fp32 in the sample layout [depth, x, y, z, reflectance] (planes 0 and 4 are read),
+ *    known (batch,1,plane) fp32 zeros and ones (the RePaint mask).  Per sample, with U = {known == 0}, G = {lo < target depth < hi},
+ *    P = {lo < pred depth < hi} (a NaN depth is in neither), E = U & G, Bo = E & P and r^ = pred depth on P, else 0:
+ *    out (batch,10) fp64 = |U|, |E|, |Bo|, |U & P \ G|, sum_E |r^ - r|, sum_E (r^ - r)^2, sum_Bo |dr|, sum_Bo dr^2, sum_E |drho|, sum_E drho^2.
+ *    Every fp32 value is widened to fp64 first (exact differences); sums are fp64 in a fixed order (no atomics): bit-reproducible, and a
+ *    sample's numbers do not depend on the rest of the batch.  scratch: the bytes the _scratch_bytes function returns for (batch, plane)
+ *    (0 for an empty or oversized problem), 8-byte aligned like out.  The fp32 pointers must be 16-byte aligned when plane is a multiple
+ *    of 4 (read as quads), else 4-byte aligned.
+ * r2dm_confusion_matrix: pred, target (batch,pixels) int64 labels, mask NULL or (batch,pixels) fp32 (0 skips the pixel) ->
+ *    counts (batch,classes,classes) int64, [b][target][pred], zeroed by the call.  One int32 table per block in LDS, merged with 64-bit
+ *    integer atomics: exact, independent of any order.  An unmasked label outside [0, classes) indexes nothing and is counted in *bad
+ *    (int64 in device memory, zeroed by the call).  Limits: 1 <= classes <= 64, batch <= 65535, batch * pixels <= 2^40.
+ * r2dm_fill_beams: the interpolation baselines.  x, out (batch,channels,height,width) fp32, rows (batch,height) bytes (non-zero = the
+ *    beam is known).  A known row is copied.  For a pixel (h, w) of an unknown row, `up` / `dn` are the nearest known rows above / below
+ *    (no wrap); an endpoint is usable if it exists and x[b][0][row][w] != nodata.  mode 0 (nearest): every channel from the usable endpoint
+ *    at the smaller row distance, `up` on a tie.  mode 1 (linear): with both usable a + (b - a) * t, t = float(h - up) / float(dn - up), in
+ *    fp32 with IEEE division and no contraction; with one usable a copy of it.  No usable endpoint: nodata in every channel.  out must
+ *    not alias x.  Limits: batch, height <= 65535. */
+size_t r2dm_completion_error_scratch_bytes(int32_t batch, int64_t plane);
+int r2dm_completion_error(const float* pred, const float* target, const float* known, float lo, float hi, int32_t batch, int64_t plane,
+                          void* scratch, double* out, void* stream);
+int r2dm_confusion_matrix(const int64_t* pred, const int64_t* target, const float* mask, int32_t batch, int64_t pixels, int32_t classes,
+                          int64_t* counts, int64_t* bad, void* stream);
+int r2dm_fill_beams(const float* x, const uint8_t* rows, float* out, int32_t batch, int32_t channels, int32_t height, int32_t width,
+                    float nodata, int32_t mode, void* stream);
+
 /* -- single kernels, exported for per-op parity tests against the oracle -------------------- */
 /* ops.Conv2d(ring) 3x3 / 1x1 (models/ops.py:149-173) with optional fused GroupNorm-affine(+SiLU)
  * prologue (aff: (B,Cin,2) or NULL; prologue 0 none, 1 affine, 2 affine+SiLU) and optional

@@ -21,6 +21,8 @@ from . import postproc  # noqa: E402  (kNN vote and CRF-RNN refinement of the la
 from .postproc import CRFRNN, KNN
 from . import loss  # noqa: E402  (the denoising loss over noise levels)
 from .loss import loss_curve
+from . import completion  # noqa: E402  (completion metrics: range / reflectance error, IoU, interpolation baselines)
+from .completion import (completion_errors, confusion_matrix, corruption_mask, evaluate_completion, fill_beams, iou_from_confusion)
 
 __all__ = [
     "ContinuousTimeGaussianDiffusion", "DiscreteTimeGaussianDiffusion", "GaussianDiffusion", "EfficientUNet",
@@ -29,5 +31,6 @@ __all__ = [
     "images_to_points", "save_scans", "save_ply", "scan_row_start", "centred_ray_angles",
     "pretrained_pointnet", "pointnet_features", "pretrained_rangenet",
     "KNN", "CRFRNN", "loss_curve",
+    "corruption_mask", "completion_errors", "confusion_matrix", "iou_from_confusion", "fill_beams", "evaluate_completion",
 ]
 __version__ = "0.4.0"

@@ -1,0 +1,344 @@
+"""Completion metrics: how good an inpainted scan is.
+
+The R2DM paper scores beam-level upsampling of held-out scans by the mean absolute error of range and reflectance over the pixels the
+model had to fill in, and by the IoU of RangeNet labels of the completed image against the labels of the real scan, next to nearest and
+linear interpolation of the known beams.  The reference has no code for it.  Here the scoring is three HIP kernels
+(``r2dm_amd/csrc/completion.hip``) and this module:
+
+- ``corruption_mask``      the corruptions, by name: ``full``, ``beams:K``, ``random_beams:P``, ``random_points:P``.
+- ``completion_errors``    per sample the four counts and six error sums of ``r2dm_completion_error`` and the values derived from them.
+- ``confusion_matrix`` / ``iou_from_confusion``   label agreement.
+- ``fill_beams``           the interpolation baselines.
+- ``evaluate_completion``  corrupt, complete (RePaint or a baseline), score; ``completion_eval.py`` is its command line.
+
+A pixel is a *return* when its metric depth lies strictly inside ``(lo, hi)``; any other depth, NaN included, is "no return".  The errors
+are taken over E: the unknown pixels (mask 0) where the real scan has a return.  A prediction without a return there counts with depth 0
+(what ``LiDARUtility.postprocess`` stores for a dropped ray) in ``mae_depth`` / ``rmse_depth`` and is left out of ``*_depth_both``, which
+are taken where both have a return; ``return_recall`` is the fraction of E with a predicted return and ``false_return_rate`` the fraction
+of the unknown pixels without a real return where one is predicted.  Everything runs on the GPU; there is no CPU fallback."""
+from __future__ import annotations
+
+import math
+from typing import Dict, Optional, Sequence
+
+import torch
+
+from . import _lib
+
+RAW_NAMES = ("unknown", "evaluated", "both", "false_returns", "abs_depth", "sq_depth", "abs_depth_both", "sq_depth_both",
+             "abs_reflectance", "sq_reflectance")
+DERIVED_NAMES = ("mae_depth", "rmse_depth", "mae_depth_both", "rmse_depth_both", "mae_reflectance", "rmse_reflectance", "return_recall",
+                 "false_return_rate")
+FILL_MODES = {"nearest": 0, "linear": 1}
+ROW_KINDS = ("full", "beams", "random_beams")  # corruptions whose mask is whole rows: what the interpolation baselines are defined for
+METHODS = ("repaint", "nearest", "linear", "target")
+
+
+# ---- corruptions -------------------------------------------------------------------------------------------------------------------------
+def parse_kind(kind: str):
+    """``"full"`` -> ("full", None); ``"beams:4"`` -> ("beams", 4); ``"random_beams:0.5"`` / ``"random_points:0.1"`` -> (name, 0.5 / 0.1)."""
+    name, sep, arg = str(kind).partition(":")
+    try:
+        if name == "full" and not sep:
+            return name, None
+        if name == "beams" and sep:
+            k = int(arg)
+            if k >= 1:
+                return name, k
+        if name in ("random_beams", "random_points") and sep:
+            p = float(arg)
+            if 0.0 <= p <= 1.0:
+                return name, p
+    except ValueError:
+        pass
+    raise ValueError(f"malformed corruption {kind!r}: expected full, beams:K (K >= 1), random_beams:P or random_points:P (0 <= P <= 1)")
+
+
+def corruption_mask(kind: str, H: int, W: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """The (1,H,W) float32 mask of a corruption on the CPU, 1 = known.  ``beams:K`` keeps rows 0, K, 2K, ... (``beams:4`` is
+    completion_demo.py's ``[::4]``); the random kinds are Bernoulli draws from ``generator`` (a CPU generator; None: the global one) in the
+    demo's shapes, (H,1) for beams and (H,W) for points."""
+    name, arg = parse_kind(kind)
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f"mask of {H}x{W}: sizes must be >= 1")
+    mask = torch.zeros(1, H, W)
+    if name == "full":
+        mask[:] = 1
+    elif name == "beams":
+        mask[:, ::arg] = 1
+    elif name == "random_beams":
+        mask[0] = torch.empty(H, 1).bernoulli_(arg, generator=generator)
+    else:
+        mask[0] = torch.empty(H, W).bernoulli_(arg, generator=generator)
+    return mask
+
+
+def scan_seed(seed: int, index: int) -> int:
+    """The seed of everything drawn for scan ``index`` under ``seed``: its corruption masks (a CPU generator, a fresh one per kind) and its
+    RePaint noise (a device generator, ``setup_rng``).  ``seed * 2**32 + index``."""
+    seed, index = int(seed), int(index)
+    if not (0 <= seed < 2 ** 31 and 0 <= index < 2 ** 32):
+        raise ValueError(f"seed must be in [0, 2^31) and the scan index in [0, 2^32), got {seed}, {index}")
+    return seed * 2 ** 32 + index
+
+
+# ---- errors ------------------------------------------------------------------------------------------------------------------------------
+def _ratio(num: torch.Tensor, den: torch.Tensor) -> torch.Tensor:
+    nan = torch.full_like(num, math.nan)
+    return torch.where(den > 0, num / torch.where(den > 0, den, torch.ones_like(den)), nan)
+
+
+def derived_errors(raw: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """(...,10) float64 raw values (``RAW_NAMES``) -> the derived values (``DERIVED_NAMES``), NaN where the denominator is 0."""
+    raw = raw.double()
+    U, E, Bo, fr = raw[..., 0], raw[..., 1], raw[..., 2], raw[..., 3]
+    return {"mae_depth": _ratio(raw[..., 4], E), "rmse_depth": _ratio(raw[..., 5], E).sqrt(),
+            "mae_depth_both": _ratio(raw[..., 6], Bo), "rmse_depth_both": _ratio(raw[..., 7], Bo).sqrt(),
+            "mae_reflectance": _ratio(raw[..., 8], E), "rmse_reflectance": _ratio(raw[..., 9], E).sqrt(),
+            "return_recall": _ratio(Bo, E), "false_return_rate": _ratio(fr, U - E)}
+
+
+def completion_error_sums(pred: torch.Tensor, target: torch.Tensor, known: torch.Tensor, lo: float, hi: float) -> torch.Tensor:
+    """(B,10) float64 on the device: ``r2dm_completion_error`` (``RAW_NAMES``)."""
+    _lib.require_gpu(pred, "pred")
+    if pred.dim() != 4 or pred.shape[1] != 5 or target.shape != pred.shape:
+        raise ValueError(f"pred {tuple(pred.shape)} and target {tuple(target.shape)} must be one (B,5,H,W) shape [depth, x, y, z, reflectance]")
+    B, _, H, W = pred.shape
+    if tuple(known.shape) != (B, 1, H, W):
+        raise ValueError(f"known {tuple(known.shape)} must be (B,1,H,W) = {(B, 1, H, W)}")
+    dev = pred.device
+    pred, target, known = _lib.f32c(pred), _lib.f32c(target.to(dev)), _lib.f32c(known.to(dev))
+    out = torch.empty(B, len(RAW_NAMES), dtype=torch.float64, device=dev)
+    if B == 0:
+        return out
+    L = _lib.lib()
+    nbytes = L.r2dm_completion_error_scratch_bytes(B, H * W)
+    if nbytes == 0:
+        raise _lib.R2DMError(f"completion_errors: empty or oversized problem (B={B}, plane={H * W})")
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.r2dm_completion_error(_lib.ptr(pred), _lib.ptr(target), _lib.ptr(known), float(lo), float(hi), B, H * W, _lib.ptr(scratch),
+                                           _lib.ptr(out), _lib.stream_ptr(dev)))
+    return out
+
+
+def completion_errors(pred: torch.Tensor, target: torch.Tensor, known: torch.Tensor, lo: float, hi: float) -> Dict[str, torch.Tensor]:
+    """``pred``, ``target`` (B,5,H,W) in the sample layout (``LiDARUtility.postprocess``, ``project_scans(layout="sample")``), ``known``
+    (B,1,H,W) zeros and ones -> (B,) float64 tensors: the ten raw values under ``RAW_NAMES`` and the derived ``DERIVED_NAMES`` (NaN where
+    the denominator is 0)."""
+    raw = completion_error_sums(pred, target, known, lo, hi)
+    out = {name: raw[:, k] for k, name in enumerate(RAW_NAMES)}
+    out.update(derived_errors(raw))
+    return out
+
+
+# ---- labels ------------------------------------------------------------------------------------------------------------------------------
+def confusion_matrix(pred: torch.Tensor, target: torch.Tensor, num_classes: int, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int64 (B,C,C) counts ``[b][target][pred]`` of two int64 label tensors (B,...) over the pixels whose ``mask`` (same shape, None: all)
+    is not 0.  An unmasked label outside ``[0, num_classes)`` raises ``ValueError`` (one read of a device counter per call)."""
+    _lib.require_gpu(pred, "pred")
+    C = int(num_classes)
+    if not 1 <= C <= 64:
+        raise ValueError(f"num_classes must be in [1, 64], got {num_classes}")
+    if pred.dim() < 1 or target.shape != pred.shape or (mask is not None and mask.shape != pred.shape):
+        raise ValueError(f"pred {tuple(pred.shape)}, target {tuple(target.shape)} and mask {None if mask is None else tuple(mask.shape)} "
+                         "must have one (B,...) shape")
+    if pred.dtype != torch.int64 or target.dtype != torch.int64:
+        raise ValueError(f"labels must be int64, got {pred.dtype} and {target.dtype}")
+    dev, B = pred.device, pred.shape[0]
+    counts = torch.zeros(B, C, C, dtype=torch.int64, device=dev)
+    n = pred.numel() // max(B, 1)
+    if B == 0 or n == 0:
+        return counts
+    pred, target = pred.reshape(B, n).contiguous(), target.to(dev).reshape(B, n).contiguous()
+    mask = None if mask is None else _lib.f32c(mask.to(dev).reshape(B, n))
+    bad = torch.zeros(1, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().r2dm_confusion_matrix(_lib.ptr(pred), _lib.ptr(target), _lib.ptr(mask), B, n, C, _lib.ptr(counts), _lib.ptr(bad),
+                                                    _lib.stream_ptr(dev)))
+        nbad = int(bad.item())
+    if nbad:
+        raise ValueError(f"confusion_matrix: {nbad} unmasked pixels carry a label outside [0, {C})")
+    return counts
+
+
+def iou_from_confusion(conf, ignore: Sequence[int] = (0,)):
+    """``conf`` (...,C,C) counts ``[target][pred]`` (leading dimensions are summed) -> ``(iou (C,) float64, mIoU float)`` on the host.  The
+    pixels whose *target* is an ignored class are dropped (SemanticKITTI's class 0 is "unlabeled"); IoU_c = tp / (tp + fp + fn); a class
+    absent from both target and prediction, and an ignored class, is NaN; mIoU is the mean over the other classes (NaN if there is none)."""
+    conf = torch.as_tensor(conf).detach().cpu().double()
+    if conf.dim() < 2 or conf.shape[-1] != conf.shape[-2]:
+        raise ValueError(f"expected (...,C,C) counts, got {tuple(conf.shape)}")
+    C = conf.shape[-1]
+    conf = conf.reshape(-1, C, C).sum(0)
+    ignore = sorted({int(c) for c in ignore})
+    if any(not 0 <= c < C for c in ignore):
+        raise ValueError(f"ignored classes {ignore} outside [0, {C})")
+    conf[ignore, :] = 0
+    tp = conf.diagonal()
+    union = conf.sum(0) + conf.sum(1) - tp  # tp + fp + fn
+    iou = _ratio(tp, union)
+    iou[ignore] = math.nan
+    valid = ~iou.isnan()
+    return iou, (iou[valid].mean().item() if valid.any() else math.nan)
+
+
+# ---- baselines ---------------------------------------------------------------------------------------------------------------------------
+def fill_beams(x: torch.Tensor, rows: torch.Tensor, mode: str, nodata: float = -1.0) -> torch.Tensor:
+    """``x`` (B,C,H,W), ``rows`` (B,H) (non-zero / True = this beam is known) -> (B,C,H,W): known rows copied, every other row from the
+    nearest known row above and below (``mode`` "nearest", the upper one on a tie, or "linear" in fp32), per column and only from endpoints
+    whose channel 0 is not ``nodata``; ``nodata`` in every channel where there is none.  Rows do not wrap."""
+    if mode not in FILL_MODES:
+        raise ValueError(f"mode must be one of {sorted(FILL_MODES)}, got {mode!r}")
+    _lib.require_gpu(x, "x")
+    if x.dim() != 4:
+        raise ValueError(f"expected x (B,C,H,W), got {tuple(x.shape)}")
+    B, C, H, W = x.shape
+    if tuple(rows.shape) != (B, H):
+        raise ValueError(f"rows {tuple(rows.shape)} must be (B,H) = {(B, H)}")
+    if math.isnan(float(nodata)):
+        raise ValueError("nodata must be a number: NaN compares unequal to itself")
+    x = _lib.f32c(x)
+    rows = (rows.to(x.device) != 0).to(torch.uint8).contiguous()
+    out = torch.empty_like(x)
+    if x.numel() == 0:
+        return out
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().r2dm_fill_beams(_lib.ptr(x), _lib.ptr(rows), _lib.ptr(out), B, C, H, W, float(nodata), FILL_MODES[mode],
+                                              _lib.stream_ptr(x.device)))
+    return out
+
+
+# ---- aggregation (host, float64) ---------------------------------------------------------------------------------------------------------
+def aggregate_errors(raw: torch.Tensor) -> dict:
+    """(N,10) per-scan raw values -> ``{"counts", "sums", "micro", "macro"}``: micro = the derived values of the sums over all scans
+    (summed errors over summed counts), macro = the mean of the per-scan derived values, ignoring the NaN ones.  NaN where undefined."""
+    raw = torch.as_tensor(raw).detach().cpu().double().reshape(-1, len(RAW_NAMES))
+    total = raw.sum(0)
+    out = {"counts": {"scans": int(raw.shape[0]), **{name: int(total[k].item()) for k, name in enumerate(RAW_NAMES[:4])}},
+           "sums": {name: total[k].item() for k, name in enumerate(RAW_NAMES) if k >= 4},
+           "micro": {name: v.item() for name, v in derived_errors(total).items()}, "macro": {}}
+    out["counts"]["unknown_without_return"] = out["counts"]["unknown"] - out["counts"]["evaluated"]
+    for name, v in derived_errors(raw).items():
+        ok = ~v.isnan()
+        out["macro"][name] = v[ok].mean().item() if ok.any() else math.nan
+    return out
+
+
+def jsonable(obj):
+    """The same structure with every non-finite float as None (JSON ``null``) and tensors as lists."""
+    if isinstance(obj, dict):
+        return {str(k): jsonable(v) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return [jsonable(v) for v in obj]
+    if isinstance(obj, torch.Tensor):
+        return jsonable(obj.tolist())
+    if isinstance(obj, float):
+        return obj if math.isfinite(obj) else None
+    return obj
+
+
+# ---- the evaluation ----------------------------------------------------------------------------------------------------------------------
+def rows_of_mask(mask: torch.Tensor) -> torch.Tensor:
+    """(B,1,H,W) mask of whole rows -> (B,H) uint8, 1 = the row is known"""
+    return (mask[:, 0] != 0).all(dim=-1).to(torch.uint8)
+
+
+def target_of_planes(planes: torch.Tensor) -> torch.Tensor:
+    """(N,6,H,W) [x, y, z, reflectance, depth, mask] -> the sample layout (N,5,H,W) [depth, x, y, z, reflectance]"""
+    return planes[:, [4, 0, 1, 2, 3]].float().contiguous()
+
+
+@torch.no_grad()
+def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence[str], methods: Sequence[str] = ("repaint",), num_steps: int = 32,
+                        num_resample_steps: int = 10, jump_length: int = 1, seed: int = 0, batch_size: int = 8, semseg=None,
+                        semseg_postprocess=None, lo: Optional[float] = None, hi: Optional[float] = None, keep: bool = False):
+    """Corrupt, complete and score ``planes`` (N,6,H,W), the masked planes of ``project_scans(layout="xyzrdm", apply_mask=True)`` at the
+    model's resolution, on the GPU.
+
+    For every kind of ``kinds`` (``corruption_mask``) and every scan i: the mask is drawn from a CPU generator seeded ``scan_seed(seed, i)``
+    and RePaint draws from ``setup_rng([scan_seed(seed, i)])``, so a scan's inputs depend neither on ``batch_size`` nor on the scans after
+    it.  ``x_in = mask * known + (1 - mask) * -1`` with ``known = known_from_scan(planes)``; a method's prediction is
+    ``lidar_utils.postprocess(x_out.clamp(-1, 1))``; the target is the scan's own measured planes, not a decode of ``known``.
+    ``methods``: "repaint"; "nearest" / "linear" (``fill_beams`` on ``x_in``; defined for the kinds whose mask is whole rows, reported as
+    skipped for the others); "target" (the target's own planes as the prediction: errors 0, mIoU 1).  ``lo``, ``hi``: the depth window of
+    a return (default: the model's ``min_depth``, ``max_depth``).  ``semseg``: a ``RangeNetExtractor``; the labels of prediction and target
+    come from the same net and ``semseg_postprocess`` (what ``segment`` accepts), the confusion matrix is taken over the target's measured
+    pixels of the whole image.
+
+    -> ``results[kind][method]`` = ``aggregate_errors`` of the scans (counts, sums, micro and macro averages) plus, with ``semseg``,
+    ``"iou": {"per_class", "miou", "pixels"}``, or ``{"skipped": why}``.  ``keep=True``: ``(results, kept)`` with ``kept[kind]`` =
+    ``{"mask", "x_in", "target", "x_out": {method}, "pred": {method}, "raw": {method}}`` and, with ``semseg``, ``"target_labels"``,
+    ``"labels": {method}`` and ``"confusion": {method}``, all on the CPU."""
+    from .inference import setup_rng
+    from .projection import known_from_scan
+
+    if planes.dim() != 4 or planes.shape[1] != 6:
+        raise ValueError(f"expected planes (N,6,H,W) [x, y, z, reflectance, depth, mask], got {tuple(planes.shape)}")
+    _lib.require_gpu(planes, "planes")
+    for m in methods:
+        if m not in METHODS:
+            raise ValueError(f"unknown method {m!r}: expected one of {METHODS}")
+    parsed = {kind: parse_kind(kind) for kind in kinds}
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+    N, _, H, W = planes.shape
+    if "repaint" in methods and tuple(ddpm.sampling_shape) != (2, H, W):
+        raise ValueError(f"planes of {H}x{W} for a model that samples {tuple(ddpm.sampling_shape)}: RePaint needs a depth + reflectance model "
+                         "at the planes' resolution")
+    dev = planes.device
+    lo = float(lidar_utils.min_depth if lo is None else lo)
+    hi = float(lidar_utils.max_depth if hi is None else hi)
+    known = known_from_scan(planes, lidar_utils, (H, W))
+    target = target_of_planes(planes)
+    measured = torch.logical_and(target[:, [0]] > lo, target[:, [0]] < hi).float()
+
+    def labels_of(img):
+        m = torch.logical_and(img[:, [0]] > lo, img[:, [0]] < hi).float()
+        return torch.cat([semseg.segment(img[k:k + batch_size], m[k:k + batch_size], postprocess=semseg_postprocess)
+                          for k in range(0, N, batch_size)]) if N else torch.empty(0, 1, H, W, dtype=torch.int64, device=dev)
+
+    target_labels = labels_of(target) if semseg is not None else None
+    results, kept = {}, {}
+    for kind, (name, _) in parsed.items():
+        mask = torch.stack([corruption_mask(kind, H, W, torch.Generator().manual_seed(scan_seed(seed, i))) for i in range(N)]).to(dev) \
+            if N else torch.empty(0, 1, H, W, device=dev)
+        x_in = mask * known + (1 - mask) * -1
+        results[kind] = {}
+        if keep:
+            kept[kind] = {"mask": mask.cpu(), "x_in": x_in.cpu(), "target": target.cpu(), "x_out": {}, "pred": {}, "raw": {}}
+            if semseg is not None:
+                kept[kind].update(target_labels=target_labels.cpu(), labels={}, confusion={})
+        for method in methods:
+            if method in FILL_MODES and name not in ROW_KINDS:
+                results[kind][method] = {"skipped": f"{method} interpolation is defined for masks of whole rows ({', '.join(ROW_KINDS)})"}
+                continue
+            if method == "repaint":
+                parts = []
+                for k in range(0, N, batch_size):
+                    rng = setup_rng([scan_seed(seed, i) for i in range(k, min(k + batch_size, N))], dev)
+                    parts.append(ddpm.repaint(known=x_in[k:k + batch_size], mask=mask[k:k + batch_size], num_steps=num_steps,
+                                              num_resample_steps=num_resample_steps, jump_length=jump_length, progress=False, rng=rng))
+                x_out = torch.cat(parts) if parts else x_in
+            elif method in FILL_MODES:
+                x_out = fill_beams(x_in, rows_of_mask(mask), method, nodata=-1.0) if N else x_in
+            else:
+                x_out = None
+            pred = target if x_out is None else lidar_utils.postprocess(x_out.clamp(-1, 1))
+            raw = completion_error_sums(pred, target, mask, lo, hi).cpu()
+            entry = aggregate_errors(raw)
+            if semseg is not None:
+                labels = target_labels if x_out is None else labels_of(pred)
+                conf = confusion_matrix(labels, target_labels, semseg.num_classes, measured).cpu()
+                iou, miou = iou_from_confusion(conf)
+                entry["iou"] = {"per_class": iou.tolist(), "miou": miou, "pixels": int(conf.sum().item())}
+            results[kind][method] = entry
+            if keep:
+                kept[kind]["x_out"][method] = None if x_out is None else x_out.cpu()
+                kept[kind]["pred"][method] = pred.cpu()
+                kept[kind]["raw"][method] = raw
+                if semseg is not None:
+                    kept[kind]["labels"][method] = labels.cpu()
+                    kept[kind]["confusion"][method] = conf
+    return (results, kept) if keep else results

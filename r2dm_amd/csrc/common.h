@@ -328,6 +328,15 @@ hipError_t launch_knn_vote(const float* depth, const long long* label, const flo
 hipError_t launch_crf_iter(const float* q_in, const float* unary, const float* xyz, const float* mask, const float* params, float* q_out, int B, int N,
                            int H, int W, int kh, int kw, int uniform_beta, hipStream_t s);
 
+// completion metrics (completion.hip): per-sample error sums over the inpainted pixels, the confusion matrix of two label images (counts and *bad are
+// zeroed by the call), the nearest / linear beam interpolation baselines (mode 0 / 1)
+size_t completion_error_scratch_bytes(int B, long plane);
+hipError_t launch_completion_error(const float* pred, const float* target, const float* known, float lo, float hi, int B, long plane, void* scratch,
+                                   double* out, hipStream_t s);
+hipError_t launch_confusion_matrix(const long long* pred, const long long* target, const float* mask, int B, long n, int classes, long long* counts,
+                                   long long* bad, hipStream_t s);
+hipError_t launch_fill_beams(const float* x, const unsigned char* rows, float* out, int B, int C, int H, int W, float nodata, int mode, hipStream_t s);
+
 // rendering of generate.py (render.hip): colour maps, the bilinear splat with 64-bit fixed-point accumulators, the fused frame renderer
 hipError_t launch_colorize(const float* x, const float* lut, uint8_t* out, long B, long hw, hipStream_t s);
 size_t rasterize_scratch_bytes(int B, int C, int H, int W);

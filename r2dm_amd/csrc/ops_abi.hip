@@ -354,4 +354,47 @@ int r2dm_crf_iter(const float* q_in, const float* unary, const float* xyz, const
     return 0;
 }
 
+static bool error_geometry_ok(int32_t B, int64_t plane) { return B >= 1 && B <= 65535 && plane >= 1 && plane <= (1LL << 40) / 5 / B; }
+
+size_t r2dm_completion_error_scratch_bytes(int32_t B, int64_t plane) {
+    return error_geometry_ok(B, plane) ? completion_error_scratch_bytes(B, plane) : 0;
+}
+
+int r2dm_completion_error(const float* pred, const float* target, const float* known, float lo, float hi, int32_t B, int64_t plane, void* scratch,
+                          double* out, void* stream) {
+    if (!pred || !target || !known || !scratch || !out) return fail(1, "null argument");
+    if (!error_geometry_ok(B, plane)) return fail(1, "completion_error: batch must be in [1, 65535], the tensors 1 to 2^40 elements");
+    const uintptr_t a = plane % 4 == 0 ? 15 : 3;  // a plane that is a multiple of 4 is read as quads
+    if (((uintptr_t)pred | (uintptr_t)target | (uintptr_t)known) & a)
+        return fail(1, "completion_error: pred, target and known must be %d-byte aligned for a plane of %lld elements", (int)a + 1, (long long)plane);
+    if (((uintptr_t)scratch | (uintptr_t)out) & 7) return fail(1, "completion_error: scratch and out must be 8-byte aligned");
+    HIP_TRY(launch_completion_error(pred, target, known, lo, hi, B, plane, scratch, out, (hipStream_t)stream));
+    return 0;
+}
+
+int r2dm_confusion_matrix(const int64_t* pred, const int64_t* target, const float* mask, int32_t B, int64_t pixels, int32_t classes, int64_t* counts,
+                          int64_t* bad, void* stream) {
+    if (!pred || !target || !counts || !bad) return fail(1, "null argument");
+    if (classes < 1 || classes > 64) return fail(1, "confusion_matrix: classes must be in [1, 64] (one table per block in LDS), got %d", classes);
+    if (B < 1 || B > 65535 || pixels < 1 || pixels > (1LL << 40) / B)
+        return fail(1, "confusion_matrix: batch must be in [1, 65535], the label images 1 to 2^40 elements");
+    if ((((uintptr_t)pred | (uintptr_t)target | (uintptr_t)counts | (uintptr_t)bad) & 7) || ((uintptr_t)mask & 3))
+        return fail(1, "confusion_matrix: pred, target, counts and bad must be 8-byte aligned, mask 4-byte aligned");
+    HIP_TRY(launch_confusion_matrix(reinterpret_cast<const long long*>(pred), reinterpret_cast<const long long*>(target), mask, B, pixels, classes,
+                                    reinterpret_cast<long long*>(counts), reinterpret_cast<long long*>(bad), (hipStream_t)stream));
+    return 0;
+}
+
+int r2dm_fill_beams(const float* x, const uint8_t* rows, float* out, int32_t B, int32_t C, int32_t H, int32_t W, float nodata, int32_t mode,
+                    void* stream) {
+    if (!x || !rows || !out) return fail(1, "null argument");
+    if (mode != 0 && mode != 1) return fail(1, "fill_beams: mode must be 0 (nearest) or 1 (linear), got %d", mode);
+    if (B < 1 || B > 65535 || H < 1 || H > 65535 || C < 1 || W < 1 || (int64_t)C * H > (1LL << 40) / W / B)
+        return fail(1, "fill_beams: batch and height must be in [1, 65535], channels and width positive, the tensor at most 2^40 elements");
+    if (((uintptr_t)x | (uintptr_t)out) & 3) return fail(1, "fill_beams: x and out must be 4-byte aligned");
+    if (x == out) return fail(1, "fill_beams: out must not alias x");
+    HIP_TRY(launch_fill_beams(x, rows, out, B, C, H, W, nodata, mode, (hipStream_t)stream));
+    return 0;
+}
+
 }  // extern "C"
