@@ -4,7 +4,9 @@
 (``--methods``), and compared with the scan itself -- mean absolute and root-mean-square error of range and reflectance over the pixels
 that had to be filled in, the recall of returns, the rate of false returns and, with ``--rangenet_weights``, the IoU of the RangeNet-53
 labels of the completed image against the labels of the real scan (r2dm_amd.completion.evaluate_completion; DESIGN.md section 4,
-"Completion metrics").
+"Completion metrics").  ``--chamfer`` also scores the completion in 3-D: Chamfer distance and the F-score at ``--fscore_threshold`` metres
+of the prediction's returns against the scan's, over the whole image and over the inpainted pixels (``results[kind][method]["geometry"]``;
+DESIGN.md section 4, "Geometry metrics").
 
 The scans come from either
   - ``--real_scans DIR``: a directory tree of raw Velodyne ``*.bin`` scans, projected here with the checkpoint's ``cfg.data.projection``
@@ -86,13 +88,16 @@ def main(argv=None):
         post = semseg_postprocess(args.semseg_postprocess, semseg.num_classes)
     out = completion.evaluate_completion(ddpm, lidar_utils, planes, kinds, methods=tuple(args.methods), num_steps=args.num_steps,
                                          num_resample_steps=args.num_resample_steps, jump_length=args.jump_length, seed=args.seed,
-                                         batch_size=args.batch_size, semseg=semseg, semseg_postprocess=post, keep=args.save_dir is not None)
+                                         batch_size=args.batch_size, semseg=semseg, semseg_postprocess=post, keep=args.save_dir is not None,
+                                         chamfer=args.chamfer, fscore_threshold=args.fscore_threshold)
     results, kept = out if args.save_dir is not None else (out, None)
     info = {"ckpt": str(args.ckpt), "source": str(args.real_scans if args.real_scans is not None else args.real_dir), "num_scans": len(files),
             "resolution": list(cfg.data.resolution), "corruptions": kinds, "methods": list(args.methods), "num_steps": args.num_steps,
             "num_resample_steps": args.num_resample_steps, "jump_length": args.jump_length, "batch_size": args.batch_size, "seed": args.seed,
             "lo": float(lidar_utils.min_depth), "hi": float(lidar_utils.max_depth), "rangenet_weights": args.rangenet_weights,
             "semseg_postprocess": args.semseg_postprocess if semseg is not None else None}
+    if args.chamfer:
+        info["fscore_threshold"] = args.fscore_threshold
     doc = completion.jsonable({"info": info, "results": results})
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     with open(args.out, "w") as f:
@@ -108,7 +113,9 @@ def main(argv=None):
                 continue
             m, iou = entry["micro"], entry.get("iou", {}).get("miou")
             print(f"{kind:>20} {method:>8}: MAE depth {m['mae_depth']:.4f} m, reflectance {m['mae_reflectance']:.4f}, recall {m['return_recall']:.4f}"
-                  + ("" if iou is None else f", mIoU {iou:.4f}"))
+                  + ("" if iou is None else f", mIoU {iou:.4f}")
+                  + (f", inpainted CD {entry['geometry']['inpainted']['micro']['cd']:.4f} m, F-score {entry['geometry']['inpainted']['micro']['fscore']:.4f}"
+                     if "geometry" in entry else ""))
     print(f"{len(files)} scans -> {args.out}")
     return doc
 
@@ -131,6 +138,9 @@ def build_parser():
                         help="the official darknet53-1024.tar.gz archive or a .pth state dict (a local file): adds per-class IoU and mIoU")
     parser.add_argument("--semseg_postprocess", choices=("none", "knn", "crf", "crf_knn"), default="none",
                         help="refine the labels of both images: the kNN vote of RangeNet++, the CRF-RNN of SqueezeSeg, or the CRF-RNN and then the vote")
+    parser.add_argument("--chamfer", action="store_true",
+                        help="also Chamfer distance and F-score of the completed scan's points against the real scan's, whole image and inpainted pixels")
+    parser.add_argument("--fscore_threshold", type=float, default=0.2, help="the F-score's distance threshold in metres (with --chamfer)")
     parser.add_argument("--save_dir", type=Path, default=None, help="also write the tensors behind the numbers, one .pt file per corruption")
     parser.add_argument("--out", type=str, default="completion.json")
     return parser

@@ -421,6 +421,31 @@ int r2dm_confusion_matrix(const int64_t* pred, const int64_t* target, const floa
 int r2dm_fill_beams(const float* x, const uint8_t* rows, float* out, int32_t batch, int32_t channels, int32_t height, int32_t width,
                     float nodata, int32_t mode, void* stream);
 
+/* -- geometry metrics: nearest neighbours between point clouds, the search behind Chamfer distance, F-score and COV / MMD / 1-NNA (the
+ *    reference has no code for them) ------------------------------------------------------------------------------------------------------
+ * r2dm_nn_pairs: a (a_total,4), b (b_total,4) fp32 rows [x, y, z, .] (16-byte aligned; the fourth value is not read) hold a_clouds /
+ *    b_clouds clouds, cloud k = rows [offsets[k], offsets[k+1]) (int64, clouds + 1 values, in device memory like everything here).
+ *    pairs (num_pairs,2) int64 [ia, ib].  For every pair and both directions (a -> b: every point of cloud ia against cloud ib; b -> a
+ *    the reverse) the squared distance to the nearest neighbour, d^2 = (ax-bx)^2 + (ay-by)^2 + (az-bz)^2 evaluated in fp32 in this
+ *    difference form (dx*dx, then two FMAs; never |a|^2 + |b|^2 - 2ab), and the neighbour's index inside its cloud, the lowest one on an
+ *    exact fp32 tie; against an empty cloud +inf and -1.
+ *    d2_ab / d2_ba: NULL or one fp32 per point of the pair's query cloud, pair p's values starting at out_ab[p] / out_ba[p] (int64,
+ *    num_pairs values; the caller sizes the buffers as the sum of the query counts); idx_ab / idx_ba: NULL or int32 alike (only with d2).
+ *    sums (num_pairs,8) fp64 = [sum d^2, sum d, #{d <= tau}] of a -> b, the same of b -> a, |cloud ia|, |cloud ib|; d = sqrt(d^2) in
+ *    fp64, d <= tau tested as d^2 <= tau^2 in fp64.  Sums are fp64 in a fixed order (per-block partials added in order by a second
+ *    kernel, no floating-point atomics): bit-reproducible, and a pair's numbers do not depend on the other pairs of the call.
+ *    status (2) int64, zeroed by the call: [0] points with a non-finite coordinate met as a query (their results are not valid),
+ *    [1] pairs whose index is outside [0, clouds) or whose offsets are not 0 <= begin <= end <= total with end - begin <= max_points
+ *    (nothing is read through them; their eight sums are NaN).
+ *    max_points: an upper bound of the points of any cloud of a pair, 1 to 2^21; it sizes the grid (2 num_pairs x ceil(max_points / 1024)
+ *    blocks, at most 2^31 - 1) and the scratch (the bytes the _scratch_bytes function returns; 0 for an empty or oversized problem),
+ *    8-byte aligned like sums and status. */
+size_t r2dm_nn_pairs_scratch_bytes(int64_t num_pairs, int64_t max_points);
+int r2dm_nn_pairs(const float* a, const int64_t* a_offsets, int64_t a_clouds, int64_t a_total, const float* b, const int64_t* b_offsets,
+                  int64_t b_clouds, int64_t b_total, const int64_t* pairs, int64_t num_pairs, int64_t max_points, double tau, float* d2_ab,
+                  int32_t* idx_ab, const int64_t* out_ab, float* d2_ba, int32_t* idx_ba, const int64_t* out_ba, void* scratch, double* sums,
+                  int64_t* status, void* stream);
+
 /* -- single kernels, exported for per-op parity tests against the oracle -------------------- */
 /* ops.Conv2d(ring) 3x3 / 1x1 (models/ops.py:149-173) with optional fused GroupNorm-affine(+SiLU)
  * prologue (aff: (B,Cin,2) or NULL; prologue 0 none, 1 affine, 2 affine+SiLU) and optional

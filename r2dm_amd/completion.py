@@ -253,7 +253,8 @@ def target_of_planes(planes: torch.Tensor) -> torch.Tensor:
 @torch.no_grad()
 def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence[str], methods: Sequence[str] = ("repaint",), num_steps: int = 32,
                         num_resample_steps: int = 10, jump_length: int = 1, seed: int = 0, batch_size: int = 8, semseg=None,
-                        semseg_postprocess=None, lo: Optional[float] = None, hi: Optional[float] = None, keep: bool = False):
+                        semseg_postprocess=None, lo: Optional[float] = None, hi: Optional[float] = None, keep: bool = False,
+                        chamfer: bool = False, fscore_threshold: float = 0.2):
     """Corrupt, complete and score ``planes`` (N,6,H,W), the masked planes of ``project_scans(layout="xyzrdm", apply_mask=True)`` at the
     model's resolution, on the GPU.
 
@@ -265,12 +266,18 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
     skipped for the others); "target" (the target's own planes as the prediction: errors 0, mIoU 1).  ``lo``, ``hi``: the depth window of
     a return (default: the model's ``min_depth``, ``max_depth``).  ``semseg``: a ``RangeNetExtractor``; the labels of prediction and target
     come from the same net and ``semseg_postprocess`` (what ``segment`` accepts), the confusion matrix is taken over the target's measured
-    pixels of the whole image.
+    pixels of the whole image.  ``chamfer``: also score the completion in 3-D (``r2dm_amd.geometry``): the prediction's returns as a point
+    cloud against the target's, over the whole image (``"all"``) and over the unknown pixels only (``"inpainted"``), with the F-score at
+    ``fscore_threshold`` metres.
 
     -> ``results[kind][method]`` = ``aggregate_errors`` of the scans (counts, sums, micro and macro averages) plus, with ``semseg``,
-    ``"iou": {"per_class", "miou", "pixels"}``, or ``{"skipped": why}``.  ``keep=True``: ``(results, kept)`` with ``kept[kind]`` =
+    ``"iou": {"per_class", "miou", "pixels"}`` and, with ``chamfer``, ``"geometry": {"all", "inpainted"}``, each the
+    ``geometry.aggregate_chamfer`` of the scans (micro and macro ``cd_sq``, ``cd``, ``precision``, ``recall``, ``fscore``, the number of
+    scans with an empty cloud); or ``{"skipped": why}``.  ``keep=True``: ``(results, kept)`` with ``kept[kind]`` =
     ``{"mask", "x_in", "target", "x_out": {method}, "pred": {method}, "raw": {method}}`` and, with ``semseg``, ``"target_labels"``,
-    ``"labels": {method}`` and ``"confusion": {method}``, all on the CPU."""
+    ``"labels": {method}`` and ``"confusion": {method}``, with ``chamfer`` ``"geometry_raw": {method: {"all", "inpainted"}}`` ((N,8) sums,
+    ``geometry.RAW_NAMES``), all on the CPU."""
+    from . import geometry
     from .inference import setup_rng
     from .projection import known_from_scan
 
@@ -283,6 +290,8 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
     parsed = {kind: parse_kind(kind) for kind in kinds}
     if batch_size < 1:
         raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+    if chamfer:
+        fscore_threshold = geometry._check_tau(fscore_threshold)
     N, _, H, W = planes.shape
     if "repaint" in methods and tuple(ddpm.sampling_shape) != (2, H, W):
         raise ValueError(f"planes of {H}x{W} for a model that samples {tuple(ddpm.sampling_shape)}: RePaint needs a depth + reflectance model "
@@ -299,6 +308,14 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
         return torch.cat([semseg.segment(img[k:k + batch_size], m[k:k + batch_size], postprocess=semseg_postprocess)
                           for k in range(0, N, batch_size)]) if N else torch.empty(0, 1, H, W, dtype=torch.int64, device=dev)
 
+    def geometry_of(pred, region):
+        raws = []
+        for k in range(0, N, batch_size):
+            reg = None if region is None else region[k:k + batch_size]
+            raws.append(geometry.chamfer_sums(*geometry.clouds_of_samples(pred[k:k + batch_size], lo, hi, reg),
+                                              *geometry.clouds_of_samples(target[k:k + batch_size], lo, hi, reg), tau=fscore_threshold).cpu())
+        return torch.cat(raws) if raws else torch.empty(0, len(geometry.RAW_NAMES), dtype=torch.float64)
+
     target_labels = labels_of(target) if semseg is not None else None
     results, kept = {}, {}
     for kind, (name, _) in parsed.items():
@@ -310,6 +327,8 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
             kept[kind] = {"mask": mask.cpu(), "x_in": x_in.cpu(), "target": target.cpu(), "x_out": {}, "pred": {}, "raw": {}}
             if semseg is not None:
                 kept[kind].update(target_labels=target_labels.cpu(), labels={}, confusion={})
+            if chamfer:
+                kept[kind]["geometry_raw"] = {}
         for method in methods:
             if method in FILL_MODES and name not in ROW_KINDS:
                 results[kind][method] = {"skipped": f"{method} interpolation is defined for masks of whole rows ({', '.join(ROW_KINDS)})"}
@@ -333,6 +352,9 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
                 conf = confusion_matrix(labels, target_labels, semseg.num_classes, measured).cpu()
                 iou, miou = iou_from_confusion(conf)
                 entry["iou"] = {"per_class": iou.tolist(), "miou": miou, "pixels": int(conf.sum().item())}
+            if chamfer:
+                graw = {"all": geometry_of(pred, None), "inpainted": geometry_of(pred, mask == 0)}
+                entry["geometry"] = {where: geometry.aggregate_chamfer(r) for where, r in graw.items()}
             results[kind][method] = entry
             if keep:
                 kept[kind]["x_out"][method] = None if x_out is None else x_out.cpu()
@@ -341,4 +363,6 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
                 if semseg is not None:
                     kept[kind]["labels"][method] = labels.cpu()
                     kept[kind]["confusion"][method] = conf
+                if chamfer:
+                    kept[kind]["geometry_raw"][method] = graw
     return (results, kept) if keep else results

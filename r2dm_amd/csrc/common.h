@@ -337,6 +337,15 @@ hipError_t launch_confusion_matrix(const long long* pred, const long long* targe
                                    long long* bad, hipStream_t s);
 hipError_t launch_fill_beams(const float* x, const unsigned char* rows, float* out, int B, int C, int H, int W, float nodata, int mode, hipStream_t s);
 
+// geometry metrics (geometry.hip): nearest neighbours of P pairs of ragged clouds in both directions -- optional per-point d^2 / index, always
+// sums (P,8) = [sum d^2, sum d, #{d <= tau}] a -> b, the same b -> a, |a|, |b|; status[2] = non-finite points met, pairs that do not check out
+size_t nn_pairs_scratch_bytes(long P, long max_points);
+long nn_pairs_chunks(long max_points);
+hipError_t launch_nn_pairs(const float* a, const long long* off_a, long clouds_a, long total_a, const float* b, const long long* off_b, long clouds_b,
+                           long total_b, const long long* pairs, long P, long max_points, double tau, float* d2_ab, int* idx_ab,
+                           const long long* out_ab, float* d2_ba, int* idx_ba, const long long* out_ba, void* scratch, double* sums,
+                           long long* status, hipStream_t s);
+
 // rendering of generate.py (render.hip): colour maps, the bilinear splat with 64-bit fixed-point accumulators, the fused frame renderer
 hipError_t launch_colorize(const float* x, const float* lut, uint8_t* out, long B, long hw, hipStream_t s);
 size_t rasterize_scratch_bytes(int B, int C, int H, int W);

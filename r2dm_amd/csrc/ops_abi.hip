@@ -397,4 +397,36 @@ int r2dm_fill_beams(const float* x, const uint8_t* rows, float* out, int32_t B, 
     return 0;
 }
 
+static bool nn_geometry_ok(int64_t P, int64_t max_points) {
+    return P >= 1 && max_points >= 1 && max_points <= (1LL << 21) && 2 * P <= 0x7fffffffLL / nn_pairs_chunks(max_points);
+}
+
+size_t r2dm_nn_pairs_scratch_bytes(int64_t P, int64_t max_points) { return nn_geometry_ok(P, max_points) ? nn_pairs_scratch_bytes(P, max_points) : 0; }
+
+int r2dm_nn_pairs(const float* a, const int64_t* a_offsets, int64_t a_clouds, int64_t a_total, const float* b, const int64_t* b_offsets,
+                  int64_t b_clouds, int64_t b_total, const int64_t* pairs, int64_t P, int64_t max_points, double tau, float* d2_ab, int32_t* idx_ab,
+                  const int64_t* out_ab, float* d2_ba, int32_t* idx_ba, const int64_t* out_ba, void* scratch, double* sums, int64_t* status,
+                  void* stream) {
+    if (!a_offsets || !b_offsets || !pairs || !scratch || !sums || !status) return fail(1, "null argument");
+    if (a_clouds < 1 || b_clouds < 1 || a_total < 0 || b_total < 0 || (!a && a_total) || (!b && b_total))
+        return fail(1, "nn_pairs: each set needs at least one cloud, and a pointer unless it has no points");
+    if (max_points > (1LL << 21)) return fail(1, "nn_pairs: clouds of up to 2^21 points, got max_points = %lld", (long long)max_points);
+    if (!nn_geometry_ok(P, max_points))
+        return fail(1, "nn_pairs: num_pairs and max_points must be >= 1 and 2 * num_pairs * ceil(max_points / 1024) at most 2^31 - 1 blocks, got %lld, %lld",
+                    (long long)P, (long long)max_points);
+    if (!(tau >= 0.0)) return fail(1, "nn_pairs: tau must be >= 0");
+    if ((idx_ab && !d2_ab) || (idx_ba && !d2_ba) || (d2_ab && !out_ab) || (d2_ba && !out_ba))
+        return fail(1, "nn_pairs: an index output needs its d2 output, a d2 output its start offsets");
+    if (((uintptr_t)a | (uintptr_t)b) & 15) return fail(1, "nn_pairs: a and b must be 16-byte aligned (rows are read as quads)");
+    if (((uintptr_t)a_offsets | (uintptr_t)b_offsets | (uintptr_t)pairs | (uintptr_t)out_ab | (uintptr_t)out_ba | (uintptr_t)scratch | (uintptr_t)sums |
+         (uintptr_t)status) & 7)
+        return fail(1, "nn_pairs: offsets, pairs, scratch, sums and status must be 8-byte aligned");
+    if (((uintptr_t)d2_ab | (uintptr_t)idx_ab | (uintptr_t)d2_ba | (uintptr_t)idx_ba) & 3) return fail(1, "nn_pairs: per-point outputs must be 4-byte aligned");
+    HIP_TRY(launch_nn_pairs(a, reinterpret_cast<const long long*>(a_offsets), a_clouds, a_total, b, reinterpret_cast<const long long*>(b_offsets), b_clouds,
+                            b_total, reinterpret_cast<const long long*>(pairs), P, max_points, tau, d2_ab, idx_ab,
+                            reinterpret_cast<const long long*>(out_ab), d2_ba, idx_ba, reinterpret_cast<const long long*>(out_ba), scratch, sums,
+                            reinterpret_cast<long long*>(status), (hipStream_t)stream));
+    return 0;
+}
+
 }  // extern "C"

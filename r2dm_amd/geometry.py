@@ -1,0 +1,327 @@
+"""Geometry metrics: how far two scans are from each other in 3-D.
+
+Clouds are sets of 3-D points in metres; ``d(x, Y) = min_{y in Y} |x - y|``.
+
+- nearest neighbour X -> Y: for every x, ``d^2(x, Y)`` and the index of the minimiser, the lowest one on an exact fp32 tie; against an
+  empty Y ``+inf`` and ``-1``.
+- Chamfer distance of a pair: ``cd_sq = mean_x d^2(x, Y) + mean_y d^2(y, X)`` and ``cd = (mean_x d(x, Y) + mean_y d(y, X)) / 2``.
+- F-score at ``tau``: ``precision = |{x: d(x, Y) <= tau}| / |X|`` with X the prediction, ``recall = |{y: d(y, X) <= tau}| / |Y|``,
+  ``fscore = 2 P R / (P + R)``, 0 if ``P + R = 0``.  All five are NaN if either cloud is empty.
+- set metrics of generated clouds G against real clouds R under ``D = cd_sq`` (the PointFlow / LiDM definitions):
+  ``COV = |{argmin_r D(g, r): g in G}| / |R|``, ``MMD = mean_r min_g D(g, r)``, ``1-NNA`` = over S = G u R the fraction of s whose nearest
+  neighbour in S \\ {s} lies in the same set as s (0.5 is ideal).  Every argmin tie goes to the lowest index, G before R.
+
+The search is one HIP kernel (``r2dm_nn_pairs``, ``r2dm_amd/csrc/geometry.hip``) over a list of cloud pairs; it has no CPU fallback.
+What is derived from its sums and from distance matrices is plain torch and works on CPU tensors too."""
+from __future__ import annotations
+
+import math
+from typing import Dict, Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+
+RAW_NAMES = ("sum_sq_ab", "sum_d_ab", "within_ab", "sum_sq_ba", "sum_d_ba", "within_ba", "count_a", "count_b")
+DERIVED_NAMES = ("cd_sq", "cd", "precision", "recall", "fscore")
+MAX_POINTS = 1 << 21          # per cloud (r2dm_nn_pairs)
+SLAB_BYTES = 64 << 20         # pairwise_chamfer: pair list + sums + scratch of one call stay below this
+
+
+# ---- the search --------------------------------------------------------------------------------------------------------------------------
+def _host_offsets(offsets, total: int, what: str) -> np.ndarray:
+    off = offsets.detach().cpu().numpy() if isinstance(offsets, torch.Tensor) else np.asarray(offsets)
+    if off.ndim != 1 or off.size < 2 or off.dtype.kind not in "iu":
+        raise ValueError(f"{what}: expected (clouds + 1,) integer offsets with at least one cloud, got shape {off.shape} {off.dtype}")
+    off = off.astype(np.int64)
+    if off[0] < 0 or (np.diff(off) < 0).any() or off[-1] > total:
+        raise ValueError(f"{what}: offsets must ascend from >= 0 to at most the {total} rows of the points")
+    if np.diff(off).max() > MAX_POINTS:
+        raise ValueError(f"{what}: a cloud of {int(np.diff(off).max())} points; the search takes clouds of up to 2^21 = {MAX_POINTS}")
+    return off
+
+
+def _points(p: torch.Tensor, what: str) -> torch.Tensor:
+    if p.dim() != 2 or p.shape[1] != 4:
+        raise ValueError(f"{what}: expected (total,4) rows [x, y, z, .], got {tuple(p.shape)}")
+    _lib.require_gpu(p, what)
+    p = _lib.f32c(p)
+    return p.clone() if p.data_ptr() % 16 else p  # rows are read as quads
+
+
+def _pairs(pairs, na: int, nb: int) -> np.ndarray:
+    if pairs is None:
+        if na != nb:
+            raise ValueError(f"pairs=None pairs cloud k with cloud k: {na} clouds against {nb}")
+        k = np.arange(na, dtype=np.int64)
+        return np.stack([k, k], axis=1)
+    pr = pairs.detach().cpu().numpy() if isinstance(pairs, torch.Tensor) else np.asarray(pairs)
+    if pr.ndim != 2 or pr.shape[1] != 2 or pr.dtype.kind not in "iu":
+        raise ValueError(f"pairs: expected (P,2) integers [ia, ib], got shape {pr.shape} {pr.dtype}")
+    pr = pr.astype(np.int64)
+    if pr.size and (pr.min() < 0 or pr[:, 0].max() >= na or pr[:, 1].max() >= nb):
+        raise ValueError(f"pairs: an index outside the {na} clouds of a or the {nb} clouds of b")
+    return pr
+
+
+def _check_tau(tau: float) -> float:
+    tau = float(tau)
+    if not (math.isfinite(tau) and tau >= 0):
+        raise ValueError(f"the F-score threshold must be a finite distance >= 0, got {tau}")
+    return tau
+
+
+def _launch(a, off_a, clouds_a, b, off_b, clouds_b, pairs_dev, max_points, tau, per_point=None):
+    """One ``r2dm_nn_pairs`` call on device tensors -> ``(sums (P,8), status (2,))``, nothing read back.  ``per_point``: None or
+    ``(d2_ab, idx_ab, start_ab, d2_ba, idx_ba, start_ba)``."""
+    dev, P = a.device, pairs_dev.shape[0]
+    L = _lib.lib()
+    nbytes = L.r2dm_nn_pairs_scratch_bytes(P, max_points)
+    if nbytes == 0:
+        raise ValueError(f"{P} pairs of clouds of up to {max_points} points: beyond the limits of r2dm_nn_pairs (clouds of up to 2^21 points, "
+                         "2 * pairs * ceil(points / 1024) at most 2^31 - 1 blocks)")
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    sums = torch.empty(P, len(RAW_NAMES), dtype=torch.float64, device=dev)
+    status = torch.empty(2, dtype=torch.int64, device=dev)
+    pp = [None] * 6 if per_point is None else [_lib.ptr(t) for t in per_point]
+    with torch.cuda.device(dev):
+        _lib.check(L.r2dm_nn_pairs(_lib.ptr(a) or None, _lib.ptr(off_a), clouds_a, a.shape[0], _lib.ptr(b) or None, _lib.ptr(off_b), clouds_b, b.shape[0],
+                                   _lib.ptr(pairs_dev), P, max_points, tau, *pp, _lib.ptr(scratch), _lib.ptr(sums), _lib.ptr(status),
+                                   _lib.stream_ptr(dev)))
+    return sums, status
+
+
+def _raise_on_status(status: torch.Tensor) -> None:
+    nonfinite, bad = (int(v) for v in status.cpu().tolist())
+    if bad:
+        raise _lib.R2DMError(f"r2dm_nn_pairs: {bad} pairs with an index or offsets that do not check out")
+    if nonfinite:
+        raise ValueError(f"nearest neighbours: {nonfinite} points with a non-finite coordinate (counted once per pair they are part of)")
+
+
+def _search(a, a_offsets, b, b_offsets, pairs, tau, per_point: bool, return_index: bool):
+    a, b = _points(a, "a"), _points(b, "b")
+    if b.device != a.device:
+        raise ValueError(f"a is on {a.device}, b on {b.device}")
+    off_a, off_b = _host_offsets(a_offsets, a.shape[0], "a_offsets"), _host_offsets(b_offsets, b.shape[0], "b_offsets")
+    pr = _pairs(pairs, off_a.size - 1, off_b.size - 1)
+    tau = _check_tau(tau)
+    dev, P = a.device, pr.shape[0]
+    out = {"sums": torch.empty(0, len(RAW_NAMES), dtype=torch.float64, device=dev)}
+    na, nb = np.diff(off_a)[pr[:, 0]], np.diff(off_b)[pr[:, 1]]
+    start_ab, start_ba = np.concatenate([[0], np.cumsum(na)]).astype(np.int64), np.concatenate([[0], np.cumsum(nb)]).astype(np.int64)
+    pp = None
+    if per_point:
+        out.update(d2_ab=torch.empty(int(start_ab[-1]), dtype=torch.float32, device=dev), start_ab=start_ab,
+                   d2_ba=torch.empty(int(start_ba[-1]), dtype=torch.float32, device=dev), start_ba=start_ba)
+        if return_index:
+            out.update(idx_ab=torch.empty(int(start_ab[-1]), dtype=torch.int32, device=dev),
+                       idx_ba=torch.empty(int(start_ba[-1]), dtype=torch.int32, device=dev))
+    if P == 0:
+        return out
+    if per_point:
+        s_ab, s_ba = torch.from_numpy(start_ab[:-1].copy()).to(dev), torch.from_numpy(start_ba[:-1].copy()).to(dev)
+        pp = (out["d2_ab"], out.get("idx_ab"), s_ab, out["d2_ba"], out.get("idx_ba"), s_ba)
+    max_points = max(int(max(na.max(), nb.max())), 1)
+    sums, status = _launch(a, torch.from_numpy(off_a).to(dev), off_a.size - 1, b, torch.from_numpy(off_b).to(dev), off_b.size - 1,
+                           torch.from_numpy(pr).to(dev), max_points, tau, pp)
+    _raise_on_status(status)
+    out["sums"] = sums
+    return out
+
+
+def nearest_neighbors(a: torch.Tensor, a_offsets, b: torch.Tensor, b_offsets, pairs=None, return_index: bool = False, tau: float = 0.2):
+    """Nearest neighbours between clouds, both ways, for a list of cloud pairs.
+
+    ``a`` ``(totalA,4)``, ``b`` ``(totalB,4)`` float32 rows ``[x, y, z, .]`` on the GPU; cloud k of a set is the rows
+    ``[offsets[k], offsets[k + 1])`` (what ``images_to_points`` returns).  ``pairs``: ``(P,2)`` integers ``[ia, ib]``; None pairs cloud k
+    with cloud k.  -> a dict: ``d2_ab`` float32, for pair p the squared distance of every point of cloud ia to cloud ib at
+    ``[start_ab[p], start_ab[p + 1])`` (``start_ab`` ``(P+1,)`` numpy int64); ``d2_ba``, ``start_ba`` the reverse; with ``return_index``
+    ``idx_ab``, ``idx_ba`` int32, the neighbour's index inside its cloud (-1 against an empty cloud); ``sums`` as ``chamfer_sums``.
+    A point with a non-finite coordinate raises ``ValueError``."""
+    return _search(a, a_offsets, b, b_offsets, pairs, tau, True, return_index)
+
+
+def chamfer_sums(a: torch.Tensor, a_offsets, b: torch.Tensor, b_offsets, pairs=None, tau: float = 0.2) -> torch.Tensor:
+    """``(P,8)`` float64 on the device (``RAW_NAMES``): per pair the sum of ``d^2``, the sum of ``d`` and the number of points with
+    ``d <= tau`` from a to b, the same from b to a, and the two counts.  Arguments as ``nearest_neighbors``."""
+    return _search(a, a_offsets, b, b_offsets, pairs, tau, False, False)["sums"]
+
+
+def chamfer_from_sums(raw: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """``(...,8)`` raw values (``RAW_NAMES``; a is the prediction) -> ``cd_sq``, ``cd``, ``precision``, ``recall``, ``fscore`` in float64,
+    NaN where either cloud is empty.  Plain torch."""
+    raw = torch.as_tensor(raw).double()
+    if raw.dim() < 1 or raw.shape[-1] != len(RAW_NAMES):
+        raise ValueError(f"expected (...,{len(RAW_NAMES)}) raw values {RAW_NAMES}, got {tuple(raw.shape)}")
+    na, nb = raw[..., 6], raw[..., 7]
+    ok = (na > 0) & (nb > 0)
+    one, nan = torch.ones_like(na), torch.full_like(na, math.nan)
+    da, db = torch.where(ok, na, one), torch.where(ok, nb, one)
+
+    def val(x):
+        return torch.where(ok, x, nan)
+
+    # (against an empty cloud a sum is +inf: kept out of the arithmetic, not multiplied by 0)
+    s = [torch.where(ok, raw[..., k], torch.zeros_like(na)) for k in range(6)]
+    p, r = s[2] / da, s[5] / db
+    pr = p + r
+    f = torch.where(pr > 0, 2 * p * r / torch.where(pr > 0, pr, one), torch.zeros_like(pr))
+    return {"cd_sq": val(s[0] / da + s[3] / db), "cd": val(0.5 * (s[1] / da + s[4] / db)), "precision": val(p), "recall": val(r), "fscore": val(f)}
+
+
+def aggregate_chamfer(raw: torch.Tensor) -> dict:
+    """(N,8) per-scan raw values -> ``{"scans", "empty", "micro", "macro"}`` over the scans whose two clouds both have points (``empty``
+    counts the others): micro = the values of the summed sums and counts, macro = the mean of the per-scan values.  NaN if no scan is left."""
+    raw = torch.as_tensor(raw).detach().cpu().double().reshape(-1, len(RAW_NAMES))
+    ok = (raw[:, 6] > 0) & (raw[:, 7] > 0)
+    used = raw[ok]
+    per_scan = chamfer_from_sums(used)
+    return {"scans": int(raw.shape[0]), "empty": int((~ok).sum().item()),
+            "micro": {k: v.item() for k, v in chamfer_from_sums(used.sum(0)).items()},
+            "macro": {k: (v.mean().item() if v.numel() else math.nan) for k, v in per_scan.items()}}
+
+
+# ---- clouds ------------------------------------------------------------------------------------------------------------------------------
+def clouds_of_samples(samples: torch.Tensor, lo: float, hi: float, region: Optional[torch.Tensor] = None):
+    """``(B,5,H,W)`` planes [depth, x, y, z, reflectance] (``LiDARUtility.postprocess``) -> ``(points (total,4), offsets (B+1,))``: the
+    returns (``lo < depth < hi``) of every image in image order (``images_to_points``).  ``region``: ``(B,1,H,W)``, non-zero = the pixel
+    may be kept."""
+    from .pointcloud import images_to_points
+
+    if samples.dim() != 4 or samples.shape[1] != 5:
+        raise ValueError(f"expected samples (B,5,H,W) [depth, x, y, z, reflectance], got {tuple(samples.shape)}")
+    if region is not None:
+        B, _, H, W = samples.shape
+        if tuple(region.shape) != (B, 1, H, W):
+            raise ValueError(f"region {tuple(region.shape)} must be (B,1,H,W) = {(B, 1, H, W)}")
+        samples = samples.float().clone()
+        samples[:, 0] = torch.where(region[:, 0].to(samples.device) != 0, samples[:, 0], torch.full_like(samples[:, 0], math.nan))  # NaN drops out
+    return images_to_points(samples, layout="sample", order="image", keep_min=float(lo), keep_max=float(hi))
+
+
+def subsample_indices(count: int, n: int, seed: int, index: int) -> torch.Tensor:
+    """The rows of cloud ``index`` (``count`` points) that ``subsample`` keeps: all of them in order if ``count <= n``, else the first n of
+    a permutation drawn from ``numpy.random.Generator(PCG64([seed, index]))`` (a seed sequence mixes both numbers) -- whatever else is in
+    the batch."""
+    count, n, seed, index = int(count), int(n), int(seed), int(index)
+    if seed < 0 or index < 0:
+        raise ValueError(f"seed and cloud index must be >= 0, got {seed}, {index}")
+    if count <= n:
+        return torch.arange(count)
+    return torch.from_numpy(np.random.Generator(np.random.PCG64([seed, index])).permutation(count)[:n].astype(np.int64))
+
+
+def subsample(points: torch.Tensor, offsets, n: int, seed: int, first_index: int = 0):
+    """Ragged clouds -> ``(clouds (N,n,4), counts (N,) int64)`` on the points' device: per cloud n points drawn without replacement
+    (``subsample_indices``; cloud k is drawn as cloud ``first_index + k``); a cloud with fewer than n points keeps all of them, zero-padded,
+    and reports its count."""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"n must be >= 1, got {n}")
+    if points.dim() != 2 or points.shape[1] != 4:
+        raise ValueError(f"expected points (total,4), got {tuple(points.shape)}")
+    off = _host_offsets(offsets, points.shape[0], "offsets")
+    N = off.size - 1
+    rows = torch.zeros(N, n, dtype=torch.int64)
+    counts = torch.zeros(N, dtype=torch.int64)
+    for k in range(N):
+        idx = subsample_indices(int(off[k + 1] - off[k]), n, seed, first_index + k)
+        rows[k, :idx.numel()] = idx + int(off[k])
+        counts[k] = idx.numel()
+    valid = torch.arange(n)[None, :] < counts[:, None]
+    out = torch.zeros(N, n, 4, dtype=torch.float32, device=points.device)
+    if points.shape[0]:
+        out = torch.where(valid[..., None].to(points.device), points.float()[rows.to(points.device)], out)
+    return out, counts.to(points.device)
+
+
+def _compact(clouds: torch.Tensor, counts: torch.Tensor, what: str):
+    if clouds.dim() != 3 or clouds.shape[2] != 4:
+        raise ValueError(f"{what}: expected (N,n,4) clouds, got {tuple(clouds.shape)}")
+    N, n, _ = clouds.shape
+    counts = torch.as_tensor(counts).to(clouds.device)
+    if tuple(counts.shape) != (N,) or counts.dtype.is_floating_point:
+        raise ValueError(f"{what}: counts must be ({N},) integers, got {tuple(counts.shape)} {counts.dtype}")
+    host = counts.cpu().numpy().astype(np.int64)
+    if N < 1 or (host < 0).any() or (host > n).any():
+        raise ValueError(f"{what}: at least one cloud, and counts in [0, {n}]")
+    keep = torch.arange(n, device=clouds.device)[None, :] < counts[:, None]
+    return clouds.float()[keep].contiguous(), np.concatenate([[0], np.cumsum(host)]).astype(np.int64)
+
+
+def pairwise_chamfer(A: torch.Tensor, countsA, B: torch.Tensor, countsB) -> torch.Tensor:
+    """``(Na,Nb)`` float64 matrix of ``cd_sq`` between every cloud of ``A`` ``(Na,n,4)`` (the first ``countsA[i]`` rows of cloud i count) and
+    every cloud of ``B``, on the device.  The same kernel as ``chamfer_sums``, over the pair list of all (i, j) generated in slabs, so
+    that the pair list, the sums and the scratch of a call stay bounded; an entry equals the pair's own ``chamfer_sums`` bit for bit."""
+    _lib.require_gpu(A, "A")
+    if B.device != A.device:
+        raise ValueError(f"A is on {A.device}, B on {B.device}")
+    a, off_a = _compact(A, countsA, "A")
+    b, off_b = _compact(B, countsB, "B")
+    a, b = _points(a, "A"), _points(b, "B")
+    dev, Na, Nb = A.device, off_a.size - 1, off_b.size - 1
+    max_points = max(int(max(np.diff(off_a).max(), np.diff(off_b).max())), 1)
+    chunks = (max_points + 1023) // 1024
+    slab = max(1, min(SLAB_BYTES // (16 + 64 + 64 * chunks), ((1 << 31) - 1) // (2 * chunks)))
+    oa, ob = torch.from_numpy(off_a).to(dev), torch.from_numpy(off_b).to(dev)
+    out = torch.empty(Na * Nb, len(RAW_NAMES), dtype=torch.float64, device=dev)
+    status = torch.zeros(2, dtype=torch.int64, device=dev)
+    for s in range(0, Na * Nb, slab):
+        k = torch.arange(s, min(s + slab, Na * Nb), dtype=torch.int64, device=dev)
+        pairs = torch.stack([k // Nb, k % Nb], dim=1).contiguous()
+        sums, st = _launch(a, oa, Na, b, ob, Nb, pairs, max_points, 0.0)
+        out[s:s + slab] = sums
+        status += st
+    _raise_on_status(status)
+    return chamfer_from_sums(out)["cd_sq"].reshape(Na, Nb)
+
+
+# ---- set metrics (plain torch) -----------------------------------------------------------------------------------------------------------
+def _matrix(D, what: str) -> torch.Tensor:
+    D = torch.as_tensor(D).double()
+    if D.dim() != 2 or D.shape[0] < 1 or D.shape[1] < 1:
+        raise ValueError(f"{what}: expected a non-empty distance matrix, got {tuple(D.shape)}")
+    if D.isnan().any():
+        raise ValueError(f"{what}: a NaN distance (an empty cloud): the set metrics are defined for clouds with points")
+    return D
+
+
+def _argmin_lowest(D: torch.Tensor) -> torch.Tensor:
+    """per row the LOWEST column index that attains the row's minimum"""
+    cols = torch.arange(D.shape[1], device=D.device).expand_as(D)
+    return torch.where(D == D.min(dim=1, keepdim=True).values, cols, torch.full_like(cols, D.shape[1])).min(dim=1).values
+
+
+def coverage(D) -> float:
+    """``D`` (generated, real) -> the fraction of real clouds that are the nearest real cloud of some generated one."""
+    D = _matrix(D, "coverage")
+    return _argmin_lowest(D).unique().numel() / D.shape[1]
+
+
+def minimum_matching_distance(D) -> float:
+    """``D`` (generated, real) -> the mean over the real clouds of the distance to their nearest generated cloud."""
+    nearest = _matrix(D, "minimum_matching_distance").min(dim=0).values
+    return math.fsum(nearest.tolist()) / nearest.numel()  # (a correctly rounded sum: the value does not depend on an order of summation)
+
+
+def one_nn_accuracy(D_gg, D_gr, D_rr) -> float:
+    """Leave-one-out 1-nearest-neighbour accuracy over S = G u R from the three blocks of its distance matrix."""
+    D_gg, D_gr, D_rr = _matrix(D_gg, "D_gg"), _matrix(D_gr, "D_gr"), _matrix(D_rr, "D_rr")
+    G, R = D_gr.shape
+    if tuple(D_gg.shape) != (G, G) or tuple(D_rr.shape) != (R, R):
+        raise ValueError(f"D_gg {tuple(D_gg.shape)}, D_gr {tuple(D_gr.shape)}, D_rr {tuple(D_rr.shape)} must be (G,G), (G,R), (R,R)")
+    D_gg, D_rr = D_gg.to(D_gr.device), D_rr.to(D_gr.device)
+    M = torch.cat([torch.cat([D_gg, D_gr], dim=1), torch.cat([D_gr.t(), D_rr], dim=1)], dim=0).clone()
+    if G + R < 2:
+        raise ValueError("1-NNA needs at least two clouds")
+    M.fill_diagonal_(math.inf)
+    nearest = _argmin_lowest(M)
+    is_g = torch.arange(G + R, device=M.device) < G
+    return ((nearest < G) == is_g).double().mean().item()
+
+
+def set_metrics(D_gg, D_gr, D_rr) -> Dict[str, float]:
+    """``{"cov", "mmd", "1-nna"}`` from the ``cd_sq`` matrices generated x generated, generated x real, real x real."""
+    return {"cov": coverage(D_gr), "mmd": minimum_matching_distance(D_gr), "1-nna": one_nn_accuracy(D_gg, D_gr, D_rr)}
