@@ -2,7 +2,9 @@
 """Scores a directory of generated ``samples_*.pth`` files ((5,H,W) [depth, x, y, z, reflectance], what sample_and_save.py writes and
 evaluate.py reads) against a real set in 3-D, on the GPU: coverage (COV), minimum matching distance (MMD) and 1-nearest-neighbour accuracy
 (1-NNA) under the squared Chamfer distance between point clouds (the PointFlow / LiDM definitions; r2dm_amd.geometry, DESIGN.md section 4,
-"Geometry metrics").
+"Geometry metrics") or, with ``--distance emd``, under the earth mover's distance (the protocol's second column: Chamfer is blind to
+density, a one-to-one matching is not).  There every scan must have ``--points`` points inside the window, and the document also carries
+``emd_eps`` and ``emd_max_gap``, the largest certified distance of an entry from its exact value.
 
 The real set comes from either
   - ``--real_dir DIR``: a directory of ``*.pth`` scans in the sample layout; or
@@ -87,13 +89,25 @@ def main(argv=None):
     if any(empty):
         raise SystemExit(f"{empty[0]} generated and {empty[1]} real scans have no point inside ({MIN_DEPTH} m, {MAX_DEPTH} m): the set metrics "
                          "are defined for clouds with points")
-    D_gr = geometry.pairwise_chamfer(G, nG, R, nR)
-    D_gg = geometry.pairwise_chamfer(G, nG, G, nG)
-    D_rr = geometry.pairwise_chamfer(R, nR, R, nR)
+    extra = {}
+    if args.distance == "emd":
+        short = int((nG < args.points).sum().item()), int((nR < args.points).sum().item())
+        if any(short):
+            raise SystemExit(f"{short[0]} generated and {short[1]} real scans have fewer than --points = {args.points} points inside ({MIN_DEPTH} m, "
+                             f"{MAX_DEPTH} m): the earth mover's distance is defined between clouds of the same size")
+        (D_gr, gap_gr), (D_gg, gap_gg), (D_rr, gap_rr) = (geometry.pairwise_emd(X, nX, Y, nY, eps=args.emd_eps, max_rounds=args.emd_max_rounds)
+                                                          for X, nX, Y, nY in ((G, nG, R, nR), (G, nG, None, None), (R, nR, None, None)))
+        # the largest certified emd - lower over all pairs: how far from the exact distance any entry can be
+        extra = {"emd_eps": args.emd_eps, "emd_max_gap": max(g.max().item() for g in (gap_gr, gap_gg, gap_rr))}
+    else:
+        D_gr = geometry.pairwise_chamfer(G, nG, R, nR)
+        D_gg = geometry.pairwise_chamfer(G, nG, G, nG)
+        D_rr = geometry.pairwise_chamfer(R, nR, R, nR)
     doc = dict(geometry.set_metrics(D_gg, D_gr, D_rr))
-    doc.update({"#fake": len(gen_files), "#real": len(real_files), "points": args.points, "seed": args.seed, "distance": "cd_sq",
+    doc.update({"#fake": len(gen_files), "#real": len(real_files), "points": args.points, "seed": args.seed, "distance": args.distance,
                 "min_depth": MIN_DEPTH, "max_depth": MAX_DEPTH, "directory": str(args.sample_dir),
                 "real": str(args.real_scans if args.real_scans is not None else args.real_dir)})
+    doc.update(extra)
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(doc, f, indent=4)
@@ -113,6 +127,10 @@ def build_parser():
     parser.add_argument("--batch_size", type=int, default=64)
     parser.add_argument("--num_workers", type=int, default=4)
     parser.add_argument("--out", type=str, default="geometry.json")
+    parser.add_argument("--distance", choices=("cd_sq", "emd"), default="cd_sq",
+                        help="the distance between two clouds: squared Chamfer, or the earth mover's distance (every scan needs --points points)")
+    parser.add_argument("--emd_eps", type=float, default=0.01, help="--distance emd: accuracy of a distance, metres per point")
+    parser.add_argument("--emd_max_rounds", type=int, default=1 << 20, help="--distance emd: bidding rounds of the auction per cloud pair")
     return parser
 
 

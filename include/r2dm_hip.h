@@ -446,6 +446,31 @@ int r2dm_nn_pairs(const float* a, const int64_t* a_offsets, int64_t a_clouds, in
                   int32_t* idx_ab, const int64_t* out_ab, float* d2_ba, int32_t* idx_ba, const int64_t* out_ba, void* scratch, double* sums,
                   int64_t* status, void* stream);
 
+/* -- earth mover's distance between clouds of equal size (the reference has no code for it) ------------------------------------------------
+ * r2dm_emd_pairs: clouds and pairs as for r2dm_nn_pairs.  For a pair of clouds A, B of n points each,
+ *    EMD = (1/n) min over permutations s of sum_i |a_i - b_s(i)| (Euclidean, metres).  The solver is a forward auction with
+ *    epsilon-scaling (Jacobi rounds, one workgroup per pair, costs c = sqrt(d^2) in fp32 with d^2 in the difference form above); it does
+ *    not promise the minimum.  Per pair, out (num_pairs,4) fp64 = [emd, lower, rounds, converged]: emd the true cost of the returned
+ *    permutation, lower = (1/n) (sum_i min_j (c_ij + p_j) - sum_j p_j) from the final prices p, a lower bound of EMD for any p (weak
+ *    duality), both summed in fp64 in a fixed order from sqrt in fp64 of the fp32 d^2: lower <= EMD <= emd, and in exact arithmetic
+ *    emd - lower <= eps.  Bit-reproducible; a pair's numbers do not depend on the other pairs of the call.
+ *    eps: the bid increment of the last phase, metres per point; finite, > 0 and a normal fp32 number.  A pair with
+ *    eps < 2^-18 * (diagonal of the two clouds' joint bounding box) is refused on the device: an increment could vanish in fp32.
+ *    max_rounds >= 1: bidding rounds of a pair over all phases; a pair that needs more ends with converged = 0.
+ *    assignment: NULL or (num_pairs, max_points) int32, s(i) for i < n and -1 beyond; prices: NULL or fp32 alike, p_j and NaN beyond.
+ *    A pair that ends without an answer has emd = lower = NaN, converged = 0, assignment -1 and prices NaN throughout, and rounds = 0,
+ *    or max_rounds at the round cap.  scratch: num_pairs int64 (r2dm_emd_pairs_scratch_bytes; 0 for an empty or oversized problem),
+ *    per pair the code 0 = solved, 1..5 = the reasons below.  status (5) int64, zeroed by the call, counts the pairs per reason:
+ *    [0] an index outside [0, clouds), offsets that are not 0 <= begin <= end <= total, more than max_points points, or n = 0;
+ *    [1] the two clouds differ in size; [2] a non-finite coordinate (or a bounding box whose diagonal overflows fp32); [3] eps below
+ *    its floor; [4] the round cap.  Nothing is read through an index or offset that does not check out.
+ *    max_points: 1 to r2dm_emd_max_points() = 3072 (48 bytes of LDS per point).  Nothing is allocated, nothing synchronises. */
+int64_t r2dm_emd_max_points(void);
+size_t r2dm_emd_pairs_scratch_bytes(int64_t num_pairs, int64_t max_points);
+int r2dm_emd_pairs(const float* a, const int64_t* a_offsets, int64_t a_clouds, int64_t a_total, const float* b, const int64_t* b_offsets,
+                   int64_t b_clouds, int64_t b_total, const int64_t* pairs, int64_t num_pairs, int64_t max_points, double eps, int64_t max_rounds,
+                   int32_t* assignment, float* prices, double* out, void* scratch, int64_t* status, void* stream);
+
 /* -- single kernels, exported for per-op parity tests against the oracle -------------------- */
 /* ops.Conv2d(ring) 3x3 / 1x1 (models/ops.py:149-173) with optional fused GroupNorm-affine(+SiLU)
  * prologue (aff: (B,Cin,2) or NULL; prologue 0 none, 1 affine, 2 affine+SiLU) and optional

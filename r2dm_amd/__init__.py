@@ -24,7 +24,7 @@ from .loss import loss_curve
 from . import completion  # noqa: E402  (completion metrics: range / reflectance error, IoU, interpolation baselines)
 from .completion import (completion_errors, confusion_matrix, corruption_mask, evaluate_completion, fill_beams, iou_from_confusion)
 from . import geometry  # noqa: E402  (Chamfer distance, F-score, COV / MMD / 1-NNA on a HIP nearest-neighbour search)
-from .geometry import chamfer_from_sums, chamfer_sums, nearest_neighbors, pairwise_chamfer, set_metrics
+from .geometry import chamfer_from_sums, chamfer_sums, emd_pairs, nearest_neighbors, pairwise_chamfer, pairwise_emd, set_metrics
 
 __all__ = [
     "ContinuousTimeGaussianDiffusion", "DiscreteTimeGaussianDiffusion", "GaussianDiffusion", "EfficientUNet",
@@ -35,5 +35,6 @@ __all__ = [
     "KNN", "CRFRNN", "loss_curve",
     "corruption_mask", "completion_errors", "confusion_matrix", "iou_from_confusion", "fill_beams", "evaluate_completion",
     "nearest_neighbors", "chamfer_sums", "chamfer_from_sums", "pairwise_chamfer", "set_metrics",
+    "emd_pairs", "pairwise_emd",
 ]
 __version__ = "0.4.0"

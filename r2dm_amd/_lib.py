@@ -153,6 +153,10 @@ SIGNATURES = {
     "r2dm_nn_pairs_scratch_bytes": (c_size_t, [c_int64, c_int64]),
     "r2dm_nn_pairs": (c_int32, [_P, _P, c_int64, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, ctypes.c_double, _P, _P, _P, _P, _P, _P, _P,
                                 _P, _P, _P]),
+    "r2dm_emd_max_points": (c_int64, []),
+    "r2dm_emd_pairs_scratch_bytes": (c_size_t, [c_int64, c_int64]),
+    "r2dm_emd_pairs": (c_int32, [_P, _P, c_int64, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, ctypes.c_double, c_int64, _P, _P, _P, _P, _P,
+                                 _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

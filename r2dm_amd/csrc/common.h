@@ -346,6 +346,15 @@ hipError_t launch_nn_pairs(const float* a, const long long* off_a, long clouds_a
                            const long long* out_ab, float* d2_ba, int* idx_ba, const long long* out_ba, void* scratch, double* sums,
                            long long* status, hipStream_t s);
 
+// earth mover's distance (emd.hip): a forward auction per pair of equally sized clouds -- out (P,4) = emd, lower, rounds, converged; optional
+// assignment / prices (P, max_points); scratch = one code per pair; status[5] = pairs ended as bad pair, unequal counts, non-finite, eps below
+// its floor, round cap
+long emd_max_points();
+size_t emd_pairs_scratch_bytes(long P);
+hipError_t launch_emd_pairs(const float* a, const long long* off_a, long clouds_a, long total_a, const float* b, const long long* off_b, long clouds_b,
+                            long total_b, const long long* pairs, long P, long max_points, double eps, long long max_rounds, int* assignment,
+                            float* prices, double* out, void* scratch, long long* status, hipStream_t s);
+
 // rendering of generate.py (render.hip): colour maps, the bilinear splat with 64-bit fixed-point accumulators, the fused frame renderer
 hipError_t launch_colorize(const float* x, const float* lut, uint8_t* out, long B, long hw, hipStream_t s);
 size_t rasterize_scratch_bytes(int B, int C, int H, int W);

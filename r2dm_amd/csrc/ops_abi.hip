@@ -429,4 +429,38 @@ int r2dm_nn_pairs(const float* a, const int64_t* a_offsets, int64_t a_clouds, in
     return 0;
 }
 
+static bool emd_geometry_ok(int64_t P, int64_t max_points, double eps, int64_t max_rounds) {
+    // (eps must also be a normal fp32 number: the auction bids in fp32)
+    return P >= 1 && P <= 0x7fffffffLL && max_points >= 1 && max_points <= emd_max_points() && eps >= 1.1754943508222875e-38 && eps <= 3.4028234663852886e38 &&
+           max_rounds >= 1;
+}
+
+int64_t r2dm_emd_max_points(void) { return emd_max_points(); }
+
+size_t r2dm_emd_pairs_scratch_bytes(int64_t P, int64_t max_points) { return emd_geometry_ok(P, max_points, 1.0, 1) ? emd_pairs_scratch_bytes(P) : 0; }
+
+int r2dm_emd_pairs(const float* a, const int64_t* a_offsets, int64_t a_clouds, int64_t a_total, const float* b, const int64_t* b_offsets,
+                   int64_t b_clouds, int64_t b_total, const int64_t* pairs, int64_t P, int64_t max_points, double eps, int64_t max_rounds,
+                   int32_t* assignment, float* prices, double* out, void* scratch, int64_t* status, void* stream) {
+    if (!a_offsets || !b_offsets || !pairs || !out || !scratch || !status) return fail(1, "null argument");
+    if (a_clouds < 1 || b_clouds < 1 || a_total < 0 || b_total < 0 || (!a && a_total) || (!b && b_total))
+        return fail(1, "emd_pairs: each set needs at least one cloud, and a pointer unless it has no points");
+    if (max_points > emd_max_points())
+        return fail(1, "emd_pairs: clouds of up to %lld points (the auction of a pair lives in one workgroup's LDS), got max_points = %lld",
+                    (long long)emd_max_points(), (long long)max_points);
+    if (!(eps > 0.0) || !(eps <= 3.4028234663852886e38) || eps < 1.1754943508222875e-38)
+        return fail(1, "emd_pairs: eps must be finite and > 0 (a normal fp32 number), got %g", eps);
+    if (max_rounds < 1) return fail(1, "emd_pairs: max_rounds must be >= 1, got %lld", (long long)max_rounds);
+    if (!emd_geometry_ok(P, max_points, eps, max_rounds))
+        return fail(1, "emd_pairs: num_pairs must be in [1, 2^31 - 1] and max_points >= 1, got %lld, %lld", (long long)P, (long long)max_points);
+    if (((uintptr_t)a | (uintptr_t)b) & 15) return fail(1, "emd_pairs: a and b must be 16-byte aligned (rows are read as quads)");
+    if (((uintptr_t)a_offsets | (uintptr_t)b_offsets | (uintptr_t)pairs | (uintptr_t)out | (uintptr_t)scratch | (uintptr_t)status) & 7)
+        return fail(1, "emd_pairs: offsets, pairs, out, scratch and status must be 8-byte aligned");
+    if (((uintptr_t)assignment | (uintptr_t)prices) & 3) return fail(1, "emd_pairs: assignment and prices must be 4-byte aligned");
+    HIP_TRY(launch_emd_pairs(a, reinterpret_cast<const long long*>(a_offsets), a_clouds, a_total, b, reinterpret_cast<const long long*>(b_offsets), b_clouds,
+                             b_total, reinterpret_cast<const long long*>(pairs), P, max_points, eps, max_rounds, assignment, prices, out, scratch,
+                             reinterpret_cast<long long*>(status), (hipStream_t)stream));
+    return 0;
+}
+
 }  // extern "C"

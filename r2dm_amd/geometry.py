@@ -10,8 +10,12 @@ Clouds are sets of 3-D points in metres; ``d(x, Y) = min_{y in Y} |x - y|``.
 - set metrics of generated clouds G against real clouds R under ``D = cd_sq`` (the PointFlow / LiDM definitions):
   ``COV = |{argmin_r D(g, r): g in G}| / |R|``, ``MMD = mean_r min_g D(g, r)``, ``1-NNA`` = over S = G u R the fraction of s whose nearest
   neighbour in S \\ {s} lies in the same set as s (0.5 is ideal).  Every argmin tie goes to the lowest index, G before R.
+- earth mover's distance of two clouds of the same number n of points: ``EMD = (1/n) min_sigma sum_i |a_i - b_sigma(i)|`` over the
+  permutations sigma (Euclidean, not squared: PointFlow's convention).  ``emd_pairs`` returns a permutation, its true cost ``emd`` and a
+  certified ``lower <= EMD <= emd``; the set metrics above take its matrix (``pairwise_emd``) as they take ``cd_sq``'s.
 
-The search is one HIP kernel (``r2dm_nn_pairs``, ``r2dm_amd/csrc/geometry.hip``) over a list of cloud pairs; it has no CPU fallback.
+The search is one HIP kernel (``r2dm_nn_pairs``, ``r2dm_amd/csrc/geometry.hip``) over a list of cloud pairs, the assignment solver another
+(``r2dm_emd_pairs``, ``r2dm_amd/csrc/emd.hip``); neither has a CPU fallback.
 What is derived from its sums and from distance matrices is plain torch and works on CPU tensors too."""
 from __future__ import annotations
 
@@ -278,6 +282,173 @@ def pairwise_chamfer(A: torch.Tensor, countsA, B: torch.Tensor, countsB) -> torc
     return chamfer_from_sums(out)["cd_sq"].reshape(Na, Nb)
 
 
+# ---- earth mover's distance --------------------------------------------------------------------------------------------------------------
+def _emd_knobs(eps, max_rounds):
+    eps, max_rounds = float(eps), int(max_rounds)
+    if not (math.isfinite(eps) and eps > 0):
+        raise ValueError(f"eps must be a finite distance > 0 (metres per point), got {eps}")
+    if max_rounds < 1:
+        raise ValueError(f"max_rounds must be >= 1, got {max_rounds}")
+    return eps, max_rounds
+
+
+def _emd_launch(a, off_a, clouds_a, b, off_b, clouds_b, pairs_dev, max_points, eps, max_rounds, assignment=False, prices=False):
+    """One ``r2dm_emd_pairs`` call on device tensors -> dict of ``out`` (P,4), ``status`` (5,), ``code`` (P,) and the optional
+    ``assignment`` / ``prices`` (P, max_points); nothing read back, nothing raised for what the device refuses."""
+    dev, P = a.device, pairs_dev.shape[0]
+    L = _lib.lib()
+    nbytes = L.r2dm_emd_pairs_scratch_bytes(P, max_points)
+    if nbytes == 0:
+        raise ValueError(f"{P} pairs of clouds of up to {max_points} points: beyond the limits of r2dm_emd_pairs (at least one pair, clouds of 1 to "
+                         f"{emd_max_points()} points)")
+    res = {"out": torch.empty(P, 4, dtype=torch.float64, device=dev), "status": torch.empty(len(EMD_STATUS), dtype=torch.int64, device=dev),
+           "code": torch.empty(nbytes // 8, dtype=torch.int64, device=dev)}
+    if assignment:
+        res["assignment"] = torch.empty(P, max_points, dtype=torch.int32, device=dev)
+    if prices:
+        res["prices"] = torch.empty(P, max_points, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.r2dm_emd_pairs(_lib.ptr(a) or None, _lib.ptr(off_a), clouds_a, a.shape[0], _lib.ptr(b) or None, _lib.ptr(off_b), clouds_b, b.shape[0],
+                                    _lib.ptr(pairs_dev), P, max_points, eps, max_rounds, _lib.ptr(res.get("assignment")), _lib.ptr(res.get("prices")),
+                                    _lib.ptr(res["out"]), _lib.ptr(res["code"]), _lib.ptr(res["status"]), _lib.stream_ptr(dev)))
+    return res
+
+
+EMD_STATUS = ("bad_pair", "unequal_counts", "non_finite", "eps_floor", "round_cap")  # status[k] counts the pairs that ended with code k + 1
+
+
+def emd_max_points() -> int:
+    """The largest cloud ``r2dm_emd_pairs`` takes (the auction of a pair lives in one workgroup's LDS)."""
+    return int(_lib.lib().r2dm_emd_max_points())
+
+
+def _raise_on_emd_status(status: torch.Tensor, code: torch.Tensor, eps: float, first: int, allow_unconverged: bool) -> None:
+    """One read of the counters; the per-pair codes are read only to name the pairs of an error."""
+    counts = dict(zip(EMD_STATUS, (int(v) for v in status.cpu().tolist())))
+    if not any(counts.values()):
+        return
+
+    def which(k):
+        at = (torch.nonzero(code == k + 1).flatten() + first).cpu().tolist()
+        return f"{at[:8]}{' ...' if len(at) > 8 else ''}"
+
+    if counts["bad_pair"]:
+        raise ValueError(f"earth mover's distance: {counts['bad_pair']} pairs {which(0)} with an index or offsets that do not check out, no points, "
+                         f"or more than {emd_max_points()} points")
+    if counts["unequal_counts"]:
+        raise ValueError(f"earth mover's distance: {counts['unequal_counts']} pairs {which(1)} whose two clouds differ in size (the distance is "
+                         "defined for equal counts)")
+    if counts["non_finite"]:
+        raise ValueError(f"earth mover's distance: {counts['non_finite']} pairs {which(2)} with a non-finite coordinate")
+    if counts["eps_floor"]:
+        raise ValueError(f"earth mover's distance: eps = {eps} is below 2^-18 of the bounding-box diagonal of {counts['eps_floor']} pairs {which(3)}: "
+                         "a bid increment could vanish in fp32")
+    if counts["round_cap"] and not allow_unconverged:
+        raise _lib.R2DMError(f"earth mover's distance: {counts['round_cap']} pairs {which(4)} did not converge within max_rounds "
+                             "(allow_unconverged=True returns NaN for them)")
+
+
+def emd_pairs(a: torch.Tensor, a_offsets, b: torch.Tensor, b_offsets, pairs=None, eps: float = 0.01, max_rounds: int = 1 << 20,
+              return_assignment: bool = False, return_prices: bool = False, allow_unconverged: bool = False) -> dict:
+    """Earth mover's distance of a list of cloud pairs: ``EMD(A, B) = (1/n) min_sigma sum_i |a_i - b_sigma(i)|`` in metres, for two clouds of
+    the same number n >= 1 of points (at most ``emd_max_points()``).  Clouds and ``pairs`` as ``nearest_neighbors``.
+
+    One HIP kernel (``r2dm_emd_pairs``, ``r2dm_amd/csrc/emd.hip``): a forward auction with epsilon-scaling, which does not promise the
+    minimum.  -> a dict of device tensors, ``(P,)`` each: ``emd`` float64, the true cost of the permutation found; ``lower`` float64, a
+    lower bound of the minimum certified by weak duality from the final prices (``lower <= EMD <= emd``; in exact arithmetic
+    ``emd - lower <= eps``); ``rounds`` int64; ``converged`` bool; with ``return_assignment`` ``assignment`` ``(P, max n)`` int32
+    (``sigma(i)``, -1 beyond a pair's n), with ``return_prices`` ``prices`` ``(P, max n)`` float32 (NaN beyond n).
+
+    ``eps`` is the accuracy knob, metres per point; below ``2^-18`` of a pair's bounding-box diagonal it is refused.  Raises ``ValueError``
+    for bad pairs, unequal counts, non-finite points and such an eps, and ``R2DMError`` naming the pairs that did not converge within
+    ``max_rounds`` bidding rounds unless ``allow_unconverged`` (their values are NaN)."""
+    a, b = _points(a, "a"), _points(b, "b")
+    if b.device != a.device:
+        raise ValueError(f"a is on {a.device}, b on {b.device}")
+    off_a, off_b = _host_offsets(a_offsets, a.shape[0], "a_offsets"), _host_offsets(b_offsets, b.shape[0], "b_offsets")
+    pr = _pairs(pairs, off_a.size - 1, off_b.size - 1)
+    eps, max_rounds = _emd_knobs(eps, max_rounds)
+    dev, P = a.device, pr.shape[0]
+    na, nb = np.diff(off_a)[pr[:, 0]], np.diff(off_b)[pr[:, 1]]
+    if (na != nb).any():
+        at = np.flatnonzero(na != nb)
+        raise ValueError(f"earth mover's distance: {at.size} pairs {at[:8].tolist()} whose two clouds differ in size ({int(na[at[0]])} and "
+                         f"{int(nb[at[0]])} points): the distance is defined for equal counts")
+    if P and (na.min() < 1 or na.max() > emd_max_points()):
+        raise ValueError(f"earth mover's distance: clouds of 1 to {emd_max_points()} points, got {int(na.min())} to {int(na.max())}")
+    width = int(na.max()) if P else 0
+    out = {"emd": torch.empty(P, dtype=torch.float64, device=dev), "lower": torch.empty(P, dtype=torch.float64, device=dev),
+           "rounds": torch.empty(P, dtype=torch.int64, device=dev), "converged": torch.empty(P, dtype=torch.bool, device=dev)}
+    if return_assignment:
+        out["assignment"] = torch.empty(P, width, dtype=torch.int32, device=dev)
+    if return_prices:
+        out["prices"] = torch.empty(P, width, dtype=torch.float32, device=dev)
+    if P == 0:
+        return out
+    res = _emd_launch(a, torch.from_numpy(off_a).to(dev), off_a.size - 1, b, torch.from_numpy(off_b).to(dev), off_b.size - 1,
+                      torch.from_numpy(pr).to(dev), width, eps, max_rounds, return_assignment, return_prices)
+    _raise_on_emd_status(res["status"], res["code"], eps, 0, allow_unconverged)
+    out.update(emd=res["out"][:, 0].contiguous(), lower=res["out"][:, 1].contiguous(), rounds=res["out"][:, 2].long(), converged=res["out"][:, 3] != 0)
+    for k in ("assignment", "prices"):
+        if k in res:
+            out[k] = res[k]
+    return out
+
+
+EMD_SLAB_PAIRS = 1 << 16      # pairwise_emd: pairs per call (32 bytes of results, 16 of pair list and 8 of codes each)
+
+
+def pairwise_emd(A: torch.Tensor, countsA, B: Optional[torch.Tensor] = None, countsB=None, eps: float = 0.01, max_rounds: int = 1 << 20):
+    """``(D, gap)``: ``(Na,Nb)`` float64 matrices on the device of ``emd`` and of the certified ``emd - lower`` between every cloud of ``A``
+    ``(Na,n,4)`` and every cloud of ``B``; the kernel of ``emd_pairs`` over the pair list of all (i, j) in slabs, an entry equal to the
+    pair's own ``emd_pairs`` bit for bit.  With ``B=None`` the matrix of ``A`` against itself: only ``i < j`` is solved and mirrored, the
+    diagonal is 0 (the auction's answers for (A, B) and (B, A) may differ inside the gap; this matrix is symmetric by construction).
+    Every cloud must hold the same number of points (``ValueError``)."""
+    _lib.require_gpu(A, "A")
+    same = B is None
+    if same:
+        if countsB is not None:
+            raise ValueError("countsB without B")
+        B, countsB = A, countsA
+    elif countsB is None:
+        raise ValueError("B needs countsB")
+    if B.device != A.device:
+        raise ValueError(f"A is on {A.device}, B on {B.device}")
+    eps, max_rounds = _emd_knobs(eps, max_rounds)
+    a, off_a = _compact(A, countsA, "A")
+    b, off_b = (a, off_a) if same else _compact(B, countsB, "B")
+    na = np.concatenate([np.diff(off_a), np.diff(off_b)])
+    if (na != na[0]).any() or na[0] < 1:
+        raise ValueError(f"earth mover's distance: every cloud must hold the same number (>= 1) of points, got counts from {int(na.min())} to "
+                         f"{int(na.max())}")
+    n = int(na[0])
+    if n > emd_max_points():
+        raise ValueError(f"earth mover's distance: clouds of up to {emd_max_points()} points, got {n}")
+    a = _points(a, "A")
+    b = a if same else _points(b, "B")
+    dev, Na, Nb = A.device, off_a.size - 1, off_b.size - 1
+    oa = torch.from_numpy(off_a).to(dev)
+    ob = oa if same else torch.from_numpy(off_b).to(dev)
+    if same:
+        iu = torch.triu_indices(Na, Na, offset=1, device=dev)
+        every = torch.stack([iu[0], iu[1]], dim=1).contiguous()
+    else:
+        k = torch.arange(Na * Nb, dtype=torch.int64, device=dev)
+        every = torch.stack([k // Nb, k % Nb], dim=1).contiguous()
+    total = every.shape[0]
+    out = torch.empty(total, 4, dtype=torch.float64, device=dev)
+    for s in range(0, total, EMD_SLAB_PAIRS):
+        res = _emd_launch(a, oa, Na, b, ob, Nb, every[s:s + EMD_SLAB_PAIRS].contiguous(), n, eps, max_rounds)
+        _raise_on_emd_status(res["status"], res["code"], eps, s, False)  # (a slab may run for minutes: an error ends the matrix here)
+        out[s:s + EMD_SLAB_PAIRS] = res["out"]
+    D, gap = torch.zeros(Na, Nb, dtype=torch.float64, device=dev), torch.zeros(Na, Nb, dtype=torch.float64, device=dev)
+    D[every[:, 0], every[:, 1]] = out[:, 0]
+    gap[every[:, 0], every[:, 1]] = out[:, 0] - out[:, 1]
+    if same:
+        D, gap = D + D.t(), gap + gap.t()  # (x + 0: exact)
+    return D, gap
+
+
 # ---- set metrics (plain torch) -----------------------------------------------------------------------------------------------------------
 def _matrix(D, what: str) -> torch.Tensor:
     D = torch.as_tensor(D).double()
@@ -323,5 +494,6 @@ def one_nn_accuracy(D_gg, D_gr, D_rr) -> float:
 
 
 def set_metrics(D_gg, D_gr, D_rr) -> Dict[str, float]:
-    """``{"cov", "mmd", "1-nna"}`` from the ``cd_sq`` matrices generated x generated, generated x real, real x real."""
+    """``{"cov", "mmd", "1-nna"}`` from the distance matrices generated x generated, generated x real, real x real -- of any distance between
+    clouds: ``cd_sq`` (``pairwise_chamfer``) or the earth mover's distance (``pairwise_emd``)."""
     return {"cov": coverage(D_gr), "mmd": minimum_matching_distance(D_gr), "1-nna": one_nn_accuracy(D_gg, D_gr, D_rr)}
