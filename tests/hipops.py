@@ -200,6 +200,28 @@ def attention(qkv, heads):
     return out
 
 
+_CANARY = 0x7FC5A5A5  # a quiet NaN with a payload: no arithmetic produces these bits
+
+
+def attention_padded(qkv, heads, C=None):
+    """r2dm_attention into the middle of a canary-filled buffer of (C + 2) N floats: the N-float row before the output and the one after it must
+    come back bit-unchanged (rows of at least 64 floats, so that N = 0 is still guarded).  If the entry refuses, the whole buffer must be, and the
+    error is raised on.  C overrides the channel count (for the refusal tests)."""
+    B, C3, N = qkv.shape
+    C = C3 // 3 if C is None else C
+    row = max(N, 64)
+    whole, out = guarded((B, C, N), torch.int32, row, qkv.device, fill=_CANARY)
+    out = out.view(torch.float32)
+    rc = _lib.lib().r2dm_attention(qkv.data_ptr(), out.data_ptr(), B, C, heads, N, _st(qkv))
+    torch.cuda.synchronize()
+    if rc != 0:
+        assert bool((whole == _CANARY).all()), "a refused launch wrote to the output"
+        _lib.check(rc)
+    assert bool((whole[:row] == _CANARY).all() and (whole[-row:] == _CANARY).all()), "write outside the output"
+    assert not bool((out.view(torch.int32) == _CANARY).any()), "an output element was not written"
+    return out
+
+
 def time_embedding(cond, freqs, w1, b1, w2, b2):
     B, T, base = cond.shape[0], w1.shape[0], w1.shape[1]
     act = torch.empty(B, T, device=cond.device)
