@@ -82,8 +82,7 @@ __host__ __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
 
 // ---- kernel launchers (each in its own .hip) ------------------------------------------
 
-// PRO_PRESPLIT (conv_f16x2 only): the input is the pre-split tensor of presplit.hip -- affine / SiLU / f16 split already applied
-enum Prologue { PRO_NONE = 0, PRO_AFFINE = 1, PRO_AFFINE_SILU = 2, PRO_PRESPLIT = 3 };
+enum Prologue { PRO_NONE = 0, PRO_AFFINE = 1, PRO_AFFINE_SILU = 2 };
 // ALGO_F32: fp32-input MFMA (conv_mfma.hip).  ALGO_BF16X3: fp32 operands split exactly into three bf16 pieces, six
 // bf16 MFMA products per fp32 product, fp32 accumulation (conv_bf16x3.hip) -- same accuracy class, 2.7x fewer
 // matrix-pipe cycles; needs 3x3, Cin % 16 == 0, Cout % 64 == 0.
@@ -179,14 +178,6 @@ hipError_t launch_conv_f16x2(const ConvParams& p, hipStream_t s);
 // can this launch (shape, tile, batch: everything but the gn_* fields) take its GroupNorm folded -- 8 groups of 8 .. 64 channels, at
 // most 4 x 256 statistics slots per group to read, every block's tiles inside ONE sample
 bool conv_f16x2_fold_supported(const ConvParams& p, int groups, int slots);
-// the operand pre-pass of conv_f16x2 (presplit.hip): xs <- [b][chunk][plane][group][H + 2][W][8 ch] fp16 of silu(x a + d) (prologue as in
-// ConvParams); a convolution with prologue = PRO_PRESPLIT and x.p0 = xs, x.bs0 = presplit_floats(1, Cin, H, W) consumes it
-long presplit_floats(int B, int Cin, int H, int W);
-bool presplit_supported(const Src& x, int Cin, int H, int W);
-hipError_t launch_presplit(const Src& x, const float2* aff, int prologue, float* xs, int B, int Cin, int H, int W, hipStream_t s);
-// ... with the GroupNorm folded in (round 6): partial = the producers' statistics slots [B][G][stride][2], of which the first nslots per group count
-hipError_t launch_presplit_fold(const Src& x, int prologue, float* xs, int B, int Cin, int H, int W, const double* partial, int stride, int nslots, int cpg,
-                                float eps, const float* gamma, const float* beta, const float* ada, long ada_stride, int* range, hipStream_t s);
 bool proj_f16x2_supported(int Cin, int Cout, int taps, int H, int W);
 long proj_f16x2_packed_floats(int Cin, int Cout);
 // taps = 9: w is the OIHW tensor of a 3x3 convolution over Cin / 9 channels, packed as the (Cout, Cin) matrix of the down-sampling GEMM (column = tap * Cin / 9 + ci)

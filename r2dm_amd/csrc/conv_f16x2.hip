@@ -40,7 +40,6 @@
 // MRK = 4 gives a multiplying wave four 32-channel row blocks -- 128-channel output tiles, 24 MFMAs and 12 fragment reads per tap,
 // half the staging work per MFMA -- with ONE accumulator for all three products (residual planes at their true scale, a weight
 // packing of its own): below an fp32 fmaf chain's rms error at every depth; conv_f16x2_pick_co_tile uses it up to Cin = 256.
-// PRO_PRESPLIT: the input arrives pre-split (presplit.hip) and the stagers only issue LDS-DMA -- an experiment, off by default.
 #include "common.h"
 #include "conv_bf16x3.h"
 #include "conv_epilogue.h"
@@ -109,7 +108,7 @@ template <int PRO, int NPLK, int MRK, int NRK, int IOM = 0>
 __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(const ConvParams p, const int total_tiles, const F2Div dv) {
     using namespace f2;
     static_assert(NPLK == 1 || NPLK == 2, "planes");
-    static_assert(IOM == 0 || (NPLK == 1 && PRO != PRO_PRESPLIT), "fp16 storage: the one-plane mode");
+    static_assert(IOM == 0 || NPLK == 1, "fp16 storage: the one-plane mode");
     constexpr bool X16 = (IOM & 1) != 0, Y16 = (IOM & 2) != 0;
     using StatT = std::conditional_t<NPLK == 2, double, float>;  // a statistics slot's sums beyond four pixels (half_stats)
     constexpr int XE = X16 ? 2 : 4, YE = Y16 ? 2 : 4;  // bytes per stored element
@@ -134,7 +133,7 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(const ConvParams p, 
     // residual loads, stores, statistics -- while the multiplier finishes the first NQ - NSQ; a second barrier ends the tile.  LDS: the wave's two waiting
     // slots (their DMA-prefetched residual is in registers by then) and, for the eight-row tile's third and fourth quarter, x buffer 1, which is dead from
     // the tile's last barrier until the stagers' next transform -- behind the second barrier; the multipliers' 1 KiB turn patches move there too.
-    constexpr bool EPI3 = ONEACC && IOM == 0 && PRO != PRO_PRESPLIT;
+    constexpr bool EPI3 = ONEACC && IOM == 0;
     constexpr int NSQ = !EPI3 ? 0 : NR == 4 ? 4 : 2;  // quarters (the last ones: whole statistics pairs) the staging partner finishes
     constexpr int XDUMP = NSQ > 2 ? NSQ - 2 : 0;      // ... of which so many wait in x buffer 1: [4 x 1 KiB patches][4 waves x XDUMP x 4 KiB]
     static_assert(4096 + 4 * XDUMP * 4096 <= XBYTES, "tile-end scratch inside x buffer 1");
@@ -291,98 +290,6 @@ __global__ __launch_bounds__(512, 2) void conv_f16x2_kernel(const ConvParams p, 
             }
         };
 
-
-        if constexpr (PRO == PRO_PRESPLIT) {
-            // ---- pre-split input (presplit.hip): affine, SiLU and the f16 split were applied ONCE, by a pre-pass that wrote the two
-            // planes as [b][chunk][plane][group][H + 2][W][8 ch]; the x tile of a chunk is NPIECE LDS-DMA pieces of 1 KiB whose lanes
-            // address their own entry (tile row outside the image: the layout's zero rows; azimuth wrap: a lane address).  No pixel
-            // loads, no transform, no LDS writes: ~16 DMA instructions per chunk and wave.  Queue of one iteration:
-            //   D0 [PPW], x(q+1) [PPX] | #1 | D1 [PPW] | #2 | D2 [PPW] | #3        (x(q+1) has three segments to land)
-            static_assert(MRK <= 2 && NRK == 2 && RING == 4, "pre-split input: 64 x 4 and 32 x 4 tiles");
-            constexpr int NENT = NPLK * XPL, NPIECE = (NENT + 63) / 64, PPX = (NPIECE + 3) / 4;
-            const int plane_px = (H + 2) * W;  // 16-byte entries per (plane, group)
-            const unsigned chunk_bytes = (unsigned)(NPL * NG * plane_px) * 16u;
-            int rowent[PPX], colx[PPX];
-            bool live[PPX];
-            unsigned ldsoff[PPX], voff[PPX];
-#pragma unroll
-            for (int i = 0; i < PPX; ++i) {
-                const int pc = wave + 4 * i < NPIECE ? wave + 4 * i : NPIECE - 1;  // (past the end: the last piece again -- uniform vmcnt bookkeeping)
-                const int e = pc * 64 + lane;
-                live[i] = e < NENT;
-                const int ee = live[i] ? e : 0;
-                const int plg = ee / (XR * XS), rem = ee - plg * (XR * XS), r = rem / XS, c = rem - r * XS;
-                rowent[i] = (plg * (H + 2) + r) * W;  // (plane, group, tile row) part; plg = plane * NG + group as in the layout
-                colx[i] = c == XS - 1 ? 0 : c - 1;    // (the dump column: any address)
-                ldsoff[i] = (unsigned)pc * 1024u;
-            }
-            int x_item = 0, x_c = 0;
-            const unsigned char* x_base = nullptr;
-            auto set_x_item = [&](int it) __attribute__((always_inline)) {
-                int cot, b, th, tw;
-                decode(it, cot, b, th, tw);
-                x_base = reinterpret_cast<const unsigned char*>(p.x.p0) + (long)b * p.x.bs0 * 4;
-#pragma unroll
-                for (int i = 0; i < PPX; ++i) {
-                    int gc = tw * TW + colx[i];
-                    if (gc < 0) gc += W;
-                    if (gc >= W) gc -= W;  // azimuth is periodic
-                    voff[i] = (unsigned)(rowent[i] + th * TH * W + gc) * 16u;
-                }
-            };
-            auto dma_x = [&](int buf) __attribute__((always_inline)) {  // the cursor's chunk -> x buffer `buf`; advances the cursor
-                const unsigned long long sv = (unsigned long long)(x_base + (size_t)x_c * chunk_bytes);
-                const unsigned char* src = (const unsigned char*)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(sv >> 32)) << 32) |
-                                                                  (unsigned)__builtin_amdgcn_readfirstlane((int)sv));
-                const unsigned l0 = lds0 + (unsigned)buf * XBYTES;
-#pragma unroll
-                for (int i = 0; i < PPX; ++i)
-                    if (live[i])
-                        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff[i]), "s"(src), "s"(l0 + ldsoff[i]) : "memory", "m0");
-                if (x_c + 1 < nchunks)
-                    ++x_c;
-                else if (x_item + 1 < nIt) {
-                    x_c = 0;
-                    set_x_item(++x_item);
-                }  // (past the end: the last chunk again, into the buffer nobody reads)
-            };
-            set_x_item(0);
-            set_dma_item(0);
-            dma_stage(0, ic<0>{});
-            dma_stage(0, ic<1>{});
-            dma_stage(0, ic<2>{});
-            dma_x(0);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();  // P
-            asm volatile("" ::: "memory");
-            constexpr int N12 = 2 * PPW + PPX, N3 = 2 * PPW;  // younger operations when the stage due at #1 / #2, at #3 (with x(q+1)) must have landed
-            for (int q = 0; q < Q; ++q) {
-                dma_stage(3 * q, ic<3>{});  // D0: stage 3q+3
-                dma_x((q + 1) & 1);         // x(q+1): its buffer was last read in chunk q-1
-                stamp(10);
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N12) : "memory");  // stage 3q+1 landed
-                stamp(11);
-                __builtin_amdgcn_s_barrier();                               // #1
-                stamp(12);
-                asm volatile("" ::: "memory");
-                dma_stage(3 * q, ic<4>{});  // D1
-                stamp(13);
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N12) : "memory");  // stage 3q+2 landed
-                stamp(14);
-                __builtin_amdgcn_s_barrier();                               // #2
-                stamp(15);
-                asm volatile("" ::: "memory");
-                dma_stage(3 * q, ic<5>{});  // D2
-                stamp(16);
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N3) : "memory");   // stage 3q+3 and x(q+1) landed
-                stamp(17);
-                __builtin_amdgcn_s_barrier();                               // #3: publishes x(q+1)
-                stamp(18);
-                asm volatile("" ::: "memory");
-            }
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // nothing may outlive the block
-            return;
-        }
         // Staging units: one aligned quad (8 channels x 4 pixels) of one tile row.  Units 0 .. 32 XR - 1 are the interior quads, the next
         // 4 XR the quads holding a halo column (the three pixels they do not need go to the dump column), anything beyond repeats the
         // last one -- see conv_bf16x3_stream_kernel.  Four-row tiles have 216 units, one per staging thread; the eight-row tile has 360:
@@ -1712,12 +1619,6 @@ template <int MRK, int NRK>
 static hipError_t launch_f2_tile(const ConvParams& p, hipStream_t s) {
     using GEO = f2::Geo<MRK, NRK>;
     const long tiles = (long)(p.Cout / GEO::COT) * (p.W / f2::TW) * (p.H / GEO::TH) * p.B;
-    if constexpr (MRK == 2 && NRK == 2) {  // pre-split input (presplit.hip): 64 x 4 tiles (and 32 x 4 below)
-        if (p.prologue == PRO_PRESPLIT) return p.pieces == 1 ? launch_f2<PRO_PRESPLIT, 1, 2, 2>(p, tiles, s) : launch_f2<PRO_PRESPLIT, 2, 2, 2>(p, tiles, s);
-    }
-    if constexpr (MRK == 1) {
-        if (p.prologue == PRO_PRESPLIT) return p.pieces == 1 ? hipErrorInvalidValue : launch_f2<PRO_PRESPLIT, 2, 1, 2>(p, tiles, s);
-    }
     if (p.pieces == 1) {  // one fp16 product per MAC (the reduced-precision bulk mode)
         const int iom = (p.x16 ? 1 : 0) | (p.y16 ? 2 : 0);  // fp16 storage of the input / of the output and residual
         if (iom) {  // (the residual blocks' convolutions -- GroupNorm + SiLU input -- and the plain-input down- / up-sampling convolutions)
@@ -1753,7 +1654,7 @@ bool conv_f16x2_fold_supported(const ConvParams& p, int groups, int slots) {
     if (!fold_on || groups != 8 || p.Cin % 8 || slots < 1 || slots > 4 * 256) return false;
     const int cpg = p.Cin / 8;
     if (cpg < 8 || cpg > 64 || (cpg & (cpg - 1))) return false;
-    if (!conv_f16x2_supported(p.Cin, p.Cout, p.taps, p.H, p.W, p.co_tile, p.px_rows) || p.prologue == PRO_NONE || p.prologue == PRO_PRESPLIT) return false;
+    if (!conv_f16x2_supported(p.Cin, p.Cout, p.taps, p.H, p.W, p.co_tile, p.px_rows) || p.prologue == PRO_NONE) return false;
     const long tps = (long)(p.Cout / p.co_tile) * (p.W / f2::TW) * (p.H / p.px_rows), tiles = tps * p.B;
     const int n_cu = f2_cu_count();
     if (tiles <= n_cu) return true;  // one tile per block
@@ -1770,10 +1671,9 @@ bool conv_f16x2_fold_supported(const ConvParams& p, int groups, int slots) {
 hipError_t launch_conv_f16x2(const ConvParams& p, hipStream_t s) {
     if (!conv_f16x2_supported(p.Cin, p.Cout, p.taps, p.H, p.W, p.co_tile, p.px_rows)) return hipErrorInvalidValue;
     if (p.x.p1 && p.x.c0 % f2::CK) return hipErrorInvalidValue;  // a chunk must not straddle the concat seam
-    if (p.prologue != PRO_NONE && p.prologue != PRO_PRESPLIT && p.aff == nullptr && p.gn_partial == nullptr) return hipErrorInvalidValue;
+    if (p.prologue != PRO_NONE && p.aff == nullptr && p.gn_partial == nullptr) return hipErrorInvalidValue;
     if ((p.x16 || p.y16) && p.pieces != 1) return hipErrorInvalidValue;  // (fp16 storage exists in the one-plane mode only)
     if (p.gn_partial && (p.aff != nullptr || p.gn_cpg * 8 != p.Cin || !conv_f16x2_fold_supported(p, 8, p.gn_slots))) return hipErrorInvalidValue;
-    if (p.prologue == PRO_PRESPLIT && ((p.co_tile != 64 && p.co_tile != 32) || p.px_rows != 4 || p.x.p1 != nullptr)) return hipErrorInvalidValue;
 #ifndef F2_PROF
     if (p.prof != nullptr) return hipErrorInvalidValue;
 #endif

@@ -226,7 +226,7 @@ int r2dm_set_conv_pieces(r2dm_handle* h, int32_t pieces) {
                        "1 (one fp16 product per MAC: reduced precision)");
     if (h) {
         h->conv_pieces = pieces;
-        h->ws_cache.clear();  // (the walk's allocation sequence depends on the mode -- folded GroupNorms, the pre-pass scratch)
+        h->ws_cache.clear();  // (the walk's allocation sequence depends on the mode -- folded GroupNorms)
     } else
         g_single_kernel_pieces = pieces;
     return 0;

@@ -218,19 +218,19 @@ struct Ctx {
     // What one convolution launch runs on and what it fuses.  choose() decides it from the layer's packings, the precision mode, the prologue, the guard on
     // the input's range, the incoming statistics, the batch and the resolution -- nothing the sizing walk does not know --, so both walks allocate alike;
     // conv() only carries it out.
-    enum NormKind { NORM_NONE, NORM_FOLDED, NORM_PRE_FOLD, NORM_FINALIZE, NORM_STREAMING };
+    enum NormKind { NORM_NONE, NORM_FOLDED, NORM_FINALIZE, NORM_STREAMING };
     struct ConvChoice {
         int algo = ALGO_F32, co_tile = 0, px_rows = 4, pieces = 3;  // the kernel, its tile and its operand pieces
-        // the GroupNorm in front: folded into the convolution's staging waves | into the operand pre-pass | the finalize launch over fused statistics | the
-        // streaming statistics pass (the last two leave `aff` for the prologue)
+        // the GroupNorm in front: folded into the convolution's staging waves | the finalize launch over fused statistics | the streaming statistics pass
+        // (the last two leave `aff` for the prologue)
         NormKind norm = NORM_NONE;
         bool fused_stats = false;      // the epilogue writes the output's statistics into ConvOpts::sink ...
         bool sink_incomplete = false;  // ... or cannot: the sink's consumer runs the streaming pass
-        // range sites, in the order they are handed out: the folded GroupNorm's output bound (NORM_FOLDED, NORM_PRE_FOLD), then ...
+        // range sites, in the order they are handed out: the folded GroupNorm's output bound (NORM_FOLDED), then ...
         bool track_out = false;        // ... max|output|
         const char* refused = nullptr;  // x16 / y16 asked of a launch that cannot take them: what a real forward reports
     };
-    ConvChoice choose(const ConvLayer& L, const Src& x, int H, int W, const ConvOpts& o) const {
+    ConvChoice choose(const ConvLayer& L, int H, int W, const ConvOpts& o) const {
         ConvChoice c;
         // the fp16 split where the input's range is guarded: GroupNorm-normalised (gn_finalize's bound) or tracked by its producer (fir_up2's running maximum)
         const bool guarded = h->f16_path() && (o.prologue != PRO_NONE || o.input_bounded);
@@ -248,13 +248,6 @@ struct Ctx {
                 bool fold = true;  // (whichever direction this launch will walk its tiles in: that is the walk's state, not the choice's)
                 for (q.reverse = 0; q.reverse < 2; ++q.reverse) fold = fold && conv_f16x2_fold_supported(q, G, k.read_slots());
                 if (fold) c.norm = NORM_FOLDED;
-                // Round 6 EXPERIMENT, off by default (R2DM_F2_PRESPLIT_NARROW=1): the launches on 32-channel tiles (u_block4: eight output-channel tiles stage the
-                // same x tile, the stagers bound a chunk at 4.5 k cycles for 1.7 k of MFMAs) take their input through the operand pre-pass with the GroupNorm
-                // folded into THAT pass (presplit_fold_kernel): bit-identical; the convolutions go 43.8 -> 28.7 us and 78.3 -> 51.7 us, and the six 12.4 us passes
-                // (a launch + three dependent round trips over an 8 MB tensor) take it all back: step 5.894 | 5.895 ms (profiles/r06_narrow_presplit.txt).
-                // (=2: also the 512 -> 512 launches of level 4 on 64-channel tiles, eight output-channel tiles per x tile as well)
-                const bool narrow_tile = L.f2_cot == 32 || (narrow_presplit() >= 2 && L.f2_cot == 64 && L.cout >= 512);
-                if (narrow_presplit() && narrow_tile && L.f2_rows == 4 && h->conv_pieces == 2 && presplit_supported(x, L.cin, H, W)) c.norm = NORM_PRE_FOLD;
             }
         }
         // (the layer's own kernel decides, whichever packing runs: conv_f16x2 and proj_f16x2 write what the kernel they stand in for writes)
@@ -269,7 +262,7 @@ struct Ctx {
     }
 
     Tensor conv(const ConvLayer& L, const Src& x, int H, int W, const ConvOpts& o) {
-        const ConvChoice c = choose(L, x, H, W, o);
+        const ConvChoice c = choose(L, H, W, o);
         const NormSpec* ns = o.norm;
         const float2* aff = o.aff;
         float2* own_aff = nullptr;
@@ -278,8 +271,6 @@ struct Ctx {
         Tensor y{o.dst, L.cout, H, W, o.y16};
         if (!y.p) y.p = (float*)ar->alloc(y.bytes(B));
         if (c.sink_incomplete) const_cast<Sink*>(o.sink)->incomplete = true;
-        // many output-channel tiles per x tile: the input transform once, by the pre-pass with the GroupNorm folded in (presplit.hip)
-        float* xs = c.norm == NORM_PRE_FOLD ? (float*)ar->alloc((size_t)presplit_floats(B, L.cin, H, W) * sizeof(float)) : nullptr;
         if (!skip()) {
             ConvParams p = conv_params(x, blob(L.w), blob(L.b), y.p, y.bs(), B, H, W, L.cin, L.cin_pad, L.cout, L.taps, c.co_tile, c.algo, o.prologue);
             p.px_rows = c.px_rows;
@@ -301,27 +292,18 @@ struct Ctx {
                 p.w = blob(L.w_p1);
                 p.wscale = blob(L.ws_p1) + 1;
             }
-            if (c.norm == NORM_FOLDED || c.norm == NORM_PRE_FOLD) {
+            if (c.norm == NORM_FOLDED) {
                 const Sink& k = *ns->stats;
-                int* site = range_site(xs ? "GroupNorm output bound |a| M + |d| (folded into the operand pre-pass)" : "GroupNorm output bound |a| M + |d| (folded into the convolution)");
-                if (xs) {
-                    run("presplit_fold", xs, [&] {
-                        return launch_presplit_fold(x, o.prologue, xs, B, L.cin, H, W, k.p, k.slots, k.read_slots(), k.cpg, h->cfg.gn_eps, ns->gamma, ns->beta, ns->ada, (long)h->ada_rows, site, st);
-                    });
-                    p.x = Src{xs, nullptr, L.cin, 0, presplit_floats(1, L.cin, H, W), 0};
-                    p.prologue = PRO_PRESPLIT;
-                } else {
-                    p.gn_partial = k.p;
-                    p.gn_stride = k.slots;
-                    p.gn_slots = k.read_slots();
-                    p.gn_cpg = k.cpg;
-                    p.gn_eps = h->cfg.gn_eps;
-                    p.gn_gamma = ns->gamma;
-                    p.gn_beta = ns->beta;
-                    p.gn_ada = ns->ada;
-                    p.gn_ada_stride = (long)h->ada_rows;
-                    p.gn_range = site;
-                }
+                p.gn_partial = k.p;
+                p.gn_stride = k.slots;
+                p.gn_slots = k.read_slots();
+                p.gn_cpg = k.cpg;
+                p.gn_eps = h->cfg.gn_eps;
+                p.gn_gamma = ns->gamma;
+                p.gn_beta = ns->beta;
+                p.gn_ada = ns->ada;
+                p.gn_ada_stride = (long)h->ada_rows;
+                p.gn_range = range_site("GroupNorm output bound |a| M + |d| (folded into the convolution)");
             }
             if (c.track_out) p.range = range_site("max|output| (raw input of the next fp16-operand kernel)");
             if (c.fused_stats) conv_stat_sink(p, o.sink->p, h->cfg.gn_num_groups, o.goff, o.sink->cpg, o.sink->slots);
@@ -336,7 +318,6 @@ struct Ctx {
             run("conv", y.p, [&] { return launch_conv(p, st); }, &p);
             if (e1) (void)hipEventRecord(e1, st);
         }
-        if (xs) ar->release(xs);  // (stream-ordered: the next user of that memory is enqueued behind this convolution)
         if (own_aff) ar->release(own_aff);
         return y;
     }
@@ -349,10 +330,6 @@ struct Ctx {
     bool act16(const ConvLayer& L) const {
         static const bool on = !getenv("R2DM_FP16_STORAGE") || atoi(getenv("R2DM_FP16_STORAGE")) != 0;
         return on && h->conv_pieces == 1 && L.f2 && !(L.f2_cot == 32 && narrow_split());
-    }
-    static int narrow_presplit() {
-        const char* e = getenv("R2DM_F2_PRESPLIT_NARROW");  // (read per call, like R2DM_GN_FOLD: the bit-identity test builds one model per setting)
-        return e ? atoi(e) : 0;
     }
     // (experiment switch, round 5) layers packed for the 32-channel tile run the two-plane kernel in every precision mode
     static bool narrow_split() {

@@ -38,7 +38,7 @@ struct ConvExtras {
     int32_t* chosen = nullptr;  // HOST int32[3] <- algo, co_tile, px_rows
 };
 
-// One convolution launch on caller-provided tensors: the algorithm and tile selection, the packing, and the IO16 / pre-pass test hooks of the
+// One convolution launch on caller-provided tensors: the algorithm and tile selection, the packing, and the IO16 test hook of the
 // single-kernel entries.  Every combination a launcher would refuse, ignore or run past the caller's buffers is refused HERE, before the first
 // launch: nothing is written then.
 static int conv2d_ring_impl(const float* x, const float* w, const float* bias, float* w_packed, const float* aff, int32_t prologue, const float* residual,
@@ -130,24 +130,6 @@ static int conv2d_ring_impl(const float* x, const float* w, const float* bias, f
     }
     // perf probe (scripts/conv_phases.py): per-block s_memtime stamps into a caller-provided device buffer
     if (const char* e = getenv("R2DM_CONV_PROF_PTR")) p.prof = (unsigned long long*)strtoull(e, nullptr, 0);
-    // per-kernel tests / probes of the operand pre-pass (presplit.hip + conv_f16x2's PRO_PRESPLIT stagers): R2DM_F2_PRESPLIT=1
-    float* xs = nullptr;
-    if (const char* e = getenv("R2DM_F2_PRESPLIT"); e && atoi(e) && p.algo == ALGO_F16X2 && p.co_tile == 64 && p.px_rows == 4 && presplit_supported(p.x, cin, H, W)) {
-        static float* scratch = nullptr;  // (test entry: one growing scratch buffer, never freed)
-        static size_t scratch_floats = 0;
-        const size_t need = (size_t)presplit_floats(B, cin, H, W);
-        if (need > scratch_floats) {
-            HIP_TRY(hipDeviceSynchronize());
-            if (scratch) HIP_TRY(hipFree(scratch));
-            HIP_TRY(hipMalloc(&scratch, need * sizeof(float)));
-            scratch_floats = need;
-        }
-        xs = scratch;
-        HIP_TRY(launch_presplit(p.x, p.aff, prologue, xs, B, cin, H, W, st));
-        p.x = Src{xs, nullptr, cin, 0, presplit_floats(1, cin, H, W), 0};
-        p.prologue = PRO_PRESPLIT;
-        p.aff = nullptr;
-    }
     HIP_TRY(launch_conv(p, st));
     return 0;
 }

@@ -1,11 +1,11 @@
 # Sourced by build.sh and scripts/build_variant.sh: the translation units of libr2dm_hip.so, the headers they depend on and the flags each gets.
-R2DM_SOURCES="conv_mfma conv_bf16x3 conv_f16x2 proj_f16x2 presplit conv_direct norm resample attention embed posterior metrics render projection pointcloud pointnet rangenet postproc completion geometry emd plan forward engine ops_abi kernel_abi"
+R2DM_SOURCES="conv_mfma conv_bf16x3 conv_f16x2 proj_f16x2 conv_direct norm resample attention embed posterior metrics render projection pointcloud pointnet rangenet postproc completion geometry emd plan forward engine ops_abi kernel_abi"
 R2DM_HEADERS="common.h conv_epilogue.h conv_bf16x3.h f16x2.h wave_ops.h gn_math.h engine.h ../../include/r2dm_hip.h"
 R2DM_FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-inline-asm"
 # flags of source $1 beyond R2DM_FLAGS (the engine's host files -- plan, forward, engine, ops_abi, kernel_abi -- get none)
 r2dm_extra_flags() {
   local extra=""
-  case $1 in conv_bf16x3*|conv_f16x2|proj_f16x2|presplit|pointnet|rangenet|postproc) extra="-fno-slp-vectorize";; esac  # packed f32 VALU next to MFMAs is an anti-lever
+  case $1 in conv_bf16x3*|conv_f16x2|proj_f16x2|pointnet|rangenet|postproc) extra="-fno-slp-vectorize";; esac  # packed f32 VALU next to MFMAs is an anti-lever
   # Round 5: NO packed-fp32 instruction selection in the kernels that share CUs and whose packed instructions would take SGPR operands (attention, in_conv /
   # out_conv, the FIR resamplers, the posterior): a v_pk_mul / v_pk_fma_f32 with an SGPR-pair source read wrong values in lanes 48-63 whenever the wave shared its
   # CU with an LDS-holding workgroup of ANOTHER PROCESS (profiles/r05_coresidency.txt: the root of the "wrong next to a second process" family).  Costs nothing

@@ -23,9 +23,8 @@ DEFAULT = (64, 1024)
 GEOMETRIES = [(DEFAULT, 8, 1), (DEFAULT, 8, 2), (DEFAULT, 8, 4), (DEFAULT, 8, 8), (DEFAULT, 1, 1), (DEFAULT, 2, 2), (DEFAULT, 4, 4), (DEFAULT, 32, 32),
               ((128, 2048), 2, 2), ((32, 256), 3, 3)]
 # every documented switch that alters the walk, at the default geometry and batch 8
-SWITCHES = [("R2DM_DOWN_GEMM", "0"), ("R2DM_DOWN_GEMM", "9"), ("R2DM_GN_FOLD", "0"), ("R2DM_F2_PRESPLIT_NARROW", "1"), ("R2DM_F2_PRESPLIT_NARROW", "2"),
-            ("R2DM_FP16_STORAGE", "0"), ("R2DM_FP16_STORAGE", "1"), ("R2DM_F2_NARROW", "0"), ("R2DM_F2_NARROW_SPLIT", "1"), ("R2DM_FIR_STATS", "0"),
-            ("R2DM_CONV_ALGO", "f32")]
+SWITCHES = [("R2DM_DOWN_GEMM", "0"), ("R2DM_DOWN_GEMM", "9"), ("R2DM_GN_FOLD", "0"), ("R2DM_FP16_STORAGE", "0"), ("R2DM_FP16_STORAGE", "1"),
+            ("R2DM_F2_NARROW", "0"), ("R2DM_F2_NARROW_SPLIT", "1"), ("R2DM_FIR_STATS", "0"), ("R2DM_CONV_ALGO", "f32")]
 FULL = {(DEFAULT, 8, 8)}  # stored line by line
 
 

@@ -27,7 +27,7 @@ def regenerated():
 def test_the_fixture_covers_every_geometry_mode_and_switch(fixture):
     want = {M.case_name(res, mb, b, mode) for res, mb, b in M.GEOMETRIES for mode in M.MODES}
     want |= {M.case_name(M.DEFAULT, 8, 8, mode, sw) for sw in M.SWITCHES for mode in M.MODES}
-    assert set(fixture) == want and len(want) == 3 * (10 + 11)
+    assert set(fixture) == want and len(want) == 3 * (10 + 9)
     for mode in M.MODES:
         assert "listing" in fixture[M.case_name(M.DEFAULT, 8, 8, mode)]
 
@@ -43,7 +43,7 @@ def test_every_listing_is_the_recorded_one(fixture, regenerated):
 
 
 def test_every_line_names_its_layer_launch_and_output(fixture):
-    launches = {"time_embedding", "ada_proj", "in_conv constant map", "group_norm", "group_norm_finalize", "presplit_fold", "conv", "attention", "fir_down2",
+    launches = {"time_embedding", "ada_proj", "in_conv constant map", "group_norm", "group_norm_finalize", "conv", "attention", "fir_down2",
                 "fir_up2", "down_planes", "down_phase_planes", "down_gemm"}
     for mode in M.MODES:
         lines = fixture[M.case_name(M.DEFAULT, 8, 8, mode)]["listing"]

@@ -510,7 +510,8 @@ def test_environment_switches_are_the_documented_set():
     assert in_lib == {n for n, who in rows if who == "library"}, sorted(in_lib ^ {n for n, who in rows if who == "library"})
     assert in_python == {n for n, who in rows if who == "Python"}, sorted(in_python ^ {n for n, who in rows if who == "Python"})
     removed = {"R2DM_RANGE_SHARED", "R2DM_F2_PRESPLIT_MIN_COUT", "R2DM_TILE_ORDER", "R2DM_PROJ_ORDER", "R2DM_F2_WIDE_MAX_CIN", "R2DM_F2_TALL",
-               "R2DM_F2_LDS_EXACT", "R2DM_F2_NONPERSISTENT", "R2DM_F2_STAGGER", "R2DM_PROJ_TALL", "R2DM_F2_MIN_TILES", "R2DM_DEBUG_FIXED_NOISE"}
+               "R2DM_F2_LDS_EXACT", "R2DM_F2_NONPERSISTENT", "R2DM_F2_STAGGER", "R2DM_PROJ_TALL", "R2DM_F2_MIN_TILES", "R2DM_DEBUG_FIXED_NOISE",
+               "R2DM_F2_PRESPLIT", "R2DM_F2_PRESPLIT_NARROW"}
     assert not removed & (in_lib | in_python)
 
 
