@@ -295,6 +295,13 @@ size_t poly_mmd_scratch_bytes(int subsets, int m);
 hipError_t launch_poly_mmd(const float* X, const float* Y, const long long* ix, const long long* iy, int subsets, int m, int D, void* scratch,
                            double* out, hipStream_t s);
 
+// Fragment-order weight packing of the split arithmetic (f16x2.h) for the kernels that read their A operand straight from global memory -- PointNet's
+// layers 2 and 3, every RangeNet layer (the kernel is in rangenet.hip): (Cout, taps, Cin) fp32 -> [chunk of 32 rows][tap][k-step of 16][plane h / l][lane]
+// [8 halves], Cout padded to 32 and Cin to 16 with zeros, scaled by a power of two; wscale[0] <- bits of max|w|, [1] <- the inverse scale;
+// *flag |= PACK_FLAG_WEIGHT for a weight that is not finite.  dst holds ceil(Cout / 32) taps ceil(Cin / 16) 2048 bytes.
+constexpr int PACK_FLAG_WEIGHT = 4;
+hipError_t launch_pack_frag_f16x2(const float* w, int Cout, int Cin, int taps, void* dst, float* wscale, int* flag, hipStream_t s);
+
 // PointNet feature extractor of the FPD (pointnet.hip): weight packing, the fused trunk (layout 0 (B,5,H,W) samples, 1 (B,N,3), 2 (B,3,N)), the per-cloud MLPs
 hipError_t launch_pointnet_pack(const float* w, int Cout, int Cin, void* dst, float* wscale, int* flag, hipStream_t s);
 size_t pointnet_scratch_bytes(int B);

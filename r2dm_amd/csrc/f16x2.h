@@ -49,6 +49,18 @@ __device__ __forceinline__ void split_f16x2(float v0, float v1, unsigned& ph, un
     pl = __builtin_bit_cast(unsigned, l);
 }
 
+// One 16-value k-step of the split product a b for a 32 x 32 tile: the cross products ah bl, then al bh, into acl (scale 2^-11), then ah bh into acc --
+// in this order wherever the step is used (proj_f16x2.hip, pointnet.hip, rangenet.hip).  ONE_PLANE: the h planes alone; al, bl and acl are not touched.
+// (attention.hip issues its cross products l h first and conv_f16x2.hip schedules its stream by hand: neither uses this.)
+template <bool ONE_PLANE = false>
+__device__ __forceinline__ void mfma_f16x2(f32x16& acc, f32x16& acl, const f16x8& ah, const f16x8& al, const f16x8& bh, const f16x8& bl) {
+    if constexpr (!ONE_PLANE) {
+        acl = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acl, 0, 0, 0);
+        acl = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acl, 0, 0, 0);
+    }
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc, 0, 0, 0);
+}
+
 // the same split with the residual at its TRUE scale, l = RNE_f16(v - h): what a single accumulator needs (all three products
 // of x w = xh wh + xh wl + xl wh + O(2^-22) on one scale).  l leaves the fp16 normals below |v| ~ 2^-3 and is then exact to 2^-25
 // absolute: O(1) activations keep ~2^-25 of absolute precision (fp32: 2^-24 relative), weights are pre-scaled per layer

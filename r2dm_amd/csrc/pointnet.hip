@@ -15,7 +15,8 @@
 //                         A non-finite coordinate or an activation outside the fp16 operand range raises bits of *flag.
 //  pointnet_head_kernel   the per-cloud MLPs 1024 -> 512 -> 256 -> 9 (+ identity: the spatial transformer) and 1024 -> 512 -> 256 -> 16
 //                         (the classifier head; writes cat(x1, x2, x3, x4), 1808 values), fp32 FMA, one block per cloud.
-//  pointnet_pack_kernel   (Cout, Cin) fp32 -> the A-operand fragment order [32 rows][16 k][plane h / l][lane][8 halves].
+//  weights                (Cout, Cin) fp32 -> the A-operand fragment order [32 rows][16 k][plane h / l][lane][8 halves]: pack_frag_f16x2_kernel
+//                         (rangenet.hip) with one tap; Cout is a multiple of 32 and Cin of 16, so nothing is padded.
 #include "common.h"
 #include "f16x2.h"
 
@@ -34,7 +35,7 @@ constexpr int OFF_W1 = OFF_W2 + W2B;          // 64 x (w0, w1, w2, bias)
 constexpr int OFF_B2 = OFF_W1 + C1 * 16;
 constexpr int OFF_MAX = OFF_B2 + C2 * 4;      // the block's running maxima
 constexpr int LDS = OFF_MAX + C3 * 4;         // 108 032 bytes: one block per CU
-constexpr int FLAG_COORD = 1, FLAG_RANGE = 2, FLAG_WEIGHT = 4;
+constexpr int FLAG_COORD = 1, FLAG_RANGE = 2;  // (4: PACK_FLAG_WEIGHT, the packer's)
 }  // namespace pn
 
 struct PointNetTrunk {
@@ -141,9 +142,7 @@ __global__ __launch_bounds__(pn::THREADS) void pointnet_trunk_kernel(const Point
             for (int m = 0; m < 2; ++m) {
                 const int f = (((half * 2 + m) * (C1 / 16) + ks) * 2) * 64 + lane;
                 const f16x8 wh = __builtin_bit_cast(f16x8, w2s[f]), wl = __builtin_bit_cast(f16x8, w2s[f + 64]);
-                acl[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xl, acl[m], 0, 0, 0);
-                acl[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, xh, acl[m], 0, 0, 0);
-                acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xh, acc[m], 0, 0, 0);
+                mfma_f16x2(acc[m], acl[m], wh, wl, xh, xl);
             }
         }
         __syncthreads();  // the previous tile's layer 3 has read its activations
@@ -199,9 +198,7 @@ __global__ __launch_bounds__(pn::THREADS) void pointnet_trunk_kernel(const Point
                     for (int nn = 0; nn < 2; ++nn) {
                         const f16x8 xh = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(xr + nn * 32 * ROW3 + ks * 32));
                         const f16x8 xl = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(xr + H2PL + nn * 32 * ROW3 + ks * 32));
-                        l3[nn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xl, l3[nn], 0, 0, 0);
-                        l3[nn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, xh, l3[nn], 0, 0, 0);
-                        a3[nn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xh, a3[nn], 0, 0, 0);
+                        mfma_f16x2(a3[nn], l3[nn], wh, wl, xh, xl);
                     }
                 }
 #pragma unroll
@@ -282,35 +279,9 @@ __global__ __launch_bounds__(256) void pointnet_head_kernel(const PointNetHead p
     }
 }
 
-__global__ void pointnet_pack_kernel(const float* __restrict__ w, unsigned* __restrict__ dst, int Cout, int Cin, long pairs,
-                                     int* __restrict__ flag, float* __restrict__ wscale) {
-    f16_saturate_mode();
-    float inv = 1.0f;
-    const float ws = f16x2_weight_scale(reinterpret_cast<const int*>(wscale)[0], &inv);
-    if (blockIdx.x == 0 && threadIdx.x == 0) wscale[1] = inv;
-    const int nks = Cin / 16;
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < pairs; i += (long)gridDim.x * blockDim.x) {
-        const int j2 = (int)(i & 3), lane = (int)((i >> 2) & 63);
-        const long rest = i >> 8;
-        const int ks = (int)(rest % nks), mc = (int)(rest / nks);
-        const int row = mc * 32 + (lane & 31), k = ks * 16 + (lane >> 5) * 8 + 2 * j2;
-        const float v0 = w[(long)row * Cin + k] * ws, v1 = w[(long)row * Cin + k + 1] * ws;
-        if (!(fabsf(v0) < 65504.f) || !(fabsf(v1) < 65504.f)) atomicOr(flag, pn::FLAG_WEIGHT);
-        unsigned ph, pl;
-        split_f16x2(v0, v1, ph, pl);
-        const long base = (((long)mc * nks + ks) * 2) * 256 + lane * 4 + j2;
-        dst[base] = ph;
-        dst[base + 256] = pl;
-    }
-}
-
 hipError_t launch_pointnet_pack(const float* w, int Cout, int Cin, void* dst, float* wscale, int* flag, hipStream_t s) {
     if (Cout < 32 || Cout % 32 || Cin < 16 || Cin % 16) return hipErrorInvalidValue;
-    hipError_t e = launch_weight_absmax(w, (long)Cout * Cin, reinterpret_cast<int*>(wscale), s);
-    if (e != hipSuccess) return e;
-    const long pairs = (long)Cout * Cin / 2;
-    pointnet_pack_kernel<<<(unsigned)((pairs + 255) / 256), 256, 0, s>>>(w, static_cast<unsigned*>(dst), Cout, Cin, pairs, flag, wscale);
-    return hipGetLastError();
+    return launch_pack_frag_f16x2(w, Cout, Cin, 1, dst, wscale, flag, s);
 }
 
 size_t pointnet_scratch_bytes(int B) { return (size_t)B * pn::C3 * sizeof(int); }

@@ -20,8 +20,9 @@
 //                         skip), fp32 NCHW.  BatchNorm is folded into weights and bias on the host.  A wave sums its k-steps in a fixed
 //                         order and no value is shared between pixels: the same bits on every call and for every batch.
 //                         *flag |= 1 for a non-finite value of an unmasked input pixel, |= 2 for an activation outside the fp16 operand range.
-//  rangenet_pack_kernel   (Cout, taps, Cin) fp32 -> [chunk of 32 rows][tap][k-step of 16][plane h / l][lane][8 halves], Cout padded to 32 and
+//  pack_frag_f16x2_kernel (Cout, taps, Cin) fp32 -> [chunk of 32 rows][tap][k-step of 16][plane h / l][lane][8 halves], Cout padded to 32 and
 //                         Cin to 16 with zeros, scaled by a power of two (max|w| into [2^9, 2^10)).  *flag |= 4 for a non-finite weight.
+//                         PointNet's layers 2 and 3 are packed by it too (one tap, no padding): launch_pack_frag_f16x2 in common.h.
 //  rangenet_argmax_kernel (B,C,H,W) logits -> (B,1,H,W) int64 labels, the lowest index on a tie.
 #include "common.h"
 #include "f16x2.h"
@@ -33,7 +34,7 @@ using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 namespace rn {
 constexpr int THREADS = 256, WAVES = 4, PIX = 32;  // a block: 4 waves x 32 pixels
 constexpr int MAX_TAPS = 9;
-constexpr int FLAG_INPUT = 1, FLAG_RANGE = 2, FLAG_WEIGHT = 4;
+constexpr int FLAG_INPUT = 1, FLAG_RANGE = 2;  // (4: PACK_FLAG_WEIGHT, the packer's)
 }  // namespace rn
 
 struct RangeNetConv {
@@ -113,9 +114,7 @@ __global__ __launch_bounds__(rn::THREADS) void rangenet_conv_kernel(const RangeN
             for (int m = 0; m < MC; ++m) {
                 const long f = ((((long)(mc0 + m) * p.ntaps + t) * p.nks + ks) * 2) * 64 + lane;
                 const f16x8 wh = __builtin_bit_cast(f16x8, p.wp[f]), wl = __builtin_bit_cast(f16x8, p.wp[f + 64]);
-                acl[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xl, acl[m], 0, 0, 0);
-                acl[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, xh, acl[m], 0, 0, 0);
-                acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xh, acc[m], 0, 0, 0);
+                mfma_f16x2(acc[m], acl[m], wh, wl, xh, xl);
             }
         }
     }
@@ -141,8 +140,8 @@ __global__ __launch_bounds__(rn::THREADS) void rangenet_conv_kernel(const RangeN
     if (bad) atomicOr(p.flag, bad);
 }
 
-__global__ void rangenet_pack_kernel(const float* __restrict__ w, unsigned* __restrict__ dst, int Cout, int Cin, int T, int nks, long pairs,
-                                     int* __restrict__ flag, float* __restrict__ wscale) {
+__global__ void pack_frag_f16x2_kernel(const float* __restrict__ w, unsigned* __restrict__ dst, int Cout, int Cin, int T, int nks, long pairs,
+                                       int* __restrict__ flag, float* __restrict__ wscale) {
     f16_saturate_mode();
     float inv = 1.0f;
     const float ws = f16x2_weight_scale(reinterpret_cast<const int*>(wscale)[0], &inv);
@@ -160,7 +159,7 @@ __global__ void rangenet_pack_kernel(const float* __restrict__ w, unsigned* __re
             if (k < Cin) v0 = wr[k] * ws;
             if (k + 1 < Cin) v1 = wr[k + 1] * ws;
         }
-        if (!(fabsf(v0) < 65504.f) || !(fabsf(v1) < 65504.f)) atomicOr(flag, rn::FLAG_WEIGHT);
+        if (!(fabsf(v0) < 65504.f) || !(fabsf(v1) < 65504.f)) atomicOr(flag, PACK_FLAG_WEIGHT);
         unsigned ph, pl;
         split_f16x2(v0, v1, ph, pl);
         const long base = ((((long)mc * T + t) * nks + ks) * 2) * 256 + lane * 4 + j2;
@@ -187,15 +186,21 @@ size_t rangenet_packed_bytes(int Cout, int Cin, int taps) {
     return (size_t)((Cout + 31) / 32 * 32) * taps * ((Cin + 15) / 16 * 16) * 2 * sizeof(_Float16);
 }
 
-hipError_t launch_rangenet_pack(const float* w, int Cout, int Cin, int taps, void* dst, float* wscale, int* flag, hipStream_t s) {
-    if (!rangenet_packed_bytes(Cout, Cin, taps)) return hipErrorInvalidValue;
+hipError_t launch_pack_frag_f16x2(const float* w, int Cout, int Cin, int taps, void* dst, float* wscale, int* flag, hipStream_t s) {
+    if (Cout < 1 || Cin < 1 || taps < 1) return hipErrorInvalidValue;
     hipError_t e = launch_weight_absmax(w, (long)Cout * taps * Cin, reinterpret_cast<int*>(wscale), s);
     if (e != hipSuccess) return e;
-    const long pairs = (long)(rangenet_packed_bytes(Cout, Cin, taps) / 8);
+    const int nks = (Cin + 15) / 16;
+    const long pairs = (long)((Cout + 31) / 32) * taps * nks * 256;  // 32 rows x 16 k / 2 per (chunk, tap, k-step)
     long blocks = (pairs + 255) / 256;
-    if (blocks > 65535) blocks = 65535;
-    rangenet_pack_kernel<<<(unsigned)blocks, 256, 0, s>>>(w, static_cast<unsigned*>(dst), Cout, Cin, taps, (Cin + 15) / 16, pairs, flag, wscale);
+    if (blocks > 65535) blocks = 65535;  // (grid-stride: every pair is written once either way)
+    pack_frag_f16x2_kernel<<<(unsigned)blocks, 256, 0, s>>>(w, static_cast<unsigned*>(dst), Cout, Cin, taps, nks, pairs, flag, wscale);
     return hipGetLastError();
+}
+
+hipError_t launch_rangenet_pack(const float* w, int Cout, int Cin, int taps, void* dst, float* wscale, int* flag, hipStream_t s) {
+    if (!rangenet_packed_bytes(Cout, Cin, taps)) return hipErrorInvalidValue;
+    return launch_pack_frag_f16x2(w, Cout, Cin, taps, dst, wscale, flag, s);
 }
 
 // kind 0: 1 x 1; 1: 3 x 3; 2: 3 x 3 stride (1,2) (Win even); 3 / 4: the even / odd output columns of the transposed 1 x 4 stride (1,2); 5: stem

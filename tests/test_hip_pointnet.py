@@ -10,13 +10,13 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN, GOLDEN_RES, ROOT, synthetic_ckpt
+from conftest import GOLDEN, GOLDEN_RES, ROOT, rnd, synthetic_ckpt
 
 sys.path.insert(0, GOLDEN)
 import make_golden_pointnet as G  # noqa: E402  (the fixture's integer-only input generators)
 import pointnet_oracle as O  # noqa: E402
 
-from r2dm_amd import metrics, pointnet, synthetic  # noqa: E402
+from r2dm_amd import _lib, metrics, pointnet, synthetic  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -130,6 +130,41 @@ def test_shapes_and_error_paths(state, extractor):
     nan["feat.conv3.weight"][5, 7, 0] = float("nan")
     with pytest.raises(ValueError, match="non-finite weight"):
         pointnet.pretrained_pointnet(nan)
+
+
+# ---- weight packing ----------------------------------------------------------------------------
+def _pack(entry, w):
+    """One layer through r2dm_pointnet_pack or r2dm_rangenet_pack (one tap): (packed bytes, wscale as bits, flag)"""
+    L, (cout, cin) = _lib.lib(), w.shape
+    point = entry == "pointnet"
+    nbytes = L.r2dm_pointnet_packed_bytes(cout, cin) if point else L.r2dm_rangenet_packed_bytes(cout, cin, 1)
+    # (a byte the kernel skips keeps its filler, and the two entries' fillers differ)
+    packed = torch.full((nbytes,), 0xA5 if point else 0x5A, dtype=torch.uint8, device="cuda")
+    scale, flag = torch.zeros(2, dtype=torch.float32, device="cuda"), torch.zeros(1, dtype=torch.int32, device="cuda")
+    args = (_lib.ptr(packed), _lib.ptr(scale), _lib.ptr(flag), _lib.stream_ptr(torch.device("cuda")))
+    _lib.check(L.r2dm_pointnet_pack(_lib.ptr(w), cout, cin, *args) if point else L.r2dm_rangenet_pack(_lib.ptr(w), cout, cin, 1, *args))
+    return packed, scale.view(torch.int32), int(flag.item())
+
+
+@pytest.mark.parametrize("cout,cin", [(32, 16), (64, 48), (1024, 128)])
+def test_pointnet_and_rangenet_packers_agree(cout, cin):
+    """The two packing entries share one kernel; where both apply (cout % 32 == 0, cin % 16 == 0, one tap: nothing is padded) they are one
+    function -- size, every packed byte, both wscale words and the flag -- for small, unit and large weights.
+    Weights outside the range: the entries' contract (include/r2dm_hip.h) is "*flag |= 4 if a weight is not finite", which covers both
+    cases checked here -- one +inf (no power-of-two scale brings it into range; the layer's maximum is then not finite and the layer
+    stays unscaled) and one NaN (caught by !(|v| < 65504)).  A large finite weight is no such case: it is rescaled."""
+    L = _lib.lib()
+    assert L.r2dm_pointnet_packed_bytes(cout, cin) == L.r2dm_rangenet_packed_bytes(cout, cin, 1) == cout * cin * 4
+    for seed, s in enumerate((1e-3, 1.0, 300.0)):
+        w = (rnd(700 + seed, cout, cin) * s).cuda()
+        (pp, ps, pf), (rp, rs, rf) = _pack("pointnet", w), _pack("rangenet", w)
+        assert torch.equal(pp, rp) and torch.equal(ps, rs) and pf == rf == 0
+        assert ps[0].item() == w.abs().max().view(torch.int32).item()  # (wscale[0]: the bits of max|w|)
+    for bad in (float("inf"), float("nan")):
+        w = rnd(703, cout, cin)
+        w[cout - 3, cin - 5] = bad
+        (_, _, pf), (_, _, rf) = _pack("pointnet", w.cuda()), _pack("rangenet", w.cuda())
+        assert pf & 4 and rf & 4, (bad, pf, rf)
 
 
 # ---- distribution metrics ----------------------------------------------------------------------
