@@ -93,6 +93,20 @@ static int conv2d_ring_impl(const float* x, const float* w, const float* bias, f
         if (ex.stat_goff < 0 || ex.stat_goff + cout / cpg > ex.stat_G) return fail(1, "conv2d_ring_ex: groups [%d, %d) outside a sink of %d", ex.stat_goff, ex.stat_goff + cout / cpg, ex.stat_G);
         if (test_io16() & 3) return fail(1, "conv2d_ring_ex: no statistics together with the fp16 storage hook");
     }
+    // per-kernel tests of the fp16 activation storage (conv_f16x2.hip, one-plane mode): R2DM_TEST_IO16 = 1 (x holds fp16), 2 (y and the
+    // residual hold fp16) or 3 -- the caller passes tensors of that type behind the float pointers.  (Bit 2 alone: only the kernel selection
+    // above -- the fp32 twin of a storage test.)  What the launchers refuse of it is refused here, before the weights are packed.
+    const int io16 = test_io16() & 3;
+    if (io16) {
+        if (!((algo == ALGO_F16X2 && pieces == 1) || algo == ALGO_DIRECT || (algo == ALGO_P1F16 && pieces == 1)))
+            return fail(1, "R2DM_TEST_IO16: this shape / mode runs on a kernel without fp16 storage");  // (never write a type the caller did not allocate)
+        // proj_f16x2.hip: one fp16-storage instantiation -- fp16 on both sides, raw input, no residual (launch_proj_f16x2)
+        if (algo == ALGO_P1F16 && (io16 != 3 || prologue != PRO_NONE || residual))
+            return fail(1, "R2DM_TEST_IO16 = %d: the fp16-operand 1 x 1 convolution stores fp16 on both sides or on neither, and then takes no prologue and no residual", io16);
+        // conv_direct.hip: the few-input kernel reads fp32 (the network input), the few-output kernel writes fp32 and reads fp16 two channels at a time
+        if (algo == ALGO_DIRECT && (cout > 4 ? (io16 & 1) != 0 : (io16 & 2) != 0 || cin % 2 != 0))
+            return fail(1, "R2DM_TEST_IO16 = %d: the direct kernels store fp16 on the side of the network's interior only", io16);
+    }
     const float* wscale = nullptr;
     if (algo == ALGO_F16X2) {  // the range flag and the weight scale: behind the packed weights (r2dm_conv_packed_elems reserves 64 floats)
         float* tail = w_packed + conv_f16x2_packed_floats(cin, cout);
@@ -120,14 +134,8 @@ static int conv2d_ring_impl(const float* x, const float* w, const float* bias, f
     p.range = ex.range;
     p.reverse = ex.reverse;
     if (ex.stat) conv_stat_sink(p, ex.stat, ex.stat_G, ex.stat_goff, ex.stat_cpg, conv_stat_slots(H, W));
-    // per-kernel tests of the fp16 activation storage (conv_f16x2.hip, one-plane mode): R2DM_TEST_IO16 = 1 (x holds fp16), 2 (y and the
-    // residual hold fp16) or 3 -- the caller passes tensors of that type behind the float pointers
-    if (const char* e = getenv("R2DM_TEST_IO16"); e && (atoi(e) & 3)) {  // (bit 2 alone: only the kernel selection above -- the fp32 twin of a storage test)
-        if (!((p.algo == ALGO_F16X2 && p.pieces == 1) || p.algo == ALGO_DIRECT || (p.algo == ALGO_P1F16 && p.pieces == 1)))
-            return fail(1, "R2DM_TEST_IO16: this shape / mode runs on a kernel without fp16 storage");  // (never write a type the caller did not allocate)
-        p.x16 = atoi(e) & 1;  // (round 6: also the in / out convolutions -- bit 1 / bit 0 -- and, with both bits, the fp16-operand 1 x 1 convolution)
-        p.y16 = (atoi(e) >> 1) & 1;
-    }
+    p.x16 = io16 & 1;  // (round 6: also the in / out convolutions -- bit 1 / bit 0 -- and, with both bits, the fp16-operand 1 x 1 convolution)
+    p.y16 = (io16 >> 1) & 1;
     // perf probe (scripts/conv_phases.py): per-block s_memtime stamps into a caller-provided device buffer
     if (const char* e = getenv("R2DM_CONV_PROF_PTR")) p.prof = (unsigned long long*)strtoull(e, nullptr, 0);
     HIP_TRY(launch_conv(p, st));

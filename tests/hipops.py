@@ -62,9 +62,16 @@ def guarded(shape, dtype, guard, device, fill=float("nan")):
     return whole, whole[guard:guard + n].view(*shape)
 
 
-def guard_intact(whole, guard):
-    """The two bands around a guarded() view still hold their NaN fill."""
-    return bool(torch.isnan(whole[:guard]).all() and torch.isnan(whole[-guard:]).all())
+def guard_intact(whole, guard, fill=float("nan")):
+    """The two bands around a guarded() view still hold their fill (NaN by default)."""
+    return fill_intact(whole[:guard], fill) and fill_intact(whole[-guard:], fill)
+
+
+def fill_intact(t, fill):
+    return bool(torch.isnan(t).all() if fill != fill else (t == fill).all())
+
+
+Y16_CANARY = -60000.0  # the finite fill of a half output and its guard bands: an fp16 number that no test's output reaches
 
 
 class ConvExResult:
@@ -78,28 +85,33 @@ ALGO_F32, ALGO_BF16X3, ALGO_DIRECT, ALGO_F16X2, ALGO_P1F16 = range(5)  # ConvAlg
 
 
 def conv2d_ring_ex(x, w, b, x1=None, aff=None, prologue=0, residual=None, res_broadcast=False, scale=None, stat_groups=0, stat_goff=0, stat_cpg=0,
-                   range_init=None, reverse=0, c1=None):
+                   range_init=None, reverse=0, c1=None, io16=0):
     """r2dm_conv2d_ring_ex: x1 -- the last channels of the input in a second allocation (x holds the first ones; c1 overrides x1's channel
     count, for the refusal tests); stat_groups > 0 -- a statistics sink of that many groups; range_init -- the two int32 the range record
     starts from (None: no record).  y and the sink start NaN-filled inside NaN guard bands (one plane / 64 doubles) that must survive the
-    call; if the entry refuses, y and the sink must still hold nothing but the fill, and the error is raised on."""
+    call; if the entry refuses, y, the sink and the packed-weight buffer (NaN-filled too) must still hold nothing but the fill, and the error
+    is raised on.
+    io16 (with R2DM_TEST_IO16 set to the same value by the caller, as for conv2d_ring): bit 0 -- x and x1 are half tensors (passed as they are
+    if they are already: a guarded view stays where it is), bit 1 -- the residual is half and y is a half tensor; y and its guard bands then
+    start as the finite Y16_CANARY, and no element of y may still hold it after a launch."""
     L = _lib.lib()
     B, c0, H, W = x.shape
     dev = x.device
     cout, k = w.shape[0], w.shape[-1]
-    w, b, x = _lib.f32c(w), _lib.f32c(b), _lib.f32c(x)
+    w, b, x = _lib.f32c(w), _lib.f32c(b), _io(x, io16)
     if x1 is not None:
-        x1 = _lib.f32c(x1)
+        x1 = _io(x1, io16)
     cin = w.shape[1]
     if c1 is None:
         c1 = 0 if x1 is None else x1.shape[1]
         assert c0 + c1 == cin
     if residual is not None:
-        residual = _lib.f32c(residual)
+        residual = residual.detach().half().contiguous() if io16 & 2 else _lib.f32c(residual)
         assert residual.shape == ((cout, H, W) if res_broadcast else (B, cout, H, W))
-    packed = torch.empty(L.r2dm_conv_packed_elems(cout, cin, k, B, H, W), device=dev)
+    packed = torch.full((L.r2dm_conv_packed_elems(cout, cin, k, B, H, W),), float("nan"), device=dev)  # (a refusal comes before the weights are packed)
     yg = (H * W + 63) // 64 * 64  # one plane, in whole 256-byte lines (the kernels store 16-byte vectors)
-    y_all, y = guarded((B, cout, H, W), torch.float32, yg, dev)
+    fill = Y16_CANARY if io16 & 2 else float("nan")
+    y_all, y = guarded((B, cout, H, W), torch.float16 if io16 & 2 else torch.float32, yg, dev, fill=fill)
     st_all = stat = None
     if stat_groups:
         st_all, stat = guarded((B, stat_groups, L.r2dm_conv_stat_slots(H, W), 2), torch.float64, 64, dev)
@@ -111,10 +123,12 @@ def conv2d_ring_ex(x, w, b, x1=None, aff=None, prologue=0, residual=None, res_br
                                ctypes.addressof(chosen), B, cin, cout, H, W, k, _st(x))
     torch.cuda.synchronize()
     if rc != 0:
-        assert torch.isnan(y_all).all() and (st_all is None or torch.isnan(st_all).all()), "a refused launch wrote to y or to the sink"
+        assert fill_intact(y_all, fill) and (st_all is None or torch.isnan(st_all).all()), "a refused launch wrote to y or to the sink"
         assert rng is None or rng.tolist() == list(range_init), "a refused launch wrote to the range record"
+        assert torch.isnan(packed).all(), "a refused launch wrote to the packed weights"
         _lib.check(rc)
-    assert guard_intact(y_all, yg), "write outside y"
+    assert guard_intact(y_all, yg, fill), "write outside y"
+    assert not io16 & 2 or not bool((y == Y16_CANARY).any()), "an output element was not written"
     assert st_all is None or guard_intact(st_all, 64), "write outside the statistics sink"
     return ConvExResult(y, stat, None if rng is None else rng.cpu(), tuple(chosen))
 
@@ -179,6 +193,41 @@ def fir_down2_stats(x, groups, io16=0):
     stat = torch.full((B, groups, slots, 2), float("nan"), device=x.device, dtype=torch.float64)
     _lib.check(_lib.lib().r2dm_fir_down2_stats(x.data_ptr(), y.data_ptr(), stat.data_ptr(), B, C, groups, H, W, _st(x)))
     torch.cuda.synchronize()
+    return y, stat
+
+
+def down_planes(x):
+    """resample.hip's down_planes_kernel: the nine FIR planes of every channel, (B, 9 C, H / 2, W / 2)."""
+    B, C, H, W = x.shape
+    x = _lib.f32c(x)
+    a = torch.full((B, 9 * C, H // 2, W // 2), float("nan"), device=x.device)
+    _lib.check(_lib.lib().r2dm_down_planes(x.data_ptr(), a.data_ptr(), B, C, H, W, _st(x)))
+    torch.cuda.synchronize()
+    return a
+
+
+def down_gemm(x, w, b, groups=0, nine=False):
+    """(y, stat): Resample(down=2)(Conv3x3(x)) through the pre-pass and the GEMM -- r2dm_down_gemm (every distinct plane stored once), or, `nine`,
+    r2dm_down_gemm_nine (all nine planes); stat (B, groups, slots, 2) float64 or None.  y starts NaN-filled between NaN guard bands of one plane that must
+    survive the call."""
+    L = _lib.lib()
+    B, cin, H, W = x.shape
+    cout = w.shape[0]
+    x, w, b = _lib.f32c(x), _lib.f32c(w), _lib.f32c(b)
+    packed = torch.empty(9 * cin * cout + 64, device=x.device)
+    planes = torch.empty(B * 9 * cin * (H // 2) * (W // 2), device=x.device)
+    yg = ((H // 2) * (W // 2) + 63) // 64 * 64
+    y_all, y = guarded((B, cout, H // 2, W // 2), torch.float32, yg, x.device)
+    stat = None
+    if groups:
+        slots = L.r2dm_down_gemm_stat_slots(cin, cout, groups, H, W)
+        assert slots > 0
+        stat = torch.full((B, groups, slots, 2), float("nan"), device=x.device, dtype=torch.float64)
+    entry = L.r2dm_down_gemm_nine if nine else L.r2dm_down_gemm
+    _lib.check(entry(x.data_ptr(), w.data_ptr(), b.data_ptr(), packed.data_ptr(), planes.data_ptr(), y.data_ptr(), _lib.ptr(stat),
+                     B, cin, cout, groups, H, W, _st(x)))
+    torch.cuda.synchronize()
+    assert guard_intact(y_all, yg), "write outside y"
     return y, stat
 
 

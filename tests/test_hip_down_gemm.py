@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN_RES, max_abs, rnd, synthetic_ckpt
+from hipops import down_gemm, down_planes  # the ctypes wrappers of the two standalone entry points
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -21,40 +22,6 @@ def O():
     from oracle import r2dm_oracle
 
     return r2dm_oracle
-
-
-# ---- ctypes wrappers of the two standalone entry points ------------------------------------------------------------------------
-def down_planes(x):
-    from r2dm_amd import _lib
-
-    B, C, H, W = x.shape
-    x = _lib.f32c(x)
-    a = torch.full((B, 9 * C, H // 2, W // 2), float("nan"), device=x.device)
-    _lib.check(_lib.lib().r2dm_down_planes(x.data_ptr(), a.data_ptr(), B, C, H, W, _lib.stream_ptr(x.device)))
-    torch.cuda.synchronize()
-    return a
-
-
-def down_gemm(x, w, b, groups=0):
-    """(y, stat): Resample(down=2)(Conv3x3(x)) through the pre-pass and the GEMM; stat (B, groups, slots, 2) float64 or None."""
-    from r2dm_amd import _lib
-
-    L = _lib.lib()
-    B, cin, H, W = x.shape
-    cout = w.shape[0]
-    x, w, b = _lib.f32c(x), _lib.f32c(w), _lib.f32c(b)
-    packed = torch.empty(9 * cin * cout + 64, device=x.device)
-    planes = torch.empty(B * 9 * cin * (H // 2) * (W // 2), device=x.device)
-    y = torch.full((B, cout, H // 2, W // 2), float("nan"), device=x.device)
-    stat = None
-    if groups:
-        slots = L.r2dm_down_gemm_stat_slots(cin, cout, groups, H, W)
-        assert slots > 0
-        stat = torch.full((B, groups, slots, 2), float("nan"), device=x.device, dtype=torch.float64)
-    _lib.check(L.r2dm_down_gemm(x.data_ptr(), w.data_ptr(), b.data_ptr(), packed.data_ptr(), planes.data_ptr(), y.data_ptr(), _lib.ptr(stat),
-                                B, cin, cout, groups, H, W, _lib.stream_ptr(x.device)))
-    torch.cuda.synchronize()
-    return y, stat
 
 
 def planes_fp64(x):
