@@ -202,6 +202,14 @@ def evaluate(args):
     if extractor is not None:  # (evaluate.py:182-187)
         results["pts"]["frechet_distance"] = metrics.compute_frechet_distance(real_feats, gen_feats)
         results["pts"]["squared_mmd"] = metrics.compute_squared_mmd(real_feats, gen_feats, rng=rng())
+    prdc_k = getattr(args, "prdc_k", None)
+    if prdc_k is not None:  # extension: the k-NN manifold metrics of each computed feature group, the real side bounded like the BEV subset
+        sub = torch.tensor(perm, device=device)
+        for group, real_f, gen_f in (("img", real_img, gen_img), ("pts", real_feats, gen_feats)):
+            if real_f is not None and gen_f is not None:
+                results[group].update(metrics.manifold_metrics(real_f[sub], gen_f, k=prdc_k))
+        results["info"]["prdc_k"] = prdc_k
+        results["info"]["prdc_#real"] = len(perm)
     if frd_asked and img_extractor is None:  # (as in the reference, which skips the FRD for such a model)
         no_frd = "img (FRD) is not computed: the checkpoint was trained without reflectance"
         results["info"]["note"] = no_frd if extractor is not None else no_frd + "; pts (FPD) is not computed: it needs the PointNet weights"
@@ -239,6 +247,9 @@ def build_parser():
                              "file; adds img.frechet_distance / img.squared_mmd for a model trained with reflectance")
     parser.add_argument("--mmd_seed", type=int, default=None,
                         help="extension: seed of the squared MMD's subset draws (default: numpy's global state, as the reference)")
+    parser.add_argument("--prdc_k", type=int, default=None,
+                        help="extension: adds precision / recall / density / coverage (k-NN manifolds, k-th nearest other sample) to each "
+                             "computed feature group, against the real subset the BEV metrics take")
     return parser
 
 

@@ -226,7 +226,24 @@ int r2dm_bev_mmd(const float* p, const float* q, int32_t np, int32_t nq, int64_t
  * r2dm_feature_moments: feats (rows,dim) fp32 -> mean (dim,) and unbiased covariance (dim,dim) in fp64, two passes, fixed order.
  * r2dm_poly_mmd: for each of `subsets` subsets, x = rows ix[s] of X and y = rows iy[s] of Y (subset_size int64 indices each, device
  *    memory, in range): out[s] = (sum_ij (x_i.y_j / dim + 1)^3, the same over x x x off the diagonal, over y x y off the diagonal),
- *    fp64 throughout, no subset_size^2 matrix.  scratch: r2dm_poly_mmd_scratch_bytes(), 256-byte aligned. */
+ *    fp64 throughout, no subset_size^2 matrix.  scratch: r2dm_poly_mmd_scratch_bytes(), 256-byte aligned.
+ * r2dm_feature_knn: the primitive of the k-NN manifold metrics (improved precision / recall, density / coverage).  x (m,dim), y (n,dim)
+ *    fp32.  D2(i,j) = max(0, |x_i|^2 + |y_j|^2 - 2 x_i.y_j): every value widened to fp64 first, the norms summed in fp64 in a fixed
+ *    order, the dot product on the fp64 matrix pipe in an order that is fixed per element and independent of the tiling.  For every
+ *    row i over the admissible columns j (all of them; same = 1, which requires y == x and m == n, drops j == i -- by index, so a
+ *    duplicate row is a neighbour at distance 0):
+ *      kth2[i]   the k-th smallest D2 (needs k >= 1);
+ *      min2[i], argmin[i]   the smallest D2 and its column, the lowest column on an equal computed value;
+ *      count[i]  the number of columns with D2 <= y_radius2[j] (needs y_radius2 (n,) fp64; a NaN radius never counts).
+ *    Each output may be NULL.  status: int64[1] of device memory, zeroed by the call, receives the number of rows of x or y (of x
+ *    alone with same = 1) that hold a non-finite value; outputs that depend on such a row are unspecified, every other row's are those
+ *    of a clean call, nothing faults.  chosen: NULL or HOST int32[2] <- the row tiles and the column splits of the launch.
+ *    The same bits on every call, no floating-point atomics; row i's outputs depend neither on the other rows of x nor on the tiling
+ *    or the number of column splits.  No m x n buffer: scratch (r2dm_feature_knn_scratch_bytes; 0 outside the limits) holds the norms
+ *    and, per row and column split, a k-list, a minimum and a count; a second kernel merges the splits in split order.
+ *    Limits: 1 <= dim <= 16384, 1 <= m, n <= 2^20, 0 <= k <= 16, at least k admissible columns; x and y 16-byte aligned when
+ *    dim % 4 == 0, else 4-byte; kth2, min2, y_radius2, scratch and status 8-byte aligned.  A refusal returns 1 and sets
+ *    r2dm_last_error before anything is launched or written.  Nothing is allocated, nothing synchronises. */
 size_t r2dm_pointnet_packed_bytes(int32_t cout, int32_t cin);
 int r2dm_pointnet_pack(const float* w, int32_t cout, int32_t cin, void* packed, float* wscale, int32_t* flag, void* stream);
 size_t r2dm_pointnet_scratch_bytes(int32_t batch);
@@ -240,6 +257,10 @@ int r2dm_feature_moments(const float* feats, int64_t rows, int32_t dim, double* 
 size_t r2dm_poly_mmd_scratch_bytes(int32_t subsets, int32_t subset_size);
 int r2dm_poly_mmd(const float* x, const float* y, const int64_t* ix, const int64_t* iy, int32_t subsets, int32_t subset_size, int32_t dim,
                   void* scratch, size_t scratch_bytes, double* out, void* stream);
+size_t r2dm_feature_knn_scratch_bytes(int64_t m, int64_t n, int32_t dim, int32_t k);
+int r2dm_feature_knn(const float* x, int64_t m, const float* y, int64_t n, int32_t dim, int32_t same, int32_t k, const double* y_radius2, double* kth2,
+                     double* min2, int32_t* argmin, int32_t* count, void* scratch, size_t scratch_bytes, int64_t* status, int32_t* chosen,
+                     void* stream);
 
 /* -- FRD of the evaluation script and the segmentation of completion_demo.py: RangeNet-53 / -21 (metrics/extractor/rangenet.py) in eval
  *    mode, every BatchNorm folded into the layer in front of it by the caller ------------------------------------------------------

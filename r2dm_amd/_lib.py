@@ -127,6 +127,8 @@ SIGNATURES = {
     "r2dm_feature_moments": (c_int32, [_P, c_int64, c_int32, _P, _P, _P]),
     "r2dm_poly_mmd_scratch_bytes": (c_size_t, [c_int32, c_int32]),
     "r2dm_poly_mmd": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, _P, c_size_t, _P, _P]),
+    "r2dm_feature_knn_scratch_bytes": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
+    "r2dm_feature_knn": (c_int32, [_P, c_int64, _P, c_int64, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, _P, c_size_t, _P, POINTER(c_int32), _P]),
     "r2dm_colorize": (c_int32, [_P, _P, _P, c_int64, c_int64, _P]),
     "r2dm_rasterize_scratch_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
     "r2dm_bilinear_rasterize": (c_int32, [_P, _P, _P, c_int32, c_int64, c_int32, c_int32, c_int32, _P, c_size_t, c_int32, _P]),

@@ -295,6 +295,13 @@ size_t poly_mmd_scratch_bytes(int subsets, int m);
 hipError_t launch_poly_mmd(const float* X, const float* Y, const long long* ix, const long long* iy, int subsets, int m, int D, void* scratch,
                            double* out, hipStream_t s);
 
+// k-NN manifold primitives of feature sets (features.hip): per row of x the k-th smallest / smallest (and its column) squared distance to the
+// admissible rows of y and the number of y's balls it falls in, fp64, Gram term on the fp64 matrix pipe; the launch it picks for (m, n)
+void feature_knn_launch_shape(long m, long n, int* row_tiles, int* splits);
+size_t feature_knn_scratch_bytes(long m, long n, int k);
+hipError_t launch_feature_knn(const float* x, long m, const float* y, long n, int dim, int same, int k, const double* y_radius2, double* kth2,
+                              double* min2, int* argmin, int* count, void* scratch, long long* status, hipStream_t s);
+
 // Fragment-order weight packing of the split arithmetic (f16x2.h) for the kernels that read their A operand straight from global memory -- PointNet's
 // layers 2 and 3, every RangeNet layer (the kernel is in rangenet.hip): (Cout, taps, Cin) fp32 -> [chunk of 32 rows][tap][k-step of 16][plane h / l][lane]
 // [8 halves], Cout padded to 32 and Cin to 16 with zeros, scaled by a power of two; wscale[0] <- bits of max|w|, [1] <- the inverse scale;

@@ -124,6 +124,42 @@ int r2dm_poly_mmd(const float* x, const float* y, const int64_t* ix, const int64
     return 0;
 }
 
+static bool knn_geometry_ok(int64_t m, int64_t n, int32_t dim, int32_t k) {
+    return m >= 1 && m <= (1LL << 20) && n >= 1 && n <= (1LL << 20) && dim >= 1 && dim <= 16384 && k >= 0 && k <= 16;
+}
+
+size_t r2dm_feature_knn_scratch_bytes(int64_t m, int64_t n, int32_t dim, int32_t k) {
+    return knn_geometry_ok(m, n, dim, k) ? feature_knn_scratch_bytes(m, n, k) : 0;
+}
+
+int r2dm_feature_knn(const float* x, int64_t m, const float* y, int64_t n, int32_t dim, int32_t same, int32_t k, const double* y_radius2, double* kth2,
+                     double* min2, int32_t* argmin, int32_t* count, void* scratch, size_t scratch_bytes, int64_t* status, int32_t* chosen,
+                     void* stream) {
+    if (!x || !y || !scratch || !status) return fail(1, "feature_knn: null argument");
+    if (dim < 1 || dim > 16384) return fail(1, "feature_knn: dim must be in [1, 16384], got %d", dim);
+    if (m < 1 || m > (1LL << 20) || n < 1 || n > (1LL << 20))
+        return fail(1, "feature_knn: m and n must be in [1, 2^20], got %lld, %lld", (long long)m, (long long)n);
+    if (k < 0 || k > 16) return fail(1, "feature_knn: k must be in [0, 16], got %d", k);
+    if (same != 0 && same != 1) return fail(1, "feature_knn: same must be 0 or 1");
+    if (same && (y != x || m != n)) return fail(1, "feature_knn: same = 1 needs y == x and m == n");
+    if (count && !y_radius2) return fail(1, "feature_knn: count needs y_radius2");
+    if (kth2 && k < 1) return fail(1, "feature_knn: kth2 needs k >= 1");
+    if (n - same < k) return fail(1, "feature_knn: %lld admissible columns, fewer than k = %d", (long long)(n - same), k);
+    const uintptr_t al = dim % 4 == 0 ? 15 : 3;  // rows of a multiple of 4 features are read as quads
+    if (((uintptr_t)x | (uintptr_t)y) & al) return fail(1, "feature_knn: x and y must be %d-byte aligned for dim = %d", (int)al + 1, dim);
+    if (((uintptr_t)kth2 | (uintptr_t)min2 | (uintptr_t)y_radius2 | (uintptr_t)scratch | (uintptr_t)status) & 7)
+        return fail(1, "feature_knn: kth2, min2, y_radius2, scratch and status must be 8-byte aligned");
+    if (((uintptr_t)argmin | (uintptr_t)count) & 3) return fail(1, "feature_knn: argmin and count must be 4-byte aligned");
+    if (scratch_bytes < feature_knn_scratch_bytes(m, n, k))
+        return fail(1, "scratch too small: %zu < %zu bytes", scratch_bytes, feature_knn_scratch_bytes(m, n, k));
+    int row_tiles, splits;
+    feature_knn_launch_shape(m, n, &row_tiles, &splits);
+    HIP_TRY(launch_feature_knn(x, m, y, n, dim, same, k, y_radius2, kth2, min2, argmin, count, scratch, reinterpret_cast<long long*>(status),
+                               (hipStream_t)stream));
+    if (chosen) chosen[0] = row_tiles, chosen[1] = splits;
+    return 0;
+}
+
 size_t r2dm_rangenet_packed_bytes(int32_t cout, int32_t cin, int32_t taps) { return rangenet_packed_bytes(cout, cin, taps); }
 
 int r2dm_rangenet_pack(const float* w, int32_t cout, int32_t cin, int32_t taps, void* packed, float* wscale, int32_t* flag, void* stream) {

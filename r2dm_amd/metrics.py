@@ -15,8 +15,16 @@ And the distribution metrics of feature sets (metrics/distribution.py), which ev
 - ``compute_frechet_distance``: those moments, then the matrix square root on the host in fp64 (scipy), as the reference.
 - ``compute_squared_mmd``: the polynomial-kernel estimator over random subsets drawn on the host as the reference draws them;
   per subset the GPU gathers the rows and sums the three kernel matrices in fp64 without writing them.
+
+And, beyond the reference, the k-NN manifold metrics on the same features (``evaluate.py --prdc_k``):
+
+- ``feature_knn``: per row the k-th smallest / smallest squared distance to another set and the number of that set's balls it falls in,
+  fp64 with the Gram term on the fp64 matrix pipe, no N x M matrix, deterministic.
+- ``knn_radii``, ``manifold_metrics``: improved precision / recall and density / coverage from four such passes.
 """
 from __future__ import annotations
+
+import ctypes
 
 import numpy as np
 import torch
@@ -224,3 +232,94 @@ def compute_squared_mmd(feats1, feats2, num_subsets: int = 100, max_subset_size:
     n1, n2 = len(feats1), len(feats2)
     idx1, idx2 = draw_mmd_subsets(n1, n2, num_subsets, max_subset_size, rng)
     return squared_mmd_from_indices(feats1, feats2, idx1, idx2)
+
+
+# ---- k-NN manifold metrics of feature sets: improved precision / recall, density / coverage ----------------------------------
+_KNN_OUTPUTS = ("kth2", "min2", "argmin", "count")
+
+
+@torch.no_grad()
+def feature_knn(x, y=None, k: int = 0, y_radius2=None, want=_KNN_OUTPUTS, return_launch: bool = False):
+    """Per row ``i`` of ``x`` (m,D) over the rows ``j`` of ``y`` (n,D), with ``D2(i,j) = max(0, |x_i|^2 + |y_j|^2 - 2 x_i.y_j)`` in fp64
+    (the Gram term on the fp64 matrix pipe, no m x n matrix):
+
+    - ``kth2`` (m,) fp64: the k-th smallest ``D2`` (needs ``k >= 1``);
+    - ``min2`` (m,) fp64 and ``argmin`` (m,) int32: the smallest ``D2`` and its row of ``y``, the lowest on an equal value;
+    - ``count`` (m,) int32: the number of ``j`` with ``D2 <= y_radius2[j]`` (needs ``y_radius2`` (n,) fp64).
+
+    ``y=None`` means the same set: ``j == i`` is left out by index, so ``k`` is the k-th nearest *other* sample and a duplicate row is a
+    neighbour at distance 0.  Returns a dict of the outputs named in ``want`` that can be computed; with ``return_launch`` also
+    ``"launch"``: (row tiles, column splits).  Raises ``R2DMError`` on a refusal or when a row of ``x`` or ``y`` holds a non-finite value."""
+    same = y is None
+    fx = _as_feats(x, "x")
+    fy = fx if same else _as_feats(y, "y")
+    if fx.device != fy.device:
+        raise ValueError(f"x on {fx.device}, y on {fy.device}")
+    if fx.shape[1] != fy.shape[1]:
+        raise ValueError(f"features of {fx.shape[1]} and {fy.shape[1]} dimensions")
+    unknown = set(want) - set(_KNN_OUTPUTS)
+    if unknown:
+        raise ValueError(f"unknown outputs {sorted(unknown)}: expected some of {_KNN_OUTPUTS}")
+    (m, d), n, dev = fx.shape, fy.shape[0], fx.device
+    r2 = None
+    if y_radius2 is not None:
+        if isinstance(y_radius2, np.ndarray):
+            y_radius2 = torch.from_numpy(np.ascontiguousarray(y_radius2))
+        r2 = y_radius2.detach().to(device=dev, dtype=torch.float64).contiguous()
+        if r2.shape != (n,):
+            raise ValueError(f"y_radius2 of shape {tuple(r2.shape)}: expected ({n},)")
+    out = {}
+    if "kth2" in want and k >= 1:
+        out["kth2"] = torch.empty(m, dtype=torch.float64, device=dev)
+    if "min2" in want:
+        out["min2"] = torch.empty(m, dtype=torch.float64, device=dev)
+    if "argmin" in want:
+        out["argmin"] = torch.empty(m, dtype=torch.int32, device=dev)
+    if "count" in want and r2 is not None:
+        out["count"] = torch.empty(m, dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    nbytes = L.r2dm_feature_knn_scratch_bytes(m, n, d, int(k))
+    scratch = torch.empty(max(nbytes, 8) // 8 + 1, dtype=torch.float64, device=dev)
+    status = torch.empty(1, dtype=torch.int64, device=dev)
+    chosen = (ctypes.c_int32 * 2)()
+    with torch.cuda.device(dev):
+        _lib.check(L.r2dm_feature_knn(_lib.ptr(fx), m, _lib.ptr(fy), n, d, int(same), int(k), _lib.ptr(r2), _lib.ptr(out.get("kth2")),
+                                      _lib.ptr(out.get("min2")), _lib.ptr(out.get("argmin")), _lib.ptr(out.get("count")), scratch.data_ptr(),
+                                      scratch.numel() * 8, _lib.ptr(status), chosen, _lib.stream_ptr(dev)))
+    bad = int(status.item())
+    if bad:
+        raise _lib.R2DMError(f"feature_knn: {bad} row(s) of the features hold a non-finite value")
+    if return_launch:
+        out["launch"] = (int(chosen[0]), int(chosen[1]))
+    return out
+
+
+def knn_radii(feats, k: int) -> torch.Tensor:
+    """(N,) fp64: per row the squared distance to its k-th nearest *other* row (the ``nearest_k`` of the ``prdc`` package)."""
+    if k < 1:
+        raise ValueError(f"knn_radii needs k >= 1, got {k}")
+    return feature_knn(feats, None, k, want=("kth2",))["kth2"]
+
+
+def manifold_metrics(real, fake, k: int = 5, per_sample: bool = False) -> dict:
+    """Improved precision and recall (Kynkaanniemi et al. 2019) and density and coverage (Naeem et al. 2020) of generated features ``fake``
+    (M,D) against ``real`` (N,D).  With ``r_i^2`` / ``s_j^2`` the squared distance of real i / fake j to its k-th nearest *other* sample of its
+    own set, and every comparison ``<=`` on squared distances (``prdc`` compares ``<``; the two differ on exact ties only):
+
+    - precision = mean_j [exists i: D2(R_i, F_j) <= r_i^2],   recall = mean_i [exists j: D2(R_i, F_j) <= s_j^2],
+    - density = 1 / (k M) sum_j #{i: D2(R_i, F_j) <= r_i^2},  coverage = mean_i [min_j D2(R_i, F_j) <= r_i^2].
+
+    Four passes of ``feature_knn``.  ``per_sample`` adds ``fake_in_real`` (M,) bool, ``fake_count`` (M,) int32, ``real_in_fake`` (N,) bool,
+    ``real_covered`` (N,) bool, ``real_radius2`` (N,) and ``fake_radius2`` (M,) fp64."""
+    r, f = _as_feats(real, "real"), _as_feats(fake, "fake")
+    r2, s2 = knn_radii(r, k), knn_radii(f, k)
+    fake_count = feature_knn(f, r, 0, r2, want=("count",))["count"]
+    rf = feature_knn(r, f, 0, s2, want=("count", "min2"))
+    fake_in_real, real_in_fake, real_covered = fake_count > 0, rf["count"] > 0, rf["min2"] <= r2
+    hits = torch.stack([fake_in_real.sum(), real_in_fake.sum(), fake_count.sum(dtype=torch.int64), real_covered.sum()]).tolist()  # exact counts, one read
+    (n, _), m = r.shape, f.shape[0]
+    out = {"precision": hits[0] / m, "recall": hits[1] / n, "density": hits[2] / (k * m), "coverage": hits[3] / n}
+    if per_sample:
+        out.update(fake_in_real=fake_in_real, fake_count=fake_count, real_in_fake=real_in_fake, real_covered=real_covered, real_radius2=r2,
+                   fake_radius2=s2)
+    return out
