@@ -178,6 +178,26 @@ int r2dm_diffusion_loss(const float* prediction, const float* x_0, const float* 
                         const float* coef, int32_t objective, int32_t criterion, int32_t batch, int32_t channels, int64_t plane,
                         void* scratch, double* num, double* den, void* stream);
 
+/* -- latent space: DDIM inversion / decoding from a given latent, and spherical interpolation of latents.
+ *    r2dm_ddim_transfer moves x from noise level t to any level u along the deterministic DDIM line (u > t inverts, u < t decodes),
+ *    without clipping.  coef is (B,4) = (alpha_t, sigma_t, alpha_u, sigma_u), host- or device-computed scalars in device memory.  Per
+ *    element, float32, not contracted, x_0 and eps in the direct form of the objective (0 eps, 1 v, 2 x_0):
+ *      eps: e = pr, x0 = (x - s_t*pr)/a_t | v: x0 = a_t*x - s_t*pr, e = s_t*x + a_t*pr | x_0: x0 = pr, e = (x - a_t*pr)/s_t
+ *      x_u = a_u*x0 + s_u*e.
+ *    per_sample must be a multiple of 4 and x_t, prediction, x_u 16-byte aligned.
+ *    r2dm_slerp: per sample, over all per_sample elements, out[k][b] = fl32(c_a)*a[b] + fl32(c_b)*b[b] for each of the K weights w_k
+ *    (HOST memory, 1 <= K <= 64, finite; values outside [0,1] extrapolate), out (K,batch,per_sample) fp32, coef64 (K,batch,2) fp64 =
+ *    (c_a, c_b).  cos = <a,b>/sqrt(<a,a><b,b>) clamped to [-1,1], omega = acos(cos), c_a = sin((1-w)omega)/sin(omega), c_b =
+ *    sin(w omega)/sin(omega); when 1 - cos^2 < 1e-10 or a norm is 0: the lerp pair (1-w, w).  The three sums are float64 sums of the
+ *    float32 products in a fixed order (no atomics): bit-reproducible, and a sample's result does not depend on the rest of the batch.
+ *    Two launches.  scratch: r2dm_slerp_scratch_bytes(batch, per_sample) bytes (0 for an empty, oversized or non-multiple-of-4
+ *    problem), 8-byte aligned; a, b, out 16-byte aligned, per_sample a multiple of 4. */
+int r2dm_ddim_transfer(const float* x_t, const float* prediction, const float* coef, float* x_u, int32_t batch, int64_t per_sample,
+                       int32_t objective, void* stream);
+size_t r2dm_slerp_scratch_bytes(int32_t batch, int64_t per_sample);
+int r2dm_slerp(const float* a, const float* b, const float* weights, int32_t K, float* out, double* coef64, int32_t batch,
+               int64_t per_sample, void* scratch, void* stream);
+
 /* -- sample post-processing: LiDARUtility.denormalize/revert_depth/to_xyz + concat
  *    (utils/lidar.py:49-61,98-120; sample_and_save.py:52-57).  x (B,2,H,W) in [-1,1],
  *    ray_angles (2,H,W) [elevation, azimuth] in rad, out (B,5,H,W) = depth,x,y,z,reflectance. */

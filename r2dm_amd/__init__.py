@@ -25,6 +25,8 @@ from . import completion  # noqa: E402  (completion metrics: range / reflectance
 from .completion import (completion_errors, confusion_matrix, corruption_mask, evaluate_completion, fill_beams, iou_from_confusion)
 from . import geometry  # noqa: E402  (Chamfer distance, F-score, COV / MMD / 1-NNA on a HIP nearest-neighbour search)
 from .geometry import chamfer_from_sums, chamfer_sums, emd_pairs, nearest_neighbors, pairwise_chamfer, pairwise_emd, set_metrics
+from . import latent  # noqa: E402  (DDIM inversion's transfer kernel, slerp, latent interpolation and reconstruction)
+from .latent import ddim_transfer, interpolate, reconstruct, slerp
 
 __all__ = [
     "ContinuousTimeGaussianDiffusion", "DiscreteTimeGaussianDiffusion", "GaussianDiffusion", "EfficientUNet",
@@ -36,5 +38,6 @@ __all__ = [
     "corruption_mask", "completion_errors", "confusion_matrix", "iou_from_confusion", "fill_beams", "evaluate_completion",
     "nearest_neighbors", "chamfer_sums", "chamfer_from_sums", "pairwise_chamfer", "set_metrics",
     "emd_pairs", "pairwise_emd",
+    "ddim_transfer", "slerp", "interpolate", "reconstruct",
 ]
 __version__ = "0.4.0"

@@ -84,6 +84,9 @@ SIGNATURES = {
     "r2dm_q_step": (c_int32, [_P, _P, _P, _P, c_int32, c_int64, _P]),
     "r2dm_diffusion_loss_scratch_bytes": (c_size_t, [c_int32, c_int32, c_int64]),
     "r2dm_diffusion_loss": (c_int32, [_P, _P, _P, _P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, c_int64, _P, _P, _P, _P]),
+    "r2dm_ddim_transfer": (c_int32, [_P, _P, _P, _P, c_int32, c_int64, c_int32, _P]),
+    "r2dm_slerp_scratch_bytes": (c_size_t, [c_int32, c_int64]),
+    "r2dm_slerp": (c_int32, [_P, _P, POINTER(c_float), c_int32, _P, _P, c_int32, c_int64, _P, _P]),
     "r2dm_lidar_postprocess": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_float, c_float, _P]),
     "r2dm_lidar_postprocess_fmt": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_float, c_float, c_int32, _P]),
     "r2dm_conv_packed_elems": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),

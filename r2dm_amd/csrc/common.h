@@ -277,6 +277,14 @@ hipError_t launch_q_step(const float* x, const float* noise, const float* coef, 
 size_t diffusion_loss_scratch_bytes(int B, int C, long plane);
 hipError_t launch_diffusion_loss(const float* pred, const float* x_0, const float* noise, const float* mask, int mask_c, const float* coef,
                                  int objective, int criterion, int B, int C, long plane, void* scratch, double* num, double* den, hipStream_t s);
+// latent space (latent.hip): the DDIM transfer x_t -> x_u with coef (B,4) = (alpha_t, sigma_t, alpha_u, sigma_u), and spherical interpolation at K
+// host weights -> out (K,B,per_sample), coef64 (K,B,2)
+hipError_t launch_ddim_transfer(const float* x_t, const float* pred, const float* coef, float* x_u, int B, long per_sample, int objective,
+                                hipStream_t s);
+constexpr int kSlerpMaxWeights = 64;  // weights of one r2dm_slerp call (they travel as a kernel argument)
+size_t slerp_scratch_bytes(int B, long per_sample);
+hipError_t launch_slerp(const float* a, const float* b, const float* weights, int K, float* out, double* coef64, int B, long per_sample,
+                        void* scratch, hipStream_t s);
 
 // (B,2,H,W) in [-1,1] -> (B,5,H,W) [depth, x, y, z, reflectance]  (reference sample_and_save.py:52-57)
 hipError_t launch_lidar_postprocess(const float* x, const float* angles, float* y, int B, int H, int W,

@@ -1,5 +1,7 @@
 // C ABI of the stand-alone operators (include/r2dm_hip.h): sampler steps, LiDAR post-processing, BEV metrics, rendering, projection and point-cloud
 // export.  Each entry validates its arguments and enqueues the operator's kernels (posterior / metrics / render / projection / pointcloud .hip).
+#include <cmath>
+
 #include "engine.h"
 
 using namespace r2dm;
@@ -53,6 +55,40 @@ int r2dm_diffusion_loss(const float* prediction, const float* x_0, const float* 
         return fail(1, "diffusion_loss: coef must be 4-byte aligned; scratch, num and den 8-byte aligned");
     HIP_TRY(launch_diffusion_loss(prediction, x_0, noise, mask, mask_channels, coef, objective, criterion, B, C, plane, scratch, num, den,
                                   (hipStream_t)stream));
+    return 0;
+}
+
+static bool latent_geometry_ok(int32_t B, int64_t per_sample) {
+    return B >= 1 && B <= 65535 && per_sample >= 4 && per_sample % 4 == 0 && per_sample <= (1LL << 40) / B;
+}
+
+int r2dm_ddim_transfer(const float* x_t, const float* prediction, const float* coef, float* x_u, int32_t B, int64_t per_sample,
+                       int32_t objective, void* stream) {
+    if (!x_t || !prediction || !coef || !x_u) return fail(1, "null argument");
+    if (objective < 0 || objective > 2) return fail(1, "ddim_transfer: objective must be 0 (eps), 1 (v) or 2 (x_0), got %d", objective);
+    if (!latent_geometry_ok(B, per_sample))
+        return fail(1, "ddim_transfer: batch must be in [1, 65535], per_sample a multiple of 4 (got %lld), the tensors at most 2^40 elements", (long long)per_sample);
+    if ((((uintptr_t)x_t | (uintptr_t)prediction | (uintptr_t)x_u) & 15) || ((uintptr_t)coef & 3))
+        return fail(1, "ddim_transfer: x_t, prediction and x_u must be 16-byte aligned, coef 4-byte aligned");
+    HIP_TRY(launch_ddim_transfer(x_t, prediction, coef, x_u, B, per_sample, objective, (hipStream_t)stream));
+    return 0;
+}
+
+size_t r2dm_slerp_scratch_bytes(int32_t B, int64_t per_sample) {
+    return latent_geometry_ok(B, per_sample) ? slerp_scratch_bytes(B, per_sample) : 0;
+}
+
+int r2dm_slerp(const float* a, const float* b, const float* weights, int32_t K, float* out, double* coef64, int32_t B, int64_t per_sample,
+               void* scratch, void* stream) {
+    if (!a || !b || !weights || !out || !coef64 || !scratch) return fail(1, "null argument");
+    if (K < 1 || K > kSlerpMaxWeights) return fail(1, "slerp: the number of weights must be in [1, %d], got %d", kSlerpMaxWeights, K);
+    for (int k = 0; k < K; ++k)
+        if (!std::isfinite(weights[k])) return fail(1, "slerp: weight %d is not finite", k);
+    if (!latent_geometry_ok(B, per_sample) || per_sample > (1LL << 40) / B / K)
+        return fail(1, "slerp: batch must be in [1, 65535], per_sample a multiple of 4 (got %lld), the output at most 2^40 elements", (long long)per_sample);
+    if ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 15) || (((uintptr_t)coef64 | (uintptr_t)scratch) & 7))
+        return fail(1, "slerp: a, b and out must be 16-byte aligned, coef64 and scratch 8-byte aligned");
+    HIP_TRY(launch_slerp(a, b, weights, K, out, coef64, B, per_sample, scratch, (hipStream_t)stream));
     return 0;
 }
 

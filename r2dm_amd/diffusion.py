@@ -32,6 +32,7 @@ from torch import nn
 from torch.special import expm1
 
 from . import _lib
+from .latent import ddim_transfer as _ddim_transfer
 
 try:  # progress bars are optional
     from tqdm.auto import tqdm
@@ -47,7 +48,7 @@ _CRITERIA = ("l2", "l1", "huber")  # base.py:39-44
 
 
 class NoCPUFallback(_lib.R2DMError, NotImplementedError):
-    """The denoising loss was asked of a model or an image batch that is not on a GPU: an ``R2DMError`` like every other entry point's
+    """The denoising loss, ``invert`` or ``sample_from`` was asked of a model or an image batch that is not on a GPU: an ``R2DMError`` like every other entry point's
     refusal, and a ``NotImplementedError`` for callers of the earlier sampling-only package, whose ``forward`` raised that."""
 
 
@@ -422,9 +423,43 @@ class GaussianDiffusion(nn.Module):
     def _clip(self) -> float:
         return float(self.clip_sample_range) if self.clip_sample else -1.0
 
-    def _posterior(self, x_t, pred, noise, coef, mode_id: int):
-        """x_s = posterior(x_t, prediction, noise) in one HIP launch."""
-        return _lib.posterior_step(x_t, pred, noise, coef, mode_id, self._objective_id(), self._clip())
+    def _posterior(self, x_t, pred, noise, coef, mode_id: int, clip: Optional[float] = None):
+        """x_s = posterior(x_t, prediction, noise) in one HIP launch (``clip``: None -- the model's setting; < 0: no clamp)."""
+        return _lib.posterior_step(x_t, pred, noise, coef, mode_id, self._objective_id(), self._clip() if clip is None else clip)
+
+    def _run_loop(self, x, num_steps: int, row, update, draw, progress: bool, return_all: bool, desc: str = "sampling"):
+        """The step loop every sampler here shares (``sample``, ``sample_from``, ``invert``): per step ``row(i) -> (cond, coef)``, the
+        step's noise (``draw(x) -> (noise, event)`` ahead of the denoiser call; None: a deterministic update, nothing is drawn), one
+        denoiser call, ``update(x, prediction, noise, coef) -> x``; under the deferred range guard, with ``_Replay``'s recovery.
+        -> the last ``x``, or with ``return_all`` the (S+1, ...) stack that starts with the given ``x``."""
+        if return_all:
+            out = [x]
+        rp = _Replay(self.model, num_steps)  # (a range-guard trip at any step: back to the last checked x, on the recorded noise)
+        rp.start(x)
+        bar = _progress_bar(num_steps, desc, progress)
+        with _range_guard(self.model):
+            i = 0
+            while i < num_steps:
+                cond_i, coef_i = row(i)
+                noise, drawn = rp.noise_for(i, lambda: draw(x)) if draw is not None else (None, None)
+                prediction = self.model(x, cond_i)
+                if drawn is not None:
+                    torch.cuda.current_stream(x.device).wait_event(drawn)
+                nxt, x = rp.after_step(i, update(x, prediction, noise, coef_i))
+                if return_all:
+                    del out[nxt + 1:]  # (after a replay: the steps that are run again; else nothing)
+                    if nxt > i:
+                        out.append(x)
+                if bar is not None:
+                    bar.update(nxt - i)
+                i = nxt
+        if bar is not None:
+            bar.close()
+        return torch.stack(out) if return_all else x
+
+    def _refuse_cpu(self, what: str, x):
+        if self.device.type != "cuda" or not x.is_cuda:
+            raise NoCPUFallback(f"{what} runs as HIP kernels on an MI355X (model on {self.device}, input on {x.device}): r2dm_amd has no CPU fallback")
 
 
 # --------------------------------------------------------------------------------------
@@ -575,19 +610,20 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
         cond, coef, _ = self.__dict__["_tables"][self._table_key(num_steps, batch_size, mode, ddim_eta, dev)]
         return cond, coef, mode_id
 
-    def _table_key(self, num_steps, batch_size, mode, ddim_eta, dev):
-        return (num_steps, batch_size, mode, float(ddim_eta), str(torch.device(dev)), self.noise_schedule, self.image_d, self.noise_d_low, self.noise_d_high,
-                self.schedule_on)
+    def _table_key(self, num_steps, batch_size, mode, ddim_eta, dev, t_start: float = 1.0):
+        key = (num_steps, batch_size, mode, float(ddim_eta), str(torch.device(dev)), self.noise_schedule, self.image_d, self.noise_d_low, self.noise_d_high,
+               self.schedule_on)
+        return key if t_start == 1.0 else key + (("t_start", float(t_start)),)  # (``sample``'s keys are what they were)
 
-    def _table_rows(self, num_steps: int, batch_size: int, mode: str, ddim_eta: float, dev):
-        """``row(i) -> (cond (B,), coef (B, 8))`` and ``mode_id`` for a ``sample`` call.  A cached table is indexed; a new one is
+    def _table_rows(self, num_steps: int, batch_size: int, mode: str, ddim_eta: float, dev, t_start: float = 1.0):
+        """``row(i) -> (cond (B,), coef (B, 8))`` and ``mode_id`` for a ``sample`` call (``sample_from``: the steps start at ``t_start``).  A cached table is indexed; a new one is
         built ROW BY ROW while the loop runs: each row is ~0.3 ms of host work (about thirty 1-element torch ops), 80 ms for 256
         steps -- with the whole table built up front that was 4.5 % of a cold 256-step call with the GPU idle (round 3:
         scripts/step_times.py, profiles/r03_step_times.txt), whereas one row per step hides under the ~6 ms the GPU needs per
         step.  Rows travel through pinned host memory (an asynchronous copy on the sampling stream: the host never waits for the
         GPU) into the device table, which enters the cache when its last row is in."""
         dev = torch.device(dev)
-        key = self._table_key(num_steps, batch_size, mode, ddim_eta, dev)
+        key = self._table_key(num_steps, batch_size, mode, ddim_eta, dev, t_start)
         cache = self.__dict__.setdefault("_tables", {})
         hit = cache.get(key)
         if hit is not None:
@@ -599,7 +635,7 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
         if self._on_device(dev):
             # the whole table at once, on the device: `steps` is the reference's own device linspace (continuous_time.py:248), and a device
             # elementwise kernel computes every element by the same instructions whatever the tensor's shape -- (S,) here, (B,) per step there
-            steps = torch.linspace(1.0, 0.0, num_steps + 1, device=dev)
+            steps = torch.linspace(float(t_start), 0.0, num_steps + 1, device=dev)
             lt, k = self._coefficient_block(steps[:-1], steps[1:], mode, ddim_eta)
             cond = lt[:, None].repeat_interleave(batch_size, dim=1).contiguous()
             coef = k[:, None, :].repeat_interleave(batch_size, dim=1).contiguous()
@@ -607,7 +643,7 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
                 cache.pop(next(iter(cache)))
             cache[key] = (cond, coef, mode_id)
             return (lambda i: (cond[i], coef[i])), mode_id
-        steps = torch.linspace(1.0, 0.0, num_steps + 1)
+        steps = torch.linspace(float(t_start), 0.0, num_steps + 1)
         pin = dev.type == "cuda"
         h_cond = torch.empty(num_steps, batch_size, pin_memory=pin)
         h_coef = torch.empty(num_steps, batch_size, _NCOEF, pin_memory=pin)
@@ -651,31 +687,58 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
         dev = self.device
         self._objective_id()
         x = self.randn(batch_size, *self.sampling_shape, rng=rng, device=dev)
-        if return_all:
-            out = [x]
-        row, mode_id = self._table_rows(num_steps, batch_size, mode, ddim_eta, dev)
-        rp = _Replay(self.model, num_steps)  # (a range-guard trip at any step: back to the last checked x, on the recorded noise)
-        rp.start(x)
-        bar = _progress_bar(num_steps, "sampling", progress)
-        with _range_guard(self.model):
-            i = 0
-            while i < num_steps:
-                cond_i, coef_i = row(i)
-                noise, drawn = rp.noise_for(i, lambda: self._randn_like_ahead(x, rng=rng))
-                prediction = self.model(x, cond_i)
-                if drawn is not None:
-                    torch.cuda.current_stream(x.device).wait_event(drawn)
-                nxt, x = rp.after_step(i, self._posterior(x, prediction, noise, coef_i, mode_id))
-                if return_all:
-                    del out[nxt + 1:]  # (after a replay: the steps that are run again; else nothing)
-                    if nxt > i:
-                        out.append(x)
-                if bar is not None:
-                    bar.update(nxt - i)
-                i = nxt
-        if bar is not None:
-            bar.close()
-        return torch.stack(out) if return_all else x
+        return self._reverse_loop(x, num_steps, 1.0, progress, rng, return_all, mode, ddim_eta)
+
+    def _reverse_loop(self, x, num_steps, t_start, progress, rng, return_all, mode, ddim_eta, clip: Optional[float] = None):
+        """The reverse process from ``x`` at ``t_start`` to t = 0 over ``linspace(t_start, 0, num_steps + 1)``: ``sample`` and ``sample_from``
+        (``clip``: None -- the model's setting, else ``_posterior``'s override)."""
+        row, mode_id = self._table_rows(num_steps, x.shape[0], mode, ddim_eta, x.device, t_start)
+        return self._run_loop(x, num_steps, row, lambda x, pred, noise, coef: self._posterior(x, pred, noise, coef, mode_id, clip),
+                              lambda x: self._randn_like_ahead(x, rng=rng), progress, return_all)
+
+    @torch.inference_mode()
+    def sample_from(self, x_t, num_steps: int, t_start: float = 1.0, progress: bool = True, rng=None, return_all: bool = False,
+                    mode: Literal["ddpm", "ddim"] = "ddpm", ddim_eta: float = 0.0, clip: Optional[bool] = None):
+        """``sample``'s reverse loop started from a given ``x_t`` (B,C,H,W) at noise level ``t_start`` instead of a fresh draw at t = 1,
+        over ``linspace(t_start, 0, num_steps + 1)``: decodes a latent of ``invert`` or an interpolated one, or -- after
+        ``q_step_from_x_0(x_0, t_start)`` -- denoises a partially noised scan.  With ``x_t = randn(B, ...)`` from the same generators and
+        ``t_start = 1`` it is ``sample``, bit for bit.  ``clip``: None keeps the model's ``clip_sample`` setting, False switches the clamp
+        of the predicted x_0 off for this call only (a round trip through ``invert`` needs that), True switches it on."""
+        self._refuse_cpu("sample_from", x_t)
+        if not 0.0 < float(t_start) <= 1.0:
+            raise ValueError(f"t_start must be in (0, 1], got {t_start}")
+        if x_t.dim() != 4 or x_t.shape[0] < 1:
+            raise ValueError(f"x_t must be (B,C,H,W) with B >= 1, got {tuple(x_t.shape)}")
+        self._objective_id()
+        return self._reverse_loop(_lib.f32c(x_t), num_steps, float(t_start), progress, rng, return_all, mode, ddim_eta,
+                                  None if clip is None else float(self.clip_sample_range) if clip else -1.0)
+
+    def _transfer_table(self, steps: torch.Tensor, batch_size: int, dev):
+        """``(cond (S,B), coef (S,B,4))`` on the device for DDIM transfers along ``steps`` (S+1,): the log-SNR of each step's start and
+        ``(alpha_t, sigma_t, alpha_u, sigma_u)`` of its two ends, evaluated where ``schedule_on`` says (on the host row by row on
+        1-element tensors, as ``_coefficients``)."""
+        cond = self._log_snr_of_steps(steps[:-1]).to(dev)
+        rows = self._alpha_sigma_rows(steps).to(dev)
+        coef = torch.cat([rows[:-1], rows[1:]], dim=-1)
+        return cond[:, None].repeat_interleave(batch_size, dim=1).contiguous(), coef[:, None, :].repeat_interleave(batch_size, dim=1).contiguous()
+
+    @torch.inference_mode()
+    def invert(self, x_0, num_steps: int, t_end: float = 1.0, progress: bool = True, return_all: bool = False):
+        """DDIM inversion: the deterministic encoding of ``x_0`` (B,C,H,W) into the latent at noise level ``t_end``, over
+        ``linspace(0, t_end, num_steps + 1)``.  Per step one denoiser call at log-SNR(t_i) and one ``r2dm_ddim_transfer`` to t_{i+1} (the
+        DDIM update with eta = 0 run towards more noise, unclipped); nothing is drawn.  ``sample_from(..., t_start=t_end, mode="ddim",
+        clip=False)`` decodes the result.  -> x at ``t_end``; with ``return_all`` the (S+1,B,C,H,W) stack that starts with ``x_0``."""
+        self._refuse_cpu("invert", x_0)
+        if not 0.0 < float(t_end) <= 1.0:
+            raise ValueError(f"t_end must be in (0, 1], got {t_end}")
+        if x_0.dim() != 4 or x_0.shape[0] < 1:
+            raise ValueError(f"x_0 must be (B,C,H,W) with B >= 1, got {tuple(x_0.shape)}")
+        objective = self._objective_id()
+        x, dev = _lib.f32c(x_0), x_0.device
+        steps = torch.linspace(0.0, float(t_end), num_steps + 1, device=dev if self._on_device(dev) else None)
+        cond, coef = self._transfer_table(steps, x.shape[0], dev)
+        return self._run_loop(x, num_steps, lambda i: (cond[i], coef[i]), lambda x, pred, _, k: _ddim_transfer(x, pred, k, objective),
+                              None, progress, return_all, desc="inverting")
 
     # -- forward process pieces used by RePaint (continuous_time.py:169-190) ----------------
     def _alpha_sigma_rows(self, steps: torch.Tensor) -> torch.Tensor:
@@ -868,30 +931,16 @@ class DiscreteTimeGaussianDiffusion(GaussianDiffusion):
         dev = self.device
         self._objective_id()
         x = self.randn(batch_size, *self.sampling_shape, rng=rng, device=dev)
-        if return_all:
-            out = [x]
         order = torch.arange(num_steps - 1, -1, -1)
         coef, mode_id = self._coefficients(order, mode, 0.0)
         coef = coef[:, None, :].expand(num_steps, batch_size, _NCOEF).contiguous().to(dev)
         cond = order[:, None].expand(num_steps, batch_size).contiguous().to(dev)
-        rp = _Replay(self.model, num_steps)  # (as ContinuousTimeGaussianDiffusion.sample)
-        rp.start(x)
-        bar = _progress_bar(num_steps, "sampling", progress)
-        with _range_guard(self.model):
-            i = 0
-            while i < num_steps:
-                noise, drawn = rp.noise_for(i, lambda: self._randn_like_ahead(x, rng=rng)) if mode_id != _M_DT_DDIM else (None, None)
-                prediction = self.model(x, cond[i])
-                if drawn is not None:
-                    torch.cuda.current_stream(x.device).wait_event(drawn)
-                nxt, x = rp.after_step(i, self._posterior(x, prediction, noise, coef[i], mode_id))
-                if return_all:
-                    del out[nxt + 1:]
-                    if nxt > i:
-                        out.append(x)
-                if bar is not None:
-                    bar.update(nxt - i)
-                i = nxt
-        if bar is not None:
-            bar.close()
-        return torch.stack(out) if return_all else x
+        draw = (lambda x: self._randn_like_ahead(x, rng=rng)) if mode_id != _M_DT_DDIM else None
+        return self._run_loop(x, num_steps, lambda i: (cond[i], coef[i]), lambda x, pred, noise, k: self._posterior(x, pred, noise, k, mode_id),
+                              draw, progress, return_all)
+
+    def invert(self, *args, **kwargs):
+        raise NotImplementedError("invert is implemented for continuous time only (ContinuousTimeGaussianDiffusion)")
+
+    def sample_from(self, *args, **kwargs):
+        raise NotImplementedError("sample_from is implemented for continuous time only (ContinuousTimeGaussianDiffusion)")
