@@ -2,7 +2,8 @@
 """Drop-in for the reference's completion_demo.py: RePaint completion of one real scan under four simulated corruptions (the full
 scan, every 4th beam, a random half of the beams, a random 10 % of the points).
 
-Same options (``--ckpt --num_steps --num_resample_steps --jump_length --seed``); the scan comes from ``--scan FILE.bin`` (a raw
+Same options (``--ckpt --num_steps --num_resample_steps --jump_length --seed``); ``--method ddnm`` (extension) completes with the
+data-consistent sampler ``ddpm.complete`` instead, ``--num_resample_steps`` then being its resampling count; the scan comes from ``--scan FILE.bin`` (a raw
 Velodyne file, projected on the GPU by r2dm_amd.projection with the checkpoint's ``cfg.data.projection``) instead of the
 HuggingFace dataset lookup, and ``--out`` names the image.  The corruption masks are drawn as the reference draws them
 (completion_demo.py:81-87: the same CPU draws after ``torch.manual_seed(seed)``), the completion is the same
@@ -104,8 +105,9 @@ def main(args):
 
     mask = corruption_masks(x_orig, args.seed).to(device)
     x_in = mask * x_orig + (1 - mask) * -1
-    x_out = ddpm.repaint(known=x_in, mask=mask, num_steps=args.num_steps, num_resample_steps=args.num_resample_steps,
-                         jump_length=args.jump_length, rng=r2dm_amd.setup_rng(range(BATCH), device=device)).clamp(-1, 1)
+    completer = ddpm.complete if getattr(args, "method", "repaint") == "ddnm" else ddpm.repaint
+    x_out = completer(known=x_in, mask=mask, num_steps=args.num_steps, num_resample_steps=args.num_resample_steps,
+                      jump_length=args.jump_length, rng=r2dm_amd.setup_rng(range(BATCH), device=device)).clamp(-1, 1)
 
     W = x_in.shape[-1]
     saved = {"x_in": x_in.cpu(), "mask": mask.cpu(), "x_out": x_out.cpu()}
@@ -138,7 +140,9 @@ def parser():
     p = ArgumentParser()
     p.add_argument("--ckpt", type=Path, required=True)
     p.add_argument("--num_steps", type=int, default=32)
-    p.add_argument("--num_resample_steps", type=int, default=16)
+    p.add_argument("--method", choices=("repaint", "ddnm"), default="repaint",
+                   help="repaint: the reference's sampler; ddnm: the data-consistent sampler (ddpm.complete), one denoiser call per step")
+    p.add_argument("--num_resample_steps", type=int, default=16, help="the chosen method's resampling count")
     p.add_argument("--jump_length", type=int, default=1)
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--scan", type=Path, required=True, help="a raw Velodyne scan (*.bin: float32 x, y, z, reflectance), instead of --sample_id")
@@ -154,6 +158,6 @@ def parser():
 if __name__ == "__main__":
     args = parser().parse_args()
     if args.out is None:
-        args.out = Path(f"completion_T-{args.num_steps:04d}_r-{args.num_resample_steps:04d}_j-{args.jump_length:04d}.png")
+        args.out = Path(("ddnm_" if args.method == "ddnm" else "") + f"completion_T-{args.num_steps:04d}_r-{args.num_resample_steps:04d}_j-{args.jump_length:04d}.png")
     print(vars(args))
     main(args)

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Scores scan completion on held-out scans, on the GPU: every scan is corrupted (``--corruption``: ``full``, ``beams:K``,
-``random_beams:P``, ``random_points:P``; repeatable), completed by RePaint and / or by nearest / linear interpolation of the known beams
-(``--methods``), and compared with the scan itself -- mean absolute and root-mean-square error of range and reflectance over the pixels
+``random_beams:P``, ``random_points:P``; repeatable), completed by RePaint, by the data-consistent sampler (``ddnm``: ``ddpm.complete``, one
+denoiser call per step; ``--ddnm_resample_steps``, and ``--ddnm_init linear --ddnm_t_start 0.5`` to start it from the interpolated scan)
+and / or by nearest / linear interpolation of the known beams (``--methods``), and compared with the scan itself -- mean absolute and root-mean-square error of range and reflectance over the pixels
 that had to be filled in, the recall of returns, the rate of false returns and, with ``--rangenet_weights``, the IoU of the RangeNet-53
 labels of the completed image against the labels of the real scan (r2dm_amd.completion.evaluate_completion; DESIGN.md section 4,
 "Completion metrics").  ``--chamfer`` also scores the completion in 3-D: Chamfer distance and the F-score at ``--fscore_threshold`` metres
@@ -89,7 +90,8 @@ def main(argv=None):
     out = completion.evaluate_completion(ddpm, lidar_utils, planes, kinds, methods=tuple(args.methods), num_steps=args.num_steps,
                                          num_resample_steps=args.num_resample_steps, jump_length=args.jump_length, seed=args.seed,
                                          batch_size=args.batch_size, semseg=semseg, semseg_postprocess=post, keep=args.save_dir is not None,
-                                         chamfer=args.chamfer, fscore_threshold=args.fscore_threshold)
+                                         chamfer=args.chamfer, fscore_threshold=args.fscore_threshold, ddnm_resample_steps=args.ddnm_resample_steps,
+                                         ddnm_init=None if args.ddnm_init == "none" else args.ddnm_init, ddnm_t_start=args.ddnm_t_start)
     results, kept = out if args.save_dir is not None else (out, None)
     info = {"ckpt": str(args.ckpt), "source": str(args.real_scans if args.real_scans is not None else args.real_dir), "num_scans": len(files),
             "resolution": list(cfg.data.resolution), "corruptions": kinds, "methods": list(args.methods), "num_steps": args.num_steps,
@@ -98,6 +100,8 @@ def main(argv=None):
             "semseg_postprocess": args.semseg_postprocess if semseg is not None else None}
     if args.chamfer:
         info["fscore_threshold"] = args.fscore_threshold
+    if "ddnm" in args.methods:
+        info.update(ddnm_resample_steps=args.ddnm_resample_steps, ddnm_init=args.ddnm_init, ddnm_t_start=args.ddnm_t_start)
     doc = completion.jsonable({"info": info, "results": results})
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     with open(args.out, "w") as f:
@@ -128,10 +132,15 @@ def build_parser():
     parser.add_argument("--limit", type=int, default=None, help="the first so many scans (sorted)")
     parser.add_argument("--corruption", action="append", default=None, metavar="KIND",
                         help="full, beams:K, random_beams:P or random_points:P; repeatable (default: beams:4)")
-    parser.add_argument("--methods", nargs="+", choices=["repaint", "nearest", "linear"], default=["repaint"])
+    parser.add_argument("--methods", nargs="+", choices=["repaint", "ddnm", "nearest", "linear"], default=["repaint"],
+                        help="ddnm: the data-consistent sampler (ddpm.complete), one denoiser call per step")
     parser.add_argument("--num_steps", type=int, default=32)
     parser.add_argument("--num_resample_steps", type=int, default=10)
     parser.add_argument("--jump_length", type=int, default=1)
+    parser.add_argument("--ddnm_resample_steps", type=int, default=1, help="resamplings per step of the ddnm method (1: none)")
+    parser.add_argument("--ddnm_init", choices=("none", "nearest", "linear"), default="none",
+                        help="start the ddnm method from this interpolation of the known beams, noised to --ddnm_t_start (masks of whole rows)")
+    parser.add_argument("--ddnm_t_start", type=float, default=1.0, help="the noise level the ddnm method starts at (< 1 needs --ddnm_init)")
     parser.add_argument("--batch_size", type=int, default=8, help="scans per RePaint call")
     parser.add_argument("--seed", type=int, default=0, help="scan i draws its masks and its noise from generators seeded from (seed, i)")
     parser.add_argument("--rangenet_weights", type=str, default=None,

@@ -152,6 +152,21 @@ int r2dm_posterior_step(const float* x_t, const float* prediction, const float* 
                         float* x_s, int32_t batch, int64_t per_sample, int32_t mode, int32_t objective,
                         float clip, void* stream);
 
+/* -- data-consistent posterior update: the step of r2dm_posterior_step with a measurement written over the x_0 estimate (the null-space
+ *    projection of DDNM, Wang et al. 2023, for a mask operator).  One pass in float32, not contracted; per element, in this order:
+ *      x0  = as r2dm_posterior_step (eps: (x - s_t*pr)/a_t | v: a_t*x - s_t*pr | x_0: pr), clamped to [-clip, clip] (clip < 0: no clamp)
+ *      x0  = m*y + (1 - m)*x0          y = known, m = mask: a per-pixel weight, not necessarily 0 / 1
+ *      x_s = mode 0 (continuous DDPM): a_s*(x*(1 - c)/a_t + c*x0) + sd*z | mode 1 (continuous DDIM): a_s*x0 + c1*z + c2*((x - a_t*x0)/s_t)
+ *    coef is the (B,8) row of r2dm_posterior_step.  mask has `mask_channels` channels (1 = broadcast over the `channels` planes of a
+ *    sample, as in r2dm_repaint_blend).  With an all-zero mask the result is r2dm_posterior_step's, bit for bit.
+ *    Refused (status 1, "posterior_step_known: ..." in r2dm_last_error, nothing launched): a null pointer (noise included); a mode other
+ *    than 0 / 1 (discrete time is not built) or an objective other than 0 / 1 / 2; a batch outside [1, 65535]; per_sample or the plane
+ *    per_sample / channels not a multiple of 4; mask_channels not 1 or `channels`; x_t, prediction, noise, known, mask or x_s not 16-byte
+ *    aligned (all are read and written as quads), coef not 4-byte aligned. */
+int r2dm_posterior_step_known(const float* x_t, const float* prediction, const float* noise, const float* known, const float* mask,
+                              const float* coef, float* x_s, int32_t batch, int64_t per_sample, int32_t channels, int32_t mask_channels,
+                              int32_t mode, int32_t objective, float clip, void* stream);
+
 /* -- RePaint completion (models/diffusion/continuous_time.py:169-190 q_step_from_x_0 / q_step, :287-303 the
  *    known/unknown blend inside repaint()).  coef is (B,2) host-computed scalars.
  *    blend:  out = mask * (known*alpha + noise*sigma) + (1 - mask) * unknown,  coef = (alpha, sigma) at step s;

@@ -80,6 +80,7 @@ SIGNATURES = {
     "r2dm_profile_read_classes": (c_int32, [_P, POINTER(ctypes.c_double), POINTER(ctypes.c_double), POINTER(c_int64)]),
     "r2dm_profile_event_overhead": (c_int32, [_P, _P, POINTER(ctypes.c_double), POINTER(ctypes.c_double)]),
     "r2dm_posterior_step": (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int64, c_int32, c_int32, c_float, _P]),
+    "r2dm_posterior_step_known": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32, c_float, _P]),
     "r2dm_repaint_blend": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int64, c_int32, c_int32, _P]),
     "r2dm_q_step": (c_int32, [_P, _P, _P, _P, c_int32, c_int64, _P]),
     "r2dm_diffusion_loss_scratch_bytes": (c_size_t, [c_int32, c_int32, c_int64]),
@@ -219,6 +220,24 @@ def posterior_step(x_t, pred, noise, coef, mode: int, objective: int, clip: floa
     with torch.cuda.device(x_t.device):
         check(lib().r2dm_posterior_step(ptr(x_t), ptr(pred), ptr(noise), ptr(coef), ptr(out), B,
                                         x_t.numel() // B, mode, objective, float(clip), stream_ptr(x_t.device)))
+    return out
+
+
+def posterior_step_known(x_t, pred, noise, known, mask, coef, mode: int, objective: int, clip: float) -> torch.Tensor:
+    """``posterior_step`` with the measurement written over the x_0 estimate, ``x0 = mask * known + (1 - mask) * x0``, in one launch;
+    ``mask`` (B | 1, 1 | C, H, W) is expanded over the batch as in ``repaint_blend``."""
+    require_gpu(x_t, "x_t")
+    x_t, pred, noise, known, coef = f32c(x_t), f32c(pred), f32c(noise), f32c(known), f32c(coef)
+    if x_t.dim() < 3 or any(t.shape != x_t.shape or t.device != x_t.device for t in (pred, noise, known)) or coef.shape != (x_t.shape[0], 8) \
+            or coef.device != x_t.device:
+        raise ValueError(f"x_t {tuple(x_t.shape)}, prediction {tuple(pred.shape)}, noise {tuple(noise.shape)} and known {tuple(known.shape)} must have "
+                         f"one (B,C,...) shape on one device, coef {tuple(coef.shape)} must be (B,8)")
+    B, C = x_t.shape[0], x_t.shape[1]
+    mask = f32c(mask.to(x_t.device).expand(B, -1, *x_t.shape[2:]))
+    out = torch.empty_like(x_t)
+    with torch.cuda.device(x_t.device):
+        check(lib().r2dm_posterior_step_known(ptr(x_t), ptr(pred), ptr(noise), ptr(known), ptr(mask), ptr(coef), ptr(out), B,
+                                              x_t.numel() // B, C, mask.shape[1], mode, objective, float(clip), stream_ptr(x_t.device)))
     return out
 
 

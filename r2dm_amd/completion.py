@@ -9,7 +9,7 @@ linear interpolation of the known beams.  The reference has no code for it.  Her
 - ``completion_errors``    per sample the four counts and six error sums of ``r2dm_completion_error`` and the values derived from them.
 - ``confusion_matrix`` / ``iou_from_confusion``   label agreement.
 - ``fill_beams``           the interpolation baselines.
-- ``evaluate_completion``  corrupt, complete (RePaint or a baseline), score; ``completion_eval.py`` is its command line.
+- ``evaluate_completion``  corrupt, complete (RePaint, the data-consistent sampler ``ddpm.complete`` or a baseline), score; ``completion_eval.py`` is its command line.
 
 A pixel is a *return* when its metric depth lies strictly inside ``(lo, hi)``; any other depth, NaN included, is "no return".  The errors
 are taken over E: the unknown pixels (mask 0) where the real scan has a return.  A prediction without a return there counts with depth 0
@@ -31,7 +31,7 @@ DERIVED_NAMES = ("mae_depth", "rmse_depth", "mae_depth_both", "rmse_depth_both",
                  "false_return_rate")
 FILL_MODES = {"nearest": 0, "linear": 1}
 ROW_KINDS = ("full", "beams", "random_beams")  # corruptions whose mask is whole rows: what the interpolation baselines are defined for
-METHODS = ("repaint", "nearest", "linear", "target")
+METHODS = ("repaint", "ddnm", "nearest", "linear", "target")
 
 
 # ---- corruptions -------------------------------------------------------------------------------------------------------------------------
@@ -254,7 +254,8 @@ def target_of_planes(planes: torch.Tensor) -> torch.Tensor:
 def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence[str], methods: Sequence[str] = ("repaint",), num_steps: int = 32,
                         num_resample_steps: int = 10, jump_length: int = 1, seed: int = 0, batch_size: int = 8, semseg=None,
                         semseg_postprocess=None, lo: Optional[float] = None, hi: Optional[float] = None, keep: bool = False,
-                        chamfer: bool = False, fscore_threshold: float = 0.2):
+                        chamfer: bool = False, fscore_threshold: float = 0.2, ddnm_resample_steps: int = 1, ddnm_init: Optional[str] = None,
+                        ddnm_t_start: float = 1.0):
     """Corrupt, complete and score ``planes`` (N,6,H,W), the masked planes of ``project_scans(layout="xyzrdm", apply_mask=True)`` at the
     model's resolution, on the GPU.
 
@@ -262,7 +263,10 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
     and RePaint draws from ``setup_rng([scan_seed(seed, i)])``, so a scan's inputs depend neither on ``batch_size`` nor on the scans after
     it.  ``x_in = mask * known + (1 - mask) * -1`` with ``known = known_from_scan(planes)``; a method's prediction is
     ``lidar_utils.postprocess(x_out.clamp(-1, 1))``; the target is the scan's own measured planes, not a decode of ``known``.
-    ``methods``: "repaint"; "nearest" / "linear" (``fill_beams`` on ``x_in``; defined for the kinds whose mask is whole rows, reported as
+    ``methods``: "repaint"; "ddnm" (``ddpm.complete`` on ``x_in`` under the mask, from the same generators as RePaint, ``num_steps`` and
+    ``jump_length`` shared with it and ``ddnm_resample_steps`` resamplings; with ``ddnm_init`` "nearest" / "linear" it starts from
+    ``fill_beams(x_in, ...)`` noised to ``ddnm_t_start`` < 1 instead of from noise at t = 1 -- defined, like the baselines, for the kinds
+    whose mask is whole rows and reported as skipped for the others); "nearest" / "linear" (``fill_beams`` on ``x_in``; defined for the kinds whose mask is whole rows, reported as
     skipped for the others); "target" (the target's own planes as the prediction: errors 0, mIoU 1).  ``lo``, ``hi``: the depth window of
     a return (default: the model's ``min_depth``, ``max_depth``).  ``semseg``: a ``RangeNetExtractor``; the labels of prediction and target
     come from the same net and ``semseg_postprocess`` (what ``segment`` accepts), the confusion matrix is taken over the target's measured
@@ -281,6 +285,15 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
     from .inference import setup_rng
     from .projection import known_from_scan
 
+    if ddnm_init is not None and ddnm_init not in FILL_MODES:
+        raise ValueError(f"ddnm_init must be None or one of {sorted(FILL_MODES)}, got {ddnm_init!r}")
+    if (ddnm_init is None) != (float(ddnm_t_start) == 1.0):
+        raise ValueError(f"ddnm_init and ddnm_t_start < 1 go together (a start from the interpolated scan, noised to ddnm_t_start): got {ddnm_init!r} "
+                         f"and {ddnm_t_start}")
+    if not 0.0 < float(ddnm_t_start) <= 1.0:
+        raise ValueError(f"ddnm_t_start must be in (0, 1], got {ddnm_t_start}")
+    if ddnm_resample_steps < 1:
+        raise ValueError(f"ddnm_resample_steps must be >= 1, got {ddnm_resample_steps}")
     if planes.dim() != 4 or planes.shape[1] != 6:
         raise ValueError(f"expected planes (N,6,H,W) [x, y, z, reflectance, depth, mask], got {tuple(planes.shape)}")
     _lib.require_gpu(planes, "planes")
@@ -293,7 +306,7 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
     if chamfer:
         fscore_threshold = geometry._check_tau(fscore_threshold)
     N, _, H, W = planes.shape
-    if "repaint" in methods and tuple(ddpm.sampling_shape) != (2, H, W):
+    if ("repaint" in methods or "ddnm" in methods) and tuple(ddpm.sampling_shape) != (2, H, W):
         raise ValueError(f"planes of {H}x{W} for a model that samples {tuple(ddpm.sampling_shape)}: RePaint needs a depth + reflectance model "
                          "at the planes' resolution")
     dev = planes.device
@@ -333,7 +346,19 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
             if method in FILL_MODES and name not in ROW_KINDS:
                 results[kind][method] = {"skipped": f"{method} interpolation is defined for masks of whole rows ({', '.join(ROW_KINDS)})"}
                 continue
-            if method == "repaint":
+            if method == "ddnm" and ddnm_init is not None and name not in ROW_KINDS:
+                results[kind][method] = {"skipped": f"ddnm_init = {ddnm_init} interpolation is defined for masks of whole rows ({', '.join(ROW_KINDS)})"}
+                continue
+            if method == "ddnm":
+                init = fill_beams(x_in, rows_of_mask(mask), ddnm_init, nodata=-1.0) if ddnm_init is not None and N else None
+                parts = []
+                for k in range(0, N, batch_size):
+                    rng = setup_rng([scan_seed(seed, i) for i in range(k, min(k + batch_size, N))], dev)
+                    parts.append(ddpm.complete(known=x_in[k:k + batch_size], mask=mask[k:k + batch_size], num_steps=num_steps,
+                                               num_resample_steps=ddnm_resample_steps, jump_length=jump_length, t_start=float(ddnm_t_start),
+                                               init=None if init is None else init[k:k + batch_size], progress=False, rng=rng))
+                x_out = torch.cat(parts) if parts else x_in
+            elif method == "repaint":
                 parts = []
                 for k in range(0, N, batch_size):
                     rng = setup_rng([scan_seed(seed, i) for i in range(k, min(k + batch_size, N))], dev)

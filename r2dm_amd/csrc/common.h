@@ -267,6 +267,9 @@ struct PosteriorParams {
     float clip;  // < 0: no clamping
 };
 hipError_t launch_posterior(const PosteriorParams& p, hipStream_t s);
+// the same step with the measurement written over the x_0 estimate: x0 = mask * known + (1 - mask) * x0 (continuous-time modes 0 / 1)
+hipError_t launch_posterior_known(const PosteriorParams& p, const float* known, const float* mask, int channels, int mask_c,
+                                  hipStream_t s);
 // RePaint (reference continuous_time.py:169-190,287-303): forward re-noising and known/unknown blend
 hipError_t launch_repaint_blend(const float* known, const float* noise, const float* unknown, const float* mask,
                                 const float* coef, float* out, int B, long per_sample, int channels, int mask_c,

@@ -16,6 +16,27 @@ int r2dm_posterior_step(const float* x_t, const float* pred, const float* noise,
     return 0;
 }
 
+int r2dm_posterior_step_known(const float* x_t, const float* pred, const float* noise, const float* known, const float* mask,
+                              const float* coef, float* x_s, int32_t B, int64_t per_sample, int32_t channels, int32_t mask_channels,
+                              int32_t mode, int32_t objective, float clip, void* stream) {
+    if (!x_t || !pred || !noise || !known || !mask || !coef || !x_s) return fail(1, "posterior_step_known: null argument");
+    if (mode < 0 || mode > 1) return fail(1, "posterior_step_known: mode must be 0 (continuous DDPM) or 1 (continuous DDIM), got %d", mode);
+    if (objective < 0 || objective > 2) return fail(1, "posterior_step_known: objective must be 0 (eps), 1 (v) or 2 (x_0), got %d", objective);
+    if (B < 1 || B > 65535) return fail(1, "posterior_step_known: batch must be in [1, 65535], got %d", B);
+    if (channels < 1 || per_sample < 4 || per_sample > (1LL << 40) / B || per_sample % channels)
+        return fail(1, "posterior_step_known: per_sample (got %lld) must be in [4, 2^40 / batch] and divide into %d channels", (long long)per_sample, channels);
+    if (per_sample % 4 || (per_sample / channels) % 4)
+        return fail(1, "posterior_step_known: per_sample (got %lld) and the plane per_sample / channels (got %lld) must each be a multiple of 4",
+                    (long long)per_sample, (long long)(per_sample / channels));
+    if (mask_channels != 1 && mask_channels != channels)
+        return fail(1, "posterior_step_known: mask_channels must be 1 or %d, got %d", channels, mask_channels);
+    if ((((uintptr_t)x_t | (uintptr_t)pred | (uintptr_t)noise | (uintptr_t)known | (uintptr_t)mask | (uintptr_t)x_s) & 15) || ((uintptr_t)coef & 3))
+        return fail(1, "posterior_step_known: x_t, prediction, noise, known, mask and x_s must be 16-byte aligned, coef 4-byte aligned");
+    PosteriorParams p{x_t, pred, noise, coef, x_s, B, per_sample, mode, objective, clip};
+    HIP_TRY(launch_posterior_known(p, known, mask, channels, mask_channels, (hipStream_t)stream));
+    return 0;
+}
+
 int r2dm_repaint_blend(const float* known, const float* noise, const float* unknown, const float* mask, const float* coef,
                        float* out, int32_t B, int64_t per_sample, int32_t channels, int32_t mask_channels, void* stream) {
     if (!known || !noise || !unknown || !mask || !coef || !out) return fail(1, "null argument");

@@ -16,8 +16,9 @@ enum { M_CT_DDPM = 0, M_CT_DDIM = 1, M_DT_DDPM = 2, M_DT_DDIM = 3, M_DT_DDIM_NOI
 enum { OBJ_EPS = 0, OBJ_V = 1, OBJ_X0 = 2 };
 
 #pragma clang fp contract(off)
+// the two halves of one element's update: the clamped estimate of x_0, and x_s from it (posterior_known_kernel puts the measurement between them)
 template <int MODE, int OBJ>
-__device__ __forceinline__ float posterior_elem(float x, float pr, float z, const float* k, float clip) {
+__device__ __forceinline__ float posterior_x0(float x, float pr, const float* k, float clip) {
     float x0;
     if (MODE == M_CT_DDPM || MODE == M_CT_DDIM) {
         const float a_t = k[0], s_t = k[1];
@@ -29,6 +30,11 @@ __device__ __forceinline__ float posterior_elem(float x, float pr, float z, cons
         else x0 = k[0] * x - k[1] * pr;
     }
     if (clip >= 0.f) x0 = fminf(fmaxf(x0, -clip), clip);
+    return x0;
+}
+
+template <int MODE>
+__device__ __forceinline__ float posterior_update(float x, float x0, float z, const float* k) {
     if (MODE == M_CT_DDPM) {
         const float a_t = k[0], a_s = k[2], c = k[4], sd = k[5];
         const float mean = a_s * (x * (1.0f - c) / a_t + c * x0);
@@ -46,6 +52,11 @@ __device__ __forceinline__ float posterior_elem(float x, float pr, float z, cons
         if (MODE == M_DT_DDIM_NOISE) xs = xs + k[6] * z;
         return xs;
     }
+}
+
+template <int MODE, int OBJ>
+__device__ __forceinline__ float posterior_elem(float x, float pr, float z, const float* k, float clip) {
+    return posterior_update<MODE>(x, posterior_x0<MODE, OBJ>(x, pr, k, clip), z, k);
 }
 
 template <int MODE, int OBJ>
@@ -101,6 +112,67 @@ hipError_t launch_posterior(const PosteriorParams& p, hipStream_t s) {
         case M_DT_DDPM: return launch_obj<M_DT_DDPM>(p, g, s);
         case M_DT_DDIM: return launch_obj<M_DT_DDIM>(p, g, s);
         case M_DT_DDIM_NOISE: return launch_obj<M_DT_DDIM_NOISE>(p, g, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+// ---- data-consistent posterior step (DDNM's null-space projection for a mask operator) ------------------------------------------
+// x_t, prediction, noise, known, mask -> x_s in one pass (5 reads + 1 write): posterior_x0, then the measurement written over the
+// estimate, x0 = m * y + (1 - m) * x0 (m a per-pixel weight, not necessarily binary), then posterior_update.  Continuous time only.
+// mask has mask_c channels (1 = broadcast over the planes of a sample); plane % 4 == 0: a quad never straddles planes.
+template <int MODE, int OBJ>
+__global__ __launch_bounds__(256) void posterior_known_kernel(PosteriorParams p, const float* __restrict__ known,
+                                                              const float* __restrict__ mask, long plane, int mask_c) {
+    const int b = blockIdx.y;
+    float k[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) k[i] = p.coef[b * 8 + i];
+    const long n4 = p.per_sample >> 2, plane4 = plane >> 2;
+    const f32x4* x4 = reinterpret_cast<const f32x4*>(p.x_t + b * p.per_sample);
+    const f32x4* p4 = reinterpret_cast<const f32x4*>(p.pred + b * p.per_sample);
+    const f32x4* z4 = reinterpret_cast<const f32x4*>(p.noise + b * p.per_sample);
+    const f32x4* y4 = reinterpret_cast<const f32x4*>(known + b * p.per_sample);
+    const f32x4* m4 = reinterpret_cast<const f32x4*>(mask + b * (mask_c == 1 ? plane : p.per_sample));
+    f32x4* o4 = reinterpret_cast<f32x4*>(p.x_s + b * p.per_sample);
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        const f32x4 x = x4[i], pr = p4[i], z = z4[i], y = y4[i];
+        const f32x4 m = m4[mask_c == 1 ? i % plane4 : i];
+        f32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float x0 = posterior_x0<MODE, OBJ>(x[j], pr[j], k, p.clip);
+            x0 = m[j] * y[j] + (1.0f - m[j]) * x0;
+            o[j] = posterior_update<MODE>(x[j], x0, z[j], k);
+        }
+        o4[i] = o;
+    }
+}
+
+template <int MODE>
+static hipError_t launch_known_obj(const PosteriorParams& p, const float* known, const float* mask, long plane, int mask_c, dim3 g,
+                                   hipStream_t s) {
+    switch (p.objective) {
+        case OBJ_EPS: posterior_known_kernel<MODE, OBJ_EPS><<<g, 256, 0, s>>>(p, known, mask, plane, mask_c); break;
+        case OBJ_V: posterior_known_kernel<MODE, OBJ_V><<<g, 256, 0, s>>>(p, known, mask, plane, mask_c); break;
+        case OBJ_X0: posterior_known_kernel<MODE, OBJ_X0><<<g, 256, 0, s>>>(p, known, mask, plane, mask_c); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// (arguments validated by r2dm_posterior_step_known; checked again here, since the kernel reads quads and has no tail)
+hipError_t launch_posterior_known(const PosteriorParams& p, const float* known, const float* mask, int channels, int mask_c,
+                                  hipStream_t s) {
+    if (p.B < 1 || p.B > 65535 || p.per_sample < 4 || (p.per_sample & 3) || channels < 1 || p.per_sample % channels ||
+        (p.per_sample / channels) % 4 || (mask_c != 1 && mask_c != channels) || !p.noise || !known || !mask)
+        return hipErrorInvalidValue;
+    long bx = (p.per_sample / 4 + 255) / 256;  // (launch_posterior's shape)
+    if (bx > 1024) bx = 1024;
+    const dim3 g((unsigned)bx, p.B);
+    const long plane = p.per_sample / channels;
+    switch (p.mode) {
+        case M_CT_DDPM: return launch_known_obj<M_CT_DDPM>(p, known, mask, plane, mask_c, g, s);
+        case M_CT_DDIM: return launch_known_obj<M_CT_DDIM>(p, known, mask, plane, mask_c, g, s);
     }
     return hipErrorInvalidValue;
 }

@@ -828,6 +828,106 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
                     x_t = x
         return torch.stack(out) if return_all else x_s
 
+    # -- data-consistent completion (DDNM's null-space projection for a mask operator; not in the reference) ----------------
+    @torch.inference_mode()
+    def complete(self, known, mask, num_steps: int, num_resample_steps: int = 1, jump_length: int = 1, t_start: float = 1.0, init=None,
+                 mode: Literal["ddpm", "ddim"] = "ddpm", ddim_eta: float = 0.0, exact_known: bool = True, progress: bool = True, rng=None,
+                 return_all: bool = False):
+        """Completion of ``known`` (B,C,H,W) under ``mask`` (B | 1, 1 | C, H, W; 1 = measured, any weight in [0, 1] is taken as such) with
+        one denoiser call per reverse sub-step: the clamped estimate of x_0 gets the measurement written over its known pixels,
+        ``x0 = mask * known + (1 - mask) * x0``, and x_s is sampled from the ordinary posterior given that x_0 -- one fused kernel
+        (``r2dm_posterior_step_known``) and one noise draw, no known-region noise and no separate blend (Wang, Yu, Zhang: DDNM, ICLR 2023).
+
+        The schedule is ``repaint``'s over ``linspace(t_start, 0, num_steps + 1)``: step i is ``jump_length`` sub-steps along
+        ``t + linspace(0, 1, jump_length + 1) * (s - t)``; after a group of reverse sub-steps ``q_step`` travels back and the group is
+        repeated, ``num_resample_steps`` times in all (not after the last one of a step, nor on the last step).  ``num_resample_steps = 1``
+        is a valid sampler of its own.  Draw order: the start (``init=None``: ``randn(B, *sampling_shape)`` at ``t_start = 1``; else
+        ``q_step_from_x_0(init, t_start)``, one ``randn_like``), one ``randn_like`` per denoiser call in every mode (as ``p_step``), one per
+        forward sub-step.  With an all-zero mask and ``num_resample_steps = jump_length = 1`` this is ``sample`` / ``sample_from`` on the same
+        draws.  ``exact_known``: the result is ``mask * known + (1 - mask) * x`` (``r2dm_repaint_blend``), equal to ``known`` on a binary
+        mask; without it the known pixels carry the last step's ``sigma(0) * z``.  ``return_all``: the stack ``repaint`` returns -- the
+        start, then the x_s of every resampling, the last one projected like the result.  A range-guard trip is handled as in ``repaint``:
+        the call is repeated once on the wide-range split from the generator states it started with."""
+        self._objective_id()
+        C, H, W = self.sampling_shape
+        if known.dim() != 4 or known.shape[0] < 1 or tuple(known.shape[1:]) != (C, H, W):
+            raise ValueError(f"known must be (B, {C}, {H}, {W}) with B >= 1, got {tuple(known.shape)}")
+        B = known.shape[0]
+        if mask.dim() != 4 or mask.shape[0] not in (1, B) or mask.shape[1] not in (1, C) or tuple(mask.shape[2:]) != (H, W):
+            raise ValueError(f"mask must be ({B} | 1, 1 | {C}, {H}, {W}), got {tuple(mask.shape)}")
+        for name, n in (("num_steps", num_steps), ("num_resample_steps", num_resample_steps), ("jump_length", jump_length)):
+            if int(n) != n or n < 1:
+                raise ValueError(f"{name} must be an integer >= 1, got {n}")
+        if not 0.0 < float(t_start) <= 1.0:
+            raise ValueError(f"t_start must be in (0, 1], got {t_start}")
+        if init is None and float(t_start) != 1.0:
+            raise ValueError(f"t_start = {t_start} needs init (the x_0 that is noised to t_start): a fresh draw starts at t_start = 1")
+        if init is not None and init.shape != known.shape:
+            raise ValueError(f"init {tuple(init.shape)} must have known's shape {tuple(known.shape)}")
+        if mode not in ("ddpm", "ddim"):
+            raise ValueError(f"invalid mode {mode}")
+        self._refuse_cpu("complete", known)
+        dev = known.device
+        known = _lib.f32c(known)
+        mask = _lib.f32c(mask.to(dev).expand(B, -1, H, W))
+        init = None if init is None else _lib.f32c(init.to(dev))
+        args = (known, mask, int(num_steps), int(num_resample_steps), int(jump_length), float(t_start), init, mode, float(ddim_eta), exact_known,
+                progress, rng, return_all)
+        snap = _rng_snapshot(rng, self.device)
+        try:
+            return self._complete(*args)
+        except _lib.R2DMRangeFallback:
+            _rng_restore(snap, rng, self.device)
+            return self._complete(*args)
+
+    def _complete(self, known, mask, num_steps, num_resample_steps, jump_length, t_start, init, mode, ddim_eta, exact_known, progress, rng,
+                  return_all):
+        B, dev = known.shape[0], known.device
+        on_dev = self._on_device(dev)  # (the grid itself is then the device's linspace, as in _table_rows)
+        if init is None:
+            x_t = self.randn(B, *self.sampling_shape, rng=rng, device=dev)
+        else:
+            x_t, _ = self.q_step_from_x_0(init, torch.full((B,), t_start, device=dev if on_dev else None), rng=rng)
+        steps = torch.linspace(t_start, 0.0, num_steps + 1, device=dev if on_dev else None)[None].repeat_interleave(B, dim=0)
+        frac = torch.linspace(0, 1, jump_length + 1, device=dev if on_dev else None)[None]
+        objective, clip = self._objective_id(), self._clip()
+        total = num_steps * num_resample_steps * jump_length
+        out = [x_t] if return_all else None
+        x_s = x_t
+        with _range_guard(self.model):
+            for i in tqdm(range(num_steps), desc="completing", leave=False, disable=not progress):
+                t, s = steps[:, [i]], steps[:, [i + 1]]
+                r = t + frac * (s - t)
+                rows = {}  # the sub-steps' scalars: evaluated once per step, shared by its resamplings
+                for j in range(num_resample_steps):
+                    x = x_t
+                    for k in range(jump_length):
+                        if k not in rows:
+                            cond, coef, mode_id = self._coefficients(r[:, k], r[:, k + 1], mode, ddim_eta)
+                            rows[k] = (cond.to(dev), coef.to(dev), mode_id)
+                        cond, coef, mode_id = rows[k]
+                        noise, drawn = self._randn_like_ahead(x, rng=rng)
+                        prediction = self.model(x, cond)
+                        if i == 0 and j == 0 and k == 0 and _early_range_check(self.model, total):
+                            prediction = self.model(x, cond)  # (repeated on the wide-range operand split)
+                        if drawn is not None:
+                            torch.cuda.current_stream(dev).wait_event(drawn)
+                        x = _lib.posterior_step_known(x, prediction, noise, known, mask, coef, mode_id, objective, clip)
+                    x_s = x
+                    if return_all:
+                        out.append(x_s)
+                    if i == num_steps - 1 or j == num_resample_steps - 1:
+                        x_t = x
+                        break
+                    for k in range(jump_length, 0, -1):
+                        x = self.q_step(x, r[:, k - 1], r[:, k], rng=rng)
+                    x_t = x
+        if exact_known:  # mask * (known * 1 + known * 0) + (1 - mask) * x: the blend kernel with known as its noise operand
+            x_s = _lib.repaint_blend(known, known, x_s, mask, torch.tensor([[1.0, 0.0]], device=dev).repeat(B, 1))
+            if return_all:
+                out[-1] = x_s
+        return torch.stack(out) if return_all else x_s
+
 
 # --------------------------------------------------------------------------------------
 class DiscreteTimeGaussianDiffusion(GaussianDiffusion):
@@ -944,3 +1044,6 @@ class DiscreteTimeGaussianDiffusion(GaussianDiffusion):
 
     def sample_from(self, *args, **kwargs):
         raise NotImplementedError("sample_from is implemented for continuous time only (ContinuousTimeGaussianDiffusion)")
+
+    def complete(self, *args, **kwargs):
+        raise NotImplementedError("complete is implemented for continuous time only (ContinuousTimeGaussianDiffusion)")
