@@ -6,7 +6,7 @@ images, and ``samples_bev.png``, the bird's-eye views; ``--render_frames`` adds 
 stack, ``--render_normals`` the view of the reference's training monitor (train.py:227-239): ``samples_normal.png``, the surface normals
 as colours, and ``samples_bev_normal.png``, the bird's-eye views coloured by them.  With ``--points_dir DIR`` the final samples are also written as Velodyne scans ``DIR/samples_%04d.bin`` (fp32 [x, y, z,
 reflectance] rows in scan order, r2dm_amd.pointcloud), with ``--points_ply`` also as ``.ply`` coloured by the bird's-eye views' viridis
-height map.  Still missing from the reference's script: the mp4 (no encoder here) and the antialiased 512-pixel resize of its frames."""
+height map.  ``--mode dpmpp`` (extension) samples with DPM-Solver++(2M), ``ddpm.sample_dpm``, meant for ``--sampling_steps`` 16 to 32.  Still missing from the reference's script: the mp4 (no encoder here) and the antialiased 512-pixel resize of its frames."""
 import argparse
 from pathlib import Path
 
@@ -20,7 +20,10 @@ def main(args):
     if args.seed is not None:
         torch.manual_seed(args.seed)
     ddpm, lidar_utils, _ = r2dm_amd.setup_model(args.ckpt, device=args.device, max_batch=args.batch_size)
-    xs = ddpm.sample(batch_size=args.batch_size, num_steps=args.sampling_steps, mode=args.mode, return_all=True).clamp(-1, 1)
+    if args.mode == "dpmpp":  # (extension: DPM-Solver++(2M), meant for 16-32 steps)
+        xs = ddpm.sample_dpm(batch_size=args.batch_size, num_steps=args.sampling_steps, return_all=True).clamp(-1, 1)
+    else:
+        xs = ddpm.sample(batch_size=args.batch_size, num_steps=args.sampling_steps, mode=args.mode, return_all=True).clamp(-1, 1)
     xs = lidar_utils.denormalize(xs)
     xs[:, :, [0]] = lidar_utils.revert_depth(xs[:, :, [0]]) / lidar_utils.max_depth
     points = lidar_utils.postprocess(_last_sample_normalized(xs, lidar_utils))
@@ -80,11 +83,12 @@ def _last_sample_normalized(xs, lidar_utils):
     return lidar_utils.normalize(last)
 
 
-if __name__ == "__main__":
+def parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("--ckpt", type=Path, required=True)
     parser.add_argument("--device", choices=["cuda"], default="cuda")
-    parser.add_argument("--mode", choices=["ddpm", "ddim"], default="ddpm")
+    parser.add_argument("--mode", choices=["ddpm", "ddim", "dpmpp"], default="ddpm",
+                        help="dpmpp (extension): the DPM-Solver++(2M) sampler, ddpm.sample_dpm; use it with --sampling_steps 16 to 32")
     parser.add_argument("--batch_size", type=int, default=1)
     parser.add_argument("--sampling_steps", type=int, default=256)
     parser.add_argument("--output", type=Path, default=Path("samples.pt"))
@@ -96,6 +100,10 @@ if __name__ == "__main__":
                         help="with --render_dir: also samples_normal.png and samples_bev_normal.png, the surface normals and the bird's-eye views coloured by them")
     parser.add_argument("--points_dir", type=Path, default=None, help="also write the final samples as Velodyne scans samples_%%04d.bin there")
     parser.add_argument("--points_ply", action="store_true", help="with --points_dir: also samples_%%04d.ply, coloured by height")
-    args = parser.parse_args()
+    return parser
+
+
+if __name__ == "__main__":
+    args = parser().parse_args()
     args.device = torch.device(args.device)
     main(args)

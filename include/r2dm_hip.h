@@ -167,6 +167,20 @@ int r2dm_posterior_step_known(const float* x_t, const float* prediction, const f
                               const float* coef, float* x_s, int32_t batch, int64_t per_sample, int32_t channels, int32_t mask_channels,
                               int32_t mode, int32_t objective, float clip, void* stream);
 
+/* -- DPM-Solver++(2M) update (Lu et al. 2022: the second-order multistep solver of the probability-flow ODE in data-prediction form, on the
+ *    half-log-SNR axis; continuous time).  One pass in float32, not contracted; per element, in this order:
+ *      x0  = as r2dm_posterior_step (eps: (x - s_t*pr)/a_t | v: a_t*x - s_t*pr | x_0: pr), clamped to [-clip, clip] (clip < 0: no clamp)
+ *      x_s = c_x*x + c_0*x0                         x0_prev NULL: a first-order row; c_1 is not read
+ *      x_s = (c_x*x + c_0*x0) + c_1*x0_prev         otherwise
+ *    coef is (B,8) = (a_t, s_t, c_x, c_0, c_1, 0, 0, 0), host-computed scalars in device memory (r2dm_amd/diffusion.py: _dpm_table).
+ *    Both x_s and x0 are written; x0, the clamped estimate, is the next step's x0_prev.  x0 may be x0_prev's buffer (every element is read
+ *    before the same thread writes it); no other aliasing of an output with an input or with the other output is supported.
+ *    Refused (status 1, "dpm_step: ..." in r2dm_last_error, nothing launched): a null pointer other than x0_prev; an objective other than
+ *    0 / 1 / 2; a batch outside [1, 65535]; per_sample not a multiple of 4; x_t, prediction, x0_prev, x_s or x0 not 16-byte aligned (all are
+ *    read and written as quads), coef not 4-byte aligned; x_s equal to x_t, prediction, x0_prev or x0, or x0 equal to x_t or prediction. */
+int r2dm_dpm_step(const float* x_t, const float* prediction, const float* x0_prev, const float* coef, float* x_s, float* x0, int32_t batch,
+                  int64_t per_sample, int32_t objective, float clip, void* stream);
+
 /* -- RePaint completion (models/diffusion/continuous_time.py:169-190 q_step_from_x_0 / q_step, :287-303 the
  *    known/unknown blend inside repaint()).  coef is (B,2) host-computed scalars.
  *    blend:  out = mask * (known*alpha + noise*sigma) + (1 - mask) * unknown,  coef = (alpha, sigma) at step s;

@@ -6,7 +6,8 @@ reference has no script for it).
 ``completion_demo.py`` does), are encoded by DDIM inversion up to ``--t_end`` (``ddpm.invert``, ``--steps`` steps), their latents are
 interpolated spherically at ``--frames`` weights from 0 to 1 (``r2dm_amd.latent.slerp``) and every frame is decoded by the DDIM sampler
 from there (``ddpm.sample_from(..., clip=False)``): ``r2dm_amd.latent.interpolate``.  ``--seed_a S --seed_b T``: the two latents are the
-draws at t = 1 that ``setup_rng([S])`` and ``setup_rng([T])`` give ``ddpm.sample``; nothing is inverted.
+draws at t = 1 that ``setup_rng([S])`` and ``setup_rng([T])`` give ``ddpm.sample``; nothing is inverted.  ``--decoder dpmpp`` decodes the
+interpolated latents with the DPM-Solver++(2M) sampler instead (``ddpm.sample_dpm(x_t=..., clip=False)``).
 
 Written to ``--out_dir``: ``interpolation.png``, one column per frame -- the colour-mapped range image over the reflectance image over the
 bird's-eye view (r2dm_amd.render) -- and ``interpolation.pt`` with ``latents`` and ``frames`` (F,1,2,H,W), for scans also ``x_a`` and
@@ -53,7 +54,7 @@ def main(args):
     saved, row = {}, None
     if scans:
         x_a, x_b = (known_of_scan(p, lidar_utils, cfg, device) for p in (args.scan_a, args.scan_b))
-        frames, latents = latent.interpolate(ddpm, x_a, x_b, args.frames, args.steps, t_end=args.t_end, return_latents=True)
+        frames, latents = latent.interpolate(ddpm, x_a, x_b, args.frames, args.steps, t_end=args.t_end, return_latents=True, decoder=args.decoder)
         saved.update(x_a=x_a.cpu(), x_b=x_b.cpu())
         cos = torch.nn.functional.cosine_similarity(latents[0].flatten(1).double(), latents[-1].flatten(1).double()).clamp(-1, 1)
         row = {"frames": args.frames, "steps": args.steps, "t_end": args.t_end, "omega": [float(f"{v:.6g}") for v in cos.acos().tolist()],
@@ -62,7 +63,11 @@ def main(args):
         z = [ddpm.randn(1, *ddpm.sampling_shape, rng=r2dm_amd.setup_rng([s], device), device=device) for s in (args.seed_a, args.seed_b)]
         latents = latent.slerp(z[0], z[1], torch.linspace(0.0, 1.0, args.frames).tolist())
         cap = ddpm.model.max_batch
-        frames = torch.cat([ddpm.sample_from(latents[k:k + cap, 0], args.steps, progress=False, mode="ddim") for k in range(0, args.frames, cap)])[:, None]
+        if args.decoder == "dpmpp":
+            decode = lambda z: ddpm.sample_dpm(z.shape[0], args.steps, x_t=z, clip=False, progress=False)
+        else:
+            decode = lambda z: ddpm.sample_from(z, args.steps, progress=False, mode="ddim")
+        frames = torch.cat([decode(latents[k:k + cap, 0]) for k in range(0, args.frames, cap)])[:, None]
     saved.update(latents=latents.cpu(), frames=frames.cpu())
 
     args.out_dir.mkdir(parents=True, exist_ok=True)
@@ -90,6 +95,8 @@ def parser():
     p.add_argument("--frames", type=int, default=8, help="frames from A to B, both ends included")
     p.add_argument("--steps", type=int, default=32, help="steps of the inversion and of the decoding")
     p.add_argument("--t_end", type=float, default=1.0, help="the noise level the scans are inverted to, in (0, 1]")
+    p.add_argument("--decoder", choices=["ddim", "dpmpp"], default="ddim",
+                   help="how the interpolated latents are decoded: the DDIM sampler, or dpmpp: DPM-Solver++(2M), ddpm.sample_dpm(x_t=..., clip=False)")
     p.add_argument("--out_dir", type=Path, default=Path("interpolation"))
     p.add_argument("--points_dir", type=Path, default=None, help="also write every frame as a Velodyne .bin file there")
     return p

@@ -81,6 +81,7 @@ SIGNATURES = {
     "r2dm_profile_event_overhead": (c_int32, [_P, _P, POINTER(ctypes.c_double), POINTER(ctypes.c_double)]),
     "r2dm_posterior_step": (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int64, c_int32, c_int32, c_float, _P]),
     "r2dm_posterior_step_known": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32, c_float, _P]),
+    "r2dm_dpm_step": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int64, c_int32, c_float, _P]),
     "r2dm_repaint_blend": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int64, c_int32, c_int32, _P]),
     "r2dm_q_step": (c_int32, [_P, _P, _P, _P, c_int32, c_int64, _P]),
     "r2dm_diffusion_loss_scratch_bytes": (c_size_t, [c_int32, c_int32, c_int64]),
@@ -239,6 +240,29 @@ def posterior_step_known(x_t, pred, noise, known, mask, coef, mode: int, objecti
         check(lib().r2dm_posterior_step_known(ptr(x_t), ptr(pred), ptr(noise), ptr(known), ptr(mask), ptr(coef), ptr(out), B,
                                               x_t.numel() // B, C, mask.shape[1], mode, objective, float(clip), stream_ptr(x_t.device)))
     return out
+
+
+def dpm_step(x_t, pred, x0_prev, coef, objective: int, clip: float, x0_out: Optional[torch.Tensor] = None):
+    """One DPM-Solver++(2M) update (``r2dm_dpm_step``) -> ``(x_s, x0)``: ``x0`` the clamped estimate of x_0 (``posterior_step``'s), ``x_s =
+    c_x x_t + c_0 x0`` with ``x0_prev=None`` (a first-order row), else ``(c_x x_t + c_0 x0) + c_1 x0_prev``; ``coef`` (B,8) = (alpha_t, sigma_t,
+    c_x, c_0, c_1, 0, 0, 0).  ``x0_out``: a float32 contiguous buffer of ``x_t``'s shape to write ``x0`` into (it may be ``x0_prev`` itself); None: a new one."""
+    require_gpu(x_t, "x_t")
+    x_t, pred, coef = f32c(x_t), f32c(pred), f32c(coef)
+    x0_prev = None if x0_prev is None else f32c(x0_prev)
+    if x_t.dim() < 2 or any(t is not None and (t.shape != x_t.shape or t.device != x_t.device) for t in (pred, x0_prev, x0_out)) \
+            or coef.shape != (x_t.shape[0], 8) or coef.device != x_t.device:
+        raise ValueError(f"x_t {tuple(x_t.shape)}, prediction {tuple(pred.shape)}, x0_prev and x0_out must have one (B,...) shape on one device, "
+                         f"coef {tuple(coef.shape)} must be (B,8)")
+    if x0_out is None:
+        x0_out = torch.empty_like(x_t)
+    elif x0_out.dtype != torch.float32 or not x0_out.is_contiguous():
+        raise ValueError("x0_out must be a contiguous float32 tensor")
+    out = torch.empty_like(x_t)
+    B = x_t.shape[0]
+    with torch.cuda.device(x_t.device):
+        check(lib().r2dm_dpm_step(ptr(x_t), ptr(pred), ptr(x0_prev), ptr(coef), ptr(out), ptr(x0_out), B, x_t.numel() // B, objective, float(clip),
+                                  stream_ptr(x_t.device)))
+    return out, x0_out
 
 
 def repaint_blend(known, noise, unknown, mask, coef) -> torch.Tensor:

@@ -270,6 +270,21 @@ hipError_t launch_posterior(const PosteriorParams& p, hipStream_t s);
 // the same step with the measurement written over the x_0 estimate: x0 = mask * known + (1 - mask) * x0 (continuous-time modes 0 / 1)
 hipError_t launch_posterior_known(const PosteriorParams& p, const float* known, const float* mask, int channels, int mask_c,
                                   hipStream_t s);
+// DPM-Solver++(2M) update: x_s = c_x x_t + c_0 x0 [+ c_1 x0_prev] with x0 the clamped estimate of the posterior step, also written out;
+// coef [B][8] = (alpha_t, sigma_t, c_x, c_0, c_1, 0, 0, 0).  x0_prev null: the first-order row.  x0 may be x0_prev's buffer.
+struct DpmParams {
+    const float* x_t;
+    const float* pred;
+    const float* x0_prev;  // may be nullptr
+    const float* coef;
+    float* x_s;
+    float* x0;
+    int B;
+    long per_sample;
+    int objective;
+    float clip;  // < 0: no clamping
+};
+hipError_t launch_dpm_step(const DpmParams& p, hipStream_t s);
 // RePaint (reference continuous_time.py:169-190,287-303): forward re-noising and known/unknown blend
 hipError_t launch_repaint_blend(const float* known, const float* noise, const float* unknown, const float* mask,
                                 const float* coef, float* out, int B, long per_sample, int channels, int mask_c,

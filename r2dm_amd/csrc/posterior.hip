@@ -177,6 +177,64 @@ hipError_t launch_posterior_known(const PosteriorParams& p, const float* known, 
     return hipErrorInvalidValue;
 }
 
+// ---- DPM-Solver++(2M) update (Lu et al. 2022, the data-prediction multistep solver on the half-log-SNR axis) --------------------------------
+// x_t, prediction[, x0_prev] -> x_s, x0 in one pass (2 or 3 reads + 2 writes).  coef[b] = (alpha_t, sigma_t, c_x, c_0, c_1, 0, 0, 0), host-computed.
+// x0 is the clamped estimate of posterior_x0 (the next step's history); x_s = c_x x + c_0 x0 (first order, x0_prev not read) or
+// (c_x x + c_0 x0) + c_1 x0_prev.  x0 may be x0_prev's buffer: a thread reads its quad of x0_prev before it writes the same quad of x0, and no
+// other thread touches that quad -- hence no __restrict__ on the two.
+template <int OBJ, bool SECOND>
+__global__ __launch_bounds__(256) void dpm_step_kernel(const float* __restrict__ x_t, const float* __restrict__ pred, const float* x0_prev,
+                                                       const float* __restrict__ coef, float* __restrict__ x_s, float* x0_out, long per_sample,
+                                                       float clip) {
+    const int b = blockIdx.y;
+    float k[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) k[i] = coef[b * 8 + i];
+    const float c_x = k[2], c_0 = k[3], c_1 = k[4];
+    const long n4 = per_sample >> 2;
+    const f32x4* x4 = reinterpret_cast<const f32x4*>(x_t + b * per_sample);
+    const f32x4* p4 = reinterpret_cast<const f32x4*>(pred + b * per_sample);
+    const f32x4* h4 = SECOND ? reinterpret_cast<const f32x4*>(x0_prev + b * per_sample) : nullptr;
+    f32x4* o4 = reinterpret_cast<f32x4*>(x_s + b * per_sample);
+    f32x4* e4 = reinterpret_cast<f32x4*>(x0_out + b * per_sample);
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        const f32x4 x = x4[i], pr = p4[i];
+        f32x4 h = {0.f, 0.f, 0.f, 0.f};
+        if (SECOND) h = h4[i];
+        f32x4 o, e;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            e[j] = posterior_x0<M_CT_DDPM, OBJ>(x[j], pr[j], k, clip);
+            o[j] = c_x * x[j] + c_0 * e[j];
+            if (SECOND) o[j] = o[j] + c_1 * h[j];
+        }
+        o4[i] = o;
+        e4[i] = e;
+    }
+}
+
+template <int OBJ>
+static hipError_t launch_dpm_obj(const DpmParams& p, dim3 g, hipStream_t s) {
+    if (p.x0_prev) dpm_step_kernel<OBJ, true><<<g, 256, 0, s>>>(p.x_t, p.pred, p.x0_prev, p.coef, p.x_s, p.x0, p.per_sample, p.clip);
+    else dpm_step_kernel<OBJ, false><<<g, 256, 0, s>>>(p.x_t, p.pred, nullptr, p.coef, p.x_s, p.x0, p.per_sample, p.clip);
+    return hipGetLastError();
+}
+
+// (arguments validated by r2dm_dpm_step; checked again here, since the kernel reads quads and has no tail)
+hipError_t launch_dpm_step(const DpmParams& p, hipStream_t s) {
+    if (p.B < 1 || p.B > 65535 || p.per_sample < 4 || (p.per_sample & 3) || !p.x_t || !p.pred || !p.coef || !p.x_s || !p.x0 || p.x_s == p.x_t)
+        return hipErrorInvalidValue;
+    long bx = (p.per_sample / 4 + 255) / 256;  // (launch_posterior's shape)
+    if (bx > 1024) bx = 1024;
+    const dim3 g((unsigned)bx, p.B);
+    switch (p.objective) {
+        case OBJ_EPS: return launch_dpm_obj<OBJ_EPS>(p, g, s);
+        case OBJ_V: return launch_dpm_obj<OBJ_V>(p, g, s);
+        case OBJ_X0: return launch_dpm_obj<OBJ_X0>(p, g, s);
+    }
+    return hipErrorInvalidValue;
+}
+
 // ---- LiDAR post-processing ("next" row f.1) ------------------------------------------------
 // sample (B,2,H,W) in [-1,1] -> (B,5,H,W): metric depth (decoded by the checkpoint's depth format, masked to
 // (min_depth, max_depth)), Cartesian x,y,z along the per-pixel ray angles, reflectance in [0,1].

@@ -78,14 +78,20 @@ def slerp(a: torch.Tensor, b: torch.Tensor, weights: Sequence[float], return_coe
     return (out, coef64) if return_coefficients else out
 
 
-def _decode(ddpm, latents: torch.Tensor, num_steps: int, t_start: float, mode: str, ddim_eta: float, rng) -> torch.Tensor:
+def _decode(ddpm, latents: torch.Tensor, num_steps: int, t_start: float, mode: str, ddim_eta: float, rng, decoder: str = "ddim") -> torch.Tensor:
     """``sample_from(..., clip=False)`` over (N,C,H,W) latents in chunks of at most the model's ``max_batch``; ``rng`` (None, one generator,
-    or a list with one generator per latent) follows the chunks."""
+    or a list with one generator per latent) follows the chunks.  ``decoder="dpmpp"``: ``sample_dpm(x_t=..., clip=False)`` instead, which draws
+    nothing (``mode``, ``ddim_eta`` and ``rng`` are not read)."""
+    if decoder not in ("ddim", "dpmpp"):
+        raise ValueError(f"decoder must be 'ddim' or 'dpmpp', got {decoder!r}")
     cap = int(getattr(getattr(ddpm.model, "_orig_mod", ddpm.model), "max_batch", 0)) or latents.shape[0]
     frames = []
     for i in range(0, latents.shape[0], cap):
         part = latents[i:i + cap]
         r = rng[i:i + cap] if isinstance(rng, list) else rng
+        if decoder == "dpmpp":
+            frames.append(ddpm.sample_dpm(part.shape[0], num_steps, x_t=part, t_start=t_start, clip=False, progress=False))
+            continue
         frames.append(ddpm.sample_from(part, num_steps, t_start=t_start, progress=False, rng=r, mode=mode, ddim_eta=ddim_eta, clip=False))
     return torch.cat(frames)
 
@@ -96,13 +102,14 @@ def _invert(ddpm, x: torch.Tensor, num_steps: int, t_end: float) -> torch.Tensor
 
 
 def interpolate(ddpm, x_a: torch.Tensor, x_b: torch.Tensor, num_frames: int, num_steps: int, t_end: float = 1.0, mode: str = "ddim",
-                ddim_eta: float = 0.0, rng=None, return_latents: bool = False):
+                ddim_eta: float = 0.0, rng=None, return_latents: bool = False, decoder: str = "ddim"):
     """Latent interpolation between two image batches ``x_a``, ``x_b`` (B,C,H,W) in [-1,1]: both are inverted to ``t_end`` in one batch
     (``ddpm.invert``, ``num_steps`` steps), the latents are slerped at ``linspace(0, 1, num_frames)`` and every frame is decoded with
     ``ddpm.sample_from(..., t_start=t_end, clip=False)`` in chunks of at most the model's ``max_batch`` -> (num_frames,B,C,H,W), frame 0
     the reconstruction of ``x_a`` and the last one that of ``x_b``.  ``rng`` is ``sample_from``'s: None, one generator, or a list of
     ``num_frames * B`` generators in frame-major order (read for ``mode="ddpm"`` and for DDIM with ``ddim_eta > 0`` only in effect).
-    ``return_latents``: also the (num_frames,B,C,H,W) interpolated latents."""
+    ``return_latents``: also the (num_frames,B,C,H,W) interpolated latents.  ``decoder="dpmpp"``: the frames are decoded by
+    ``ddpm.sample_dpm(x_t=..., t_start=t_end, clip=False)`` (DPM-Solver++(2M), ``num_steps`` steps; the inversion stays DDIM's)."""
     if x_a.shape != x_b.shape or x_a.dim() != 4:
         raise ValueError(f"x_a {tuple(x_a.shape)} and x_b {tuple(x_b.shape)} must have one (B,C,H,W) shape")
     if int(num_frames) < 2:
@@ -110,7 +117,7 @@ def interpolate(ddpm, x_a: torch.Tensor, x_b: torch.Tensor, num_frames: int, num
     B = x_a.shape[0]
     z = _invert(ddpm, torch.cat([x_a, x_b.to(x_a.device)]), num_steps, t_end)
     latents = slerp(z[:B], z[B:], torch.linspace(0.0, 1.0, int(num_frames)).tolist())
-    frames = _decode(ddpm, latents.flatten(0, 1), num_steps, t_end, mode, ddim_eta, rng).reshape(latents.shape)
+    frames = _decode(ddpm, latents.flatten(0, 1), num_steps, t_end, mode, ddim_eta, rng, decoder).reshape(latents.shape)
     return (frames, latents) if return_latents else frames
 
 
