@@ -3,7 +3,7 @@
 scan, every 4th beam, a random half of the beams, a random 10 % of the points).
 
 Same options (``--ckpt --num_steps --num_resample_steps --jump_length --seed``); ``--method ddnm`` (extension) completes with the
-data-consistent sampler ``ddpm.complete`` instead, ``--num_resample_steps`` then being its resampling count; the scan comes from ``--scan FILE.bin`` (a raw
+data-consistent sampler ``ddpm.complete`` instead, ``--num_resample_steps`` then being its resampling count, ``--method dpmpp`` with ``ddpm.complete_dpm`` (the same projection on DPM-Solver++(2M), ``--dpmpp_eta``; no resampling; its image is named ``dpmpp_completion_...``); the scan comes from ``--scan FILE.bin`` (a raw
 Velodyne file, projected on the GPU by r2dm_amd.projection with the checkpoint's ``cfg.data.projection``) instead of the
 HuggingFace dataset lookup, and ``--out`` names the image.  The corruption masks are drawn as the reference draws them
 (completion_demo.py:81-87: the same CPU draws after ``torch.manual_seed(seed)``), the completion is the same
@@ -19,7 +19,7 @@ labels with the reference's post-processors at their defaults (r2dm_amd.postproc
 the refined labels are the ones drawn and saved.  ``--out_scan FILE.bin`` (extension) also writes the completed scan -- the completion of
 the full input, the first column -- as a Velodyne file in scan order (r2dm_amd.pointcloud)."""
 import math
-from argparse import ArgumentParser
+from argparse import SUPPRESS, ArgumentParser
 from pathlib import Path
 
 import torch
@@ -105,9 +105,13 @@ def main(args):
 
     mask = corruption_masks(x_orig, args.seed).to(device)
     x_in = mask * x_orig + (1 - mask) * -1
-    completer = ddpm.complete if getattr(args, "method", "repaint") == "ddnm" else ddpm.repaint
-    x_out = completer(known=x_in, mask=mask, num_steps=args.num_steps, num_resample_steps=args.num_resample_steps,
-                      jump_length=args.jump_length, rng=r2dm_amd.setup_rng(range(BATCH), device=device)).clamp(-1, 1)
+    if getattr(args, "method", "repaint") == "dpmpp":  # (no resampling on the multistep solver: --num_resample_steps, --jump_length are not read)
+        x_out = ddpm.complete_dpm(known=x_in, mask=mask, num_steps=args.num_steps, eta=getattr(args, "dpmpp_eta", 1.0),
+                                  rng=r2dm_amd.setup_rng(range(BATCH), device=device)).clamp(-1, 1)
+    else:
+        completer = ddpm.complete if getattr(args, "method", "repaint") == "ddnm" else ddpm.repaint
+        x_out = completer(known=x_in, mask=mask, num_steps=args.num_steps, num_resample_steps=args.num_resample_steps,
+                          jump_length=args.jump_length, rng=r2dm_amd.setup_rng(range(BATCH), device=device)).clamp(-1, 1)
 
     W = x_in.shape[-1]
     saved = {"x_in": x_in.cpu(), "mask": mask.cpu(), "x_out": x_out.cpu()}
@@ -140,8 +144,11 @@ def parser():
     p = ArgumentParser()
     p.add_argument("--ckpt", type=Path, required=True)
     p.add_argument("--num_steps", type=int, default=32)
-    p.add_argument("--method", choices=("repaint", "ddnm"), default="repaint",
-                   help="repaint: the reference's sampler; ddnm: the data-consistent sampler (ddpm.complete), one denoiser call per step")
+    p.add_argument("--method", choices=("repaint", "ddnm", "dpmpp"), default="repaint",
+                   help="repaint: the reference's sampler; ddnm: the data-consistent sampler (ddpm.complete), one denoiser call per step; "
+                        "dpmpp: the same projection on DPM-Solver++(2M) (ddpm.complete_dpm), use it with --num_steps 16 to 32")
+    p.add_argument("--dpmpp_eta", type=float, default=SUPPRESS,  # (an attribute of the parsed arguments only when given)
+                   help="the dpmpp method's share of fresh noise per step (default 1: SDE-DPM-Solver++(2M); 0: deterministic)")
     p.add_argument("--num_resample_steps", type=int, default=16, help="the chosen method's resampling count")
     p.add_argument("--jump_length", type=int, default=1)
     p.add_argument("--seed", type=int, default=0)
@@ -158,6 +165,6 @@ def parser():
 if __name__ == "__main__":
     args = parser().parse_args()
     if args.out is None:
-        args.out = Path(("ddnm_" if args.method == "ddnm" else "") + f"completion_T-{args.num_steps:04d}_r-{args.num_resample_steps:04d}_j-{args.jump_length:04d}.png")
+        args.out = Path({"ddnm": "ddnm_", "dpmpp": "dpmpp_"}.get(args.method, "") + f"completion_T-{args.num_steps:04d}_r-{args.num_resample_steps:04d}_j-{args.jump_length:04d}.png")
     print(vars(args))
     main(args)

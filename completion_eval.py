@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Scores scan completion on held-out scans, on the GPU: every scan is corrupted (``--corruption``: ``full``, ``beams:K``,
 ``random_beams:P``, ``random_points:P``; repeatable), completed by RePaint, by the data-consistent sampler (``ddnm``: ``ddpm.complete``, one
-denoiser call per step; ``--ddnm_resample_steps``, and ``--ddnm_init linear --ddnm_t_start 0.5`` to start it from the interpolated scan)
+denoiser call per step; ``--ddnm_resample_steps``, and ``--ddnm_init linear --ddnm_t_start 0.5`` to start it from the interpolated scan), by
+the same projection on DPM-Solver++(2M) (``dpmpp``: ``ddpm.complete_dpm``, meant for ``--num_steps`` 16 to 32; ``--dpmpp_eta``, ``--dpmpp_order``,
+``--dpmpp_init``, ``--dpmpp_t_start``)
 and / or by nearest / linear interpolation of the known beams (``--methods``), and compared with the scan itself -- mean absolute and root-mean-square error of range and reflectance over the pixels
 that had to be filled in, the recall of returns, the rate of false returns and, with ``--rangenet_weights``, the IoU of the RangeNet-53
 labels of the completed image against the labels of the real scan (r2dm_amd.completion.evaluate_completion; DESIGN.md section 4,
@@ -22,7 +24,7 @@ Writes one JSON document to ``--out``: ``info`` (checkpoint, number of scans, se
 sums, micro and macro averages, per-class IoU and mIoU, or ``skipped``); an undefined value is ``null``.  ``--save_dir DIR`` also writes
 the tensors behind the numbers, one ``.pt`` file per corruption."""
 import json
-from argparse import ArgumentParser
+from argparse import SUPPRESS, ArgumentParser
 from pathlib import Path
 
 import torch
@@ -87,11 +89,13 @@ def main(argv=None):
     if args.rangenet_weights is not None:
         semseg = r2dm_amd.rangenet.pretrained_rangenet(args.rangenet_weights, device=device)
         post = semseg_postprocess(args.semseg_postprocess, semseg.num_classes)
+    dpmpp = dpmpp_settings(args)
     out = completion.evaluate_completion(ddpm, lidar_utils, planes, kinds, methods=tuple(args.methods), num_steps=args.num_steps,
                                          num_resample_steps=args.num_resample_steps, jump_length=args.jump_length, seed=args.seed,
                                          batch_size=args.batch_size, semseg=semseg, semseg_postprocess=post, keep=args.save_dir is not None,
                                          chamfer=args.chamfer, fscore_threshold=args.fscore_threshold, ddnm_resample_steps=args.ddnm_resample_steps,
-                                         ddnm_init=None if args.ddnm_init == "none" else args.ddnm_init, ddnm_t_start=args.ddnm_t_start)
+                                         ddnm_init=None if args.ddnm_init == "none" else args.ddnm_init, ddnm_t_start=args.ddnm_t_start,
+                                         **{**dpmpp, "dpmpp_init": None if dpmpp["dpmpp_init"] == "none" else dpmpp["dpmpp_init"]})
     results, kept = out if args.save_dir is not None else (out, None)
     info = {"ckpt": str(args.ckpt), "source": str(args.real_scans if args.real_scans is not None else args.real_dir), "num_scans": len(files),
             "resolution": list(cfg.data.resolution), "corruptions": kinds, "methods": list(args.methods), "num_steps": args.num_steps,
@@ -102,6 +106,8 @@ def main(argv=None):
         info["fscore_threshold"] = args.fscore_threshold
     if "ddnm" in args.methods:
         info.update(ddnm_resample_steps=args.ddnm_resample_steps, ddnm_init=args.ddnm_init, ddnm_t_start=args.ddnm_t_start)
+    if "dpmpp" in args.methods:
+        info.update(dpmpp)
     doc = completion.jsonable({"info": info, "results": results})
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     with open(args.out, "w") as f:
@@ -124,6 +130,14 @@ def main(argv=None):
     return doc
 
 
+DPMPP_DEFAULTS = {"dpmpp_eta": 1.0, "dpmpp_order": 2, "dpmpp_init": "none", "dpmpp_t_start": 1.0}
+
+
+def dpmpp_settings(args):
+    """the dpmpp method's settings of parsed arguments, the defaults where an option was not given"""
+    return {name: getattr(args, name, default) for name, default in DPMPP_DEFAULTS.items()}
+
+
 def build_parser():
     parser = ArgumentParser()
     parser.add_argument("--ckpt", type=Path, required=True)
@@ -132,8 +146,9 @@ def build_parser():
     parser.add_argument("--limit", type=int, default=None, help="the first so many scans (sorted)")
     parser.add_argument("--corruption", action="append", default=None, metavar="KIND",
                         help="full, beams:K, random_beams:P or random_points:P; repeatable (default: beams:4)")
-    parser.add_argument("--methods", nargs="+", choices=["repaint", "ddnm", "nearest", "linear"], default=["repaint"],
-                        help="ddnm: the data-consistent sampler (ddpm.complete), one denoiser call per step")
+    parser.add_argument("--methods", nargs="+", choices=["repaint", "ddnm", "dpmpp", "nearest", "linear"], default=["repaint"],
+                        help="ddnm: the data-consistent sampler (ddpm.complete), one denoiser call per step; dpmpp: the same projection on "
+                             "DPM-Solver++(2M) (ddpm.complete_dpm), use it with --num_steps 16 to 32")
     parser.add_argument("--num_steps", type=int, default=32)
     parser.add_argument("--num_resample_steps", type=int, default=10)
     parser.add_argument("--jump_length", type=int, default=1)
@@ -141,6 +156,14 @@ def build_parser():
     parser.add_argument("--ddnm_init", choices=("none", "nearest", "linear"), default="none",
                         help="start the ddnm method from this interpolation of the known beams, noised to --ddnm_t_start (masks of whole rows)")
     parser.add_argument("--ddnm_t_start", type=float, default=1.0, help="the noise level the ddnm method starts at (< 1 needs --ddnm_init)")
+    # (the dpmpp method's settings are attributes of the parsed arguments only when given: ``dpmpp_settings`` fills in DPMPP_DEFAULTS)
+    parser.add_argument("--dpmpp_eta", type=float, default=SUPPRESS,
+                        help="the dpmpp method's share of fresh noise per step (default 1: SDE-DPM-Solver++(2M); 0: deterministic)")
+    parser.add_argument("--dpmpp_order", type=int, choices=(1, 2), default=SUPPRESS, help="the dpmpp method's solver order (default 2)")
+    parser.add_argument("--dpmpp_init", choices=("none", "nearest", "linear"), default=SUPPRESS,
+                        help="start the dpmpp method from this interpolation of the known beams, noised to --dpmpp_t_start (masks of whole rows; default none)")
+    parser.add_argument("--dpmpp_t_start", type=float, default=SUPPRESS,
+                        help="the noise level the dpmpp method starts at (default 1; < 1 needs --dpmpp_init)")
     parser.add_argument("--batch_size", type=int, default=8, help="scans per RePaint call")
     parser.add_argument("--seed", type=int, default=0, help="scan i draws its masks and its noise from generators seeded from (seed, i)")
     parser.add_argument("--rangenet_weights", type=str, default=None,

@@ -6,7 +6,7 @@ images, and ``samples_bev.png``, the bird's-eye views; ``--render_frames`` adds 
 stack, ``--render_normals`` the view of the reference's training monitor (train.py:227-239): ``samples_normal.png``, the surface normals
 as colours, and ``samples_bev_normal.png``, the bird's-eye views coloured by them.  With ``--points_dir DIR`` the final samples are also written as Velodyne scans ``DIR/samples_%04d.bin`` (fp32 [x, y, z,
 reflectance] rows in scan order, r2dm_amd.pointcloud), with ``--points_ply`` also as ``.ply`` coloured by the bird's-eye views' viridis
-height map.  ``--mode dpmpp`` (extension) samples with DPM-Solver++(2M), ``ddpm.sample_dpm``, meant for ``--sampling_steps`` 16 to 32.  Still missing from the reference's script: the mp4 (no encoder here) and the antialiased 512-pixel resize of its frames."""
+height map.  ``--mode dpmpp`` (extension) samples with DPM-Solver++(2M), ``ddpm.sample_dpm``, meant for ``--sampling_steps`` 16 to 32 (``--dpm_eta 1``: its stochastic member, SDE-DPM-Solver++(2M)).  Still missing from the reference's script: the mp4 (no encoder here) and the antialiased 512-pixel resize of its frames."""
 import argparse
 from pathlib import Path
 
@@ -21,7 +21,7 @@ def main(args):
         torch.manual_seed(args.seed)
     ddpm, lidar_utils, _ = r2dm_amd.setup_model(args.ckpt, device=args.device, max_batch=args.batch_size)
     if args.mode == "dpmpp":  # (extension: DPM-Solver++(2M), meant for 16-32 steps)
-        xs = ddpm.sample_dpm(batch_size=args.batch_size, num_steps=args.sampling_steps, return_all=True).clamp(-1, 1)
+        xs = ddpm.sample_dpm(batch_size=args.batch_size, num_steps=args.sampling_steps, return_all=True, eta=args.dpm_eta).clamp(-1, 1)
     else:
         xs = ddpm.sample(batch_size=args.batch_size, num_steps=args.sampling_steps, mode=args.mode, return_all=True).clamp(-1, 1)
     xs = lidar_utils.denormalize(xs)
@@ -89,6 +89,7 @@ def parser():
     parser.add_argument("--device", choices=["cuda"], default="cuda")
     parser.add_argument("--mode", choices=["ddpm", "ddim", "dpmpp"], default="ddpm",
                         help="dpmpp (extension): the DPM-Solver++(2M) sampler, ddpm.sample_dpm; use it with --sampling_steps 16 to 32")
+    parser.add_argument("--dpm_eta", type=float, default=0.0, help="--mode dpmpp: the share of fresh noise per step (0: deterministic, 1: SDE-DPM-Solver++(2M))")
     parser.add_argument("--batch_size", type=int, default=1)
     parser.add_argument("--sampling_steps", type=int, default=256)
     parser.add_argument("--output", type=Path, default=Path("samples.pt"))

@@ -181,6 +181,25 @@ int r2dm_posterior_step_known(const float* x_t, const float* prediction, const f
 int r2dm_dpm_step(const float* x_t, const float* prediction, const float* x0_prev, const float* coef, float* x_s, float* x0, int32_t batch,
                   int64_t per_sample, int32_t objective, float clip, void* stream);
 
+/* -- DPM-Solver++(2M) update with a measurement and a noise operand: completion on the multistep solver (DDNM's projection of the x_0
+ *    estimate) and its stochastic member (SDE-DPM-Solver++(2M) with the table of eta = 1).  One pass in float32, not contracted; per element:
+ *      x0  = as r2dm_posterior_step (eps: (x - s_t*pr)/a_t | v: a_t*x - s_t*pr | x_0: pr), clamped to [-clip, clip] (clip < 0: no clamp)
+ *      x0  = m*y + (1 - m)*x0                   only when known (y) and mask (m) are given: both NULL or both non-NULL
+ *      x_s = c_x*x + c_0*x0
+ *      x_s = x_s + c_1*x0_prev                  only when x0_prev != NULL
+ *      x_s = x_s + c_z*z                        only when noise (z) != NULL
+ *    coef is (B,8) = (a_t, s_t, c_x, c_0, c_1, c_z, 0, 0) (r2dm_amd/diffusion.py: _dpm_table with eta).  Both x_s and x0 are written; x0 is
+ *    the estimate AFTER the measurement has been written in: the history the next step extrapolates from.  mask has `mask_channels`
+ *    channels (1 = broadcast over the `channels` planes of a sample), as in r2dm_posterior_step_known.  x0 may be x0_prev's buffer, as in
+ *    r2dm_dpm_step; no other aliasing is supported.  With noise, known and mask NULL the result is r2dm_dpm_step's, bit for bit.
+ *    Refused (status 1, "dpm_step_known: ..." in r2dm_last_error, nothing launched): everything r2dm_dpm_step refuses; what
+ *    r2dm_posterior_step_known refuses about known, mask, channels and mask_channels (per_sample must divide into `channels` planes of a
+ *    multiple of 4 elements, mask_channels 1 or `channels` -- with or without a measurement); exactly one of known / mask given; noise,
+ *    known or mask not 16-byte aligned; x_s or x0 equal to noise, known or mask. */
+int r2dm_dpm_step_known(const float* x_t, const float* prediction, const float* x0_prev, const float* noise, const float* known,
+                        const float* mask, const float* coef, float* x_s, float* x0, int32_t batch, int64_t per_sample, int32_t channels,
+                        int32_t mask_channels, int32_t objective, float clip, void* stream);
+
 /* -- RePaint completion (models/diffusion/continuous_time.py:169-190 q_step_from_x_0 / q_step, :287-303 the
  *    known/unknown blend inside repaint()).  coef is (B,2) host-computed scalars.
  *    blend:  out = mask * (known*alpha + noise*sigma) + (1 - mask) * unknown,  coef = (alpha, sigma) at step s;

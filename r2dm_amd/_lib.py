@@ -82,6 +82,7 @@ SIGNATURES = {
     "r2dm_posterior_step": (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int64, c_int32, c_int32, c_float, _P]),
     "r2dm_posterior_step_known": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32, c_float, _P]),
     "r2dm_dpm_step": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int64, c_int32, c_float, _P]),
+    "r2dm_dpm_step_known": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int64, c_int32, c_int32, c_int32, c_float, _P]),
     "r2dm_repaint_blend": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int64, c_int32, c_int32, _P]),
     "r2dm_q_step": (c_int32, [_P, _P, _P, _P, c_int32, c_int64, _P]),
     "r2dm_diffusion_loss_scratch_bytes": (c_size_t, [c_int32, c_int32, c_int64]),
@@ -262,6 +263,34 @@ def dpm_step(x_t, pred, x0_prev, coef, objective: int, clip: float, x0_out: Opti
     with torch.cuda.device(x_t.device):
         check(lib().r2dm_dpm_step(ptr(x_t), ptr(pred), ptr(x0_prev), ptr(coef), ptr(out), ptr(x0_out), B, x_t.numel() // B, objective, float(clip),
                                   stream_ptr(x_t.device)))
+    return out, x0_out
+
+
+def dpm_step_known(x_t, pred, x0_prev, noise, known, mask, coef, objective: int, clip: float, x0_out: Optional[torch.Tensor] = None):
+    """``dpm_step`` with a measurement and a noise operand (``r2dm_dpm_step_known``) -> ``(x_s, x0)``: the clamped estimate gets ``x0 = mask *
+    known + (1 - mask) * x0`` (``known`` and ``mask`` both given or both None; ``mask`` (B | 1, 1 | C, ...) is expanded over the batch as in
+    ``repaint_blend``), ``x_s = c_x x_t + c_0 x0 [+ c_1 x0_prev] [+ c_z noise]``; ``coef`` (B,8) = (alpha_t, sigma_t, c_x, c_0, c_1, c_z, 0, 0).
+    ``x0`` is the estimate after the projection.  ``x0_out`` as in ``dpm_step``."""
+    require_gpu(x_t, "x_t")
+    x_t, pred, coef = f32c(x_t), f32c(pred), f32c(coef)
+    x0_prev, noise, known = (None if t is None else f32c(t) for t in (x0_prev, noise, known))
+    if (known is None) != (mask is None):
+        raise ValueError("known and mask are given together or not at all")
+    if x_t.dim() < 3 or any(t is not None and (t.shape != x_t.shape or t.device != x_t.device) for t in (pred, x0_prev, noise, known, x0_out)) \
+            or coef.shape != (x_t.shape[0], 8) or coef.device != x_t.device:
+        raise ValueError(f"x_t {tuple(x_t.shape)}, prediction {tuple(pred.shape)}, x0_prev, noise, known and x0_out must have one (B,C,...) shape on one "
+                         f"device, coef {tuple(coef.shape)} must be (B,8)")
+    B, C = x_t.shape[0], x_t.shape[1]
+    if mask is not None:
+        mask = f32c(mask.to(x_t.device).expand(B, -1, *x_t.shape[2:]))
+    if x0_out is None:
+        x0_out = torch.empty_like(x_t)
+    elif x0_out.dtype != torch.float32 or not x0_out.is_contiguous():
+        raise ValueError("x0_out must be a contiguous float32 tensor")
+    out = torch.empty_like(x_t)
+    with torch.cuda.device(x_t.device):
+        check(lib().r2dm_dpm_step_known(ptr(x_t), ptr(pred), ptr(x0_prev), ptr(noise), ptr(known), ptr(mask), ptr(coef), ptr(out), ptr(x0_out), B,
+                                        x_t.numel() // B, C, 1 if mask is None else mask.shape[1], objective, float(clip), stream_ptr(x_t.device)))
     return out, x0_out
 
 

@@ -9,7 +9,7 @@ linear interpolation of the known beams.  The reference has no code for it.  Her
 - ``completion_errors``    per sample the four counts and six error sums of ``r2dm_completion_error`` and the values derived from them.
 - ``confusion_matrix`` / ``iou_from_confusion``   label agreement.
 - ``fill_beams``           the interpolation baselines.
-- ``evaluate_completion``  corrupt, complete (RePaint, the data-consistent sampler ``ddpm.complete`` or a baseline), score; ``completion_eval.py`` is its command line.
+- ``evaluate_completion``  corrupt, complete (RePaint, the data-consistent sampler ``ddpm.complete``, the same on DPM-Solver++(2M), ``ddpm.complete_dpm``, or a baseline), score; ``completion_eval.py`` is its command line.
 
 A pixel is a *return* when its metric depth lies strictly inside ``(lo, hi)``; any other depth, NaN included, is "no return".  The errors
 are taken over E: the unknown pixels (mask 0) where the real scan has a return.  A prediction without a return there counts with depth 0
@@ -31,7 +31,7 @@ DERIVED_NAMES = ("mae_depth", "rmse_depth", "mae_depth_both", "rmse_depth_both",
                  "false_return_rate")
 FILL_MODES = {"nearest": 0, "linear": 1}
 ROW_KINDS = ("full", "beams", "random_beams")  # corruptions whose mask is whole rows: what the interpolation baselines are defined for
-METHODS = ("repaint", "ddnm", "nearest", "linear", "target")
+METHODS = ("repaint", "ddnm", "dpmpp", "nearest", "linear", "target")
 
 
 # ---- corruptions -------------------------------------------------------------------------------------------------------------------------
@@ -255,7 +255,8 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
                         num_resample_steps: int = 10, jump_length: int = 1, seed: int = 0, batch_size: int = 8, semseg=None,
                         semseg_postprocess=None, lo: Optional[float] = None, hi: Optional[float] = None, keep: bool = False,
                         chamfer: bool = False, fscore_threshold: float = 0.2, ddnm_resample_steps: int = 1, ddnm_init: Optional[str] = None,
-                        ddnm_t_start: float = 1.0):
+                        ddnm_t_start: float = 1.0, dpmpp_eta: float = 1.0, dpmpp_order: int = 2, dpmpp_init: Optional[str] = None,
+                        dpmpp_t_start: float = 1.0):
     """Corrupt, complete and score ``planes`` (N,6,H,W), the masked planes of ``project_scans(layout="xyzrdm", apply_mask=True)`` at the
     model's resolution, on the GPU.
 
@@ -266,7 +267,9 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
     ``methods``: "repaint"; "ddnm" (``ddpm.complete`` on ``x_in`` under the mask, from the same generators as RePaint, ``num_steps`` and
     ``jump_length`` shared with it and ``ddnm_resample_steps`` resamplings; with ``ddnm_init`` "nearest" / "linear" it starts from
     ``fill_beams(x_in, ...)`` noised to ``ddnm_t_start`` < 1 instead of from noise at t = 1 -- defined, like the baselines, for the kinds
-    whose mask is whole rows and reported as skipped for the others); "nearest" / "linear" (``fill_beams`` on ``x_in``; defined for the kinds whose mask is whole rows, reported as
+    whose mask is whole rows and reported as skipped for the others); "dpmpp" (``ddpm.complete_dpm``: the same projection on DPM-Solver++(2M),
+    ``num_steps`` steps of order ``dpmpp_order`` with ``dpmpp_eta``, from the same generators as RePaint, no resampling; ``dpmpp_init`` /
+    ``dpmpp_t_start`` as ``ddnm_init`` / ``ddnm_t_start``, with the same rules); "nearest" / "linear" (``fill_beams`` on ``x_in``; defined for the kinds whose mask is whole rows, reported as
     skipped for the others); "target" (the target's own planes as the prediction: errors 0, mIoU 1).  ``lo``, ``hi``: the depth window of
     a return (default: the model's ``min_depth``, ``max_depth``).  ``semseg``: a ``RangeNetExtractor``; the labels of prediction and target
     come from the same net and ``semseg_postprocess`` (what ``segment`` accepts), the confusion matrix is taken over the target's measured
@@ -294,6 +297,17 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
         raise ValueError(f"ddnm_t_start must be in (0, 1], got {ddnm_t_start}")
     if ddnm_resample_steps < 1:
         raise ValueError(f"ddnm_resample_steps must be >= 1, got {ddnm_resample_steps}")
+    if dpmpp_init is not None and dpmpp_init not in FILL_MODES:
+        raise ValueError(f"dpmpp_init must be None or one of {sorted(FILL_MODES)}, got {dpmpp_init!r}")
+    if (dpmpp_init is None) != (float(dpmpp_t_start) == 1.0):
+        raise ValueError(f"dpmpp_init and dpmpp_t_start < 1 go together (a start from the interpolated scan, noised to dpmpp_t_start): got {dpmpp_init!r} "
+                         f"and {dpmpp_t_start}")
+    if not 0.0 < float(dpmpp_t_start) <= 1.0:
+        raise ValueError(f"dpmpp_t_start must be in (0, 1], got {dpmpp_t_start}")
+    if dpmpp_order not in (1, 2):
+        raise ValueError(f"dpmpp_order must be 1 or 2, got {dpmpp_order!r}")
+    if not float(dpmpp_eta) >= 0.0 or float(dpmpp_eta) == float("inf"):
+        raise ValueError(f"dpmpp_eta must be finite and >= 0, got {dpmpp_eta}")
     if planes.dim() != 4 or planes.shape[1] != 6:
         raise ValueError(f"expected planes (N,6,H,W) [x, y, z, reflectance, depth, mask], got {tuple(planes.shape)}")
     _lib.require_gpu(planes, "planes")
@@ -306,7 +320,7 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
     if chamfer:
         fscore_threshold = geometry._check_tau(fscore_threshold)
     N, _, H, W = planes.shape
-    if ("repaint" in methods or "ddnm" in methods) and tuple(ddpm.sampling_shape) != (2, H, W):
+    if ("repaint" in methods or "ddnm" in methods or "dpmpp" in methods) and tuple(ddpm.sampling_shape) != (2, H, W):
         raise ValueError(f"planes of {H}x{W} for a model that samples {tuple(ddpm.sampling_shape)}: RePaint needs a depth + reflectance model "
                          "at the planes' resolution")
     dev = planes.device
@@ -349,7 +363,19 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
             if method == "ddnm" and ddnm_init is not None and name not in ROW_KINDS:
                 results[kind][method] = {"skipped": f"ddnm_init = {ddnm_init} interpolation is defined for masks of whole rows ({', '.join(ROW_KINDS)})"}
                 continue
-            if method == "ddnm":
+            if method == "dpmpp" and dpmpp_init is not None and name not in ROW_KINDS:
+                results[kind][method] = {"skipped": f"dpmpp_init = {dpmpp_init} interpolation is defined for masks of whole rows ({', '.join(ROW_KINDS)})"}
+                continue
+            if method == "dpmpp":
+                init = fill_beams(x_in, rows_of_mask(mask), dpmpp_init, nodata=-1.0) if dpmpp_init is not None and N else None
+                parts = []
+                for k in range(0, N, batch_size):
+                    rng = setup_rng([scan_seed(seed, i) for i in range(k, min(k + batch_size, N))], dev)
+                    parts.append(ddpm.complete_dpm(known=x_in[k:k + batch_size], mask=mask[k:k + batch_size], num_steps=num_steps, order=dpmpp_order,
+                                                   eta=float(dpmpp_eta), t_start=float(dpmpp_t_start),
+                                                   init=None if init is None else init[k:k + batch_size], progress=False, rng=rng))
+                x_out = torch.cat(parts) if parts else x_in
+            elif method == "ddnm":
                 init = fill_beams(x_in, rows_of_mask(mask), ddnm_init, nodata=-1.0) if ddnm_init is not None and N else None
                 parts = []
                 for k in range(0, N, batch_size):

@@ -285,6 +285,9 @@ struct DpmParams {
     float clip;  // < 0: no clamping
 };
 hipError_t launch_dpm_step(const DpmParams& p, hipStream_t s);
+// the same update with coef[5] = c_z: x0 = mask * known + (1 - mask) * x0 before it (known, mask: both or neither), + c_z * noise behind it (noise may be nullptr)
+hipError_t launch_dpm_step_known(const DpmParams& p, const float* noise, const float* known, const float* mask, int channels, int mask_c,
+                                 hipStream_t s);
 // RePaint (reference continuous_time.py:169-190,287-303): forward re-noising and known/unknown blend
 hipError_t launch_repaint_blend(const float* known, const float* noise, const float* unknown, const float* mask,
                                 const float* coef, float* out, int B, long per_sample, int channels, int mask_c,

@@ -53,6 +53,32 @@ int r2dm_dpm_step(const float* x_t, const float* pred, const float* x0_prev, con
     return 0;
 }
 
+int r2dm_dpm_step_known(const float* x_t, const float* pred, const float* x0_prev, const float* noise, const float* known, const float* mask,
+                        const float* coef, float* x_s, float* x0, int32_t B, int64_t per_sample, int32_t channels, int32_t mask_channels,
+                        int32_t objective, float clip, void* stream) {
+    if (!x_t || !pred || !coef || !x_s || !x0) return fail(1, "dpm_step_known: null argument (only x0_prev, noise and the pair known, mask may be null)");
+    if (!known != !mask) return fail(1, "dpm_step_known: known and mask are given together or not at all (null argument)");
+    if (objective < 0 || objective > 2) return fail(1, "dpm_step_known: objective must be 0 (eps), 1 (v) or 2 (x_0), got %d", objective);
+    if (B < 1 || B > 65535) return fail(1, "dpm_step_known: batch must be in [1, 65535], got %d", B);
+    if (channels < 1 || per_sample < 4 || per_sample > (1LL << 40) / B || per_sample % channels)
+        return fail(1, "dpm_step_known: per_sample (got %lld) must be in [4, 2^40 / batch] and divide into %d channels", (long long)per_sample, channels);
+    if (per_sample % 4 || (per_sample / channels) % 4)
+        return fail(1, "dpm_step_known: per_sample (got %lld) and the plane per_sample / channels (got %lld) must each be a multiple of 4",
+                    (long long)per_sample, (long long)(per_sample / channels));
+    if (mask_channels != 1 && mask_channels != channels)
+        return fail(1, "dpm_step_known: mask_channels must be 1 or %d, got %d", channels, mask_channels);
+    if ((((uintptr_t)x_t | (uintptr_t)pred | (uintptr_t)x0_prev | (uintptr_t)noise | (uintptr_t)known | (uintptr_t)mask | (uintptr_t)x_s | (uintptr_t)x0) & 15) ||
+        ((uintptr_t)coef & 3))
+        return fail(1, "dpm_step_known: x_t, prediction, x0_prev, noise, known, mask, x_s and x0 must be 16-byte aligned, coef 4-byte aligned");
+    if (x_s == x_t || x_s == pred || x_s == x0_prev || x_s == x0 || x0 == x_t || x0 == pred)
+        return fail(1, "dpm_step_known: an output may not alias an input or the other output (only x0 may be x0_prev's buffer)");
+    for (const float* in : {noise, known, mask})
+        if (in && (in == x_s || in == x0)) return fail(1, "dpm_step_known: an output may not alias noise, known or mask");
+    DpmParams p{x_t, pred, x0_prev, coef, x_s, x0, B, per_sample, objective, clip};
+    HIP_TRY(launch_dpm_step_known(p, noise, known, mask, channels, mask_channels, (hipStream_t)stream));
+    return 0;
+}
+
 int r2dm_repaint_blend(const float* known, const float* noise, const float* unknown, const float* mask, const float* coef,
                        float* out, int32_t B, int64_t per_sample, int32_t channels, int32_t mask_channels, void* stream) {
     if (!known || !noise || !unknown || !mask || !coef || !out) return fail(1, "null argument");

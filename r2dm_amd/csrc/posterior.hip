@@ -235,6 +235,85 @@ hipError_t launch_dpm_step(const DpmParams& p, hipStream_t s) {
     return hipErrorInvalidValue;
 }
 
+// ---- DPM-Solver++(2M) update with a measurement and a noise operand: completion and the stochastic member (SDE-DPM-Solver++(2M)) ------------
+// x_t, prediction[, x0_prev][, noise][, known, mask] -> x_s, x0 in one pass (2 to 6 reads + 2 writes).  coef[b] = (alpha_t, sigma_t, c_x, c_0, c_1,
+// c_z, 0, 0).  dpm_step_kernel's update with DDNM's projection between its halves, x0 = m y + (1 - m) x0 (posterior_known_kernel's), and
+// + c_z z behind them; x0 is written AFTER the projection: that is the history the next step extrapolates from.  An absent operand is a
+// template argument: no load, no arithmetic.  x0 may be x0_prev's buffer, as in dpm_step_kernel.
+template <int OBJ, bool SECOND, bool NOISE, bool KNOWN>
+__global__ __launch_bounds__(256) void dpm_step_known_kernel(DpmParams p, const float* __restrict__ noise, const float* __restrict__ known,
+                                                             const float* __restrict__ mask, long plane, int mask_c) {
+    const int b = blockIdx.y;
+    float k[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) k[i] = p.coef[b * 8 + i];
+    const float c_x = k[2], c_0 = k[3], c_1 = k[4], c_z = k[5];
+    const long n4 = p.per_sample >> 2, plane4 = plane >> 2;
+    const f32x4* x4 = reinterpret_cast<const f32x4*>(p.x_t + b * p.per_sample);
+    const f32x4* p4 = reinterpret_cast<const f32x4*>(p.pred + b * p.per_sample);
+    const f32x4* h4 = SECOND ? reinterpret_cast<const f32x4*>(p.x0_prev + b * p.per_sample) : nullptr;
+    const f32x4* z4 = NOISE ? reinterpret_cast<const f32x4*>(noise + b * p.per_sample) : nullptr;
+    const f32x4* y4 = KNOWN ? reinterpret_cast<const f32x4*>(known + b * p.per_sample) : nullptr;
+    const f32x4* m4 = KNOWN ? reinterpret_cast<const f32x4*>(mask + b * (mask_c == 1 ? plane : p.per_sample)) : nullptr;
+    f32x4* o4 = reinterpret_cast<f32x4*>(p.x_s + b * p.per_sample);
+    f32x4* e4 = reinterpret_cast<f32x4*>(p.x0 + b * p.per_sample);
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        const f32x4 x = x4[i], pr = p4[i];
+        f32x4 h = {0.f, 0.f, 0.f, 0.f}, z = h, y = h, m = h;
+        if (SECOND) h = h4[i];
+        if (NOISE) z = z4[i];
+        if (KNOWN) y = y4[i], m = m4[mask_c == 1 ? i % plane4 : i];
+        f32x4 o, e;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            e[j] = posterior_x0<M_CT_DDPM, OBJ>(x[j], pr[j], k, p.clip);
+            if (KNOWN) e[j] = m[j] * y[j] + (1.0f - m[j]) * e[j];
+            o[j] = c_x * x[j] + c_0 * e[j];
+            if (SECOND) o[j] = o[j] + c_1 * h[j];
+            if (NOISE) o[j] = o[j] + c_z * z[j];
+        }
+        o4[i] = o;
+        e4[i] = e;
+    }
+}
+
+template <int OBJ, bool SECOND, bool NOISE>
+static hipError_t launch_dpm_known_k(const DpmParams& p, const float* noise, const float* known, const float* mask, long plane, int mask_c, dim3 g,
+                                     hipStream_t s) {
+    if (known) dpm_step_known_kernel<OBJ, SECOND, NOISE, true><<<g, 256, 0, s>>>(p, noise, known, mask, plane, mask_c);
+    else dpm_step_known_kernel<OBJ, SECOND, NOISE, false><<<g, 256, 0, s>>>(p, noise, nullptr, nullptr, plane, mask_c);
+    return hipGetLastError();
+}
+
+template <int OBJ>
+static hipError_t launch_dpm_known_obj(const DpmParams& p, const float* noise, const float* known, const float* mask, long plane, int mask_c, dim3 g,
+                                       hipStream_t s) {
+    if (p.x0_prev) {
+        return noise ? launch_dpm_known_k<OBJ, true, true>(p, noise, known, mask, plane, mask_c, g, s)
+                     : launch_dpm_known_k<OBJ, true, false>(p, noise, known, mask, plane, mask_c, g, s);
+    }
+    return noise ? launch_dpm_known_k<OBJ, false, true>(p, noise, known, mask, plane, mask_c, g, s)
+                 : launch_dpm_known_k<OBJ, false, false>(p, noise, known, mask, plane, mask_c, g, s);
+}
+
+// (arguments validated by r2dm_dpm_step_known; checked again here, since the kernel reads quads and has no tail)
+hipError_t launch_dpm_step_known(const DpmParams& p, const float* noise, const float* known, const float* mask, int channels, int mask_c,
+                                 hipStream_t s) {
+    if (p.B < 1 || p.B > 65535 || p.per_sample < 4 || (p.per_sample & 3) || !p.x_t || !p.pred || !p.coef || !p.x_s || !p.x0 || p.x_s == p.x_t ||
+        channels < 1 || p.per_sample % channels || (p.per_sample / channels) % 4 || (mask_c != 1 && mask_c != channels) || !known != !mask)
+        return hipErrorInvalidValue;
+    long bx = (p.per_sample / 4 + 255) / 256;  // (launch_posterior's shape)
+    if (bx > 1024) bx = 1024;
+    const dim3 g((unsigned)bx, p.B);
+    const long plane = p.per_sample / channels;
+    switch (p.objective) {
+        case OBJ_EPS: return launch_dpm_known_obj<OBJ_EPS>(p, noise, known, mask, plane, mask_c, g, s);
+        case OBJ_V: return launch_dpm_known_obj<OBJ_V>(p, noise, known, mask, plane, mask_c, g, s);
+        case OBJ_X0: return launch_dpm_known_obj<OBJ_X0>(p, noise, known, mask, plane, mask_c, g, s);
+    }
+    return hipErrorInvalidValue;
+}
+
 // ---- LiDAR post-processing ("next" row f.1) ------------------------------------------------
 // sample (B,2,H,W) in [-1,1] -> (B,5,H,W): metric depth (decoded by the checkpoint's depth format, masked to
 // (min_depth, max_depth)), Cartesian x,y,z along the per-pixel ray angles, reflectance in [0,1].

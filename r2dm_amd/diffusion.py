@@ -714,9 +714,9 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
                                   None if clip is None else float(self.clip_sample_range) if clip else -1.0)
 
     # -- DPM-Solver++(2M): a second-order multistep solver of the probability-flow ODE on the log-SNR axis (not in the reference) ------------
-    def _dpm_table(self, num_steps: int, batch_size: int, order: int, grid: str, t_start: float, lower_order_final: bool, dev):
+    def _dpm_table(self, num_steps: int, batch_size: int, order: int, grid: str, t_start: float, lower_order_final: bool, dev, eta: float = 0.0):
         """``(cond (S,B), coef (S,B,8) on the device, second (S,) bool on the host)`` of a ``sample_dpm`` call; rows of ``r2dm_dpm_step``:
-        ``(alpha_t, sigma_t, c_x, c_0, c_1, 0, 0, 0)``.
+        ``(alpha_t, sigma_t, c_x, c_0, c_1, 0, 0, 0)``, with ``eta > 0`` of ``r2dm_dpm_step_known``: ``(alpha_t, sigma_t, c_x, c_0, c_1, c_z, 0, 0)``.
 
         The log-SNR values lambda_0 .. lambda_S in float32: ``grid="logsnr"`` is ``linspace(lambda(t_start), lambda(0), S + 1)``, ``grid="time"`` is
         ``lambda(linspace(t_start, 0, S + 1))`` evaluated row by row as ``_coefficients`` does, so its ``cond`` rows are ``sample_from``'s bit for
@@ -727,11 +727,17 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
         second-order row with ``r = h_{i-1} / h_i`` has ``c_0 = m (1 + 1/(2r))``, ``c_1 = -m / (2r)``.  Row 0 is first-order (there is no
         history), every row is with ``order=1``, and with ``lower_order_final`` so is the last one.
 
+        ``eta`` (>= 0) is the share of the step's noise that is drawn anew (SDE-DPM-Solver++(2M) at eta = 1): ``c_x = (sigma_s / sigma_t)
+        exp(-eta h_i)``, ``m = -alpha_s expm1(-(1 + eta) h_i)`` and ``c_z = sigma_s sqrt(-expm1(-2 eta h_i))`` in slot 5, c_0 and c_1 from m as
+        above.  At eta = 0 every entry is what it was, bit for bit, and c_z = 0.  A first-order row at eta = 1 is the ancestral posterior in
+        another operation order: with ``c = 1 - exp(-2 h)``, ``c_x = alpha_s (1 - c) / alpha_t``, ``m = alpha_s c`` and ``c_z = sigma_s sqrt(c)``.
+
         ``schedule_on`` does not apply: the table is always evaluated on the host (its scalars are differences of neighbouring log-SNR values
         in float64, which a float32 device evaluation cannot give).  Cached like ``_tables``, under a key of its own."""
         dev = torch.device(dev)
+        eta = float(eta)
         key = (int(num_steps), int(batch_size), int(order), grid, float(t_start), bool(lower_order_final), str(dev), self.noise_schedule, self.image_d,
-               self.noise_d_low, self.noise_d_high)
+               self.noise_d_low, self.noise_d_high, eta)
         cache = self.__dict__.setdefault("_dpm_tables", {})
         hit = cache.get(key)
         if hit is not None:
@@ -752,14 +758,16 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
         rows, second = [], []
         for i in range(S):
             a_t, s_t = log_snr_to_alpha_sigma(lam[i:i + 1])
-            m = -alpha(l64[i + 1]) * math.expm1(-h[i])
+            m = -alpha(l64[i + 1]) * math.expm1(-(1.0 + eta) * h[i])
             is2 = order == 2 and i > 0 and not (lower_order_final and i == S - 1)
             if is2:
                 r = h[i - 1] / h[i]
                 c_0, c_1 = m * (1.0 + 1.0 / (2.0 * r)), -m / (2.0 * r)
             else:
                 c_0, c_1 = m, 0.0
-            rows.append([a_t.item(), s_t.item(), sigma(l64[i + 1]) / sigma(l64[i]), c_0, c_1, 0.0, 0.0, 0.0])
+            c_x = sigma(l64[i + 1]) / sigma(l64[i]) * math.exp(-eta * h[i])  # (eta = 0: times exp(-0.0) = 1.0 -- the values of before)
+            c_z = sigma(l64[i + 1]) * math.sqrt(-math.expm1(-2.0 * eta * h[i]))
+            rows.append([a_t.item(), s_t.item(), c_x, c_0, c_1, c_z, 0.0, 0.0])
             second.append(is2)
         k = torch.tensor(rows, dtype=torch.float64).float()  # (alpha_t, sigma_t are float32 values already: unchanged by the round trip)
         cond = lam[:-1, None].repeat_interleave(batch_size, dim=1).contiguous().to(dev)
@@ -771,7 +779,8 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
 
     @torch.inference_mode()
     def sample_dpm(self, batch_size: int, num_steps: int, order: int = 2, grid: Literal["logsnr", "time"] = "logsnr", progress: bool = True, rng=None,
-                   return_all: bool = False, x_t=None, t_start: float = 1.0, clip: Optional[bool] = None, lower_order_final: bool = True):
+                   return_all: bool = False, x_t=None, t_start: float = 1.0, clip: Optional[bool] = None, lower_order_final: bool = True,
+                   eta: float = 0.0):
         """DPM-Solver++(2M) sampling (Lu et al. 2022): a deterministic second-order multistep solver of the probability-flow ODE in
         data-prediction form, on ``num_steps + 1`` log-SNR values from ``t_start`` to t = 0.  Per step one denoiser call at ``cond[i]`` and one
         ``r2dm_dpm_step``, which forms the clamped estimate of x_0 as the other samplers do, keeps it as the next step's history and combines
@@ -788,6 +797,10 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
         without it is 1.5-3 x FURTHER from the exact solution than the first-order run at up to 32 steps (tests/test_dpm_cpu.py).
         ``clip``: None keeps the model's ``clip_sample`` setting, False / True switch the clamp of the x_0 estimate off / on for this call.
         ``return_all``: the (S+1,B,C,H,W) stack that starts with the start tensor.
+        ``eta``: 0 (default) is the deterministic solver above, unchanged.  ``eta > 0`` is the stochastic member of the family (eta = 1:
+        SDE-DPM-Solver++(2M); order 1 at eta = 1: the ancestral step): one ``randn_like`` per step on ``rng``, drawn ahead of the denoiser call on
+        the side stream as in ``sample``, and the step is ``r2dm_dpm_step_known`` with that noise and no measurement.  A replay after a
+        range-guard trip runs on the recorded noise.
 
         Runs under the deferred range guard with ``_Replay``'s recovery, whose checkpoint here is the pair (x, previous x_0 estimate): after a
         trip the loop goes back at most ``_CHECK_EVERY`` steps WITH the history those steps were taken with, on the wide-range split.
@@ -802,6 +815,8 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
             raise ValueError(f"t_start must be in (0, 1], got {t_start}")
         if int(batch_size) != batch_size or batch_size < 1:
             raise ValueError(f"batch_size must be an integer >= 1, got {batch_size}")
+        if not float(eta) >= 0.0 or math.isinf(float(eta)):
+            raise ValueError(f"eta must be finite and >= 0, got {eta}")
         if x_t is None:
             if float(t_start) != 1.0:
                 raise ValueError(f"t_start = {t_start} needs x_t (the tensor at that noise level): a fresh draw starts at t_start = 1")
@@ -813,27 +828,38 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
                                 + ("" if x_t is None else f", input on {x_t.device}") + "): r2dm_amd has no CPU fallback")
         dev = self.device if x_t is None else x_t.device
         x = self.randn(batch_size, *self.sampling_shape, rng=rng, device=dev) if x_t is None else _lib.f32c(x_t)
-        cond, coef, second = self._dpm_table(int(num_steps), int(batch_size), order, grid, float(t_start), lower_order_final, dev)
+        cond, coef, second = self._dpm_table(int(num_steps), int(batch_size), order, grid, float(t_start), lower_order_final, dev, float(eta))
         clip_value = self._clip() if clip is None else float(self.clip_sample_range) if clip else -1.0
-        return self._dpm_loop(x, cond, coef, second.tolist(), clip_value, progress, return_all)
+        draw = (lambda x: self._randn_like_ahead(x, rng=rng)) if float(eta) > 0.0 else None
+        return self._dpm_loop(x, cond, coef, second.tolist(), clip_value, progress, return_all, draw)
 
-    def _dpm_loop(self, x, cond, coef, second, clip: float, progress: bool, return_all: bool):
+    def _dpm_loop(self, x, cond, coef, second, clip: float, progress: bool, return_all: bool, draw=None, known=None, mask=None, desc: str = "sampling"):
         """The multistep loop beside ``_run_loop``: the state a step hands on is (x, x0_prev), and that pair is what ``_Replay`` keeps.  The
         estimates ping-pong between two buffers; ``_Replay`` only stores the object it is given, so at a step whose check is due it is given a
-        COPY of the estimate -- the checkpoint's history is then a buffer no later step writes."""
+        COPY of the estimate -- the checkpoint's history is then a buffer no later step writes.
+        ``draw(x) -> (noise, event)``: the step's noise, drawn ahead of the denoiser call and kept by ``_Replay`` (``noise_for``) as in
+        ``_run_loop``; ``known``, ``mask``: the measurement written over every estimate.  With neither the step is ``r2dm_dpm_step``, else
+        ``r2dm_dpm_step_known``."""
         num_steps, objective = len(second), self._objective_id()
+        plain = draw is None and known is None
         out = [x] if return_all else None
         rp = _Replay(self.model, num_steps)
         rp.start((x, None))
         bufs = (torch.empty_like(x), torch.empty_like(x))
         x0_prev = None
-        bar = _progress_bar(num_steps, "sampling", progress)
+        bar = _progress_bar(num_steps, desc, progress)
         with _range_guard(self.model):
             i = 0
             while i < num_steps:
+                noise, drawn = rp.noise_for(i, lambda: draw(x)) if draw is not None else (None, None)
                 prediction = self.model(x, cond[i])
+                if drawn is not None:
+                    torch.cuda.current_stream(x.device).wait_event(drawn)
                 target = bufs[1] if x0_prev is bufs[0] else bufs[0]
-                x_s, x0 = _lib.dpm_step(x, prediction, x0_prev if second[i] else None, coef[i], objective, clip, x0_out=target)
+                if plain:
+                    x_s, x0 = _lib.dpm_step(x, prediction, x0_prev if second[i] else None, coef[i], objective, clip, x0_out=target)
+                else:
+                    x_s, x0 = _lib.dpm_step_known(x, prediction, x0_prev if second[i] else None, noise, known, mask, coef[i], objective, clip, x0_out=target)
                 nxt, (x, x0_prev) = rp.after_step(i, (x_s, x0.clone() if rp.record and rp.due(i) else x0))
                 if return_all:
                     del out[nxt + 1:]  # (after a replay: the steps that are run again; else nothing)
@@ -1062,6 +1088,72 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
         return torch.stack(out) if return_all else x_s
 
 
+    # -- completion on DPM-Solver++(2M): the projection of ``complete`` inside the multistep solver's update (not in the reference) --------
+    @torch.inference_mode()
+    def complete_dpm(self, known, mask, num_steps: int, order: int = 2, grid: Literal["logsnr", "time"] = "logsnr", eta: float = 1.0,
+                     t_start: float = 1.0, init=None, exact_known: bool = True, clip: Optional[bool] = None, lower_order_final: bool = True,
+                     progress: bool = True, rng=None, return_all: bool = False):
+        """Completion of ``known`` (B,C,H,W) under ``mask`` (B | 1, 1 | C, H, W; 1 = measured, any weight in [0, 1] is taken as such) on
+        ``sample_dpm``'s solver: per step one denoiser call and one ``r2dm_dpm_step_known``, which forms the clamped estimate of x_0, writes
+        the measurement over it (``x0 = mask * known + (1 - mask) * x0``, ``complete``'s projection), keeps THAT as the next step's history
+        and takes the multistep update from it, plus ``c_z`` times the step's noise.  ``num_steps``, ``order``, ``grid``, ``clip`` and
+        ``lower_order_final`` are ``sample_dpm``'s; the table is ``_dpm_table(..., eta)``.
+
+        ``eta``: the share of each step's noise that is drawn anew.  Default 1 (SDE-DPM-Solver++(2M)): it continues ``complete``'s default,
+        the ancestral posterior, which is this sampler at order 1 on the time grid -- fresh noise is what lets the unknown region
+        re-harmonise with the pixels that were written in.  ``eta = 0`` is the deterministic solver with hard replacement.
+        Draw order: the start (``init=None``: ``randn(B, *sampling_shape)`` at ``t_start = 1``; else ``q_step_from_x_0(init, t_start)``, one
+        ``randn_like``), then one ``randn_like`` per step when ``eta > 0`` (ahead of the denoiser call, on the side stream), none when
+        ``eta == 0``.  With an all-zero mask this is ``sample_dpm`` with the same ``eta`` on the same draws.
+        There is NO resampling (``num_resample_steps`` / ``jump_length`` of ``complete`` and ``repaint``): a travel back through ``q_step``
+        lands on a state that the kept estimate of x_0 was not formed from, so it invalidates the multistep history.
+        ``exact_known``: the result is ``mask * known + (1 - mask) * x`` (``r2dm_repaint_blend``), equal to ``known`` on a binary mask.
+        ``return_all``: the (S+1,B,C,H,W) stack from the start, the last entry projected like the result.
+        A range-guard trip is handled by ``_Replay`` as in ``sample_dpm``: back at most ``_CHECK_EVERY`` steps with the checkpointed pair
+        (x, previous estimate), on the recorded noise, on the wide-range split."""
+        self._objective_id()
+        C, H, W = self.sampling_shape
+        if known.dim() != 4 or known.shape[0] < 1 or tuple(known.shape[1:]) != (C, H, W):
+            raise ValueError(f"known must be (B, {C}, {H}, {W}) with B >= 1, got {tuple(known.shape)}")
+        B = known.shape[0]
+        if mask.dim() != 4 or mask.shape[0] not in (1, B) or mask.shape[1] not in (1, C) or tuple(mask.shape[2:]) != (H, W):
+            raise ValueError(f"mask must be ({B} | 1, 1 | {C}, {H}, {W}), got {tuple(mask.shape)}")
+        if int(num_steps) != num_steps or num_steps < 1:
+            raise ValueError(f"num_steps must be an integer >= 1, got {num_steps}")
+        if order not in (1, 2):
+            raise ValueError(f"order must be 1 or 2, got {order!r}")
+        if grid not in ("logsnr", "time"):
+            raise ValueError(f"grid must be 'logsnr' or 'time', got {grid!r}")
+        if not float(eta) >= 0.0 or math.isinf(float(eta)):
+            raise ValueError(f"eta must be finite and >= 0, got {eta}")
+        if not 0.0 < float(t_start) <= 1.0:
+            raise ValueError(f"t_start must be in (0, 1], got {t_start}")
+        if init is None and float(t_start) != 1.0:
+            raise ValueError(f"t_start = {t_start} needs init (the x_0 that is noised to t_start): a fresh draw starts at t_start = 1")
+        if init is not None and init.shape != known.shape:
+            raise ValueError(f"init {tuple(init.shape)} must have known's shape {tuple(known.shape)}")
+        self._refuse_cpu("complete_dpm", known)
+        dev = known.device
+        known = _lib.f32c(known)
+        mask = _lib.f32c(mask.to(dev).expand(B, -1, H, W))
+        if init is None:
+            x = self.randn(B, *self.sampling_shape, rng=rng, device=dev)
+        else:
+            x, _ = self.q_step_from_x_0(_lib.f32c(init.to(dev)), torch.full((B,), float(t_start), device=dev if self._on_device(dev) else None), rng=rng)
+        cond, coef, second = self._dpm_table(int(num_steps), B, order, grid, float(t_start), lower_order_final, dev, float(eta))
+        clip_value = self._clip() if clip is None else float(self.clip_sample_range) if clip else -1.0
+        draw = (lambda x: self._randn_like_ahead(x, rng=rng)) if float(eta) > 0.0 else None
+        out = self._dpm_loop(x, cond, coef, second.tolist(), clip_value, progress, return_all, draw, known, mask, desc="completing")
+        if not exact_known:
+            return out
+        # mask * (known * 1 + known * 0) + (1 - mask) * x: the blend kernel with known as its noise operand, as in ``complete``
+        x_s = _lib.repaint_blend(known, known, out[-1] if return_all else out, mask, torch.tensor([[1.0, 0.0]], device=dev).repeat(B, 1))
+        if return_all:
+            out[-1] = x_s
+            return out
+        return x_s
+
+
 # --------------------------------------------------------------------------------------
 class DiscreteTimeGaussianDiffusion(GaussianDiffusion):
     """DDPM / DDIM over an integer-step beta schedule (discrete_time.py:51-201)."""
@@ -1183,3 +1275,6 @@ class DiscreteTimeGaussianDiffusion(GaussianDiffusion):
 
     def sample_dpm(self, *args, **kwargs):
         raise NotImplementedError("sample_dpm is implemented for continuous time only (ContinuousTimeGaussianDiffusion)")
+
+    def complete_dpm(self, *args, **kwargs):
+        raise NotImplementedError("complete_dpm is implemented for continuous time only (ContinuousTimeGaussianDiffusion)")

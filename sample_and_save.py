@@ -10,7 +10,7 @@ Precision: fp32 parity by default (``--precision fp32``: 22-bit split fp16 opera
 utils/option.py:49); ``--precision fp16`` is that bulk mode here: one fp16 product per MAC, fp32 accumulation and tensors,
 its own tolerance class (tests/test_hip_fp16_mode.py).
 ``--max-batch`` / the batch size fix the layer tilings: per-seed results are bit-reproducible for a fixed batch size only.
-``--mode dpmpp`` (extension) samples with DPM-Solver++(2M), ``ddpm.sample_dpm``: use it with ``--num_steps`` 16 to 32.
+``--mode dpmpp`` (extension) samples with DPM-Solver++(2M), ``ddpm.sample_dpm``: use it with ``--num_steps`` 16 to 32 (``--dpm_eta 1``: its stochastic member).
 ``--points_dir DIR`` (extension) also writes every sample as a Velodyne scan ``DIR/samples_{seed:010d}.bin``: the pixels inside the
 checkpoint's depth window as fp32 [x, y, z, reflectance] rows in scan order (r2dm_amd.pointcloud)."""
 import os
@@ -56,7 +56,7 @@ def sample(args):
         seeds = mine[i: i + args.batch_size]
         rng = r2dm_amd.setup_rng(seeds, device=device)
         if args.mode == "dpmpp":  # (extension: DPM-Solver++(2M), meant for 16-32 steps)
-            samples = ddpm.sample_dpm(batch_size=len(seeds), num_steps=args.num_steps, rng=rng, progress=False).clamp(-1, 1)
+            samples = ddpm.sample_dpm(batch_size=len(seeds), num_steps=args.num_steps, rng=rng, progress=False, eta=args.dpm_eta).clamp(-1, 1)
         else:
             samples = ddpm.sample(batch_size=len(seeds), num_steps=args.num_steps, mode=args.mode, rng=rng, progress=False).clamp(-1, 1)
         samples = lidar_utils.postprocess(samples)  # denormalize -> revert_depth -> to_xyz -> concat, one kernel
@@ -79,6 +79,7 @@ def parser():
     parser.add_argument("--num_steps", type=int, default=256)
     parser.add_argument("--mode", choices=["ddpm", "ddim", "dpmpp"], default="ddpm",
                         help="dpmpp (extension): the DPM-Solver++(2M) sampler, ddpm.sample_dpm; use it with --num_steps 16 to 32")
+    parser.add_argument("--dpm_eta", type=float, default=0.0, help="--mode dpmpp: the share of fresh noise per step (0: deterministic, 1: SDE-DPM-Solver++(2M))")
     parser.add_argument("--precision", choices=["fp32", "fp32-bf16x3", "fp16"], default="fp32")
     parser.add_argument("--max-batch", type=int, default=0, help="extension: the batch size the layer tilings are planned for (default: --batch_size)")
     parser.add_argument("--points_dir", type=str, default=None, help="extension: also write every sample as a Velodyne scan samples_<seed>.bin there")
