@@ -246,41 +246,28 @@ def posterior_step_known(x_t, pred, noise, known, mask, coef, mode: int, objecti
 def dpm_step(x_t, pred, x0_prev, coef, objective: int, clip: float, x0_out: Optional[torch.Tensor] = None):
     """One DPM-Solver++(2M) update (``r2dm_dpm_step``) -> ``(x_s, x0)``: ``x0`` the clamped estimate of x_0 (``posterior_step``'s), ``x_s =
     c_x x_t + c_0 x0`` with ``x0_prev=None`` (a first-order row), else ``(c_x x_t + c_0 x0) + c_1 x0_prev``; ``coef`` (B,8) = (alpha_t, sigma_t,
-    c_x, c_0, c_1, 0, 0, 0).  ``x0_out``: a float32 contiguous buffer of ``x_t``'s shape to write ``x0`` into (it may be ``x0_prev`` itself); None: a new one."""
-    require_gpu(x_t, "x_t")
-    x_t, pred, coef = f32c(x_t), f32c(pred), f32c(coef)
-    x0_prev = None if x0_prev is None else f32c(x0_prev)
-    if x_t.dim() < 2 or any(t is not None and (t.shape != x_t.shape or t.device != x_t.device) for t in (pred, x0_prev, x0_out)) \
-            or coef.shape != (x_t.shape[0], 8) or coef.device != x_t.device:
-        raise ValueError(f"x_t {tuple(x_t.shape)}, prediction {tuple(pred.shape)}, x0_prev and x0_out must have one (B,...) shape on one device, "
-                         f"coef {tuple(coef.shape)} must be (B,8)")
-    if x0_out is None:
-        x0_out = torch.empty_like(x_t)
-    elif x0_out.dtype != torch.float32 or not x0_out.is_contiguous():
-        raise ValueError("x0_out must be a contiguous float32 tensor")
-    out = torch.empty_like(x_t)
-    B = x_t.shape[0]
-    with torch.cuda.device(x_t.device):
-        check(lib().r2dm_dpm_step(ptr(x_t), ptr(pred), ptr(x0_prev), ptr(coef), ptr(out), ptr(x0_out), B, x_t.numel() // B, objective, float(clip),
-                                  stream_ptr(x_t.device)))
-    return out, x0_out
+    c_x, c_0, c_1, 0, 0, 0).  ``x0_out``: a float32 contiguous buffer of ``x_t``'s shape to write ``x0`` into (it may be ``x0_prev`` itself); None: a new one.
+    Operands of any (B,...) shape: without a measurement there are no channels to speak of."""
+    return dpm_step_known(x_t, pred, x0_prev, None, None, None, coef, objective, clip, x0_out, _entry="r2dm_dpm_step")
 
 
-def dpm_step_known(x_t, pred, x0_prev, noise, known, mask, coef, objective: int, clip: float, x0_out: Optional[torch.Tensor] = None):
+def dpm_step_known(x_t, pred, x0_prev, noise, known, mask, coef, objective: int, clip: float, x0_out: Optional[torch.Tensor] = None,
+                   _entry: str = "r2dm_dpm_step_known"):
     """``dpm_step`` with a measurement and a noise operand (``r2dm_dpm_step_known``) -> ``(x_s, x0)``: the clamped estimate gets ``x0 = mask *
     known + (1 - mask) * x0`` (``known`` and ``mask`` both given or both None; ``mask`` (B | 1, 1 | C, ...) is expanded over the batch as in
     ``repaint_blend``), ``x_s = c_x x_t + c_0 x0 [+ c_1 x0_prev] [+ c_z noise]``; ``coef`` (B,8) = (alpha_t, sigma_t, c_x, c_0, c_1, c_z, 0, 0).
-    ``x0`` is the estimate after the projection.  ``x0_out`` as in ``dpm_step``."""
+    ``x0`` is the estimate after the projection.  ``x0_out`` as in ``dpm_step``.  (``_entry``: ``dpm_step``'s own, which takes neither.)"""
+    measured = _entry == "r2dm_dpm_step_known"
     require_gpu(x_t, "x_t")
     x_t, pred, coef = f32c(x_t), f32c(pred), f32c(coef)
     x0_prev, noise, known = (None if t is None else f32c(t) for t in (x0_prev, noise, known))
     if (known is None) != (mask is None):
         raise ValueError("known and mask are given together or not at all")
-    if x_t.dim() < 3 or any(t is not None and (t.shape != x_t.shape or t.device != x_t.device) for t in (pred, x0_prev, noise, known, x0_out)) \
+    if x_t.dim() < (3 if measured else 2) or any(t is not None and (t.shape != x_t.shape or t.device != x_t.device) for t in (pred, x0_prev, noise, known, x0_out)) \
             or coef.shape != (x_t.shape[0], 8) or coef.device != x_t.device:
-        raise ValueError(f"x_t {tuple(x_t.shape)}, prediction {tuple(pred.shape)}, x0_prev, noise, known and x0_out must have one (B,C,...) shape on one "
-                         f"device, coef {tuple(coef.shape)} must be (B,8)")
-    B, C = x_t.shape[0], x_t.shape[1]
+        raise ValueError(f"x_t {tuple(x_t.shape)}, prediction {tuple(pred.shape)}, x0_prev, noise, known and x0_out must have one "
+                         f"{'(B,C,...)' if measured else '(B,...)'} shape on one device, coef {tuple(coef.shape)} must be (B,8)")
+    B = x_t.shape[0]
     if mask is not None:
         mask = f32c(mask.to(x_t.device).expand(B, -1, *x_t.shape[2:]))
     if x0_out is None:
@@ -288,9 +275,12 @@ def dpm_step_known(x_t, pred, x0_prev, noise, known, mask, coef, objective: int,
     elif x0_out.dtype != torch.float32 or not x0_out.is_contiguous():
         raise ValueError("x0_out must be a contiguous float32 tensor")
     out = torch.empty_like(x_t)
+    args = [ptr(x_t), ptr(pred), ptr(x0_prev), ptr(coef), ptr(out), ptr(x0_out), B, x_t.numel() // B, objective, float(clip), stream_ptr(x_t.device)]
+    if measured:  # r2dm_dpm_step_known's further operands, where its signature has them
+        args[3:3] = [ptr(noise), ptr(known), ptr(mask)]
+        args[11:11] = [x_t.shape[1], 1 if mask is None else mask.shape[1]]
     with torch.cuda.device(x_t.device):
-        check(lib().r2dm_dpm_step_known(ptr(x_t), ptr(pred), ptr(x0_prev), ptr(noise), ptr(known), ptr(mask), ptr(coef), ptr(out), ptr(x0_out), B,
-                                        x_t.numel() // B, C, 1 if mask is None else mask.shape[1], objective, float(clip), stream_ptr(x_t.device)))
+        check(getattr(lib(), _entry)(*args))
     return out, x0_out
 
 
@@ -318,7 +308,7 @@ def q_step(x_s, noise, coef) -> torch.Tensor:
     return out
 
 
-LOSS_OBJECTIVES = {"eps": 0, "v": 1, "x_0": 2}
+OBJECTIVES = {"eps": 0, "v": 1, "x_0": 2}  # what the denoiser predicts (csrc/common.h OBJ_*): the one table, for samplers and loss alike
 LOSS_CRITERIA = {"l2": 0, "l1": 1, "huber": 2}
 
 
@@ -327,7 +317,7 @@ def diffusion_loss(prediction, x_0, noise, mask, coef, objective: str, criterion
     the mask over its own elements (``C*H*W`` for ``mask=None``) -- base.py:133-136 in one pass.  ``mask``: None, (B,1,H,W) or (B,C,H,W);
     ``coef`` (B,2) = (alpha, sigma), read for the ``v`` objective only."""
     require_gpu(prediction, "prediction")
-    if objective not in LOSS_OBJECTIVES:
+    if objective not in OBJECTIVES:
         raise ValueError(f"invalid objective {objective}")
     if criterion not in LOSS_CRITERIA:
         raise ValueError(f"invalid criterion: {criterion}")
@@ -352,7 +342,7 @@ def diffusion_loss(prediction, x_0, noise, mask, coef, objective: str, criterion
     num = torch.empty(B, C, device=dev, dtype=torch.float64)
     den = torch.empty(B, device=dev, dtype=torch.float64)
     with torch.cuda.device(dev):
-        check(lib().r2dm_diffusion_loss(ptr(prediction), ptr(x_0), ptr(noise), ptr(mask), mask_c, ptr(coef), LOSS_OBJECTIVES[objective],
+        check(lib().r2dm_diffusion_loss(ptr(prediction), ptr(x_0), ptr(noise), ptr(mask), mask_c, ptr(coef), OBJECTIVES[objective],
                                         LOSS_CRITERIA[criterion], B, C, plane, ptr(scratch), ptr(num), ptr(den), stream_ptr(dev)))
     return num, den
 

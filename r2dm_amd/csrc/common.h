@@ -255,10 +255,19 @@ hipError_t launch_time_embedding(const EmbedParams& p, hipStream_t s);
 hipError_t launch_ada_proj(const float* act, const float* w, const float* bias, float* out, int B, int T,
                            int rows, hipStream_t s);
 
+// ---- sampler steps (posterior.hip, latent.hip) ----
+enum { OBJ_EPS = 0, OBJ_V = 1, OBJ_X0 = 2 };  // what the denoiser predicts
+
+// launch shape of the kernels that stream B samples of per_sample floats in 16-byte quads, grid-stride: 256 threads, at most 1024 blocks a sample
+inline dim3 quad_grid(int B, long per_sample) {
+    const long bx = (per_sample / 4 + 255) / 256;
+    return dim3((unsigned)(bx < 1 ? 1 : bx > 1024 ? 1024 : bx), (unsigned)B);
+}
+
 struct PosteriorParams {
     const float* x_t;
     const float* pred;
-    const float* noise;  // may be nullptr for deterministic modes
+    const float* noise;  // nullptr for mode 3 (discrete DDIM, eta = 0), which reads none
     const float* coef;   // [B][8]
     float* x_s;
     int B;
@@ -272,6 +281,7 @@ hipError_t launch_posterior_known(const PosteriorParams& p, const float* known, 
                                   hipStream_t s);
 // DPM-Solver++(2M) update: x_s = c_x x_t + c_0 x0 [+ c_1 x0_prev] with x0 the clamped estimate of the posterior step, also written out;
 // coef [B][8] = (alpha_t, sigma_t, c_x, c_0, c_1, 0, 0, 0).  x0_prev null: the first-order row.  x0 may be x0_prev's buffer.
+// (launch_dpm_step is launch_dpm_step_known without noise and measurement)
 struct DpmParams {
     const float* x_t;
     const float* pred;

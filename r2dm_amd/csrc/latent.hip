@@ -6,8 +6,6 @@
 
 namespace r2dm {
 
-enum { OBJ_EPS = 0, OBJ_V = 1, OBJ_X0 = 2 };
-
 // ---- DDIM transfer  x_t, prediction -> x_u  along the deterministic line, t -> u in either direction, no clipping -------------
 // coef[b] = (alpha_t, sigma_t, alpha_u, sigma_u).  x_0 and eps come from the prediction in the DIRECT form of each objective: the
 // indirect eps = (x - alpha_t x_0) / sigma_t cancels at t = 0 (sigma_t ~ 5.5e-4), where an inversion starts.
@@ -47,16 +45,13 @@ __global__ __launch_bounds__(256) void ddim_transfer_kernel(const float* __restr
 }
 #pragma clang fp contract(fast)
 
-// (launch shape and alignment rules of launch_posterior)
+// (alignment rules of launch_posterior)
 hipError_t launch_ddim_transfer(const float* x_t, const float* pred, const float* coef, float* x_u, int B, long per_sample, int objective,
                                 hipStream_t s) {
     if ((per_sample & 3) || (reinterpret_cast<uintptr_t>(x_t) & 15) || (reinterpret_cast<uintptr_t>(pred) & 15) ||
         (reinterpret_cast<uintptr_t>(x_u) & 15))
         return hipErrorInvalidValue;
-    long bx = (per_sample / 4 + 255) / 256;
-    if (bx < 1) bx = 1;
-    if (bx > 1024) bx = 1024;
-    const dim3 g((unsigned)bx, B);
+    const dim3 g = quad_grid(B, per_sample);
     switch (objective) {
         case OBJ_EPS: ddim_transfer_kernel<OBJ_EPS><<<g, 256, 0, s>>>(x_t, pred, coef, x_u, per_sample); break;
         case OBJ_V: ddim_transfer_kernel<OBJ_V><<<g, 256, 0, s>>>(x_t, pred, coef, x_u, per_sample); break;
@@ -170,10 +165,7 @@ hipError_t launch_slerp(const float* a, const float* b, const float* weights, in
     if (e != hipSuccess) return e;
     SlerpWeights w{};
     for (int k = 0; k < K; ++k) w.w[k] = weights[k];
-    long bx = (per_sample / 4 + 255) / 256;
-    if (bx < 1) bx = 1;
-    if (bx > 1024) bx = 1024;
-    slerp_blend_kernel<<<dim3((unsigned)bx, (unsigned)B), 256, 0, s>>>(a, b, part, w, K, blocks, out, coef64, per_sample);
+    slerp_blend_kernel<<<quad_grid(B, per_sample), 256, 0, s>>>(a, b, part, w, K, blocks, out, coef64, per_sample);
     return hipGetLastError();
 }
 

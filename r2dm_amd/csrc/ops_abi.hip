@@ -1,6 +1,7 @@
 // C ABI of the stand-alone operators (include/r2dm_hip.h): sampler steps, LiDAR post-processing, BEV metrics, rendering, projection and point-cloud
 // export.  Each entry validates its arguments and enqueues the operator's kernels (posterior / metrics / render / projection / pointcloud .hip).
 #include <cmath>
+#include <initializer_list>
 
 #include "engine.h"
 
@@ -16,22 +17,43 @@ int r2dm_posterior_step(const float* x_t, const float* pred, const float* noise,
     return 0;
 }
 
+// What r2dm_posterior_step_known, r2dm_dpm_step and r2dm_dpm_step_known refuse alike, `name` in front of every message.  `need`: the operands that
+// may not be null (`nullable`: the message's word on the rest); `quads`: every tensor the kernel reads or writes as 16-byte quads, absent ones null.  The geometry is
+// per_sample in `channels` planes of whole quads under a mask of 1 or `channels` planes (one channel: whole quads, nothing more).  x0 given: the DPM
+// entries' two outputs may not alias an input or each other, only x0 may be x0_prev's buffer.
+static int step_refused(const char* name, std::initializer_list<const void*> need, const char* nullable, std::initializer_list<const void*> quads,
+                        const float* known, const float* mask, const float* coef, int32_t B, int64_t per_sample, int32_t channels, int32_t mask_channels,
+                        int32_t objective, const float* x0_prev = nullptr, const float* x_s = nullptr, const float* x0 = nullptr) {
+    for (const void* q : need)
+        if (!q) return fail(1, "%s: null argument%s", name, nullable);
+    if (!known != !mask) return fail(1, "%s: known and mask are given together or not at all (null argument)", name);
+    if (objective < 0 || objective > 2) return fail(1, "%s: objective must be 0 (eps), 1 (v) or 2 (x_0), got %d", name, objective);
+    if (B < 1 || B > 65535) return fail(1, "%s: batch must be in [1, 65535], got %d", name, B);
+    if (per_sample < 4 || per_sample > (1LL << 40) / B || per_sample % 4)
+        return fail(1, "%s: per_sample (got %lld) must be a multiple of 4 in [4, 2^40 / batch]", name, (long long)per_sample);
+    if (channels < 1 || per_sample % channels) return fail(1, "%s: per_sample (got %lld) must divide into %d channels", name, (long long)per_sample, channels);
+    if ((per_sample / channels) % 4)
+        return fail(1, "%s: the plane per_sample / channels (got %lld) must be a multiple of 4", name, (long long)(per_sample / channels));
+    if (mask_channels != 1 && mask_channels != channels) return fail(1, "%s: mask_channels must be 1 or %d, got %d", name, channels, mask_channels);
+    uintptr_t bits = 0;
+    for (const void* q : quads) bits |= (uintptr_t)q;
+    if ((bits & 15) || ((uintptr_t)coef & 3)) return fail(1, "%s: the tensors must be 16-byte aligned, coef 4-byte aligned", name);
+    if (x0) {  // each output stands once among the operands, x0 twice where it is x0_prev
+        int n_s = 0, n_0 = 0;
+        for (const void* q : quads) n_s += q == x_s, n_0 += q == x0;
+        if (n_s != 1 || n_0 != 1 + (x0 == x0_prev))
+            return fail(1, "%s: an output may not alias an input or the other output (only x0 may be x0_prev's buffer)", name);
+    }
+    return 0;
+}
+
 int r2dm_posterior_step_known(const float* x_t, const float* pred, const float* noise, const float* known, const float* mask,
                               const float* coef, float* x_s, int32_t B, int64_t per_sample, int32_t channels, int32_t mask_channels,
                               int32_t mode, int32_t objective, float clip, void* stream) {
-    if (!x_t || !pred || !noise || !known || !mask || !coef || !x_s) return fail(1, "posterior_step_known: null argument");
+    if (step_refused("posterior_step_known", {x_t, pred, noise, known, mask, coef, x_s}, "", {x_t, pred, noise, known, mask, x_s}, known, mask, coef,
+                     B, per_sample, channels, mask_channels, objective))
+        return 1;
     if (mode < 0 || mode > 1) return fail(1, "posterior_step_known: mode must be 0 (continuous DDPM) or 1 (continuous DDIM), got %d", mode);
-    if (objective < 0 || objective > 2) return fail(1, "posterior_step_known: objective must be 0 (eps), 1 (v) or 2 (x_0), got %d", objective);
-    if (B < 1 || B > 65535) return fail(1, "posterior_step_known: batch must be in [1, 65535], got %d", B);
-    if (channels < 1 || per_sample < 4 || per_sample > (1LL << 40) / B || per_sample % channels)
-        return fail(1, "posterior_step_known: per_sample (got %lld) must be in [4, 2^40 / batch] and divide into %d channels", (long long)per_sample, channels);
-    if (per_sample % 4 || (per_sample / channels) % 4)
-        return fail(1, "posterior_step_known: per_sample (got %lld) and the plane per_sample / channels (got %lld) must each be a multiple of 4",
-                    (long long)per_sample, (long long)(per_sample / channels));
-    if (mask_channels != 1 && mask_channels != channels)
-        return fail(1, "posterior_step_known: mask_channels must be 1 or %d, got %d", channels, mask_channels);
-    if ((((uintptr_t)x_t | (uintptr_t)pred | (uintptr_t)noise | (uintptr_t)known | (uintptr_t)mask | (uintptr_t)x_s) & 15) || ((uintptr_t)coef & 3))
-        return fail(1, "posterior_step_known: x_t, prediction, noise, known, mask and x_s must be 16-byte aligned, coef 4-byte aligned");
     PosteriorParams p{x_t, pred, noise, coef, x_s, B, per_sample, mode, objective, clip};
     HIP_TRY(launch_posterior_known(p, known, mask, channels, mask_channels, (hipStream_t)stream));
     return 0;
@@ -39,15 +61,9 @@ int r2dm_posterior_step_known(const float* x_t, const float* pred, const float* 
 
 int r2dm_dpm_step(const float* x_t, const float* pred, const float* x0_prev, const float* coef, float* x_s, float* x0, int32_t B,
                   int64_t per_sample, int32_t objective, float clip, void* stream) {
-    if (!x_t || !pred || !coef || !x_s || !x0) return fail(1, "dpm_step: null argument (only x0_prev may be null)");
-    if (objective < 0 || objective > 2) return fail(1, "dpm_step: objective must be 0 (eps), 1 (v) or 2 (x_0), got %d", objective);
-    if (B < 1 || B > 65535) return fail(1, "dpm_step: batch must be in [1, 65535], got %d", B);
-    if (per_sample < 4 || per_sample > (1LL << 40) / B || per_sample % 4)
-        return fail(1, "dpm_step: per_sample (got %lld) must be a multiple of 4 in [4, 2^40 / batch]", (long long)per_sample);
-    if ((((uintptr_t)x_t | (uintptr_t)pred | (uintptr_t)x0_prev | (uintptr_t)x_s | (uintptr_t)x0) & 15) || ((uintptr_t)coef & 3))
-        return fail(1, "dpm_step: x_t, prediction, x0_prev, x_s and x0 must be 16-byte aligned, coef 4-byte aligned");
-    if (x_s == x_t || x_s == pred || x_s == x0_prev || x_s == x0 || x0 == x_t || x0 == pred)
-        return fail(1, "dpm_step: an output may not alias an input or the other output (only x0 may be x0_prev's buffer)");
+    if (step_refused("dpm_step", {x_t, pred, coef, x_s, x0}, " (only x0_prev may be null)", {x_t, pred, x0_prev, x_s, x0}, nullptr, nullptr, coef, B, per_sample, 1, 1, objective,
+                     x0_prev, x_s, x0))
+        return 1;
     DpmParams p{x_t, pred, x0_prev, coef, x_s, x0, B, per_sample, objective, clip};
     HIP_TRY(launch_dpm_step(p, (hipStream_t)stream));
     return 0;
@@ -56,24 +72,9 @@ int r2dm_dpm_step(const float* x_t, const float* pred, const float* x0_prev, con
 int r2dm_dpm_step_known(const float* x_t, const float* pred, const float* x0_prev, const float* noise, const float* known, const float* mask,
                         const float* coef, float* x_s, float* x0, int32_t B, int64_t per_sample, int32_t channels, int32_t mask_channels,
                         int32_t objective, float clip, void* stream) {
-    if (!x_t || !pred || !coef || !x_s || !x0) return fail(1, "dpm_step_known: null argument (only x0_prev, noise and the pair known, mask may be null)");
-    if (!known != !mask) return fail(1, "dpm_step_known: known and mask are given together or not at all (null argument)");
-    if (objective < 0 || objective > 2) return fail(1, "dpm_step_known: objective must be 0 (eps), 1 (v) or 2 (x_0), got %d", objective);
-    if (B < 1 || B > 65535) return fail(1, "dpm_step_known: batch must be in [1, 65535], got %d", B);
-    if (channels < 1 || per_sample < 4 || per_sample > (1LL << 40) / B || per_sample % channels)
-        return fail(1, "dpm_step_known: per_sample (got %lld) must be in [4, 2^40 / batch] and divide into %d channels", (long long)per_sample, channels);
-    if (per_sample % 4 || (per_sample / channels) % 4)
-        return fail(1, "dpm_step_known: per_sample (got %lld) and the plane per_sample / channels (got %lld) must each be a multiple of 4",
-                    (long long)per_sample, (long long)(per_sample / channels));
-    if (mask_channels != 1 && mask_channels != channels)
-        return fail(1, "dpm_step_known: mask_channels must be 1 or %d, got %d", channels, mask_channels);
-    if ((((uintptr_t)x_t | (uintptr_t)pred | (uintptr_t)x0_prev | (uintptr_t)noise | (uintptr_t)known | (uintptr_t)mask | (uintptr_t)x_s | (uintptr_t)x0) & 15) ||
-        ((uintptr_t)coef & 3))
-        return fail(1, "dpm_step_known: x_t, prediction, x0_prev, noise, known, mask, x_s and x0 must be 16-byte aligned, coef 4-byte aligned");
-    if (x_s == x_t || x_s == pred || x_s == x0_prev || x_s == x0 || x0 == x_t || x0 == pred)
-        return fail(1, "dpm_step_known: an output may not alias an input or the other output (only x0 may be x0_prev's buffer)");
-    for (const float* in : {noise, known, mask})
-        if (in && (in == x_s || in == x0)) return fail(1, "dpm_step_known: an output may not alias noise, known or mask");
+    if (step_refused("dpm_step_known", {x_t, pred, coef, x_s, x0}, " (only x0_prev, noise and the pair known, mask may be null)", {x_t, pred, x0_prev, noise, known, mask, x_s, x0},
+                     known, mask, coef, B, per_sample, channels, mask_channels, objective, x0_prev, x_s, x0))
+        return 1;
     DpmParams p{x_t, pred, x0_prev, coef, x_s, x0, B, per_sample, objective, clip};
     HIP_TRY(launch_dpm_step_known(p, noise, known, mask, channels, mask_channels, (hipStream_t)stream));
     return 0;

@@ -6,17 +6,39 @@
 //   discrete time    /root/reference/models/diffusion/discrete_time.py:140-177
 // All schedule scalars arrive in coef[b][8], computed on the host with the reference's torch ops.
 //
-// also: K12 LiDAR post-processing of finished samples (reference sample_and_save.py:52-57).
+// The sampler steps are two kernels over the same two halves (posterior_x0, then the update from it):
+//   posterior_kernel<MODE, OBJ, KNOWN>          r2dm_posterior_step, and with a measurement r2dm_posterior_step_known (DDNM)
+//   dpm_step_kernel<OBJ, SECOND, NOISE, KNOWN>  r2dm_dpm_step and r2dm_dpm_step_known (DPM-Solver++(2M))
+//
+// also: K12 LiDAR post-processing of finished samples (reference sample_and_save.py:52-57), the RePaint pieces and the denoising loss.
 #include "common.h"
 #include "wave_ops.h"
 
 namespace r2dm {
 
 enum { M_CT_DDPM = 0, M_CT_DDIM = 1, M_DT_DDPM = 2, M_DT_DDIM = 3, M_DT_DDIM_NOISE = 4 };
-enum { OBJ_EPS = 0, OBJ_V = 1, OBJ_X0 = 2 };
+
+// The measurement of a data-consistent step: known (B, per_sample) and its per-pixel weight mask, which has mask_c channels of `plane`
+// elements (1 = broadcast over the planes of a sample).  plane % 4 == 0: a quad never straddles planes.
+struct Measurement {
+    const float* known;
+    const float* mask;
+    long plane;
+    int mask_c;
+};
+
+// the mask's quad for quad i of sample b
+__device__ __forceinline__ f32x4 mask_quad(const float* mask, int b, long i, long per_sample, long plane, int mask_c) {
+    return *reinterpret_cast<const f32x4*>(mask + (mask_c == 1 ? b * plane + (i << 2) % plane : b * per_sample + (i << 2)));
+}
+
+__device__ __forceinline__ void load_coef_row(const float* coef, int b, float (&k)[8]) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) k[i] = coef[b * 8 + i];
+}
 
 #pragma clang fp contract(off)
-// the two halves of one element's update: the clamped estimate of x_0, and x_s from it (posterior_known_kernel puts the measurement between them)
+// the two halves of one element's update: the clamped estimate of x_0, and x_s from it (a measurement goes between them: project_known)
 template <int MODE, int OBJ>
 __device__ __forceinline__ float posterior_x0(float x, float pr, const float* k, float clip) {
     float x0;
@@ -32,6 +54,9 @@ __device__ __forceinline__ float posterior_x0(float x, float pr, const float* k,
     if (clip >= 0.f) x0 = fminf(fmaxf(x0, -clip), clip);
     return x0;
 }
+
+// DDNM's null-space projection for a mask operator: the measurement y written over the estimate with weight m (not necessarily binary)
+__device__ __forceinline__ float project_known(float m, float y, float x0) { return m * y + (1.0f - m) * x0; }
 
 template <int MODE>
 __device__ __forceinline__ float posterior_update(float x, float x0, float z, const float* k) {
@@ -54,207 +79,102 @@ __device__ __forceinline__ float posterior_update(float x, float x0, float z, co
     }
 }
 
-template <int MODE, int OBJ>
-__device__ __forceinline__ float posterior_elem(float x, float pr, float z, const float* k, float clip) {
-    return posterior_update<MODE>(x, posterior_x0<MODE, OBJ>(x, pr, k, clip), z, k);
-}
-
-template <int MODE, int OBJ>
-__global__ __launch_bounds__(256) void posterior_kernel(PosteriorParams p) {
+// x_t, prediction[, noise][, known, mask] -> x_s in one pass of 16-byte quads (2 to 5 reads + 1 write).  The noise is a property of MODE: M_DT_DDIM
+// reads none, every other mode needs it.  KNOWN: project_known between the two halves (r2dm_posterior_step_known); ms is not read without it.
+template <int MODE, int OBJ, bool KNOWN>
+__global__ __launch_bounds__(256) void posterior_kernel(PosteriorParams p, Measurement ms) {
+    constexpr bool NOISE = MODE != M_DT_DDIM;
     const int b = blockIdx.y;
     float k[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) k[i] = p.coef[b * 8 + i];
+    load_coef_row(p.coef, b, k);
     const long n4 = p.per_sample >> 2;
     const f32x4* x4 = reinterpret_cast<const f32x4*>(p.x_t + b * p.per_sample);
     const f32x4* p4 = reinterpret_cast<const f32x4*>(p.pred + b * p.per_sample);
-    const f32x4* z4 = p.noise ? reinterpret_cast<const f32x4*>(p.noise + b * p.per_sample) : nullptr;
+    const f32x4* z4 = NOISE ? reinterpret_cast<const f32x4*>(p.noise + b * p.per_sample) : nullptr;
+    const f32x4* y4 = KNOWN ? reinterpret_cast<const f32x4*>(ms.known + b * p.per_sample) : nullptr;
     f32x4* o4 = reinterpret_cast<f32x4*>(p.x_s + b * p.per_sample);
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
         const f32x4 x = x4[i], pr = p4[i];
-        f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        if (z4) z = z4[i];
-        f32x4 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = posterior_elem<MODE, OBJ>(x[j], pr[j], z[j], k, p.clip);
-        o4[i] = o;
-    }
-    // tail (per_sample not a multiple of 4)
-    for (long i = (n4 << 2) + blockIdx.x * 256L + threadIdx.x; i < p.per_sample; i += (long)gridDim.x * 256) {
-        const long e = b * p.per_sample + i;
-        p.x_s[e] = posterior_elem<MODE, OBJ>(p.x_t[e], p.pred[e], p.noise ? p.noise[e] : 0.f, k, p.clip);
-    }
-}
-
-template <int MODE>
-static hipError_t launch_obj(const PosteriorParams& p, dim3 g, hipStream_t s) {
-    switch (p.objective) {
-        case OBJ_EPS: posterior_kernel<MODE, OBJ_EPS><<<g, 256, 0, s>>>(p); break;
-        case OBJ_V: posterior_kernel<MODE, OBJ_V><<<g, 256, 0, s>>>(p); break;
-        case OBJ_X0: posterior_kernel<MODE, OBJ_X0><<<g, 256, 0, s>>>(p); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_posterior(const PosteriorParams& p, hipStream_t s) {
-    if ((p.per_sample & 3) || (reinterpret_cast<uintptr_t>(p.x_t) & 15) || (reinterpret_cast<uintptr_t>(p.pred) & 15) ||
-        (reinterpret_cast<uintptr_t>(p.x_s) & 15) || (reinterpret_cast<uintptr_t>(p.noise) & 15))
-        return hipErrorInvalidValue;
-    if (p.noise == nullptr && p.mode != M_DT_DDIM) return hipErrorInvalidValue;
-    long bx = (p.per_sample / 4 + 255) / 256;
-    if (bx < 1) bx = 1;
-    if (bx > 1024) bx = 1024;
-    const dim3 g((unsigned)bx, p.B);
-    switch (p.mode) {
-        case M_CT_DDPM: return launch_obj<M_CT_DDPM>(p, g, s);
-        case M_CT_DDIM: return launch_obj<M_CT_DDIM>(p, g, s);
-        case M_DT_DDPM: return launch_obj<M_DT_DDPM>(p, g, s);
-        case M_DT_DDIM: return launch_obj<M_DT_DDIM>(p, g, s);
-        case M_DT_DDIM_NOISE: return launch_obj<M_DT_DDIM_NOISE>(p, g, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-// ---- data-consistent posterior step (DDNM's null-space projection for a mask operator) ------------------------------------------
-// x_t, prediction, noise, known, mask -> x_s in one pass (5 reads + 1 write): posterior_x0, then the measurement written over the
-// estimate, x0 = m * y + (1 - m) * x0 (m a per-pixel weight, not necessarily binary), then posterior_update.  Continuous time only.
-// mask has mask_c channels (1 = broadcast over the planes of a sample); plane % 4 == 0: a quad never straddles planes.
-template <int MODE, int OBJ>
-__global__ __launch_bounds__(256) void posterior_known_kernel(PosteriorParams p, const float* __restrict__ known,
-                                                              const float* __restrict__ mask, long plane, int mask_c) {
-    const int b = blockIdx.y;
-    float k[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) k[i] = p.coef[b * 8 + i];
-    const long n4 = p.per_sample >> 2, plane4 = plane >> 2;
-    const f32x4* x4 = reinterpret_cast<const f32x4*>(p.x_t + b * p.per_sample);
-    const f32x4* p4 = reinterpret_cast<const f32x4*>(p.pred + b * p.per_sample);
-    const f32x4* z4 = reinterpret_cast<const f32x4*>(p.noise + b * p.per_sample);
-    const f32x4* y4 = reinterpret_cast<const f32x4*>(known + b * p.per_sample);
-    const f32x4* m4 = reinterpret_cast<const f32x4*>(mask + b * (mask_c == 1 ? plane : p.per_sample));
-    f32x4* o4 = reinterpret_cast<f32x4*>(p.x_s + b * p.per_sample);
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-        const f32x4 x = x4[i], pr = p4[i], z = z4[i], y = y4[i];
-        const f32x4 m = m4[mask_c == 1 ? i % plane4 : i];
+        f32x4 z = {0.f, 0.f, 0.f, 0.f}, y = z, m = z;
+        if (NOISE) z = z4[i];
+        if (KNOWN) y = y4[i], m = mask_quad(ms.mask, b, i, p.per_sample, ms.plane, ms.mask_c);
         f32x4 o;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float x0 = posterior_x0<MODE, OBJ>(x[j], pr[j], k, p.clip);
-            x0 = m[j] * y[j] + (1.0f - m[j]) * x0;
+            if (KNOWN) x0 = project_known(m[j], y[j], x0);
             o[j] = posterior_update<MODE>(x[j], x0, z[j], k);
         }
         o4[i] = o;
     }
 }
 
-template <int MODE>
-static hipError_t launch_known_obj(const PosteriorParams& p, const float* known, const float* mask, long plane, int mask_c, dim3 g,
-                                   hipStream_t s) {
+template <int MODE, bool KNOWN>
+static hipError_t launch_posterior_obj(const PosteriorParams& p, const Measurement& ms, hipStream_t s) {
+    const dim3 g = quad_grid(p.B, p.per_sample);
     switch (p.objective) {
-        case OBJ_EPS: posterior_known_kernel<MODE, OBJ_EPS><<<g, 256, 0, s>>>(p, known, mask, plane, mask_c); break;
-        case OBJ_V: posterior_known_kernel<MODE, OBJ_V><<<g, 256, 0, s>>>(p, known, mask, plane, mask_c); break;
-        case OBJ_X0: posterior_known_kernel<MODE, OBJ_X0><<<g, 256, 0, s>>>(p, known, mask, plane, mask_c); break;
+        case OBJ_EPS: posterior_kernel<MODE, OBJ_EPS, KNOWN><<<g, 256, 0, s>>>(p, ms); break;
+        case OBJ_V: posterior_kernel<MODE, OBJ_V, KNOWN><<<g, 256, 0, s>>>(p, ms); break;
+        case OBJ_X0: posterior_kernel<MODE, OBJ_X0, KNOWN><<<g, 256, 0, s>>>(p, ms); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
 
-// (arguments validated by r2dm_posterior_step_known; checked again here, since the kernel reads quads and has no tail)
+// (the kernel reads quads and has no tail)
+hipError_t launch_posterior(const PosteriorParams& p, hipStream_t s) {
+    if ((p.per_sample & 3) || (reinterpret_cast<uintptr_t>(p.x_t) & 15) || (reinterpret_cast<uintptr_t>(p.pred) & 15) ||
+        (reinterpret_cast<uintptr_t>(p.x_s) & 15) || (reinterpret_cast<uintptr_t>(p.noise) & 15))
+        return hipErrorInvalidValue;
+    if (p.noise == nullptr && p.mode != M_DT_DDIM) return hipErrorInvalidValue;
+    switch (p.mode) {
+        case M_CT_DDPM: return launch_posterior_obj<M_CT_DDPM, false>(p, {}, s);
+        case M_CT_DDIM: return launch_posterior_obj<M_CT_DDIM, false>(p, {}, s);
+        case M_DT_DDPM: return launch_posterior_obj<M_DT_DDPM, false>(p, {}, s);
+        case M_DT_DDIM: return launch_posterior_obj<M_DT_DDIM, false>(p, {}, s);
+        case M_DT_DDIM_NOISE: return launch_posterior_obj<M_DT_DDIM_NOISE, false>(p, {}, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+// the geometry a measurement needs: whole planes of whole quads, a mask of one plane or of all
+static bool measurement_ok(long per_sample, int channels, int mask_c) {
+    return channels >= 1 && per_sample % channels == 0 && (per_sample / channels) % 4 == 0 && (mask_c == 1 || mask_c == channels);
+}
+
+// The data-consistent posterior step, continuous time only.  (arguments validated by r2dm_posterior_step_known; checked again here, since the kernel
+// reads quads and has no tail)
 hipError_t launch_posterior_known(const PosteriorParams& p, const float* known, const float* mask, int channels, int mask_c,
                                   hipStream_t s) {
-    if (p.B < 1 || p.B > 65535 || p.per_sample < 4 || (p.per_sample & 3) || channels < 1 || p.per_sample % channels ||
-        (p.per_sample / channels) % 4 || (mask_c != 1 && mask_c != channels) || !p.noise || !known || !mask)
+    if (p.B < 1 || p.B > 65535 || p.per_sample < 4 || (p.per_sample & 3) || !measurement_ok(p.per_sample, channels, mask_c) || !p.noise || !known || !mask)
         return hipErrorInvalidValue;
-    long bx = (p.per_sample / 4 + 255) / 256;  // (launch_posterior's shape)
-    if (bx > 1024) bx = 1024;
-    const dim3 g((unsigned)bx, p.B);
-    const long plane = p.per_sample / channels;
+    const Measurement ms{known, mask, p.per_sample / channels, mask_c};
     switch (p.mode) {
-        case M_CT_DDPM: return launch_known_obj<M_CT_DDPM>(p, known, mask, plane, mask_c, g, s);
-        case M_CT_DDIM: return launch_known_obj<M_CT_DDIM>(p, known, mask, plane, mask_c, g, s);
+        case M_CT_DDPM: return launch_posterior_obj<M_CT_DDPM, true>(p, ms, s);
+        case M_CT_DDIM: return launch_posterior_obj<M_CT_DDIM, true>(p, ms, s);
     }
     return hipErrorInvalidValue;
 }
 
 // ---- DPM-Solver++(2M) update (Lu et al. 2022, the data-prediction multistep solver on the half-log-SNR axis) --------------------------------
-// x_t, prediction[, x0_prev] -> x_s, x0 in one pass (2 or 3 reads + 2 writes).  coef[b] = (alpha_t, sigma_t, c_x, c_0, c_1, 0, 0, 0), host-computed.
-// x0 is the clamped estimate of posterior_x0 (the next step's history); x_s = c_x x + c_0 x0 (first order, x0_prev not read) or
-// (c_x x + c_0 x0) + c_1 x0_prev.  x0 may be x0_prev's buffer: a thread reads its quad of x0_prev before it writes the same quad of x0, and no
-// other thread touches that quad -- hence no __restrict__ on the two.
-template <int OBJ, bool SECOND>
-__global__ __launch_bounds__(256) void dpm_step_kernel(const float* __restrict__ x_t, const float* __restrict__ pred, const float* x0_prev,
-                                                       const float* __restrict__ coef, float* __restrict__ x_s, float* x0_out, long per_sample,
-                                                       float clip) {
-    const int b = blockIdx.y;
-    float k[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) k[i] = coef[b * 8 + i];
-    const float c_x = k[2], c_0 = k[3], c_1 = k[4];
-    const long n4 = per_sample >> 2;
-    const f32x4* x4 = reinterpret_cast<const f32x4*>(x_t + b * per_sample);
-    const f32x4* p4 = reinterpret_cast<const f32x4*>(pred + b * per_sample);
-    const f32x4* h4 = SECOND ? reinterpret_cast<const f32x4*>(x0_prev + b * per_sample) : nullptr;
-    f32x4* o4 = reinterpret_cast<f32x4*>(x_s + b * per_sample);
-    f32x4* e4 = reinterpret_cast<f32x4*>(x0_out + b * per_sample);
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-        const f32x4 x = x4[i], pr = p4[i];
-        f32x4 h = {0.f, 0.f, 0.f, 0.f};
-        if (SECOND) h = h4[i];
-        f32x4 o, e;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            e[j] = posterior_x0<M_CT_DDPM, OBJ>(x[j], pr[j], k, clip);
-            o[j] = c_x * x[j] + c_0 * e[j];
-            if (SECOND) o[j] = o[j] + c_1 * h[j];
-        }
-        o4[i] = o;
-        e4[i] = e;
-    }
-}
-
-template <int OBJ>
-static hipError_t launch_dpm_obj(const DpmParams& p, dim3 g, hipStream_t s) {
-    if (p.x0_prev) dpm_step_kernel<OBJ, true><<<g, 256, 0, s>>>(p.x_t, p.pred, p.x0_prev, p.coef, p.x_s, p.x0, p.per_sample, p.clip);
-    else dpm_step_kernel<OBJ, false><<<g, 256, 0, s>>>(p.x_t, p.pred, nullptr, p.coef, p.x_s, p.x0, p.per_sample, p.clip);
-    return hipGetLastError();
-}
-
-// (arguments validated by r2dm_dpm_step; checked again here, since the kernel reads quads and has no tail)
-hipError_t launch_dpm_step(const DpmParams& p, hipStream_t s) {
-    if (p.B < 1 || p.B > 65535 || p.per_sample < 4 || (p.per_sample & 3) || !p.x_t || !p.pred || !p.coef || !p.x_s || !p.x0 || p.x_s == p.x_t)
-        return hipErrorInvalidValue;
-    long bx = (p.per_sample / 4 + 255) / 256;  // (launch_posterior's shape)
-    if (bx > 1024) bx = 1024;
-    const dim3 g((unsigned)bx, p.B);
-    switch (p.objective) {
-        case OBJ_EPS: return launch_dpm_obj<OBJ_EPS>(p, g, s);
-        case OBJ_V: return launch_dpm_obj<OBJ_V>(p, g, s);
-        case OBJ_X0: return launch_dpm_obj<OBJ_X0>(p, g, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-// ---- DPM-Solver++(2M) update with a measurement and a noise operand: completion and the stochastic member (SDE-DPM-Solver++(2M)) ------------
 // x_t, prediction[, x0_prev][, noise][, known, mask] -> x_s, x0 in one pass (2 to 6 reads + 2 writes).  coef[b] = (alpha_t, sigma_t, c_x, c_0, c_1,
-// c_z, 0, 0).  dpm_step_kernel's update with DDNM's projection between its halves, x0 = m y + (1 - m) x0 (posterior_known_kernel's), and
-// + c_z z behind them; x0 is written AFTER the projection: that is the history the next step extrapolates from.  An absent operand is a
-// template argument: no load, no arithmetic.  x0 may be x0_prev's buffer, as in dpm_step_kernel.
+// c_z, 0, 0), host-computed.  x0 is the clamped estimate of posterior_x0, with a measurement projected like posterior_kernel's; it is written AFTER
+// the projection: that is the history the next step extrapolates from.  x_s = c_x x + c_0 x0 (first order, x0_prev not read) or
+// (c_x x + c_0 x0) + c_1 x0_prev, then + c_z z: completion and the stochastic member (SDE-DPM-Solver++(2M)).  An absent operand is a template
+// argument: no load, no arithmetic; r2dm_dpm_step is <OBJ, SECOND, false, false>.  x0 may be x0_prev's buffer: a thread reads its quad of x0_prev
+// before it writes the same quad of x0, and no other thread touches that quad -- hence no __restrict__ on the two (DpmParams' members).
 template <int OBJ, bool SECOND, bool NOISE, bool KNOWN>
-__global__ __launch_bounds__(256) void dpm_step_known_kernel(DpmParams p, const float* __restrict__ noise, const float* __restrict__ known,
-                                                             const float* __restrict__ mask, long plane, int mask_c) {
+__global__ __launch_bounds__(256) void dpm_step_kernel(DpmParams p, const float* __restrict__ noise, Measurement ms) {
     const int b = blockIdx.y;
     float k[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) k[i] = p.coef[b * 8 + i];
+    load_coef_row(p.coef, b, k);
     const float c_x = k[2], c_0 = k[3], c_1 = k[4], c_z = k[5];
-    const long n4 = p.per_sample >> 2, plane4 = plane >> 2;
+    const long n4 = p.per_sample >> 2;
     const f32x4* x4 = reinterpret_cast<const f32x4*>(p.x_t + b * p.per_sample);
     const f32x4* p4 = reinterpret_cast<const f32x4*>(p.pred + b * p.per_sample);
     const f32x4* h4 = SECOND ? reinterpret_cast<const f32x4*>(p.x0_prev + b * p.per_sample) : nullptr;
     const f32x4* z4 = NOISE ? reinterpret_cast<const f32x4*>(noise + b * p.per_sample) : nullptr;
-    const f32x4* y4 = KNOWN ? reinterpret_cast<const f32x4*>(known + b * p.per_sample) : nullptr;
-    const f32x4* m4 = KNOWN ? reinterpret_cast<const f32x4*>(mask + b * (mask_c == 1 ? plane : p.per_sample)) : nullptr;
+    const f32x4* y4 = KNOWN ? reinterpret_cast<const f32x4*>(ms.known + b * p.per_sample) : nullptr;
     f32x4* o4 = reinterpret_cast<f32x4*>(p.x_s + b * p.per_sample);
     f32x4* e4 = reinterpret_cast<f32x4*>(p.x0 + b * p.per_sample);
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
@@ -262,12 +182,12 @@ __global__ __launch_bounds__(256) void dpm_step_known_kernel(DpmParams p, const 
         f32x4 h = {0.f, 0.f, 0.f, 0.f}, z = h, y = h, m = h;
         if (SECOND) h = h4[i];
         if (NOISE) z = z4[i];
-        if (KNOWN) y = y4[i], m = m4[mask_c == 1 ? i % plane4 : i];
+        if (KNOWN) y = y4[i], m = mask_quad(ms.mask, b, i, p.per_sample, ms.plane, ms.mask_c);
         f32x4 o, e;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             e[j] = posterior_x0<M_CT_DDPM, OBJ>(x[j], pr[j], k, p.clip);
-            if (KNOWN) e[j] = m[j] * y[j] + (1.0f - m[j]) * e[j];
+            if (KNOWN) e[j] = project_known(m[j], y[j], e[j]);
             o[j] = c_x * x[j] + c_0 * e[j];
             if (SECOND) o[j] = o[j] + c_1 * h[j];
             if (NOISE) o[j] = o[j] + c_z * z[j];
@@ -278,41 +198,36 @@ __global__ __launch_bounds__(256) void dpm_step_known_kernel(DpmParams p, const 
 }
 
 template <int OBJ, bool SECOND, bool NOISE>
-static hipError_t launch_dpm_known_k(const DpmParams& p, const float* noise, const float* known, const float* mask, long plane, int mask_c, dim3 g,
-                                     hipStream_t s) {
-    if (known) dpm_step_known_kernel<OBJ, SECOND, NOISE, true><<<g, 256, 0, s>>>(p, noise, known, mask, plane, mask_c);
-    else dpm_step_known_kernel<OBJ, SECOND, NOISE, false><<<g, 256, 0, s>>>(p, noise, nullptr, nullptr, plane, mask_c);
+static hipError_t launch_dpm_k(const DpmParams& p, const float* noise, const Measurement& ms, hipStream_t s) {
+    const dim3 g = quad_grid(p.B, p.per_sample);
+    if (ms.known) dpm_step_kernel<OBJ, SECOND, NOISE, true><<<g, 256, 0, s>>>(p, noise, ms);
+    else dpm_step_kernel<OBJ, SECOND, NOISE, false><<<g, 256, 0, s>>>(p, noise, ms);
     return hipGetLastError();
 }
 
 template <int OBJ>
-static hipError_t launch_dpm_known_obj(const DpmParams& p, const float* noise, const float* known, const float* mask, long plane, int mask_c, dim3 g,
-                                       hipStream_t s) {
-    if (p.x0_prev) {
-        return noise ? launch_dpm_known_k<OBJ, true, true>(p, noise, known, mask, plane, mask_c, g, s)
-                     : launch_dpm_known_k<OBJ, true, false>(p, noise, known, mask, plane, mask_c, g, s);
-    }
-    return noise ? launch_dpm_known_k<OBJ, false, true>(p, noise, known, mask, plane, mask_c, g, s)
-                 : launch_dpm_known_k<OBJ, false, false>(p, noise, known, mask, plane, mask_c, g, s);
+static hipError_t launch_dpm_obj(const DpmParams& p, const float* noise, const Measurement& ms, hipStream_t s) {
+    if (p.x0_prev) return noise ? launch_dpm_k<OBJ, true, true>(p, noise, ms, s) : launch_dpm_k<OBJ, true, false>(p, noise, ms, s);
+    return noise ? launch_dpm_k<OBJ, false, true>(p, noise, ms, s) : launch_dpm_k<OBJ, false, false>(p, noise, ms, s);
 }
 
 // (arguments validated by r2dm_dpm_step_known; checked again here, since the kernel reads quads and has no tail)
 hipError_t launch_dpm_step_known(const DpmParams& p, const float* noise, const float* known, const float* mask, int channels, int mask_c,
                                  hipStream_t s) {
     if (p.B < 1 || p.B > 65535 || p.per_sample < 4 || (p.per_sample & 3) || !p.x_t || !p.pred || !p.coef || !p.x_s || !p.x0 || p.x_s == p.x_t ||
-        channels < 1 || p.per_sample % channels || (p.per_sample / channels) % 4 || (mask_c != 1 && mask_c != channels) || !known != !mask)
+        !measurement_ok(p.per_sample, channels, mask_c) || !known != !mask)
         return hipErrorInvalidValue;
-    long bx = (p.per_sample / 4 + 255) / 256;  // (launch_posterior's shape)
-    if (bx > 1024) bx = 1024;
-    const dim3 g((unsigned)bx, p.B);
-    const long plane = p.per_sample / channels;
+    const Measurement ms{known, mask, p.per_sample / channels, mask_c};
     switch (p.objective) {
-        case OBJ_EPS: return launch_dpm_known_obj<OBJ_EPS>(p, noise, known, mask, plane, mask_c, g, s);
-        case OBJ_V: return launch_dpm_known_obj<OBJ_V>(p, noise, known, mask, plane, mask_c, g, s);
-        case OBJ_X0: return launch_dpm_known_obj<OBJ_X0>(p, noise, known, mask, plane, mask_c, g, s);
+        case OBJ_EPS: return launch_dpm_obj<OBJ_EPS>(p, noise, ms, s);
+        case OBJ_V: return launch_dpm_obj<OBJ_V>(p, noise, ms, s);
+        case OBJ_X0: return launch_dpm_obj<OBJ_X0>(p, noise, ms, s);
     }
     return hipErrorInvalidValue;
 }
+
+// no noise, no measurement: one plane, which asks nothing of per_sample beyond whole quads
+hipError_t launch_dpm_step(const DpmParams& p, hipStream_t s) { return launch_dpm_step_known(p, nullptr, nullptr, nullptr, 1, 1, s); }
 
 // ---- LiDAR post-processing ("next" row f.1) ------------------------------------------------
 // sample (B,2,H,W) in [-1,1] -> (B,5,H,W): metric depth (decoded by the checkpoint's depth format, masked to
@@ -377,14 +292,10 @@ __global__ __launch_bounds__(256) void repaint_blend_kernel(const float* __restr
     for (long i = (blockIdx.x * 256L + threadIdx.x) * 4; i < per_sample; i += (long)gridDim.x * 1024) {
         const f32x4 k = *reinterpret_cast<const f32x4*>(known + base + i), z = *reinterpret_cast<const f32x4*>(noise + base + i);
         const f32x4 u = *reinterpret_cast<const f32x4*>(unknown + base + i);
-        const long mi = mask_c == 1 ? b * plane + i % plane : base + i;  // plane % 4 == 0: a quad never straddles planes
-        const f32x4 m = *reinterpret_cast<const f32x4*>(mask + mi);
+        const f32x4 m = mask_quad(mask, b, i >> 2, per_sample, plane, mask_c);
         f32x4 o;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float ks = k[e] * alpha + z[e] * sigma;
-            o[e] = m[e] * ks + (1.0f - m[e]) * u[e];
-        }
+        for (int e = 0; e < 4; ++e) o[e] = project_known(m[e], k[e] * alpha + z[e] * sigma, u[e]);
         *reinterpret_cast<f32x4*>(out + base + i) = o;
     }
 }
@@ -407,8 +318,7 @@ __global__ __launch_bounds__(256) void q_step_kernel(const float* __restrict__ x
 hipError_t launch_repaint_blend(const float* known, const float* noise, const float* unknown, const float* mask,
                                 const float* coef, float* out, int B, long per_sample, int channels, int mask_c,
                                 hipStream_t s) {
-    if (per_sample % 4 || channels <= 0 || per_sample % channels || (per_sample / channels) % 4) return hipErrorInvalidValue;
-    if (mask_c != 1 && mask_c != channels) return hipErrorInvalidValue;
+    if (per_sample % 4 || !measurement_ok(per_sample, channels, mask_c)) return hipErrorInvalidValue;
     long bx = (per_sample / 4 + 255) / 256;
     if (bx > 256) bx = 256;
     repaint_blend_kernel<<<dim3((unsigned)bx, B), 256, 0, s>>>(known, noise, unknown, mask, coef, out, per_sample,

@@ -15,6 +15,11 @@ MI355X design, not a translation:
   * Noise stays in ``torch.randn(generator=...)`` so that seeds mean what they mean in the
     reference (base.py:71-94).
 
+Every sampler is one of two walks.  ``_run_loop`` is the step loop of ``sample``, ``sample_from``, ``invert``, ``sample_dpm`` and
+``complete_dpm``: one denoiser call and one fused update per step (``r2dm_posterior_step``, ``r2dm_ddim_transfer``, ``r2dm_dpm_step[_known]``),
+with ``_Replay``'s recovery from a range-guard trip.  ``_resample_walk`` is the RePaint schedule of ``repaint`` and ``complete``
+(``r2dm_posterior_step_known``): sub-steps, travel back through ``q_step``, resample.  Host-side schedule scalars all go through ``_rows``.
+
 The denoising loss ``ddpm(x_0, loss_mask)`` (base.py:122-149) is evaluated forward-only: one noising (``r2dm_q_step``), one denoiser
 call and one fused HIP reduction (``r2dm_diffusion_loss``); there is no autograd and no optimizer here.
 """
@@ -40,7 +45,6 @@ except Exception:  # pragma: no cover
     def tqdm(it, **_):
         return it
 
-_OBJECTIVES = {"eps": 0, "v": 1, "x_0": 2}
 # posterior kernel modes (csrc/posterior.hip)
 _M_CT_DDPM, _M_CT_DDIM, _M_DT_DDPM, _M_DT_DDIM, _M_DT_DDIM_NOISE = 0, 1, 2, 3, 4
 _NCOEF = 8
@@ -159,6 +163,48 @@ def _rng_restore(snap, rng, dev):
     else:
         for g, s in zip(rng, snap):
             g.set_state(s)
+
+
+def _rows(fn, whole: bool, cols):
+    """``fn`` of (N,) tensors -> a tensor, or a tuple of tensors, of N rows: applied to ``cols`` as they are (``whole``: device tensors), or row
+    by row to their 1-element slices and concatenated (host tensors).
+
+    Why rows on the host: torch's CPU elementwise kernels round the last bit differently in their SIMD body and in their scalar tail, and the
+    reference evaluates the schedule on (B,)-shaped tensors (continuous_time.py:203-206), i.e. on the scalar path for its CPU-runnable batch
+    sizes (BASELINE configs[0]: batch 1).  Row-wise evaluation reproduces those values bit for bit and makes a table independent of the
+    number of its rows.  A device elementwise kernel computes every element by the same instructions whatever the tensor's shape."""
+    if whole:
+        return fn(*cols)
+    parts = [fn(*(c[i:i + 1] for c in cols)) for i in range(cols[0].numel())]
+    return tuple(torch.cat(p) for p in zip(*parts)) if isinstance(parts[0], tuple) else torch.cat(parts)
+
+
+def _cache_put(cache: dict, key, value):
+    """Insert into one of the table caches, which hold 8 entries: the oldest goes first."""
+    if len(cache) >= 8:
+        cache.pop(next(iter(cache)))
+    cache[key] = value
+    return value
+
+
+def _check_count(**named):
+    for name, n in named.items():
+        if int(n) != n or n < 1:
+            raise ValueError(f"{name} must be an integer >= 1, got {n}")
+
+
+def _check_level(t, name: str = "t_start"):
+    if not 0.0 < float(t) <= 1.0:
+        raise ValueError(f"{name} must be in (0, 1], got {t}")
+
+
+def _check_solver(order, grid, eta):
+    if order not in (1, 2):
+        raise ValueError(f"order must be 1 or 2, got {order!r}")
+    if grid not in ("logsnr", "time"):
+        raise ValueError(f"grid must be 'logsnr' or 'time', got {grid!r}")
+    if not float(eta) >= 0.0 or math.isinf(float(eta)):
+        raise ValueError(f"eta must be finite and >= 0, got {eta}")
 
 
 def _log(t: torch.Tensor, eps: float = 1e-20) -> torch.Tensor:
@@ -416,26 +462,50 @@ class GaussianDiffusion(nn.Module):
         return self.p_loss(x_0, steps, loss_mask, rng=rng)
 
     def _objective_id(self) -> int:
-        if self.objective not in _OBJECTIVES:
+        if self.objective not in _lib.OBJECTIVES:
             raise ValueError(f"invalid objective {self.objective}")
-        return _OBJECTIVES[self.objective]
+        return _lib.OBJECTIVES[self.objective]
 
-    def _clip(self) -> float:
-        return float(self.clip_sample_range) if self.clip_sample else -1.0
+    def _clip(self, clip: Optional[bool] = None) -> float:
+        """The clamp of the x_0 estimate as the kernels take it (< 0: none).  ``clip``: None -- the model's ``clip_sample`` setting; True / False: on / off for one call."""
+        return float(self.clip_sample_range) if (self.clip_sample if clip is None else clip) else -1.0
 
     def _posterior(self, x_t, pred, noise, coef, mode_id: int, clip: Optional[float] = None):
         """x_s = posterior(x_t, prediction, noise) in one HIP launch (``clip``: None -- the model's setting; < 0: no clamp)."""
         return _lib.posterior_step(x_t, pred, noise, coef, mode_id, self._objective_id(), self._clip() if clip is None else clip)
 
+    def _denoise(self, x, cond, early_check: int = 0):
+        """One denoiser call.  ``early_check``: the first call of a loop under the deferred range guard passes the loop's length -- the guard
+        is read right after it (``_early_range_check``), and on a trip the call is repeated on the wide-range operand split."""
+        prediction = self.model(x, cond)
+        if early_check and _early_range_check(self.model, early_check):
+            prediction = self.model(x, cond)
+        return prediction
+
+    def _twice_on_fallback(self, rng, call):
+        """``call()``; a range-guard trip that only shows at the loop's end (``R2DMRangeFallback``) leaves the denoiser switched to the wide-range
+        split: the call is then repeated once, from the generator states it started with -- same draws, no exception."""
+        snap = _rng_snapshot(rng, self.device)
+        try:
+            return call()
+        except _lib.R2DMRangeFallback:
+            _rng_restore(snap, rng, self.device)
+            return call()
+
     def _run_loop(self, x, num_steps: int, row, update, draw, progress: bool, return_all: bool, desc: str = "sampling"):
-        """The step loop every sampler here shares (``sample``, ``sample_from``, ``invert``): per step ``row(i) -> (cond, coef)``, the
-        step's noise (``draw(x) -> (noise, event)`` ahead of the denoiser call; None: a deterministic update, nothing is drawn), one
-        denoiser call, ``update(x, prediction, noise, coef) -> x``; under the deferred range guard, with ``_Replay``'s recovery.
+        """The step loop every sampler here shares (``sample``, ``sample_from``, ``invert``, ``sample_dpm``, ``complete_dpm``): per step
+        ``row(i) -> (cond, coef)``, the step's noise (``draw(x) -> (noise, event)`` ahead of the denoiser call; None: a deterministic update,
+        nothing is drawn), one denoiser call, ``update(x, prediction, noise, coef, hist) -> (x, hist)``; under the deferred range guard, with
+        ``_Replay``'s recovery.  ``hist`` is what a multistep update hands to its next step beside ``x`` (the previous estimate of x_0; None
+        before the first step and for the one-step samplers), and the pair is what ``_Replay`` keeps.  ``_Replay`` only stores the object it
+        is given and an update may write ``hist``'s buffer again two steps on, so at a step whose check is due the loop hands on a COPY: the
+        checkpoint's history is then a buffer no later step writes.
         -> the last ``x``, or with ``return_all`` the (S+1, ...) stack that starts with the given ``x``."""
         if return_all:
             out = [x]
-        rp = _Replay(self.model, num_steps)  # (a range-guard trip at any step: back to the last checked x, on the recorded noise)
-        rp.start(x)
+        rp = _Replay(self.model, num_steps)  # (a range-guard trip at any step: back to the last checked state, on the recorded noise)
+        rp.start((x, None))
+        hist = None
         bar = _progress_bar(num_steps, desc, progress)
         with _range_guard(self.model):
             i = 0
@@ -445,7 +515,10 @@ class GaussianDiffusion(nn.Module):
                 prediction = self.model(x, cond_i)
                 if drawn is not None:
                     torch.cuda.current_stream(x.device).wait_event(drawn)
-                nxt, x = rp.after_step(i, update(x, prediction, noise, coef_i))
+                x_s, hist = update(x, prediction, noise, coef_i, hist)
+                if hist is not None and rp.record and rp.due(i):
+                    hist = hist.clone()
+                nxt, (x, hist) = rp.after_step(i, (x_s, hist))
                 if return_all:
                     del out[nxt + 1:]  # (after a replay: the steps that are run again; else nothing)
                     if nxt > i:
@@ -524,13 +597,15 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
     def sample_timesteps(self, batch_size: int, device) -> torch.Tensor:
         return torch.rand(batch_size, device=device, dtype=torch.float32)
 
+    def _placed(self, *steps):
+        """``(whole, cols)`` for ``_rows``: the steps as float32 (N,) tensors where ``schedule_on`` says -- on the first one's device, or on the host."""
+        whole = self._on_device(steps[0].device)
+        return whole, [s.detach().to(steps[0].device if whole else "cpu", torch.float32).reshape(-1) for s in steps]
+
     def _log_snr_of_steps(self, steps) -> torch.Tensor:
-        """(B,) log-SNR where ``schedule_on`` says: on the host row by row on 1-element tensors (see ``_coefficients``: the values of the
-        reference's CPU run, and a row does not depend on the batch), or with the same ops on the device."""
-        if self._on_device(steps.device):
-            return self._log_snr_1d(steps.detach().float().reshape(-1))
-        steps = steps.detach().to("cpu", torch.float32).reshape(-1)
-        return torch.cat([self._log_snr_1d(steps[i:i + 1]) for i in range(steps.numel())])
+        """(B,) log-SNR where ``schedule_on`` says: on the host row by row (see ``_rows``: the values of the reference's CPU run, and a row does
+        not depend on the batch), or with the same ops on the device."""
+        return _rows(self._log_snr_1d, *self._placed(steps))
 
     def _loss_coef(self, steps) -> torch.Tensor:
         return self._alpha_sigma_rows(steps)
@@ -549,18 +624,10 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
 
     def get_loss_weight(self, steps):
         """(B,1,1,1) min-SNR loss weights (continuous_time.py:153-167), on ``steps``' device."""
-        log_snr = self._log_snr_of_steps(steps)
-        if self._on_device(steps.device):
-            return self._loss_weight_of_snr(log_snr.exp())[:, None, None, None]
-        rows = [self._loss_weight_of_snr(log_snr[i:i + 1].exp()) for i in range(log_snr.numel())]  # (host: row by row, as the log-SNR)
-        return torch.cat(rows)[:, None, None, None].to(steps.device)
+        weight = _rows(lambda l: self._loss_weight_of_snr(l.exp()), self._on_device(steps.device), [self._log_snr_of_steps(steps)])
+        return weight[:, None, None, None].to(steps.device)
 
     # -- host-side coefficient table -------------------------------------------------------
-    def _coefficient_row(self, t: torch.Tensor, s: torch.Tensor, mode: str, ddim_eta: float):
-        """Scalars of continuous_time.py:203-229 for ONE (t, s) pair, as 1-element float32 tensors."""
-        lt, coef = self._coefficient_block(t, s, mode, ddim_eta)
-        return lt, coef[0]
-
     def _coefficient_block(self, t: torch.Tensor, s: torch.Tensor, mode: str, ddim_eta: float):
         """Scalars of continuous_time.py:203-229 for (N,) step pairs, with the reference's own torch expressions, WHERE t lives:
         -> (log-SNR (N,), coefficients (N, 8))."""
@@ -578,28 +645,23 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
         raise ValueError(f"invalid mode {mode}")
 
     def _coefficients(self, step_t: torch.Tensor, step_s: torch.Tensor, mode: str, ddim_eta: float):
-        """Per-row schedule scalars, float32 on the host.  Returns (cond (N,), coef (N,8), kernel mode).
-
-        Each row is evaluated on 1-element tensors: torch's CPU elementwise kernels round the last bit
-        differently in their SIMD body and in their scalar tail, and the reference evaluates the schedule on
-        (B,)-shaped tensors (continuous_time.py:203-206), i.e. on the scalar path for its CPU-runnable
-        batch sizes (BASELINE configs[0]: batch 1).  Row-wise evaluation reproduces those values bit for
-        bit and makes the table independent of the number of steps."""
+        """Per-row schedule scalars, float32, where ``schedule_on`` says (on the host row by row: see ``_rows``; on the device (B,)-shaped
+        tensors through the same ops, as the reference on a GPU).  Returns (cond (N,), coef (N,8), kernel mode)."""
         if mode not in ("ddpm", "ddim"):
             raise ValueError(f"invalid mode {mode}")
-        if self._on_device(step_t.device):  # (B,)-shaped device tensors through the same ops, as the reference on a GPU
-            lt, coef = self._coefficient_block(step_t.detach().float().reshape(-1), step_s.detach().to(step_t.device).float().reshape(-1), mode, ddim_eta)
-            return lt, coef.contiguous(), (_M_CT_DDPM if mode == "ddpm" else _M_CT_DDIM)
-        step_t = step_t.detach().to("cpu", torch.float32).reshape(-1)
-        step_s = step_s.detach().to("cpu", torch.float32).reshape(-1)
-        memo, conds, rows = {}, [], []
-        for i in range(step_t.numel()):
-            key = (step_t[i].item(), step_s[i].item())
+        whole, cols = self._placed(step_t, step_s)
+        memo = {}  # (host rows: the samples of a batch share one (t, s) pair -- evaluated once)
+
+        def block(t, s):
+            if whole:
+                return self._coefficient_block(t, s, mode, ddim_eta)
+            key = (t.item(), s.item())
             if key not in memo:
-                memo[key] = self._coefficient_row(step_t[i:i + 1], step_s[i:i + 1], mode, ddim_eta)
-            conds.append(memo[key][0])
-            rows.append(memo[key][1])
-        return torch.cat(conds), torch.stack(rows).contiguous(), (_M_CT_DDPM if mode == "ddpm" else _M_CT_DDIM)
+                memo[key] = self._coefficient_block(t, s, mode, ddim_eta)
+            return memo[key]
+
+        lt, coef = _rows(block, whole, cols)
+        return lt, coef.contiguous(), (_M_CT_DDPM if mode == "ddpm" else _M_CT_DDIM)
 
     def _sample_tables(self, num_steps: int, batch_size: int, mode: str, ddim_eta: float, dev):
         """(cond (S, B), coef (S, B, 8), kernel mode) of a whole ``sample`` call on the device: ``_table_rows`` walked to its
@@ -639,9 +701,7 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
             lt, k = self._coefficient_block(steps[:-1], steps[1:], mode, ddim_eta)
             cond = lt[:, None].repeat_interleave(batch_size, dim=1).contiguous()
             coef = k[:, None, :].repeat_interleave(batch_size, dim=1).contiguous()
-            if len(cache) >= 8:
-                cache.pop(next(iter(cache)))
-            cache[key] = (cond, coef, mode_id)
+            _cache_put(cache, key, (cond, coef, mode_id))
             return (lambda i: (cond[i], coef[i])), mode_id
         steps = torch.linspace(float(t_start), 0.0, num_steps + 1)
         pin = dev.type == "cuda"
@@ -657,9 +717,7 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
             cond[i].copy_(h_cond[i], non_blocking=True)
             coef[i].copy_(h_coef[i], non_blocking=True)
             if i == num_steps - 1:
-                if len(cache) >= 8:
-                    cache.pop(next(iter(cache)))
-                cache[key] = (cond, coef, mode_id)
+                _cache_put(cache, key, (cond, coef, mode_id))
             return cond[i], coef[i]
 
         return row, mode_id
@@ -674,9 +732,7 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
         if self._on_device(dev):
             step_t, step_s = step_t.to(dev), step_s.to(dev)
         cond, coef, mode_id = self._coefficients(step_t, step_s, mode, ddim_eta)
-        prediction = self.model(x_t, cond.to(dev))
-        if _early_check and _early_range_check(self.model, _early_check):
-            prediction = self.model(x_t, cond.to(dev))  # (repeated on the wide-range operand split)
+        prediction = self._denoise(x_t, cond.to(dev), _early_check)
         noise = self.randn_like(x_t, rng=rng)
         return self._posterior(x_t, prediction, noise, coef.to(dev), mode_id)
 
@@ -693,7 +749,7 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
         """The reverse process from ``x`` at ``t_start`` to t = 0 over ``linspace(t_start, 0, num_steps + 1)``: ``sample`` and ``sample_from``
         (``clip``: None -- the model's setting, else ``_posterior``'s override)."""
         row, mode_id = self._table_rows(num_steps, x.shape[0], mode, ddim_eta, x.device, t_start)
-        return self._run_loop(x, num_steps, row, lambda x, pred, noise, coef: self._posterior(x, pred, noise, coef, mode_id, clip),
+        return self._run_loop(x, num_steps, row, lambda x, pred, noise, coef, _: (self._posterior(x, pred, noise, coef, mode_id, clip), None),
                               lambda x: self._randn_like_ahead(x, rng=rng), progress, return_all)
 
     @torch.inference_mode()
@@ -705,13 +761,11 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
         ``t_start = 1`` it is ``sample``, bit for bit.  ``clip``: None keeps the model's ``clip_sample`` setting, False switches the clamp
         of the predicted x_0 off for this call only (a round trip through ``invert`` needs that), True switches it on."""
         self._refuse_cpu("sample_from", x_t)
-        if not 0.0 < float(t_start) <= 1.0:
-            raise ValueError(f"t_start must be in (0, 1], got {t_start}")
+        _check_level(t_start)
         if x_t.dim() != 4 or x_t.shape[0] < 1:
             raise ValueError(f"x_t must be (B,C,H,W) with B >= 1, got {tuple(x_t.shape)}")
         self._objective_id()
-        return self._reverse_loop(_lib.f32c(x_t), num_steps, float(t_start), progress, rng, return_all, mode, ddim_eta,
-                                  None if clip is None else float(self.clip_sample_range) if clip else -1.0)
+        return self._reverse_loop(_lib.f32c(x_t), num_steps, float(t_start), progress, rng, return_all, mode, ddim_eta, self._clip(clip))
 
     # -- DPM-Solver++(2M): a second-order multistep solver of the probability-flow ODE on the log-SNR axis (not in the reference) ------------
     def _dpm_table(self, num_steps: int, batch_size: int, order: int, grid: str, t_start: float, lower_order_final: bool, dev, eta: float = 0.0):
@@ -743,7 +797,7 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
         if hit is not None:
             return hit
         S = int(num_steps)
-        one = lambda t: torch.cat([self._log_snr_1d(t[i:i + 1]) for i in range(t.numel())])  # (row by row: see _coefficients)
+        one = lambda t: _rows(self._log_snr_1d, False, [t])
         if grid == "time":
             lam = one(torch.linspace(float(t_start), 0.0, S + 1))
         elif grid == "logsnr":
@@ -772,10 +826,7 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
         k = torch.tensor(rows, dtype=torch.float64).float()  # (alpha_t, sigma_t are float32 values already: unchanged by the round trip)
         cond = lam[:-1, None].repeat_interleave(batch_size, dim=1).contiguous().to(dev)
         coef = k[:, None, :].repeat_interleave(batch_size, dim=1).contiguous().to(dev)
-        if len(cache) >= 8:
-            cache.pop(next(iter(cache)))
-        cache[key] = (cond, coef, torch.tensor(second, dtype=torch.bool))
-        return cache[key]
+        return _cache_put(cache, key, (cond, coef, torch.tensor(second, dtype=torch.bool)))
 
     @torch.inference_mode()
     def sample_dpm(self, batch_size: int, num_steps: int, order: int = 2, grid: Literal["logsnr", "time"] = "logsnr", progress: bool = True, rng=None,
@@ -805,18 +856,10 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
         Runs under the deferred range guard with ``_Replay``'s recovery, whose checkpoint here is the pair (x, previous x_0 estimate): after a
         trip the loop goes back at most ``_CHECK_EVERY`` steps WITH the history those steps were taken with, on the wide-range split.
         ``schedule_on`` does not apply (see ``_dpm_table``)."""
-        if order not in (1, 2):
-            raise ValueError(f"order must be 1 or 2, got {order!r}")
-        if grid not in ("logsnr", "time"):
-            raise ValueError(f"grid must be 'logsnr' or 'time', got {grid!r}")
-        if int(num_steps) != num_steps or num_steps < 1:
-            raise ValueError(f"num_steps must be an integer >= 1, got {num_steps}")
-        if not 0.0 < float(t_start) <= 1.0:
-            raise ValueError(f"t_start must be in (0, 1], got {t_start}")
-        if int(batch_size) != batch_size or batch_size < 1:
-            raise ValueError(f"batch_size must be an integer >= 1, got {batch_size}")
-        if not float(eta) >= 0.0 or math.isinf(float(eta)):
-            raise ValueError(f"eta must be finite and >= 0, got {eta}")
+        _check_solver(order, grid, eta)
+        _check_count(num_steps=num_steps)
+        _check_level(t_start)
+        _check_count(batch_size=batch_size)
         if x_t is None:
             if float(t_start) != 1.0:
                 raise ValueError(f"t_start = {t_start} needs x_t (the tensor at that noise level): a fresh draw starts at t_start = 1")
@@ -826,56 +869,33 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
         if self.device.type != "cuda" or (x_t is not None and not x_t.is_cuda):
             raise NoCPUFallback(f"sample_dpm runs as HIP kernels on an MI355X (model on {self.device}"
                                 + ("" if x_t is None else f", input on {x_t.device}") + "): r2dm_amd has no CPU fallback")
-        dev = self.device if x_t is None else x_t.device
-        x = self.randn(batch_size, *self.sampling_shape, rng=rng, device=dev) if x_t is None else _lib.f32c(x_t)
-        cond, coef, second = self._dpm_table(int(num_steps), int(batch_size), order, grid, float(t_start), lower_order_final, dev, float(eta))
-        clip_value = self._clip() if clip is None else float(self.clip_sample_range) if clip else -1.0
-        draw = (lambda x: self._randn_like_ahead(x, rng=rng)) if float(eta) > 0.0 else None
-        return self._dpm_loop(x, cond, coef, second.tolist(), clip_value, progress, return_all, draw)
+        x = self.randn(batch_size, *self.sampling_shape, rng=rng, device=self.device) if x_t is None else _lib.f32c(x_t)
+        return self._dpm_solve(x, num_steps, order, grid, t_start, lower_order_final, eta, clip, progress, rng, return_all)
 
-    def _dpm_loop(self, x, cond, coef, second, clip: float, progress: bool, return_all: bool, draw=None, known=None, mask=None, desc: str = "sampling"):
-        """The multistep loop beside ``_run_loop``: the state a step hands on is (x, x0_prev), and that pair is what ``_Replay`` keeps.  The
-        estimates ping-pong between two buffers; ``_Replay`` only stores the object it is given, so at a step whose check is due it is given a
-        COPY of the estimate -- the checkpoint's history is then a buffer no later step writes.
-        ``draw(x) -> (noise, event)``: the step's noise, drawn ahead of the denoiser call and kept by ``_Replay`` (``noise_for``) as in
-        ``_run_loop``; ``known``, ``mask``: the measurement written over every estimate.  With neither the step is ``r2dm_dpm_step``, else
-        ``r2dm_dpm_step_known``."""
-        num_steps, objective = len(second), self._objective_id()
-        plain = draw is None and known is None
-        out = [x] if return_all else None
-        rp = _Replay(self.model, num_steps)
-        rp.start((x, None))
+    def _dpm_solve(self, x, num_steps, order, grid, t_start, lower_order_final, eta, clip, progress, rng, return_all, known=None, mask=None,
+                  desc: str = "sampling"):
+        """``sample_dpm`` and ``complete_dpm`` from their start tensor: ``_run_loop`` over ``_dpm_table`` with the multistep update, whose history is
+        the previous estimate of x_0.  The estimates ping-pong between two buffers (``_run_loop`` copies the one a checkpoint keeps).  The step's
+        noise (``eta > 0``) is drawn ahead of the denoiser call; ``known``, ``mask``: the measurement written over every estimate.  With neither
+        the step is ``r2dm_dpm_step``, else ``r2dm_dpm_step_known``."""
+        cond, coef, second = self._dpm_table(int(num_steps), x.shape[0], order, grid, float(t_start), lower_order_final, x.device, float(eta))
+        second, objective, clip = second.tolist(), self._objective_id(), self._clip(clip)
+        draw = (lambda x: self._randn_like_ahead(x, rng=rng)) if float(eta) > 0.0 else None
         bufs = (torch.empty_like(x), torch.empty_like(x))
-        x0_prev = None
-        bar = _progress_bar(num_steps, desc, progress)
-        with _range_guard(self.model):
-            i = 0
-            while i < num_steps:
-                noise, drawn = rp.noise_for(i, lambda: draw(x)) if draw is not None else (None, None)
-                prediction = self.model(x, cond[i])
-                if drawn is not None:
-                    torch.cuda.current_stream(x.device).wait_event(drawn)
-                target = bufs[1] if x0_prev is bufs[0] else bufs[0]
-                if plain:
-                    x_s, x0 = _lib.dpm_step(x, prediction, x0_prev if second[i] else None, coef[i], objective, clip, x0_out=target)
-                else:
-                    x_s, x0 = _lib.dpm_step_known(x, prediction, x0_prev if second[i] else None, noise, known, mask, coef[i], objective, clip, x0_out=target)
-                nxt, (x, x0_prev) = rp.after_step(i, (x_s, x0.clone() if rp.record and rp.due(i) else x0))
-                if return_all:
-                    del out[nxt + 1:]  # (after a replay: the steps that are run again; else nothing)
-                    if nxt > i:
-                        out.append(x)
-                if bar is not None:
-                    bar.update(nxt - i)
-                i = nxt
-        if bar is not None:
-            bar.close()
-        return torch.stack(out) if return_all else x
+
+        def update(x, prediction, noise, row, x0_prev):
+            coef_i, second_i = row
+            target = bufs[1] if x0_prev is bufs[0] else bufs[0]
+            if draw is None and known is None:
+                return _lib.dpm_step(x, prediction, x0_prev if second_i else None, coef_i, objective, clip, x0_out=target)
+            return _lib.dpm_step_known(x, prediction, x0_prev if second_i else None, noise, known, mask, coef_i, objective, clip, x0_out=target)
+
+        return self._run_loop(x, len(second), lambda i: (cond[i], (coef[i], second[i])), update, draw, progress, return_all, desc)
 
     def _transfer_table(self, steps: torch.Tensor, batch_size: int, dev):
         """``(cond (S,B), coef (S,B,4))`` on the device for DDIM transfers along ``steps`` (S+1,): the log-SNR of each step's start and
-        ``(alpha_t, sigma_t, alpha_u, sigma_u)`` of its two ends, evaluated where ``schedule_on`` says (on the host row by row on
-        1-element tensors, as ``_coefficients``)."""
+        ``(alpha_t, sigma_t, alpha_u, sigma_u)`` of its two ends, evaluated where ``schedule_on`` says (on the host row by row: see
+        ``_rows``)."""
         cond = self._log_snr_of_steps(steps[:-1]).to(dev)
         rows = self._alpha_sigma_rows(steps).to(dev)
         coef = torch.cat([rows[:-1], rows[1:]], dim=-1)
@@ -888,46 +908,30 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
         DDIM update with eta = 0 run towards more noise, unclipped); nothing is drawn.  ``sample_from(..., t_start=t_end, mode="ddim",
         clip=False)`` decodes the result.  -> x at ``t_end``; with ``return_all`` the (S+1,B,C,H,W) stack that starts with ``x_0``."""
         self._refuse_cpu("invert", x_0)
-        if not 0.0 < float(t_end) <= 1.0:
-            raise ValueError(f"t_end must be in (0, 1], got {t_end}")
+        _check_level(t_end, "t_end")
         if x_0.dim() != 4 or x_0.shape[0] < 1:
             raise ValueError(f"x_0 must be (B,C,H,W) with B >= 1, got {tuple(x_0.shape)}")
         objective = self._objective_id()
         x, dev = _lib.f32c(x_0), x_0.device
         steps = torch.linspace(0.0, float(t_end), num_steps + 1, device=dev if self._on_device(dev) else None)
         cond, coef = self._transfer_table(steps, x.shape[0], dev)
-        return self._run_loop(x, num_steps, lambda i: (cond[i], coef[i]), lambda x, pred, _, k: _ddim_transfer(x, pred, k, objective),
+        return self._run_loop(x, num_steps, lambda i: (cond[i], coef[i]), lambda x, pred, _, k, __: (_ddim_transfer(x, pred, k, objective), None),
                               None, progress, return_all, desc="inverting")
 
     # -- forward process pieces used by RePaint (continuous_time.py:169-190) ----------------
     def _alpha_sigma_rows(self, steps: torch.Tensor) -> torch.Tensor:
-        """(alpha, sigma) per row, float32 on the host, each row evaluated on 1-element tensors (see _coefficients)."""
-        if self._on_device(steps.device):
-            return torch.stack(log_snr_to_alpha_sigma(self._log_snr_1d(steps.detach().float().reshape(-1))), dim=-1).contiguous()
-        steps = steps.detach().to("cpu", torch.float32).reshape(-1)
-        rows = []
-        for i in range(steps.numel()):
-            a, sg = log_snr_to_alpha_sigma(self._log_snr_1d(steps[i:i + 1]))
-            rows.append(torch.cat([a, sg]))
-        return torch.stack(rows).contiguous()
+        """(alpha, sigma) per row, float32, where ``schedule_on`` says (on the host row by row: see ``_rows``)."""
+        return _rows(lambda t: torch.stack(log_snr_to_alpha_sigma(self._log_snr_1d(t)), dim=-1), *self._placed(steps)).contiguous()
 
     def _q_coef_rows(self, step_t: torch.Tensor, step_s: torch.Tensor) -> torch.Tensor:
-        """(alpha_t/alpha_s, sqrt(sigma_t^2 - alpha_ts^2 sigma_s^2)) per row (continuous_time.py:181-189)."""
-        if self._on_device(step_t.device):
-            a_t, s_t = log_snr_to_alpha_sigma(self._log_snr_1d(step_t.detach().float().reshape(-1)))
-            a_s, s_s = log_snr_to_alpha_sigma(self._log_snr_1d(step_s.detach().to(step_t.device).float().reshape(-1)))
+        """(alpha_t/alpha_s, sqrt(sigma_t^2 - alpha_ts^2 sigma_s^2)) per row (continuous_time.py:181-189), evaluated as ``_alpha_sigma_rows``."""
+        def rows(t, s):
+            a_t, s_t = log_snr_to_alpha_sigma(self._log_snr_1d(t))
+            a_s, s_s = log_snr_to_alpha_sigma(self._log_snr_1d(s))
             a_ts = a_t / a_s
-            return torch.stack([a_ts, (s_t.pow(2) - a_ts.pow(2) * s_s.pow(2)).sqrt()], dim=-1).contiguous()
-        step_t = step_t.detach().to("cpu", torch.float32).reshape(-1)
-        step_s = step_s.detach().to("cpu", torch.float32).reshape(-1)
-        rows = []
-        for i in range(step_t.numel()):
-            a_t, s_t = log_snr_to_alpha_sigma(self._log_snr_1d(step_t[i:i + 1]))
-            a_s, s_s = log_snr_to_alpha_sigma(self._log_snr_1d(step_s[i:i + 1]))
-            a_ts = a_t / a_s
-            var = s_t.pow(2) - a_ts.pow(2) * s_s.pow(2)
-            rows.append(torch.cat([a_ts, var.sqrt()]))
-        return torch.stack(rows).contiguous()
+            return torch.stack([a_ts, (s_t.pow(2) - a_ts.pow(2) * s_s.pow(2)).sqrt()], dim=-1)
+
+        return _rows(rows, *self._placed(step_t, step_s)).contiguous()
 
     def q_step_from_x_0(self, x_0, step_t, rng=None):
         """Forward process q(z_t | x_0) (continuous_time.py:169-176); HIP kernel r2dm_q_step."""
@@ -947,45 +951,96 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
         """RePaint inpainting on top of the same p_step (continuous_time.py:260-317).  A range-guard trip that only shows after the
         first step (``_early_check``) ends the loop with the denoiser switched to the wide-range split: the call is then repeated
         once, from the generator states it started with -- same draws, no exception (the reference runs any finite checkpoint)."""
-        snap = _rng_snapshot(rng, self.device)
-        try:
-            return self._repaint(known, mask, num_steps, num_resample_steps, jump_length, progress, rng, return_all)
-        except _lib.R2DMRangeFallback:
-            _rng_restore(snap, rng, self.device)
-            return self._repaint(known, mask, num_steps, num_resample_steps, jump_length, progress, rng, return_all)
-
-    def _repaint(self, known, mask, num_steps, num_resample_steps, jump_length, progress, rng, return_all):
         assert num_resample_steps > 0
         assert jump_length > 0
-        B = known.shape[0]
         dev = self.device
-        x_t = self.randn(B, *self.sampling_shape, rng=rng, device=dev)
-        steps = torch.linspace(1, 0, num_steps + 1)[None].repeat_interleave(B, dim=0)
-        if return_all:
-            out = [x_t]
+
+        def prepare(r, k):
+            return r[:, k], r[:, k + 1], self._alpha_sigma_rows(r[:, k + 1]).to(dev)
+
+        def substep(x, row, early_check):
+            # q_step_from_x_0(known) and the mask blend are one kernel; the draw order (known-region noise, then p_step's noise) is the reference's
+            noise_k = self.randn_like(known, rng=rng)
+            unknown_s = self.p_step(x, row[0], row[1], rng=rng, _early_check=early_check)
+            return _lib.repaint_blend(known, noise_k, unknown_s, mask, row[2])
+
+        def run():
+            x_t = self.randn(known.shape[0], *self.sampling_shape, rng=rng, device=dev)
+            return self._resample_walk(x_t, torch.linspace(1, 0, num_steps + 1), torch.linspace(0, 1, jump_length + 1), num_resample_steps, prepare,
+                                       substep, progress, rng, return_all, "RePaint")
+
+        return self._twice_on_fallback(rng, run)
+
+    def _resample_walk(self, x_t, steps, frac, num_resample_steps: int, prepare, substep, progress: bool, rng, return_all: bool, desc: str):
+        """The RePaint schedule (continuous_time.py:260-317) that ``repaint`` and ``complete`` share, from ``x_t`` over ``steps`` (S+1,): step i is
+        J sub-steps along ``r = t + frac * (s - t)`` (``frac`` (J+1,) from 0 to 1), each ``substep(x, row, early_check) -> x`` with ``row =
+        prepare(r, k)`` evaluated once per step and shared by its resamplings (``early_check``: the walk's number of denoiser calls on the first
+        one, else 0); after a group of sub-steps ``q_step`` travels back and the group is repeated, ``num_resample_steps`` times in all -- not
+        after the last resampling of a step, nor on the last step.  Under the deferred range guard.
+        -> the last x_s, or with ``return_all`` the stack of ``x_t`` and every resampling's x_s."""
+        B, num_steps, jump_length = x_t.shape[0], steps.numel() - 1, frac.numel() - 1
+        steps = steps[None].repeat_interleave(B, dim=0)
+        out = [x_t] if return_all else None
+        x_s = x_t
         with _range_guard(self.model):
-            for i in tqdm(range(num_steps), desc="RePaint", leave=False, disable=not progress):
+            for i in tqdm(range(num_steps), desc=desc, leave=False, disable=not progress):
+                t, s = steps[:, [i]], steps[:, [i + 1]]
+                r = t + frac[None] * (s - t)
+                rows = [prepare(r, k) for k in range(jump_length)]
                 for j in range(num_resample_steps):
-                    t, s = steps[:, [i]], steps[:, [i + 1]]
-                    r = t + torch.linspace(0, 1, jump_length + 1)[None] * (s - t)
                     x = x_t
                     for k in range(jump_length):
-                        # q_step_from_x_0(known) and the mask blend are one kernel; the draw order (known-region noise,
-                        # then p_step's noise) is the reference's
-                        noise_k = self.randn_like(known, rng=rng)
-                        first = i == 0 and j == 0 and k == 0
-                        unknown_s = self.p_step(x, r[:, k], r[:, k + 1], rng=rng, _early_check=num_steps * num_resample_steps * jump_length if first else 0)
-                        x = _lib.repaint_blend(known, noise_k, unknown_s, mask, self._alpha_sigma_rows(r[:, k + 1]).to(dev))
+                        x = substep(x, rows[k], num_steps * num_resample_steps * jump_length if i == j == k == 0 else 0)
                     x_s = x
                     if return_all:
                         out.append(x_s)
-                    if (i == num_steps - 1) or (j == num_resample_steps - 1):
+                    if i == num_steps - 1 or j == num_resample_steps - 1:
                         x_t = x
                         break
                     for k in range(jump_length, 0, -1):
                         x = self.q_step(x, r[:, k - 1], r[:, k], rng=rng)
                     x_t = x
         return torch.stack(out) if return_all else x_s
+
+    def _completion_args(self, what: str, known, mask, counts: dict, t_start, init, solver=None, mode=None):
+        """The argument checks ``complete`` and ``complete_dpm`` share -> ``(known, mask, init)`` as the kernels take them: float32 and contiguous on
+        ``known``'s device, the mask expanded over the batch.  ``solver``: ``complete_dpm``'s (order, grid, eta); ``mode``: ``complete``'s."""
+        self._objective_id()
+        C, H, W = self.sampling_shape
+        if known.dim() != 4 or known.shape[0] < 1 or tuple(known.shape[1:]) != (C, H, W):
+            raise ValueError(f"known must be (B, {C}, {H}, {W}) with B >= 1, got {tuple(known.shape)}")
+        B = known.shape[0]
+        if mask.dim() != 4 or mask.shape[0] not in (1, B) or mask.shape[1] not in (1, C) or tuple(mask.shape[2:]) != (H, W):
+            raise ValueError(f"mask must be ({B} | 1, 1 | {C}, {H}, {W}), got {tuple(mask.shape)}")
+        _check_count(**counts)
+        if solver is not None:
+            _check_solver(*solver)
+        _check_level(t_start)
+        if init is None and float(t_start) != 1.0:
+            raise ValueError(f"t_start = {t_start} needs init (the x_0 that is noised to t_start): a fresh draw starts at t_start = 1")
+        if init is not None and init.shape != known.shape:
+            raise ValueError(f"init {tuple(init.shape)} must have known's shape {tuple(known.shape)}")
+        if mode is not None and mode not in ("ddpm", "ddim"):
+            raise ValueError(f"invalid mode {mode}")
+        self._refuse_cpu(what, known)
+        dev = known.device
+        return _lib.f32c(known), _lib.f32c(mask.to(dev).expand(B, -1, H, W)), None if init is None else _lib.f32c(init.to(dev))
+
+    def _completion_start(self, known, init, t_start: float, rng):
+        """A completion's start tensor: ``randn(B, *sampling_shape)``, or ``init`` noised to ``t_start`` (one ``randn_like``)."""
+        B, dev = known.shape[0], known.device
+        if init is None:
+            return self.randn(B, *self.sampling_shape, rng=rng, device=dev)
+        return self.q_step_from_x_0(init, torch.full((B,), float(t_start), device=dev if self._on_device(dev) else None), rng=rng)[0]
+
+    def _known_exact(self, out, known, mask, return_all: bool):
+        """``exact_known``: the result, or with ``return_all`` the stack's last entry, becomes ``mask * known + (1 - mask) * x`` -- the blend kernel
+        with known as its noise operand, mask * (known * 1 + known * 0) + (1 - mask) * x."""
+        x_s = _lib.repaint_blend(known, known, out[-1] if return_all else out, mask, torch.tensor([[1.0, 0.0]], device=known.device).repeat(known.shape[0], 1))
+        if not return_all:
+            return x_s
+        out[-1] = x_s
+        return out
 
     # -- data-consistent completion (DDNM's null-space projection for a mask operator; not in the reference) ----------------
     @torch.inference_mode()
@@ -1007,86 +1062,31 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
         mask; without it the known pixels carry the last step's ``sigma(0) * z``.  ``return_all``: the stack ``repaint`` returns -- the
         start, then the x_s of every resampling, the last one projected like the result.  A range-guard trip is handled as in ``repaint``:
         the call is repeated once on the wide-range split from the generator states it started with."""
-        self._objective_id()
-        C, H, W = self.sampling_shape
-        if known.dim() != 4 or known.shape[0] < 1 or tuple(known.shape[1:]) != (C, H, W):
-            raise ValueError(f"known must be (B, {C}, {H}, {W}) with B >= 1, got {tuple(known.shape)}")
-        B = known.shape[0]
-        if mask.dim() != 4 or mask.shape[0] not in (1, B) or mask.shape[1] not in (1, C) or tuple(mask.shape[2:]) != (H, W):
-            raise ValueError(f"mask must be ({B} | 1, 1 | {C}, {H}, {W}), got {tuple(mask.shape)}")
-        for name, n in (("num_steps", num_steps), ("num_resample_steps", num_resample_steps), ("jump_length", jump_length)):
-            if int(n) != n or n < 1:
-                raise ValueError(f"{name} must be an integer >= 1, got {n}")
-        if not 0.0 < float(t_start) <= 1.0:
-            raise ValueError(f"t_start must be in (0, 1], got {t_start}")
-        if init is None and float(t_start) != 1.0:
-            raise ValueError(f"t_start = {t_start} needs init (the x_0 that is noised to t_start): a fresh draw starts at t_start = 1")
-        if init is not None and init.shape != known.shape:
-            raise ValueError(f"init {tuple(init.shape)} must have known's shape {tuple(known.shape)}")
-        if mode not in ("ddpm", "ddim"):
-            raise ValueError(f"invalid mode {mode}")
-        self._refuse_cpu("complete", known)
+        known, mask, init = self._completion_args("complete", known, mask, dict(num_steps=num_steps, num_resample_steps=num_resample_steps,
+                                                                                jump_length=jump_length), t_start, init, mode=mode)
         dev = known.device
-        known = _lib.f32c(known)
-        mask = _lib.f32c(mask.to(dev).expand(B, -1, H, W))
-        init = None if init is None else _lib.f32c(init.to(dev))
-        args = (known, mask, int(num_steps), int(num_resample_steps), int(jump_length), float(t_start), init, mode, float(ddim_eta), exact_known,
-                progress, rng, return_all)
-        snap = _rng_snapshot(rng, self.device)
-        try:
-            return self._complete(*args)
-        except _lib.R2DMRangeFallback:
-            _rng_restore(snap, rng, self.device)
-            return self._complete(*args)
-
-    def _complete(self, known, mask, num_steps, num_resample_steps, jump_length, t_start, init, mode, ddim_eta, exact_known, progress, rng,
-                  return_all):
-        B, dev = known.shape[0], known.device
-        on_dev = self._on_device(dev)  # (the grid itself is then the device's linspace, as in _table_rows)
-        if init is None:
-            x_t = self.randn(B, *self.sampling_shape, rng=rng, device=dev)
-        else:
-            x_t, _ = self.q_step_from_x_0(init, torch.full((B,), t_start, device=dev if on_dev else None), rng=rng)
-        steps = torch.linspace(t_start, 0.0, num_steps + 1, device=dev if on_dev else None)[None].repeat_interleave(B, dim=0)
-        frac = torch.linspace(0, 1, jump_length + 1, device=dev if on_dev else None)[None]
+        where = dev if self._on_device(dev) else None  # (the grid itself is then the device's linspace, as in _table_rows)
         objective, clip = self._objective_id(), self._clip()
-        total = num_steps * num_resample_steps * jump_length
-        out = [x_t] if return_all else None
-        x_s = x_t
-        with _range_guard(self.model):
-            for i in tqdm(range(num_steps), desc="completing", leave=False, disable=not progress):
-                t, s = steps[:, [i]], steps[:, [i + 1]]
-                r = t + frac * (s - t)
-                rows = {}  # the sub-steps' scalars: evaluated once per step, shared by its resamplings
-                for j in range(num_resample_steps):
-                    x = x_t
-                    for k in range(jump_length):
-                        if k not in rows:
-                            cond, coef, mode_id = self._coefficients(r[:, k], r[:, k + 1], mode, ddim_eta)
-                            rows[k] = (cond.to(dev), coef.to(dev), mode_id)
-                        cond, coef, mode_id = rows[k]
-                        noise, drawn = self._randn_like_ahead(x, rng=rng)
-                        prediction = self.model(x, cond)
-                        if i == 0 and j == 0 and k == 0 and _early_range_check(self.model, total):
-                            prediction = self.model(x, cond)  # (repeated on the wide-range operand split)
-                        if drawn is not None:
-                            torch.cuda.current_stream(dev).wait_event(drawn)
-                        x = _lib.posterior_step_known(x, prediction, noise, known, mask, coef, mode_id, objective, clip)
-                    x_s = x
-                    if return_all:
-                        out.append(x_s)
-                    if i == num_steps - 1 or j == num_resample_steps - 1:
-                        x_t = x
-                        break
-                    for k in range(jump_length, 0, -1):
-                        x = self.q_step(x, r[:, k - 1], r[:, k], rng=rng)
-                    x_t = x
-        if exact_known:  # mask * (known * 1 + known * 0) + (1 - mask) * x: the blend kernel with known as its noise operand
-            x_s = _lib.repaint_blend(known, known, x_s, mask, torch.tensor([[1.0, 0.0]], device=dev).repeat(B, 1))
-            if return_all:
-                out[-1] = x_s
-        return torch.stack(out) if return_all else x_s
 
+        def prepare(r, k):
+            cond, coef, mode_id = self._coefficients(r[:, k], r[:, k + 1], mode, float(ddim_eta))
+            return cond.to(dev), coef.to(dev), mode_id
+
+        def substep(x, row, early_check):
+            cond, coef, mode_id = row
+            noise, drawn = self._randn_like_ahead(x, rng=rng)
+            prediction = self._denoise(x, cond, early_check)
+            if drawn is not None:
+                torch.cuda.current_stream(dev).wait_event(drawn)
+            return _lib.posterior_step_known(x, prediction, noise, known, mask, coef, mode_id, objective, clip)
+
+        def run():
+            out = self._resample_walk(self._completion_start(known, init, t_start, rng), torch.linspace(float(t_start), 0.0, int(num_steps) + 1, device=where),
+                                      torch.linspace(0, 1, int(jump_length) + 1, device=where), int(num_resample_steps), prepare, substep, progress,
+                                      rng, return_all, "completing")
+            return self._known_exact(out, known, mask, return_all) if exact_known else out
+
+        return self._twice_on_fallback(rng, run)
 
     # -- completion on DPM-Solver++(2M): the projection of ``complete`` inside the multistep solver's update (not in the reference) --------
     @torch.inference_mode()
@@ -1111,47 +1111,10 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
         ``return_all``: the (S+1,B,C,H,W) stack from the start, the last entry projected like the result.
         A range-guard trip is handled by ``_Replay`` as in ``sample_dpm``: back at most ``_CHECK_EVERY`` steps with the checkpointed pair
         (x, previous estimate), on the recorded noise, on the wide-range split."""
-        self._objective_id()
-        C, H, W = self.sampling_shape
-        if known.dim() != 4 or known.shape[0] < 1 or tuple(known.shape[1:]) != (C, H, W):
-            raise ValueError(f"known must be (B, {C}, {H}, {W}) with B >= 1, got {tuple(known.shape)}")
-        B = known.shape[0]
-        if mask.dim() != 4 or mask.shape[0] not in (1, B) or mask.shape[1] not in (1, C) or tuple(mask.shape[2:]) != (H, W):
-            raise ValueError(f"mask must be ({B} | 1, 1 | {C}, {H}, {W}), got {tuple(mask.shape)}")
-        if int(num_steps) != num_steps or num_steps < 1:
-            raise ValueError(f"num_steps must be an integer >= 1, got {num_steps}")
-        if order not in (1, 2):
-            raise ValueError(f"order must be 1 or 2, got {order!r}")
-        if grid not in ("logsnr", "time"):
-            raise ValueError(f"grid must be 'logsnr' or 'time', got {grid!r}")
-        if not float(eta) >= 0.0 or math.isinf(float(eta)):
-            raise ValueError(f"eta must be finite and >= 0, got {eta}")
-        if not 0.0 < float(t_start) <= 1.0:
-            raise ValueError(f"t_start must be in (0, 1], got {t_start}")
-        if init is None and float(t_start) != 1.0:
-            raise ValueError(f"t_start = {t_start} needs init (the x_0 that is noised to t_start): a fresh draw starts at t_start = 1")
-        if init is not None and init.shape != known.shape:
-            raise ValueError(f"init {tuple(init.shape)} must have known's shape {tuple(known.shape)}")
-        self._refuse_cpu("complete_dpm", known)
-        dev = known.device
-        known = _lib.f32c(known)
-        mask = _lib.f32c(mask.to(dev).expand(B, -1, H, W))
-        if init is None:
-            x = self.randn(B, *self.sampling_shape, rng=rng, device=dev)
-        else:
-            x, _ = self.q_step_from_x_0(_lib.f32c(init.to(dev)), torch.full((B,), float(t_start), device=dev if self._on_device(dev) else None), rng=rng)
-        cond, coef, second = self._dpm_table(int(num_steps), B, order, grid, float(t_start), lower_order_final, dev, float(eta))
-        clip_value = self._clip() if clip is None else float(self.clip_sample_range) if clip else -1.0
-        draw = (lambda x: self._randn_like_ahead(x, rng=rng)) if float(eta) > 0.0 else None
-        out = self._dpm_loop(x, cond, coef, second.tolist(), clip_value, progress, return_all, draw, known, mask, desc="completing")
-        if not exact_known:
-            return out
-        # mask * (known * 1 + known * 0) + (1 - mask) * x: the blend kernel with known as its noise operand, as in ``complete``
-        x_s = _lib.repaint_blend(known, known, out[-1] if return_all else out, mask, torch.tensor([[1.0, 0.0]], device=dev).repeat(B, 1))
-        if return_all:
-            out[-1] = x_s
-            return out
-        return x_s
+        known, mask, init = self._completion_args("complete_dpm", known, mask, dict(num_steps=num_steps), t_start, init, solver=(order, grid, eta))
+        out = self._dpm_solve(self._completion_start(known, init, t_start, rng), num_steps, order, grid, t_start, lower_order_final, eta, clip, progress,
+                              rng, return_all, known, mask, desc="completing")
+        return self._known_exact(out, known, mask, return_all) if exact_known else out
 
 
 # --------------------------------------------------------------------------------------
@@ -1176,10 +1139,9 @@ class DiscreteTimeGaussianDiffusion(GaussianDiffusion):
 
     def _log_snr_of_steps(self, steps) -> torch.Tensor:
         """(B,) ``log(snr[steps])`` where ``schedule_on`` says: on the host row by row (a row does not depend on the batch), or on the device."""
-        if self._on_device(steps.device):
-            return self.snr[steps.to(self.snr.device).long().reshape(-1), 0, 0, 0].log()
-        snr = self.snr.detach().cpu()[steps.detach().to("cpu", torch.long).reshape(-1), 0, 0, 0]
-        return torch.cat([snr[i:i + 1].log() for i in range(snr.numel())])
+        whole = self._on_device(steps.device)
+        snr = self.snr if whole else self.snr.detach().cpu()
+        return _rows(torch.log, whole, [snr[steps.detach().to(snr.device, torch.long).reshape(-1), 0, 0, 0]])
 
     def _loss_coef(self, steps) -> torch.Tensor:
         """(sqrt(alpha_bar), sqrt(1 - alpha_bar)) rows on the host (discrete_time.py:122-123).  The roots are taken in float64 and rounded
@@ -1261,7 +1223,7 @@ class DiscreteTimeGaussianDiffusion(GaussianDiffusion):
         coef = coef[:, None, :].expand(num_steps, batch_size, _NCOEF).contiguous().to(dev)
         cond = order[:, None].expand(num_steps, batch_size).contiguous().to(dev)
         draw = (lambda x: self._randn_like_ahead(x, rng=rng)) if mode_id != _M_DT_DDIM else None
-        return self._run_loop(x, num_steps, lambda i: (cond[i], coef[i]), lambda x, pred, noise, k: self._posterior(x, pred, noise, k, mode_id),
+        return self._run_loop(x, num_steps, lambda i: (cond[i], coef[i]), lambda x, pred, noise, k, _: (self._posterior(x, pred, noise, k, mode_id), None),
                               draw, progress, return_all)
 
     def invert(self, *args, **kwargs):

@@ -23,9 +23,9 @@ def ddim_transfer(x_t: torch.Tensor, prediction: torch.Tensor, coef: torch.Tenso
     ``r2dm_ddim_transfer``: float32, not contracted, x_0 and eps in the direct form of the objective."""
     _lib.require_gpu(x_t, "x_t")
     if isinstance(objective, str):
-        if objective not in _lib.LOSS_OBJECTIVES:
+        if objective not in _lib.OBJECTIVES:
             raise ValueError(f"invalid objective {objective}")
-        objective = _lib.LOSS_OBJECTIVES[objective]
+        objective = _lib.OBJECTIVES[objective]
     if prediction.shape != x_t.shape or x_t.dim() < 2:
         raise ValueError(f"x_t {tuple(x_t.shape)} and prediction {tuple(prediction.shape)} must have one (B,...) shape")
     B = x_t.shape[0]

@@ -395,6 +395,66 @@ def test_posterior_discrete_bit_exact():
         assert max_abs(got, want) < 2e-6, obj
 
 
+# 4096: one pass of four blocks.  1024 blocks x 256 threads x 4 elements is one pass of the capped grid: 4 KiB more is a second pass
+POSTERIOR_PER_SAMPLE = [4096, 1024 * 256 * 4 + 4096]
+POSTERIOR_MODES = ["ct_ddpm", "ct_ddim", "dt_ddpm", "dt_ddim", "dt_ddim_noise"]  # (the kernel's mode ids 0 .. 4, in this order)
+
+
+@pytest.mark.parametrize("objective", ["eps", "v", "x_0"])
+@pytest.mark.parametrize("mode", POSTERIOR_MODES)
+def test_posterior_every_instantiation_bit_exact_vs_torch_ops(mode, objective):
+    """All 15 (mode, objective) instantiations of the posterior kernel, each on three real table rows (one per sample), with and without the
+    clamp, on one pass of a few blocks and on one quad-row past a full pass of the capped grid: bit-identical to the same expression evaluated
+    op by op by torch on the device from the same uploaded float32 coefficients (one IEEE rounding per operation, no contraction).  The
+    coefficients are evaluated on the host, so the discrete modes are as exact as the continuous ones.  Discrete step 0 is among the rows: its
+    ``live`` factor zeroes the noise.  Mode 3 (discrete DDIM, eta = 0) reads no noise, whether or not it is given one."""
+    from r2dm_amd import _lib, diffusion as D
+
+    class Stub(torch.nn.Module):
+        resolution, in_channels = (16, 128), 2
+
+    B, obj_id, mode_id = 3, ["eps", "v", "x_0"].index(objective), POSTERIOR_MODES.index(mode)
+    if mode.startswith("ct"):
+        dd = D.ContinuousTimeGaussianDiffusion(Stub(), prediction_type=objective)
+        _, coef, mid = dd._coefficients(torch.tensor([1.0, 0.5, 0.1]), torch.tensor([0.9, 0.4, 0.0]), mode[3:], 0.7)
+    else:
+        dd = D.DiscreteTimeGaussianDiffusion(Stub(), prediction_type=objective, num_training_steps=1000)
+        coef, mid = dd._coefficients(torch.tensor([999, 321, 0]), mode[3:7], 0.5 if mode == "dt_ddim_noise" else 0.0)
+        assert mode == "dt_ddim" or (coef[2, 4 if mode == "dt_ddpm" else 6] == 0 and (coef[:2, 4 if mode == "dt_ddpm" else 6] != 0).all())
+    assert mid == mode_id and coef.shape == (B, 8) and coef.dtype == torch.float32
+    coef = coef.to(DEV)
+    k = [coef[:, j][:, None] for j in range(8)]
+    for per_sample in POSTERIOR_PER_SAMPLE:
+        g = torch.Generator(device=DEV).manual_seed(per_sample % 1000 + 10 * mode_id + obj_id)
+        x, pr, z = (torch.randn(B, per_sample, generator=g, device=DEV) for _ in range(3))
+        for clip in (1.0, -1.0):
+            if objective == "x_0":
+                x0 = pr
+            elif mode.startswith("ct") and objective == "eps":
+                x0 = (x - k[1] * pr) / k[0]
+            else:
+                x0 = k[0] * x - k[1] * pr
+            if clip >= 0:
+                x0 = x0.clamp(-clip, clip)
+            if mode == "ct_ddpm":
+                want = k[2] * (x * (1 - k[4]) / k[0] + k[4] * x0) + k[5] * z
+            elif mode == "ct_ddim":
+                want = k[2] * x0 + k[6] * z + k[7] * ((x - k[0] * x0) / k[1])
+            elif mode == "dt_ddpm":
+                want = k[2] * x0 + k[3] * x + k[4] * z
+            else:
+                want = k[5] * x0 + k[4] * ((x - k[2] * x0) / k[3])
+                if mode == "dt_ddim_noise":
+                    want = want + k[6] * z
+            got = _lib.posterior_step(x, pr, z, coef, mode_id, obj_id, clip)
+            assert got.dtype == torch.float32 and got.shape == x.shape and torch.isfinite(got).all()
+            assert torch.equal(got, want), (per_sample, clip, max_abs(got, want))
+            if mode == "dt_ddim":
+                assert torch.equal(_lib.posterior_step(x, pr, None, coef, mode_id, obj_id, clip), got)
+            elif mode.startswith("dt"):
+                assert torch.equal(got[2], _lib.posterior_step(x, pr, z.flip(-1), coef, mode_id, obj_id, clip)[2])  # step 0: no noise
+
+
 def test_lidar_postprocess(golden):
     from r2dm_amd import _lib
 
