@@ -17,7 +17,9 @@ row of label-coloured images under the completed ones, the completed bird's-eye 
 ``labels`` in ``completion.pt``.  Without it there is no segmentation row.  ``--semseg_postprocess {none,knn,crf,crf_knn}`` refines those
 labels with the reference's post-processors at their defaults (r2dm_amd.postproc: the CRF-RNN on the logits, the kNN vote on the labels);
 the refined labels are the ones drawn and saved.  ``--out_scan FILE.bin`` (extension) also writes the completed scan -- the completion of
-the full input, the first column -- as a Velodyne file in scan order (r2dm_amd.pointcloud)."""
+the full input, the first column -- as a Velodyne file in scan order (r2dm_amd.pointcloud).  ``--ensemble K`` (extension) completes every
+corruption K times (member 0 is the image's completion) and adds two rows, the fraction of members with a return at each pixel and the
+standard deviation of their depth (0 to 5 m), turbo-coloured; ``completion.pt`` gains ``maps`` (4,8,H,W), r2dm_amd.ensemble_scores' maps."""
 import math
 from argparse import SUPPRESS, ArgumentParser
 from pathlib import Path
@@ -95,6 +97,39 @@ def to_bev(x, lidar_utils, size, colors=None):
     return (1 - render_point_clouds(points, colors, size=size, R=R, t=t)).clamp(0, 1)
 
 
+STD_SCALE = 5.0  # metres: the depth std that gets the colour map's last colour
+
+
+def complete(args, ddpm, x_in, mask, rng):
+    """the chosen method's completion of the four corrupted inputs from the generators ``rng``, clamped"""
+    if getattr(args, "method", "repaint") == "dpmpp":  # (no resampling on the multistep solver: --num_resample_steps, --jump_length are not read)
+        return ddpm.complete_dpm(known=x_in, mask=mask, num_steps=args.num_steps, eta=getattr(args, "dpmpp_eta", 1.0), rng=rng).clamp(-1, 1)
+    completer = ddpm.complete if getattr(args, "method", "repaint") == "ddnm" else ddpm.repaint
+    return completer(known=x_in, mask=mask, num_steps=args.num_steps, num_resample_steps=args.num_resample_steps,
+                     jump_length=args.jump_length, rng=rng).clamp(-1, 1)
+
+
+def ensemble_maps(args, ddpm, lidar_utils, x_orig, x_in, mask, x_out):
+    """``--ensemble K``: K - 1 further completions of every corruption (member k of corruption c seeded by ``member_seed(seed, c, k)``;
+    member 0 is ``x_out``) -> the (4,8,H,W) per-pixel maps of ``r2dm_amd.ensemble_scores`` against the scan itself"""
+    from r2dm_amd.completion import member_seed
+
+    if not 1 <= args.ensemble <= 64:
+        raise ValueError(f"--ensemble must be in [1, 64], got {args.ensemble}")
+    members = [x_out] + [complete(args, ddpm, x_in, mask, r2dm_amd.setup_rng([member_seed(args.seed, c, k) for c in range(BATCH)], device=x_in.device))
+                         for k in range(1, args.ensemble)]
+    samples = torch.stack([lidar_utils.postprocess(m) for m in members], dim=1)
+    target = lidar_utils.postprocess(x_orig.clamp(-1, 1)).expand(BATCH, -1, -1, -1)
+    return r2dm_amd.ensemble_scores(samples, target, mask[:, :1], lidar_utils.min_depth, lidar_utils.max_depth)["maps"]
+
+
+def uncertainty_rows(maps):
+    """two image rows (B,3,H,W) in [0,1]: the members' return probability and their depth std (0 to STD_SCALE metres), turbo-coloured"""
+    from r2dm_amd.render import colorize
+
+    return [colorize(maps[:, [0]].clamp(0, 1), "turbo").float() / 255, colorize((maps[:, [2]] / STD_SCALE).clamp(0, 1), "turbo").float() / 255]
+
+
 def main(args):
     from r2dm_amd.render import make_grid, save_png
 
@@ -105,17 +140,15 @@ def main(args):
 
     mask = corruption_masks(x_orig, args.seed).to(device)
     x_in = mask * x_orig + (1 - mask) * -1
-    if getattr(args, "method", "repaint") == "dpmpp":  # (no resampling on the multistep solver: --num_resample_steps, --jump_length are not read)
-        x_out = ddpm.complete_dpm(known=x_in, mask=mask, num_steps=args.num_steps, eta=getattr(args, "dpmpp_eta", 1.0),
-                                  rng=r2dm_amd.setup_rng(range(BATCH), device=device)).clamp(-1, 1)
-    else:
-        completer = ddpm.complete if getattr(args, "method", "repaint") == "ddnm" else ddpm.repaint
-        x_out = completer(known=x_in, mask=mask, num_steps=args.num_steps, num_resample_steps=args.num_resample_steps,
-                          jump_length=args.jump_length, rng=r2dm_amd.setup_rng(range(BATCH), device=device)).clamp(-1, 1)
+    x_out = complete(args, ddpm, x_in, mask, r2dm_amd.setup_rng(range(BATCH), device=device))
 
     W = x_in.shape[-1]
     saved = {"x_in": x_in.cpu(), "mask": mask.cpu(), "x_out": x_out.cpu()}
     rows = [to_img(x_in, lidar_utils), to_bev(x_in, lidar_utils, W), to_img(x_out, lidar_utils)]
+    if getattr(args, "ensemble", None) is not None:
+        maps = ensemble_maps(args, ddpm, lidar_utils, x_orig, x_in, mask, x_out)
+        rows += uncertainty_rows(maps)
+        saved["maps"] = maps.cpu()
     if getattr(args, "rangenet_weights", None) is not None:  # completion_demo.py:105-106,138-140
         from r2dm_amd.render import colorize_labels
 
@@ -158,6 +191,9 @@ def parser():
                    help="the official darknet53-1024.tar.gz archive or a .pth state dict (a local file): adds the segmentation row and label colours")
     p.add_argument("--semseg_postprocess", choices=("none", "knn", "crf", "crf_knn"), default="none",
                    help="refine the labels of --rangenet_weights: the kNN vote of RangeNet++, the CRF-RNN of SqueezeSeg, or the CRF-RNN and then the vote")
+    p.add_argument("--ensemble", type=int, default=SUPPRESS, metavar="K",  # (an attribute of the parsed arguments only when given)
+                   help="complete every corruption K times and add two image rows, the members' return probability and depth std "
+                        "(the per-pixel maps go into completion.pt)")
     p.add_argument("--out_scan", type=Path, default=None, help="also write the completed scan (of the full input) as a Velodyne .bin file")
     return p
 

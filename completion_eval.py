@@ -22,7 +22,14 @@ its RePaint noise from generators seeded from ``(--seed, i)`` (r2dm_amd.completi
 
 Writes one JSON document to ``--out``: ``info`` (checkpoint, number of scans, settings) and ``results[kind][method]`` (counts, error
 sums, micro and macro averages, per-class IoU and mIoU, or ``skipped``); an undefined value is ``null``.  ``--save_dir DIR`` also writes
-the tensors behind the numbers, one ``.pt`` file per corruption."""
+the tensors behind the numbers, one ``.pt`` file per corruption.
+
+``--ensemble K`` draws K completions per scan with every stochastic method (member k of scan i seeded by
+r2dm_amd.completion.member_seed; member 0 is the single draw, on which everything above is still scored) and adds
+``results[kind][method]["ensemble"]``: the continuous ranked probability score of range and reflectance (the mean absolute error at K = 1,
+so the interpolation baselines share the column), the rank histogram and the spread / skill ratio (calibration), the Brier score of ray
+drop, best-of-K and the errors of the consensus scan ("Ensemble scores"); ``--save_dir`` then also keeps the per-pixel
+return-probability, mean, std and median maps."""
 import json
 from argparse import SUPPRESS, ArgumentParser
 from pathlib import Path
@@ -95,7 +102,8 @@ def main(argv=None):
                                          batch_size=args.batch_size, semseg=semseg, semseg_postprocess=post, keep=args.save_dir is not None,
                                          chamfer=args.chamfer, fscore_threshold=args.fscore_threshold, ddnm_resample_steps=args.ddnm_resample_steps,
                                          ddnm_init=None if args.ddnm_init == "none" else args.ddnm_init, ddnm_t_start=args.ddnm_t_start,
-                                         **{**dpmpp, "dpmpp_init": None if dpmpp["dpmpp_init"] == "none" else dpmpp["dpmpp_init"]})
+                                         **{**dpmpp, "dpmpp_init": None if dpmpp["dpmpp_init"] == "none" else dpmpp["dpmpp_init"]},
+                                         **({"ensemble": args.ensemble} if hasattr(args, "ensemble") else {}))
     results, kept = out if args.save_dir is not None else (out, None)
     info = {"ckpt": str(args.ckpt), "source": str(args.real_scans if args.real_scans is not None else args.real_dir), "num_scans": len(files),
             "resolution": list(cfg.data.resolution), "corruptions": kinds, "methods": list(args.methods), "num_steps": args.num_steps,
@@ -108,6 +116,8 @@ def main(argv=None):
         info.update(ddnm_resample_steps=args.ddnm_resample_steps, ddnm_init=args.ddnm_init, ddnm_t_start=args.ddnm_t_start)
     if "dpmpp" in args.methods:
         info.update(dpmpp)
+    if hasattr(args, "ensemble"):
+        info["ensemble"] = args.ensemble
     doc = completion.jsonable({"info": info, "results": results})
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     with open(args.out, "w") as f:
@@ -126,6 +136,11 @@ def main(argv=None):
                   + ("" if iou is None else f", mIoU {iou:.4f}")
                   + (f", inpainted CD {entry['geometry']['inpainted']['micro']['cd']:.4f} m, F-score {entry['geometry']['inpainted']['micro']['fscore']:.4f}"
                      if "geometry" in entry else ""))
+            if "ensemble" in entry:
+                e = entry["ensemble"]
+                print(f"{'':>20} {'':>8}  {e['members']} members: CRPS depth {e['micro']['crps_depth']:.4f} m, spread / skill "
+                      f"{e['micro']['spread_skill_depth']:.3f}, Brier {e['micro']['brier_return']:.4f}, best-of-K MAE {e['micro']['best_mae_depth']:.4f} m, "
+                      f"consensus MAE {e['consensus']['micro']['mae_depth']:.4f} m")
     print(f"{len(files)} scans -> {args.out}")
     return doc
 
@@ -173,6 +188,9 @@ def build_parser():
     parser.add_argument("--chamfer", action="store_true",
                         help="also Chamfer distance and F-score of the completed scan's points against the real scan's, whole image and inpainted pixels")
     parser.add_argument("--fscore_threshold", type=float, default=0.2, help="the F-score's distance threshold in metres (with --chamfer)")
+    parser.add_argument("--ensemble", type=int, default=SUPPRESS, metavar="K",  # (an attribute of the parsed arguments only when given)
+                        help="draw K members per scan with every stochastic method and score them as an ensemble: CRPS, rank histogram, "
+                             "spread against skill, Brier score of ray drop, best-of-K, the consensus scan (--save_dir keeps the per-pixel maps)")
     parser.add_argument("--save_dir", type=Path, default=None, help="also write the tensors behind the numbers, one .pt file per corruption")
     parser.add_argument("--out", type=str, default="completion.json")
     return parser

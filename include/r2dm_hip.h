@@ -501,7 +501,31 @@ int r2dm_crf_iter(const float* q_in, const float* unary, const float* xyz, const
  *    (no wrap); an endpoint is usable if it exists and x[b][0][row][w] != nodata.  mode 0 (nearest): every channel from the usable endpoint
  *    at the smaller row distance, `up` on a tie.  mode 1 (linear): with both usable a + (b - a) * t, t = float(h - up) / float(dn - up), in
  *    fp32 with IEEE division and no contraction; with one usable a copy of it.  No usable endpoint: nodata in every channel.  out must
- *    not alias x.  Limits: batch, height <= 65535. */
+ *    not alias x.  Limits: batch, height <= 65535.
+ * r2dm_ensemble_score: K completions ("members") of each scan scored as an ensemble.  samples (batch,members,5,plane) fp32 in the sample
+ *    layout, a scan's members adjacent (planes 0 and 4 are read); target, known, lo, hi, U, G, E as for r2dm_completion_error.  Member k
+ *    returns at a pixel iff lo < d_k < hi (NaN is in neither); r^_k = d_k then, else 0; n = the returning members; g = [pixel in G]; a NaN
+ *    member reflectance counts as 0.  With K = members and m = (1/K) sum_k r^_k:
+ *    raw (batch,13) fp64 = |U|, |E|, sum_E sum_k |r^_k - r|, sum_E sum_{k<l} |r^_k - r^_l|, sum_E (m - r)^2,
+ *      sum_E (1/(K-1)) sum_k (r^_k - m)^2 (0 at K = 1), the same four sums for reflectance (on the stored values), sum_U (n/K - g)^2,
+ *      sum_E n/K, sum_{U \ G} n/K.  Un-normalised: CRPS = (raw[2]/K - raw[3]/K^2) / |E|, which is the mean absolute error at K = 1.
+ *    member (batch,2,members) fp64 = sum_E |r^_k - r| and sum_E |rho_k - rho| per member, in member order.
+ *    rank (batch,members+1) int64 = over E the histogram of #{k : r^_k < r}, zeroed by the call (int32 table per block in LDS, 64-bit
+ *      integer atomics: exact in any order).
+ *    maps NULL or (batch,8,plane) fp32, written for every pixel: n/K; over the returning members the mean, the population standard
+ *      deviation (two-pass; 0 if n < 2), the median (even n: the fp64 mean of the two middle values), the minimum and the maximum of depth
+ *      (0 if n = 0); the mean and the population standard deviation of reflectance over all members.  fp64, rounded once to fp32.  maps
+ *      must not overlap an input.
+ *    Every fp32 value is widened to fp64 first.  Per pixel and channel the members are sorted ascending and every sum over members runs in
+ *    sorted order, the pair term as sum_{i=1}^{K-1} i (K - i) (x_(i+1) - x_(i)): everything but `member` is bit-identical under any
+ *    permutation of the members.  Float sums run in a fixed order (per-block partials added in index order by a second kernel, no float
+ *    atomics): the same bits on every call, and a scan's numbers do not depend on the batch.  scratch: the bytes the _scratch_bytes
+ *    function returns for (batch, members, plane) (0 for an empty or oversized problem); scratch, raw, member and rank 8-byte aligned; the
+ *    fp32 pointers 16-byte aligned when plane is a multiple of 4, else 4-byte aligned.  Limits: batch <= 65535, 1 <= members <= 64,
+ *    plane <= 2^40, samples of at most 2^40 elements. */
+size_t r2dm_ensemble_score_scratch_bytes(int32_t batch, int32_t members, int64_t plane);
+int r2dm_ensemble_score(const float* samples, const float* target, const float* known, float lo, float hi, int32_t batch, int32_t members,
+                        int64_t plane, void* scratch, double* raw, double* member, int64_t* rank, float* maps, void* stream);
 size_t r2dm_completion_error_scratch_bytes(int32_t batch, int64_t plane);
 int r2dm_completion_error(const float* pred, const float* target, const float* known, float lo, float hi, int32_t batch, int64_t plane,
                           void* scratch, double* out, void* stream);

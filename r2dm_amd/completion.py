@@ -9,6 +9,9 @@ linear interpolation of the known beams.  The reference has no code for it.  Her
 - ``completion_errors``    per sample the four counts and six error sums of ``r2dm_completion_error`` and the values derived from them.
 - ``confusion_matrix`` / ``iou_from_confusion``   label agreement.
 - ``fill_beams``           the interpolation baselines.
+- ``ensemble_scores``      K completions per scan scored as an ensemble (``r2dm_ensemble_score``): CRPS, the rank histogram, spread against
+  skill, the Brier score of ray drop, best-of-K and per-pixel return probability / mean / std / median maps; ``ensemble_consensus`` turns the
+  maps into one scan, ``aggregate_ensemble`` sums over scans, ``member_seed`` seeds member k of scan i.
 - ``evaluate_completion``  corrupt, complete (RePaint, the data-consistent sampler ``ddpm.complete``, the same on DPM-Solver++(2M), ``ddpm.complete_dpm``, or a baseline), score; ``completion_eval.py`` is its command line.
 
 A pixel is a *return* when its metric depth lies strictly inside ``(lo, hi)``; any other depth, NaN included, is "no return".  The errors
@@ -29,6 +32,16 @@ RAW_NAMES = ("unknown", "evaluated", "both", "false_returns", "abs_depth", "sq_d
              "abs_reflectance", "sq_reflectance")
 DERIVED_NAMES = ("mae_depth", "rmse_depth", "mae_depth_both", "rmse_depth_both", "mae_reflectance", "rmse_reflectance", "return_recall",
                  "false_return_rate")
+ENSEMBLE_RAW_NAMES = ("unknown", "evaluated", "abs_depth_members", "pair_depth", "sq_depth_mean", "var_depth", "abs_reflectance_members",
+                      "pair_reflectance", "sq_reflectance_mean", "var_reflectance", "brier", "returns_expected", "false_expected")
+ENSEMBLE_DERIVED_NAMES = ("crps_depth", "crps_fair_depth", "mae_depth_members", "best_mae_depth", "rmse_depth_mean", "spread_depth",
+                          "spread_skill_depth", "crps_reflectance", "crps_fair_reflectance", "mae_reflectance_members", "best_mae_reflectance",
+                          "rmse_reflectance_mean", "spread_reflectance", "spread_skill_reflectance", "brier_return", "return_recall",
+                          "false_return_rate")
+ENSEMBLE_MAP_NAMES = ("return_probability", "depth_mean", "depth_std", "depth_median", "depth_min", "depth_max", "reflectance_mean",
+                      "reflectance_std")
+MAX_MEMBERS = 64
+STOCHASTIC_METHODS = ("repaint", "ddnm", "dpmpp")
 FILL_MODES = {"nearest": 0, "linear": 1}
 ROW_KINDS = ("full", "beams", "random_beams")  # corruptions whose mask is whole rows: what the interpolation baselines are defined for
 METHODS = ("repaint", "ddnm", "dpmpp", "nearest", "linear", "target")
@@ -83,6 +96,20 @@ def scan_seed(seed: int, index: int) -> int:
     return seed * 2 ** 32 + index
 
 
+def member_seed(seed: int, index: int, k: int) -> int:
+    """The seed of member ``k`` of scan ``index``'s ensemble under ``seed``.  Member 0 is the scan's single draw: ``scan_seed(seed, index)``.
+    For k > 0 the first 64-bit word of ``numpy.random.SeedSequence([seed, index, k]).generate_state(1, numpy.uint64)`` with its top bit
+    cleared: a pure function of the three into [0, 2^63), what a ``torch.Generator`` takes."""
+    import numpy as np
+
+    base, k = scan_seed(seed, index), int(k)
+    if not 0 <= k < 2 ** 32:
+        raise ValueError(f"the member index must be in [0, 2^32), got {k}")
+    if k == 0:
+        return base
+    return int(np.random.SeedSequence([int(seed), int(index), k]).generate_state(1, np.uint64)[0]) >> 1
+
+
 # ---- errors ------------------------------------------------------------------------------------------------------------------------------
 def _ratio(num: torch.Tensor, den: torch.Tensor) -> torch.Tensor:
     nan = torch.full_like(num, math.nan)
@@ -130,6 +157,107 @@ def completion_errors(pred: torch.Tensor, target: torch.Tensor, known: torch.Ten
     raw = completion_error_sums(pred, target, known, lo, hi)
     out = {name: raw[:, k] for k, name in enumerate(RAW_NAMES)}
     out.update(derived_errors(raw))
+    return out
+
+
+# ---- ensembles: K completions of a scan scored as a probabilistic forecast ----------------------------------------------------------------
+def derived_ensemble(raw: torch.Tensor, member: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """(...,13) raw values (``ENSEMBLE_RAW_NAMES``) and (...,2,K) per-member sums -> the derived values (``ENSEMBLE_DERIVED_NAMES``), NaN
+    where a denominator is 0.  CRPS = E|X - y| - E|X - X'| / 2 with both expectations over the K members (``crps_fair`` with the second over
+    the K (K - 1) pairs of distinct members: unbiased for the underlying distribution, NaN at K = 1); ``spread_skill`` =
+    sqrt((K + 1) / K * mean variance / mean squared error of the ensemble mean), 1 for a calibrated ensemble."""
+    raw, member = raw.double(), member.double()
+    K = member.shape[-1]
+    U, E = raw[..., 0], raw[..., 1]
+    nan = torch.full_like(E, math.nan)
+    out = {}
+    for c, name in ((2, "depth"), (6, "reflectance")):
+        a, pr, sq, var = raw[..., c], raw[..., c + 1], raw[..., c + 2], raw[..., c + 3]
+        best = member[..., 0 if name == "depth" else 1, :].min(dim=-1).values if K else nan
+        out["crps_" + name] = _ratio(a / K - pr / K ** 2, E)
+        out["crps_fair_" + name] = _ratio(a / K - pr / (K * (K - 1)), E) if K > 1 else nan
+        out["mae_" + name + "_members"] = _ratio(a, K * E)
+        out["best_mae_" + name] = _ratio(best, E)
+        out["rmse_" + name + "_mean"] = _ratio(sq, E).sqrt()
+        out["spread_" + name] = _ratio(var, E).sqrt()
+        out["spread_skill_" + name] = ((K + 1) / K * _ratio(var, sq)).sqrt()
+    out["brier_return"] = _ratio(raw[..., 10], U)
+    out["return_recall"] = _ratio(raw[..., 11], E)
+    out["false_return_rate"] = _ratio(raw[..., 12], U - E)
+    return {name: out[name] for name in ENSEMBLE_DERIVED_NAMES}
+
+
+def ensemble_score_sums(samples: torch.Tensor, target: torch.Tensor, known: torch.Tensor, lo: float, hi: float, maps: bool = True):
+    """``r2dm_ensemble_score`` on the device: ``samples`` (B,K,5,H,W) -> ``(raw (B,13) float64, member (B,2,K) float64, rank (B,K+1) int64,
+    maps (B,8,H,W) float32 or None)``."""
+    _lib.require_gpu(samples, "samples")
+    if samples.dim() != 5 or samples.shape[2] != 5:
+        raise ValueError(f"samples {tuple(samples.shape)} must be (B,K,5,H,W): K members per scan in the layout [depth, x, y, z, reflectance]")
+    B, K, _, H, W = samples.shape
+    if not 1 <= K <= MAX_MEMBERS:
+        raise ValueError(f"an ensemble has 1 to {MAX_MEMBERS} members, got {K}")
+    if tuple(target.shape) != (B, 5, H, W) or tuple(known.shape) != (B, 1, H, W):
+        raise ValueError(f"target {tuple(target.shape)} must be {(B, 5, H, W)} and known {tuple(known.shape)} {(B, 1, H, W)}")
+    dev = samples.device
+    samples, target, known = _lib.f32c(samples), _lib.f32c(target.to(dev)), _lib.f32c(known.to(dev))
+    raw = torch.empty(B, len(ENSEMBLE_RAW_NAMES), dtype=torch.float64, device=dev)
+    member = torch.empty(B, 2, K, dtype=torch.float64, device=dev)
+    rank = torch.empty(B, K + 1, dtype=torch.int64, device=dev)
+    out = torch.empty(B, len(ENSEMBLE_MAP_NAMES), H, W, dtype=torch.float32, device=dev) if maps else None
+    if B == 0:
+        return raw, member, rank, out
+    L = _lib.lib()
+    nbytes = L.r2dm_ensemble_score_scratch_bytes(B, K, H * W)
+    if nbytes == 0:
+        raise _lib.R2DMError(f"ensemble_scores: empty or oversized problem (B={B}, K={K}, plane={H * W})")
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.r2dm_ensemble_score(_lib.ptr(samples), _lib.ptr(target), _lib.ptr(known), float(lo), float(hi), B, K, H * W, _lib.ptr(scratch),
+                                         _lib.ptr(raw), _lib.ptr(member), _lib.ptr(rank), _lib.ptr(out), _lib.stream_ptr(dev)))
+    return raw, member, rank, out
+
+
+def ensemble_scores(samples: torch.Tensor, target: torch.Tensor, known: torch.Tensor, lo: float, hi: float, maps: bool = True) -> dict:
+    """K completions per scan scored as an ensemble.  ``samples`` (B,K,5,H,W) in the sample layout, the K members of a scan adjacent;
+    ``target`` (B,5,H,W), ``known`` (B,1,H,W) as for ``completion_errors`` -> a dict of (B,) float64 tensors, the raw sums under
+    ``ENSEMBLE_RAW_NAMES`` and the derived values under ``ENSEMBLE_DERIVED_NAMES`` (NaN where a denominator is 0), plus
+    ``member_abs_depth`` / ``member_abs_reflectance`` (B,K), ``rank_histogram`` (B,K+1) int64 (over E, how many members lie below the
+    measured depth: flat for a calibrated ensemble) and ``maps`` (B,8,H,W) float32 (``ENSEMBLE_MAP_NAMES``; None with ``maps=False``).
+    ``crps_depth`` at K = 1 is ``completion_errors``' ``mae_depth``."""
+    raw, member, rank, out = ensemble_score_sums(samples, target, known, lo, hi, maps)
+    res = {name: raw[:, k] for k, name in enumerate(ENSEMBLE_RAW_NAMES)}
+    res.update(derived_ensemble(raw, member))
+    res.update(member_abs_depth=member[:, 0], member_abs_reflectance=member[:, 1], rank_histogram=rank, maps=out)
+    return res
+
+
+def ensemble_consensus(maps: torch.Tensor, lidar_utils) -> torch.Tensor:
+    """The ensemble's point forecast, (B,5,H,W) in the sample layout: depth = the median of the returning members where at least half of
+    the members return, else 0 (no return); xyz = ``lidar_utils.to_xyz`` of it; reflectance = the members' mean.  What
+    ``completion_errors``, the Chamfer metrics and the segmentation take."""
+    if maps.dim() != 4 or maps.shape[1] != len(ENSEMBLE_MAP_NAMES):
+        raise ValueError(f"expected maps (B,8,H,W) ({', '.join(ENSEMBLE_MAP_NAMES)}), got {tuple(maps.shape)}")
+    depth = torch.where(maps[:, [0]] >= 0.5, maps[:, [3]], torch.zeros_like(maps[:, [3]]))
+    return torch.cat([depth, lidar_utils.to_xyz(depth), maps[:, [6]]], dim=1).float().contiguous()
+
+
+def aggregate_ensemble(raw: torch.Tensor, member: torch.Tensor, rank: torch.Tensor) -> dict:
+    """Per-scan (N,13), (N,2,K), (N,K+1) -> ``{"counts", "sums", "micro", "macro", "rank_histogram"}`` in the shape of ``aggregate_errors``:
+    micro = the derived values of the sums over all scans (``best_mae`` from the summed per-member errors: the best member over the whole
+    set), macro = the mean of the per-scan derived values, ignoring the NaN ones; the rank histogram is summed."""
+    raw = torch.as_tensor(raw).detach().cpu().double().reshape(-1, len(ENSEMBLE_RAW_NAMES))
+    member = torch.as_tensor(member).detach().cpu().double()
+    K = member.shape[-1]
+    member, rank = member.reshape(-1, 2, K), torch.as_tensor(rank).detach().cpu().long().reshape(-1, K + 1)
+    total = raw.sum(0)
+    out = {"counts": {"scans": int(raw.shape[0]), "members": int(K), **{name: int(total[k].item()) for k, name in enumerate(ENSEMBLE_RAW_NAMES[:2])}},
+           "sums": {name: total[k].item() for k, name in enumerate(ENSEMBLE_RAW_NAMES) if k >= 2},
+           "micro": {name: v.item() for name, v in derived_ensemble(total, member.sum(0)).items()}, "macro": {},
+           "rank_histogram": rank.sum(0).tolist()}
+    out["counts"]["unknown_without_return"] = out["counts"]["unknown"] - out["counts"]["evaluated"]
+    for name, v in derived_ensemble(raw, member).items():
+        ok = ~v.isnan()
+        out["macro"][name] = v[ok].mean().item() if ok.any() else math.nan
     return out
 
 
@@ -256,7 +384,7 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
                         semseg_postprocess=None, lo: Optional[float] = None, hi: Optional[float] = None, keep: bool = False,
                         chamfer: bool = False, fscore_threshold: float = 0.2, ddnm_resample_steps: int = 1, ddnm_init: Optional[str] = None,
                         ddnm_t_start: float = 1.0, dpmpp_eta: float = 1.0, dpmpp_order: int = 2, dpmpp_init: Optional[str] = None,
-                        dpmpp_t_start: float = 1.0):
+                        dpmpp_t_start: float = 1.0, ensemble: Optional[int] = None):
     """Corrupt, complete and score ``planes`` (N,6,H,W), the masked planes of ``project_scans(layout="xyzrdm", apply_mask=True)`` at the
     model's resolution, on the GPU.
 
@@ -283,7 +411,16 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
     scans with an empty cloud); or ``{"skipped": why}``.  ``keep=True``: ``(results, kept)`` with ``kept[kind]`` =
     ``{"mask", "x_in", "target", "x_out": {method}, "pred": {method}, "raw": {method}}`` and, with ``semseg``, ``"target_labels"``,
     ``"labels": {method}`` and ``"confusion": {method}``, with ``chamfer`` ``"geometry_raw": {method: {"all", "inpainted"}}`` ((N,8) sums,
-    ``geometry.RAW_NAMES``), all on the CPU."""
+    ``geometry.RAW_NAMES``), all on the CPU.
+
+    ``ensemble`` = K (1 to 64): every stochastic method ("repaint", "ddnm", "dpmpp") draws K members per scan, member k of scan i from
+    ``setup_rng([member_seed(seed, i, k)])``, all under the scan's one mask; members fill the batch (``batch_size`` counts members) and, the
+    generators being per sample, a member does not depend on the batch it is drawn in.  Member 0 is the single draw of a run without
+    ``ensemble``, and everything above is still scored on it.  A deterministic method is an ensemble of one.  Every entry gains
+    ``"ensemble"``: ``{"members", **aggregate_ensemble(...), "consensus"}`` with ``consensus`` the ``aggregate_errors`` of
+    ``ensemble_consensus`` (median depth where at least half of the members return, mean reflectance); ``kept[kind]["ensemble"][method]`` =
+    ``{"raw" (N,13), "member" (N,2,K), "rank" (N,K+1), "consensus_raw" (N,10), "maps" (N,8,H,W), "x_out" (N,K,2,H,W) or None}``.  None
+    (the default): nothing of this is computed, and keys and numbers are what they were."""
     from . import geometry
     from .inference import setup_rng
     from .projection import known_from_scan
@@ -308,6 +445,8 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
         raise ValueError(f"dpmpp_order must be 1 or 2, got {dpmpp_order!r}")
     if not float(dpmpp_eta) >= 0.0 or float(dpmpp_eta) == float("inf"):
         raise ValueError(f"dpmpp_eta must be finite and >= 0, got {dpmpp_eta}")
+    if ensemble is not None and not (isinstance(ensemble, int) and 1 <= ensemble <= MAX_MEMBERS):
+        raise ValueError(f"ensemble must be None or a number of members in [1, {MAX_MEMBERS}], got {ensemble!r}")
     if planes.dim() != 4 or planes.shape[1] != 6:
         raise ValueError(f"expected planes (N,6,H,W) [x, y, z, reflectance, depth, mask], got {tuple(planes.shape)}")
     _lib.require_gpu(planes, "planes")
@@ -366,31 +505,29 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
             if method == "dpmpp" and dpmpp_init is not None and name not in ROW_KINDS:
                 results[kind][method] = {"skipped": f"dpmpp_init = {dpmpp_init} interpolation is defined for masks of whole rows ({', '.join(ROW_KINDS)})"}
                 continue
-            if method == "dpmpp":
-                init = fill_beams(x_in, rows_of_mask(mask), dpmpp_init, nodata=-1.0) if dpmpp_init is not None and N else None
+            members = ensemble if ensemble is not None and method in STOCHASTIC_METHODS else 1
+            x_members = None
+            if method in STOCHASTIC_METHODS:
+                how = {"dpmpp": dpmpp_init, "ddnm": ddnm_init, "repaint": None}[method]
+                init = fill_beams(x_in, rows_of_mask(mask), how, nodata=-1.0) if how is not None and N else None
+                jobs = [(i, k) for i in range(N) for k in range(members)]  # a scan's members adjacent; member 0 is the single draw
                 parts = []
-                for k in range(0, N, batch_size):
-                    rng = setup_rng([scan_seed(seed, i) for i in range(k, min(k + batch_size, N))], dev)
-                    parts.append(ddpm.complete_dpm(known=x_in[k:k + batch_size], mask=mask[k:k + batch_size], num_steps=num_steps, order=dpmpp_order,
-                                                   eta=float(dpmpp_eta), t_start=float(dpmpp_t_start),
-                                                   init=None if init is None else init[k:k + batch_size], progress=False, rng=rng))
-                x_out = torch.cat(parts) if parts else x_in
-            elif method == "ddnm":
-                init = fill_beams(x_in, rows_of_mask(mask), ddnm_init, nodata=-1.0) if ddnm_init is not None and N else None
-                parts = []
-                for k in range(0, N, batch_size):
-                    rng = setup_rng([scan_seed(seed, i) for i in range(k, min(k + batch_size, N))], dev)
-                    parts.append(ddpm.complete(known=x_in[k:k + batch_size], mask=mask[k:k + batch_size], num_steps=num_steps,
-                                               num_resample_steps=ddnm_resample_steps, jump_length=jump_length, t_start=float(ddnm_t_start),
-                                               init=None if init is None else init[k:k + batch_size], progress=False, rng=rng))
-                x_out = torch.cat(parts) if parts else x_in
-            elif method == "repaint":
-                parts = []
-                for k in range(0, N, batch_size):
-                    rng = setup_rng([scan_seed(seed, i) for i in range(k, min(k + batch_size, N))], dev)
-                    parts.append(ddpm.repaint(known=x_in[k:k + batch_size], mask=mask[k:k + batch_size], num_steps=num_steps,
-                                              num_resample_steps=num_resample_steps, jump_length=jump_length, progress=False, rng=rng))
-                x_out = torch.cat(parts) if parts else x_in
+                for j in range(0, len(jobs), batch_size):
+                    job = jobs[j:j + batch_size]
+                    idx = torch.tensor([i for i, _ in job], device=dev)
+                    rng = setup_rng([member_seed(seed, i, k) for i, k in job], dev)
+                    kn, mk, it = x_in[idx], mask[idx], None if init is None else init[idx]
+                    if method == "dpmpp":
+                        parts.append(ddpm.complete_dpm(known=kn, mask=mk, num_steps=num_steps, order=dpmpp_order, eta=float(dpmpp_eta),
+                                                       t_start=float(dpmpp_t_start), init=it, progress=False, rng=rng))
+                    elif method == "ddnm":
+                        parts.append(ddpm.complete(known=kn, mask=mk, num_steps=num_steps, num_resample_steps=ddnm_resample_steps,
+                                                   jump_length=jump_length, t_start=float(ddnm_t_start), init=it, progress=False, rng=rng))
+                    else:
+                        parts.append(ddpm.repaint(known=kn, mask=mk, num_steps=num_steps, num_resample_steps=num_resample_steps,
+                                                  jump_length=jump_length, progress=False, rng=rng))
+                x_members = torch.cat(parts).reshape(N, members, *x_in.shape[1:]) if parts else x_in[:, None]
+                x_out = x_members[:, 0].contiguous()
             elif method in FILL_MODES:
                 x_out = fill_beams(x_in, rows_of_mask(mask), method, nodata=-1.0) if N else x_in
             else:
@@ -406,8 +543,32 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
             if chamfer:
                 graw = {"all": geometry_of(pred, None), "inpainted": geometry_of(pred, mask == 0)}
                 entry["geometry"] = {where: geometry.aggregate_chamfer(r) for where, r in graw.items()}
+            if ensemble is not None:
+                eraw, emember, erank, emaps, craw = [], [], [], [], []
+                for k in range(0, N, batch_size):
+                    if x_members is None or members == 1:
+                        samples = pred[k:k + batch_size, None]
+                    else:
+                        xs = x_members[k:k + batch_size]
+                        samples = lidar_utils.postprocess(xs.flatten(0, 1).clamp(-1, 1)).reshape(xs.shape[0], members, 5, H, W)
+                    r, m, h, maps = ensemble_score_sums(samples, target[k:k + batch_size], mask[k:k + batch_size], lo, hi, maps=True)
+                    craw.append(completion_error_sums(ensemble_consensus(maps, lidar_utils), target[k:k + batch_size], mask[k:k + batch_size],
+                                                      lo, hi).cpu())
+                    eraw.append(r.cpu()), emember.append(m.cpu()), erank.append(h.cpu())
+                    if keep:
+                        emaps.append(maps.cpu())
+                eraw = torch.cat(eraw) if eraw else torch.empty(0, len(ENSEMBLE_RAW_NAMES), dtype=torch.float64)
+                emember = torch.cat(emember) if emember else torch.empty(0, 2, members, dtype=torch.float64)
+                erank = torch.cat(erank) if erank else torch.empty(0, members + 1, dtype=torch.int64)
+                craw = torch.cat(craw) if craw else torch.empty(0, len(RAW_NAMES), dtype=torch.float64)
+                entry["ensemble"] = {"members": members, **aggregate_ensemble(eraw, emember, erank), "consensus": aggregate_errors(craw)}
             results[kind][method] = entry
             if keep:
+                if ensemble is not None:
+                    kept[kind].setdefault("ensemble", {})[method] = {
+                        "raw": eraw, "member": emember, "rank": erank, "consensus_raw": craw,
+                        "maps": torch.cat(emaps) if emaps else torch.empty(0, len(ENSEMBLE_MAP_NAMES), H, W),
+                        "x_out": None if x_members is None else x_members.cpu()}
                 kept[kind]["x_out"][method] = None if x_out is None else x_out.cpu()
                 kept[kind]["pred"][method] = pred.cpu()
                 kept[kind]["raw"][method] = raw

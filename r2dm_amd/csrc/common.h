@@ -380,6 +380,10 @@ hipError_t launch_completion_error(const float* pred, const float* target, const
 hipError_t launch_confusion_matrix(const long long* pred, const long long* target, const float* mask, int B, long n, int classes, long long* counts,
                                    long long* bad, hipStream_t s);
 hipError_t launch_fill_beams(const float* x, const unsigned char* rows, float* out, int B, int C, int H, int W, float nodata, int mode, hipStream_t s);
+// ... and K completions of a scan scored as an ensemble: raw (B,13), member (B,2,K), rank (B,K+1) (zeroed by the call), maps (B,8,plane) or null
+size_t ensemble_score_scratch_bytes(int B, int K, long plane);
+hipError_t launch_ensemble_score(const float* samples, const float* target, const float* known, float lo, float hi, int B, int K, long plane,
+                                 void* scratch, double* raw, double* member, long long* rank, float* maps, hipStream_t s);
 
 // geometry metrics (geometry.hip): nearest neighbours of P pairs of ragged clouds in both directions -- optional per-point d^2 / index, always
 // sums (P,8) = [sum d^2, sum d, #{d <= tau}] a -> b, the same b -> a, |a|, |b|; status[2] = non-finite points met, pairs that do not check out

@@ -508,6 +508,39 @@ int r2dm_completion_error(const float* pred, const float* target, const float* k
     return 0;
 }
 
+static bool ensemble_geometry_ok(int32_t B, int32_t K, int64_t plane) {
+    return B >= 1 && B <= 65535 && K >= 1 && K <= 64 && plane >= 1 && plane <= (1LL << 40) / 5 / K / B;
+}
+
+size_t r2dm_ensemble_score_scratch_bytes(int32_t B, int32_t K, int64_t plane) {
+    return ensemble_geometry_ok(B, K, plane) ? ensemble_score_scratch_bytes(B, K, plane) : 0;
+}
+
+int r2dm_ensemble_score(const float* samples, const float* target, const float* known, float lo, float hi, int32_t B, int32_t K, int64_t plane,
+                        void* scratch, double* raw, double* member, int64_t* rank, float* maps, void* stream) {
+    if (!samples || !target || !known || !scratch || !raw || !member || !rank) return fail(1, "ensemble_score: null argument (only maps may be null)");
+    if (B < 1 || B > 65535) return fail(1, "ensemble_score: batch must be in [1, 65535], got %d", B);
+    if (K < 1 || K > 64) return fail(1, "ensemble_score: members must be in [1, 64] (the members of a pixel are sorted in registers), got %d", K);
+    if (plane < 1 || plane > (1LL << 40)) return fail(1, "ensemble_score: plane must be in [1, 2^40], got %lld", (long long)plane);
+    if (!ensemble_geometry_ok(B, K, plane)) return fail(1, "ensemble_score: samples of more than 2^40 elements");
+    const uintptr_t a = plane % 4 == 0 ? 15 : 3;
+    if (((uintptr_t)samples | (uintptr_t)target | (uintptr_t)known | (uintptr_t)maps) & a)
+        return fail(1, "ensemble_score: samples, target, known and maps must be %d-byte aligned for a plane of %lld elements", (int)a + 1,
+                    (long long)plane);
+    if (((uintptr_t)scratch | (uintptr_t)raw | (uintptr_t)member | (uintptr_t)rank) & 7)
+        return fail(1, "ensemble_score: scratch, raw, member and rank must be 8-byte aligned");
+    if (maps) {  // the kernel writes a pixel's maps before other threads have read their inputs
+        const uintptr_t m0 = (uintptr_t)maps, m1 = m0 + (uintptr_t)B * 8 * plane * 4;
+        const uintptr_t in[3][2] = {{(uintptr_t)samples, (uintptr_t)B * K * 5 * plane * 4}, {(uintptr_t)target, (uintptr_t)B * 5 * plane * 4},
+                                    {(uintptr_t)known, (uintptr_t)B * plane * 4}};
+        for (const auto& r : in)
+            if (m0 < r[0] + r[1] && r[0] < m1) return fail(1, "ensemble_score: maps must not alias an input");
+    }
+    HIP_TRY(launch_ensemble_score(samples, target, known, lo, hi, B, K, plane, scratch, raw, member, reinterpret_cast<long long*>(rank), maps,
+                                  (hipStream_t)stream));
+    return 0;
+}
+
 int r2dm_confusion_matrix(const int64_t* pred, const int64_t* target, const float* mask, int32_t B, int64_t pixels, int32_t classes, int64_t* counts,
                           int64_t* bad, void* stream) {
     if (!pred || !target || !counts || !bad) return fail(1, "null argument");
