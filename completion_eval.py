@@ -29,7 +29,12 @@ r2dm_amd.completion.member_seed; member 0 is the single draw, on which everythin
 ``results[kind][method]["ensemble"]``: the continuous ranked probability score of range and reflectance (the mean absolute error at K = 1,
 so the interpolation baselines share the column), the rank histogram and the spread / skill ratio (calibration), the Brier score of ray
 drop, best-of-K and the errors of the consensus scan ("Ensemble scores"); ``--save_dir`` then also keeps the per-pixel
-return-probability, mean, std and median maps."""
+return-probability, mean, std and median maps.
+
+``--ensemble_coherence`` (with ``--ensemble``) also scores the members across pixels, which none of the above does: the energy score and
+the variogram score of order 0.5 over ``--coherence_offsets`` (pairs "dh,dw"; default r2dm_amd.completion.DEFAULT_OFFSETS), which tell a
+coherent draw from per-pixel noise with the same marginals (``results[kind][method]["ensemble"]["coherence"]``; DESIGN.md section 4,
+"Ensemble coherence")."""
 import json
 from argparse import SUPPRESS, ArgumentParser
 from pathlib import Path
@@ -74,7 +79,9 @@ def main(argv=None):
     from completion_demo import semseg_postprocess
     from r2dm_amd import completion
 
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    coherence = coherence_settings(parser, args)
     if (args.real_scans is None) == (args.real_dir is None):
         raise SystemExit("give one of --real_scans DIR / --real_dir DIR")
     kinds = list(dict.fromkeys(args.corruption or ["beams:4"]))
@@ -103,7 +110,7 @@ def main(argv=None):
                                          chamfer=args.chamfer, fscore_threshold=args.fscore_threshold, ddnm_resample_steps=args.ddnm_resample_steps,
                                          ddnm_init=None if args.ddnm_init == "none" else args.ddnm_init, ddnm_t_start=args.ddnm_t_start,
                                          **{**dpmpp, "dpmpp_init": None if dpmpp["dpmpp_init"] == "none" else dpmpp["dpmpp_init"]},
-                                         **({"ensemble": args.ensemble} if hasattr(args, "ensemble") else {}))
+                                         **({"ensemble": args.ensemble} if hasattr(args, "ensemble") else {}), **coherence)
     results, kept = out if args.save_dir is not None else (out, None)
     info = {"ckpt": str(args.ckpt), "source": str(args.real_scans if args.real_scans is not None else args.real_dir), "num_scans": len(files),
             "resolution": list(cfg.data.resolution), "corruptions": kinds, "methods": list(args.methods), "num_steps": args.num_steps,
@@ -118,6 +125,8 @@ def main(argv=None):
         info.update(dpmpp)
     if hasattr(args, "ensemble"):
         info["ensemble"] = args.ensemble
+    if coherence:
+        info["ensemble_coherence"] = True
     doc = completion.jsonable({"info": info, "results": results})
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     with open(args.out, "w") as f:
@@ -140,7 +149,9 @@ def main(argv=None):
                 e = entry["ensemble"]
                 print(f"{'':>20} {'':>8}  {e['members']} members: CRPS depth {e['micro']['crps_depth']:.4f} m, spread / skill "
                       f"{e['micro']['spread_skill_depth']:.3f}, Brier {e['micro']['brier_return']:.4f}, best-of-K MAE {e['micro']['best_mae_depth']:.4f} m, "
-                      f"consensus MAE {e['consensus']['micro']['mae_depth']:.4f} m")
+                      f"consensus MAE {e['consensus']['micro']['mae_depth']:.4f} m"
+                      + (f", energy depth {e['coherence']['macro']['energy_depth']:.4f} m, variogram depth "
+                         f"{e['coherence']['micro']['variogram_total_depth']:.4f} m" if "coherence" in e else ""))
     print(f"{len(files)} scans -> {args.out}")
     return doc
 
@@ -151,6 +162,32 @@ DPMPP_DEFAULTS = {"dpmpp_eta": 1.0, "dpmpp_order": 2, "dpmpp_init": "none", "dpm
 def dpmpp_settings(args):
     """the dpmpp method's settings of parsed arguments, the defaults where an option was not given"""
     return {name: getattr(args, name, default) for name, default in DPMPP_DEFAULTS.items()}
+
+
+def parse_offsets(text):
+    """``"0,1 0,2 1,0"`` -> ((0, 1), (0, 2), (1, 0)); ValueError for anything else"""
+    out = []
+    for item in str(text).split():
+        parts = item.split(",")
+        if len(parts) != 2:
+            raise ValueError(f"an offset is dh,dw, got {item!r}")
+        out.append((int(parts[0]), int(parts[1])))
+    return tuple(out)
+
+
+def coherence_settings(parser, args):
+    """the keyword arguments of ``evaluate_completion`` behind --ensemble_coherence / --coherence_offsets: none when the option is not given"""
+    on, offsets = hasattr(args, "ensemble_coherence"), getattr(args, "coherence_offsets", None)
+    if (on or offsets is not None) and not hasattr(args, "ensemble"):
+        parser.error("--ensemble_coherence scores the members of an ensemble: give --ensemble K as well")
+    if offsets is not None and not on:
+        parser.error("--coherence_offsets goes with --ensemble_coherence")
+    if not on:
+        return {}
+    try:
+        return {"ensemble_coherence": True, "coherence_offsets": None if offsets is None else parse_offsets(offsets)}
+    except ValueError as e:
+        parser.error(f"--coherence_offsets: {e}")
 
 
 def build_parser():
@@ -191,6 +228,10 @@ def build_parser():
     parser.add_argument("--ensemble", type=int, default=SUPPRESS, metavar="K",  # (an attribute of the parsed arguments only when given)
                         help="draw K members per scan with every stochastic method and score them as an ensemble: CRPS, rank histogram, "
                              "spread against skill, Brier score of ray drop, best-of-K, the consensus scan (--save_dir keeps the per-pixel maps)")
+    parser.add_argument("--ensemble_coherence", action="store_true", default=SUPPRESS,  # (attributes only when given, as --ensemble)
+                        help="with --ensemble: also the energy score and the variogram score of the members across pixels (a draw's spatial coherence)")
+    parser.add_argument("--coherence_offsets", type=str, default=SUPPRESS, metavar='"DH,DW ..."',
+                        help='the pixel offsets of the variogram score, e.g. "0,1 0,2 1,0" (default: r2dm_amd.completion.DEFAULT_OFFSETS)')
     parser.add_argument("--save_dir", type=Path, default=None, help="also write the tensors behind the numbers, one .pt file per corruption")
     parser.add_argument("--out", type=str, default="completion.json")
     return parser

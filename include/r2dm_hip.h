@@ -522,7 +522,30 @@ int r2dm_crf_iter(const float* q_in, const float* unary, const float* xyz, const
  *    atomics): the same bits on every call, and a scan's numbers do not depend on the batch.  scratch: the bytes the _scratch_bytes
  *    function returns for (batch, members, plane) (0 for an empty or oversized problem); scratch, raw, member and rank 8-byte aligned; the
  *    fp32 pointers 16-byte aligned when plane is a multiple of 4, else 4-byte aligned.  Limits: batch <= 65535, 1 <= members <= 64,
- *    plane <= 2^40, samples of at most 2^40 elements. */
+ *    plane <= 2^40, samples of at most 2^40 elements.
+ * r2dm_ensemble_coherence: the same ensemble scored across pixels -- what the energy score and the variogram score are made of.  samples
+ *    (batch,members,5,height,width), target, known, lo, hi, U, G, E as for r2dm_ensemble_score.  Per channel c (0 depth, 1 reflectance)
+ *    the values v_i, i in [0, K]: for i < K member i's (depth d if lo < d < hi, else 0; reflectance as stored, NaN read as 0), v_K the
+ *    target's, as stored.  Every fp32 value is widened to fp64 first.
+ *    counts (batch,2) fp64 = |U|, |E|.
+ *    dist NULL or (batch,2,K+1,K+1) fp64: dist[b][c][i][j] = sum over E of (v_i - v_j)^2, in the difference form; the full matrix, the
+ *      diagonal an exact 0, [i][j] and [j][i] equal bit for bit.
+ *    vario NULL or (batch,2,offsets,4) fp64, the variogram of order 0.5: for offset (dh, dw) over the ordered pairs p = (h, w) in E,
+ *      q = (h + dh, (w + dw) mod width) in E with 0 <= h + dh < height (azimuth wraps, elevation does not), with
+ *      a = sqrt|v_K at p - v_K at q| and m = (1/K) sum_k sqrt|v_k at p - v_k at q| (members added in member order, IEEE fp64 sqrt):
+ *      the number of pairs, sum (a - m)^2, sum a^2, sum m^2.
+ *    offsets_hw: a HOST pointer to (offsets,2) int32 (dh, dw), read before the call returns.  A part whose pointer is NULL is skipped.
+ *    No float atomics: per-block partials are added in index order by a second kernel, their number depends on (height, width) alone --
+ *    the same bits on every call, a scan's numbers do not depend on the batch.  The order in which pixels enter dist[i][j] does not
+ *    depend on (i, j): permuting the members permutes the rows and columns of dist bit for bit (vario is not promised to be invariant).
+ *    scratch: the bytes the _scratch_bytes function returns (0 for an empty or oversized problem); scratch, counts, dist and vario 8-byte
+ *    aligned, the fp32 pointers as for r2dm_ensemble_score.  Limits: batch <= 65535, 1 <= members <= 64, height, width >= 1,
+ *    height * width < 2^31, 0 <= offsets <= 16, every offset with |dh| < height, |dw| < width and not both 0, samples of at most 2^40
+ *    elements. */
+size_t r2dm_ensemble_coherence_scratch_bytes(int32_t batch, int32_t members, int32_t height, int32_t width, int32_t offsets);
+int r2dm_ensemble_coherence(const float* samples, const float* target, const float* known, float lo, float hi, int32_t batch, int32_t members,
+                            int32_t height, int32_t width, const int32_t* offsets_hw, int32_t offsets, void* scratch, double* counts,
+                            double* dist, double* vario, void* stream);
 size_t r2dm_ensemble_score_scratch_bytes(int32_t batch, int32_t members, int64_t plane);
 int r2dm_ensemble_score(const float* samples, const float* target, const float* known, float lo, float hi, int32_t batch, int32_t members,
                         int64_t plane, void* scratch, double* raw, double* member, int64_t* rank, float* maps, void* stream);

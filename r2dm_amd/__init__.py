@@ -22,8 +22,8 @@ from .postproc import CRFRNN, KNN
 from . import loss  # noqa: E402  (the denoising loss over noise levels)
 from .loss import loss_curve
 from . import completion  # noqa: E402  (completion metrics: range / reflectance error, IoU, interpolation baselines)
-from .completion import (aggregate_ensemble, completion_errors, confusion_matrix, corruption_mask, ensemble_consensus, ensemble_scores,
-                         evaluate_completion, fill_beams, iou_from_confusion, member_seed)
+from .completion import (aggregate_coherence, aggregate_ensemble, completion_errors, confusion_matrix, corruption_mask, ensemble_coherence,
+                         ensemble_consensus, ensemble_scores, evaluate_completion, fill_beams, iou_from_confusion, member_seed)
 from . import geometry  # noqa: E402  (Chamfer distance, F-score, COV / MMD / 1-NNA on a HIP nearest-neighbour search)
 from .geometry import chamfer_from_sums, chamfer_sums, emd_pairs, nearest_neighbors, pairwise_chamfer, pairwise_emd, set_metrics
 from . import latent  # noqa: E402  (DDIM inversion's transfer kernel, slerp, latent interpolation and reconstruction)
@@ -38,6 +38,7 @@ __all__ = [
     "KNN", "CRFRNN", "loss_curve",
     "corruption_mask", "completion_errors", "confusion_matrix", "iou_from_confusion", "fill_beams", "evaluate_completion",
     "ensemble_scores", "ensemble_consensus", "aggregate_ensemble", "member_seed",
+    "ensemble_coherence", "aggregate_coherence",
     "nearest_neighbors", "chamfer_sums", "chamfer_from_sums", "pairwise_chamfer", "set_metrics",
     "emd_pairs", "pairwise_emd",
     "ddim_transfer", "slerp", "interpolate", "reconstruct",

@@ -158,6 +158,8 @@ SIGNATURES = {
     "r2dm_completion_error": (c_int32, [_P, _P, _P, c_float, c_float, c_int32, c_int64, _P, _P, _P]),
     "r2dm_ensemble_score_scratch_bytes": (c_size_t, [c_int32, c_int32, c_int64]),
     "r2dm_ensemble_score": (c_int32, [_P, _P, _P, c_float, c_float, c_int32, c_int32, c_int64, _P, _P, _P, _P, _P, _P]),
+    "r2dm_ensemble_coherence_scratch_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "r2dm_ensemble_coherence": (c_int32, [_P, _P, _P, c_float, c_float, c_int32, c_int32, c_int32, c_int32, _P, c_int32, _P, _P, _P, _P, _P]),
     "r2dm_confusion_matrix": (c_int32, [_P, _P, _P, c_int32, c_int64, c_int32, _P, _P, _P]),
     "r2dm_fill_beams": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_float, c_int32, _P]),
     "r2dm_nn_pairs_scratch_bytes": (c_size_t, [c_int64, c_int64]),

@@ -12,6 +12,8 @@ linear interpolation of the known beams.  The reference has no code for it.  Her
 - ``ensemble_scores``      K completions per scan scored as an ensemble (``r2dm_ensemble_score``): CRPS, the rank histogram, spread against
   skill, the Brier score of ray drop, best-of-K and per-pixel return probability / mean / std / median maps; ``ensemble_consensus`` turns the
   maps into one scan, ``aggregate_ensemble`` sums over scans, ``member_seed`` seeds member k of scan i.
+- ``ensemble_coherence``   the same K completions scored across pixels (``r2dm_ensemble_coherence``): the energy score and the variogram
+  score, which tell a coherent draw from per-pixel noise with the same marginals; ``aggregate_coherence`` averages over scans.
 - ``evaluate_completion``  corrupt, complete (RePaint, the data-consistent sampler ``ddpm.complete``, the same on DPM-Solver++(2M), ``ddpm.complete_dpm``, or a baseline), score; ``completion_eval.py`` is its command line.
 
 A pixel is a *return* when its metric depth lies strictly inside ``(lo, hi)``; any other depth, NaN included, is "no return".  The errors
@@ -40,6 +42,10 @@ ENSEMBLE_DERIVED_NAMES = ("crps_depth", "crps_fair_depth", "mae_depth_members", 
                           "false_return_rate")
 ENSEMBLE_MAP_NAMES = ("return_probability", "depth_mean", "depth_std", "depth_median", "depth_min", "depth_max", "reflectance_mean",
                       "reflectance_std")
+COHERENCE_DERIVED_NAMES = tuple(stem + "_" + name for name in ("depth", "reflectance") for stem in (
+    "energy", "energy_fair", "member_rmse", "best_rmse", "diversity", "spread_skill_energy", "variogram", "variogram_total", "variogram_rel"))
+DEFAULT_OFFSETS = ((0, 1), (0, 2), (0, 4), (0, 8), (1, 0), (2, 0), (1, 1), (1, -1))  # (dh, dw): along a beam, across beams, the diagonals
+MAX_OFFSETS = 16
 MAX_MEMBERS = 64
 STOCHASTIC_METHODS = ("repaint", "ddnm", "dpmpp")
 FILL_MODES = {"nearest": 0, "linear": 1}
@@ -261,6 +267,139 @@ def aggregate_ensemble(raw: torch.Tensor, member: torch.Tensor, rank: torch.Tens
     return out
 
 
+# ---- ensemble coherence: the energy score and the variogram score, across pixels ----------------------------------------------------------
+def _check_offsets(offsets, H: int, W: int):
+    out = []
+    for o in offsets:
+        try:
+            dh, dw = (int(v) for v in o)
+            if (dh, dw) != tuple(o):
+                raise TypeError
+        except (TypeError, ValueError):
+            raise ValueError(f"an offset is a pair of integers (dh, dw), got {o!r}") from None
+        if (dh, dw) == (0, 0) or abs(dh) >= H or abs(dw) >= W:
+            raise ValueError(f"offset {(dh, dw)} must satisfy |dh| < {H}, |dw| < {W} and not be (0, 0)")
+        out.append((dh, dw))
+    if len(out) > MAX_OFFSETS:
+        raise ValueError(f"at most {MAX_OFFSETS} offsets, got {len(out)}")
+    return tuple(out)
+
+
+def ensemble_coherence_sums(samples: torch.Tensor, target: torch.Tensor, known: torch.Tensor, lo: float, hi: float, offsets=None):
+    """``r2dm_ensemble_coherence`` on the device: ``samples`` (B,K,5,H,W) -> ``(counts (B,2), dist (B,2,K+1,K+1), vario (B,2,O,4), offsets)``,
+    float64.  ``offsets``: pairs (dh, dw) with |dh| < H, |dw| < W, not (0, 0), at most 16 (an invalid one is a ``ValueError``); None: the
+    members of ``DEFAULT_OFFSETS`` that are valid for (H, W), possibly none.  The offsets used are returned as a tuple."""
+    _lib.require_gpu(samples, "samples")
+    if samples.dim() != 5 or samples.shape[2] != 5:
+        raise ValueError(f"samples {tuple(samples.shape)} must be (B,K,5,H,W): K members per scan in the layout [depth, x, y, z, reflectance]")
+    B, K, _, H, W = samples.shape
+    if not 1 <= K <= MAX_MEMBERS:
+        raise ValueError(f"an ensemble has 1 to {MAX_MEMBERS} members, got {K}")
+    if tuple(target.shape) != (B, 5, H, W) or tuple(known.shape) != (B, 1, H, W):
+        raise ValueError(f"target {tuple(target.shape)} must be {(B, 5, H, W)} and known {tuple(known.shape)} {(B, 1, H, W)}")
+    if H < 1 or W < 1:
+        raise ValueError(f"scans of {H}x{W}: sizes must be >= 1")
+    if offsets is None:
+        offsets = tuple((dh, dw) for dh, dw in DEFAULT_OFFSETS if abs(dh) < H and abs(dw) < W)
+    else:
+        offsets = _check_offsets(offsets, H, W)
+    n = len(offsets)
+    dev = samples.device
+    samples, target, known = _lib.f32c(samples), _lib.f32c(target.to(dev)), _lib.f32c(known.to(dev))
+    counts = torch.empty(B, 2, dtype=torch.float64, device=dev)
+    dist = torch.empty(B, 2, K + 1, K + 1, dtype=torch.float64, device=dev)
+    vario = torch.empty(B, 2, n, 4, dtype=torch.float64, device=dev)
+    if B == 0:
+        return counts, dist, vario, offsets
+    L = _lib.lib()
+    nbytes = L.r2dm_ensemble_coherence_scratch_bytes(B, K, H, W, n)
+    if nbytes == 0:
+        raise _lib.R2DMError(f"ensemble_coherence: empty or oversized problem (B={B}, K={K}, {H}x{W}, {n} offsets)")
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    import ctypes
+
+    host = (ctypes.c_int32 * (2 * max(n, 1)))(*[v for o in offsets for v in o])
+    with torch.cuda.device(dev):
+        _lib.check(L.r2dm_ensemble_coherence(_lib.ptr(samples), _lib.ptr(target), _lib.ptr(known), float(lo), float(hi), B, K, H, W,
+                                             ctypes.cast(host, ctypes.c_void_p), n, _lib.ptr(scratch), _lib.ptr(counts), _lib.ptr(dist),
+                                             _lib.ptr(vario) if n else None, _lib.stream_ptr(dev)))
+    return counts, dist, vario, offsets
+
+
+def derived_coherence(counts: torch.Tensor, dist: torch.Tensor, vario: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """(...,2) counts, (...,2,K+1,K+1) squared distances between the K members and, as row K, the target, (...,2,O,4) variogram sums -> the
+    derived values (``COHERENCE_DERIVED_NAMES``), NaN where a denominator is 0.  With D_ij = sqrt(dist[i][j]), per channel:
+    ``energy`` = [(1/K) sum_k D_kK - (1/(2 K^2)) sum_{k != l} D_kl] / sqrt|E| (``energy_fair``: 1/(2 K (K - 1)) on the second term, NaN at
+    K = 1), both sums over the roots sorted ascending, so the same bits under any permutation of the members; at K = 1 it is
+    ``completion_errors``' ``rmse``.  ``member_rmse`` (...,K) = D_kK / sqrt|E|, ``best_rmse`` its least; ``diversity`` = the mean over k < l of
+    D_kl / sqrt|E| (NaN at K = 1); ``spread_skill_energy`` = the mean pair distance over the mean distance to the target, 1 when the truth is
+    exchangeable with the members.  ``variogram`` (...,O) = sum (a - m)^2 / pairs per offset, ``variogram_total`` the same over all
+    offsets, ``variogram_rel`` = sum (a - m)^2 / sum a^2 over all offsets."""
+    counts, dist, vario = counts.double(), dist.double(), vario.double()
+    K = dist.shape[-1] - 1
+    E = counts[..., 1]
+    nan = torch.full_like(E, math.nan)
+    rootE = E.sqrt()
+    out = {}
+    for c, name in enumerate(("depth", "reflectance")):
+        d = dist[..., c, :, :]
+        to_target = d[..., :K, K].sqrt().sort(dim=-1).values                    # (...,K) ascending
+        pairs = d[..., :K, :K].sqrt().flatten(-2).sort(dim=-1).values.sum(-1)   # both orders of every pair; the K diagonal zeros add nothing
+        skill = to_target.sum(-1) / K
+        out["energy_" + name] = _ratio(skill - pairs / (2 * K * K), rootE)
+        out["energy_fair_" + name] = _ratio(skill - pairs / (2 * K * (K - 1)), rootE) if K > 1 else nan
+        rmse = _ratio(d[..., :K, K], E[..., None].expand(d[..., :K, K].shape)).sqrt()
+        out["member_rmse_" + name] = rmse
+        out["best_rmse_" + name] = rmse.min(dim=-1).values
+        between = _ratio(d[..., :K, :K], E[..., None, None].expand(d[..., :K, :K].shape)).sqrt().flatten(-2).sort(dim=-1).values.sum(-1)
+        out["diversity_" + name] = between / (K * (K - 1)) if K > 1 else nan
+        out["spread_skill_energy_" + name] = _ratio(out["diversity_" + name], rmse.sort(dim=-1).values.sum(-1) / K) if K > 1 else nan
+        v = vario[..., c, :, :]
+        out["variogram_" + name] = _ratio(v[..., 1], v[..., 0])
+        out["variogram_total_" + name] = _ratio(v[..., 1].sum(-1), v[..., 0].sum(-1))
+        out["variogram_rel_" + name] = _ratio(v[..., 1].sum(-1), v[..., 2].sum(-1))
+    return {name: out[name] for name in COHERENCE_DERIVED_NAMES}
+
+
+def ensemble_coherence(samples: torch.Tensor, target: torch.Tensor, known: torch.Tensor, lo: float, hi: float, offsets=None) -> dict:
+    """K completions per scan scored across pixels, where ``ensemble_scores`` scores each pixel alone: shuffle the members independently
+    at every pixel and every score of ``ensemble_scores`` keeps its bits, while the energy score rises and the variogram score rises by an
+    order of magnitude.  Arguments as for ``ensemble_scores``; ``offsets`` as for ``ensemble_coherence_sums`` -> a dict: ``counts`` (B,2)
+    [|U|, |E|], ``dist`` (B,2,K+1,K+1), ``vario`` (B,2,O,4) [pairs, sum (a - m)^2, sum a^2, sum m^2], ``offsets`` (the tuple used) and
+    the values of ``derived_coherence`` under ``COHERENCE_DERIVED_NAMES``."""
+    counts, dist, vario, used = ensemble_coherence_sums(samples, target, known, lo, hi, offsets)
+    res = {"counts": counts, "dist": dist, "vario": vario, "offsets": used}
+    res.update(derived_coherence(counts, dist, vario))
+    return res
+
+
+def aggregate_coherence(counts: torch.Tensor, dist: torch.Tensor, vario: torch.Tensor, offsets) -> dict:
+    """Per-scan (N,2), (N,2,K+1,K+1), (N,2,O,4) -> ``{"counts", "offsets", "sums", "micro", "macro"}``.  ``macro``: the mean of the per-scan
+    derived values, ignoring the NaN ones (a value with one entry per member or per offset: entry by entry).  The energy-score family --
+    per-scan norms, not additive -- appears there only; ``micro`` holds the variogram values of the sums over all scans and ``sums`` those
+    sums, per channel (O,3) [sum (a - m)^2, sum a^2, sum m^2]; ``counts["pairs"]`` is per offset."""
+    dist = torch.as_tensor(dist).detach().cpu().double()
+    K = dist.shape[-1] - 1
+    dist = dist.reshape(-1, 2, K + 1, K + 1)
+    vario = torch.as_tensor(vario).detach().cpu().double()
+    O = vario.shape[-2]
+    vario, counts = vario.reshape(-1, 2, O, 4), torch.as_tensor(counts).detach().cpu().double().reshape(-1, 2)
+    total = vario.sum(0)
+    out = {"counts": {"scans": int(counts.shape[0]), "members": int(K), "unknown": int(counts[:, 0].sum().item()),
+                      "evaluated": int(counts[:, 1].sum().item()), "pairs": [int(v) for v in total[0, :, 0].tolist()]},
+           "offsets": [[int(dh), int(dw)] for dh, dw in offsets],
+           "sums": {name: total[c, :, 1:].tolist() for c, name in enumerate(("depth", "reflectance"))}, "micro": {}, "macro": {}}
+    micro = derived_coherence(counts.sum(0), torch.zeros(2, K + 1, K + 1, dtype=torch.float64), total)
+    for name, v in micro.items():
+        if name.startswith("variogram"):
+            out["micro"][name] = v.tolist() if v.dim() else v.item()
+    for name, v in derived_coherence(counts, dist, vario).items():
+        ok = ~v.isnan()
+        mean = torch.where(ok, v, torch.zeros_like(v)).sum(0) / ok.sum(0)  # 0 / 0 = NaN where no scan has the value
+        out["macro"][name] = mean.tolist() if mean.dim() else mean.item()
+    return out
+
+
 # ---- labels ------------------------------------------------------------------------------------------------------------------------------
 def confusion_matrix(pred: torch.Tensor, target: torch.Tensor, num_classes: int, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """int64 (B,C,C) counts ``[b][target][pred]`` of two int64 label tensors (B,...) over the pixels whose ``mask`` (same shape, None: all)
@@ -384,7 +523,8 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
                         semseg_postprocess=None, lo: Optional[float] = None, hi: Optional[float] = None, keep: bool = False,
                         chamfer: bool = False, fscore_threshold: float = 0.2, ddnm_resample_steps: int = 1, ddnm_init: Optional[str] = None,
                         ddnm_t_start: float = 1.0, dpmpp_eta: float = 1.0, dpmpp_order: int = 2, dpmpp_init: Optional[str] = None,
-                        dpmpp_t_start: float = 1.0, ensemble: Optional[int] = None):
+                        dpmpp_t_start: float = 1.0, ensemble: Optional[int] = None, ensemble_coherence: bool = False,
+                        coherence_offsets=None):
     """Corrupt, complete and score ``planes`` (N,6,H,W), the masked planes of ``project_scans(layout="xyzrdm", apply_mask=True)`` at the
     model's resolution, on the GPU.
 
@@ -420,7 +560,12 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
     ``"ensemble"``: ``{"members", **aggregate_ensemble(...), "consensus"}`` with ``consensus`` the ``aggregate_errors`` of
     ``ensemble_consensus`` (median depth where at least half of the members return, mean reflectance); ``kept[kind]["ensemble"][method]`` =
     ``{"raw" (N,13), "member" (N,2,K), "rank" (N,K+1), "consensus_raw" (N,10), "maps" (N,8,H,W), "x_out" (N,K,2,H,W) or None}``.  None
-    (the default): nothing of this is computed, and keys and numbers are what they were."""
+    (the default): nothing of this is computed, and keys and numbers are what they were.
+
+    ``ensemble_coherence=True`` (with ``ensemble``; without it a ``ValueError``): the members are also scored across pixels
+    (``ensemble_coherence_sums`` with ``coherence_offsets``, None: ``DEFAULT_OFFSETS``): every entry's ``"ensemble"`` gains ``"coherence"``
+    = ``aggregate_coherence(...)`` (energy score, variogram score, diversity) and ``kept[kind]["ensemble"][method]`` gains ``"counts"``
+    (N,2), ``"dist"`` (N,2,K+1,K+1), ``"vario"`` (N,2,O,4) and ``"offsets"``.  False (the default): none of it is computed."""
     from . import geometry
     from .inference import setup_rng
     from .projection import known_from_scan
@@ -447,6 +592,8 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
         raise ValueError(f"dpmpp_eta must be finite and >= 0, got {dpmpp_eta}")
     if ensemble is not None and not (isinstance(ensemble, int) and 1 <= ensemble <= MAX_MEMBERS):
         raise ValueError(f"ensemble must be None or a number of members in [1, {MAX_MEMBERS}], got {ensemble!r}")
+    if ensemble_coherence and ensemble is None:
+        raise ValueError("ensemble_coherence scores the members of an ensemble: give ensemble = K as well")
     if planes.dim() != 4 or planes.shape[1] != 6:
         raise ValueError(f"expected planes (N,6,H,W) [x, y, z, reflectance, depth, mask], got {tuple(planes.shape)}")
     _lib.require_gpu(planes, "planes")
@@ -459,6 +606,9 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
     if chamfer:
         fscore_threshold = geometry._check_tau(fscore_threshold)
     N, _, H, W = planes.shape
+    if ensemble_coherence:
+        coherence_offsets = tuple(o for o in DEFAULT_OFFSETS if abs(o[0]) < H and abs(o[1]) < W) if coherence_offsets is None \
+            else _check_offsets(coherence_offsets, H, W)
     if ("repaint" in methods or "ddnm" in methods or "dpmpp" in methods) and tuple(ddpm.sampling_shape) != (2, H, W):
         raise ValueError(f"planes of {H}x{W} for a model that samples {tuple(ddpm.sampling_shape)}: RePaint needs a depth + reflectance model "
                          "at the planes' resolution")
@@ -545,6 +695,7 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
                 entry["geometry"] = {where: geometry.aggregate_chamfer(r) for where, r in graw.items()}
             if ensemble is not None:
                 eraw, emember, erank, emaps, craw = [], [], [], [], []
+                ccounts, cdist, cvario = [], [], []
                 for k in range(0, N, batch_size):
                     if x_members is None or members == 1:
                         samples = pred[k:k + batch_size, None]
@@ -555,6 +706,9 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
                     craw.append(completion_error_sums(ensemble_consensus(maps, lidar_utils), target[k:k + batch_size], mask[k:k + batch_size],
                                                       lo, hi).cpu())
                     eraw.append(r.cpu()), emember.append(m.cpu()), erank.append(h.cpu())
+                    if ensemble_coherence:
+                        cc, cd, cv, _ = ensemble_coherence_sums(samples, target[k:k + batch_size], mask[k:k + batch_size], lo, hi, coherence_offsets)
+                        ccounts.append(cc.cpu()), cdist.append(cd.cpu()), cvario.append(cv.cpu())
                     if keep:
                         emaps.append(maps.cpu())
                 eraw = torch.cat(eraw) if eraw else torch.empty(0, len(ENSEMBLE_RAW_NAMES), dtype=torch.float64)
@@ -562,6 +716,11 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
                 erank = torch.cat(erank) if erank else torch.empty(0, members + 1, dtype=torch.int64)
                 craw = torch.cat(craw) if craw else torch.empty(0, len(RAW_NAMES), dtype=torch.float64)
                 entry["ensemble"] = {"members": members, **aggregate_ensemble(eraw, emember, erank), "consensus": aggregate_errors(craw)}
+                if ensemble_coherence:
+                    ccounts = torch.cat(ccounts) if ccounts else torch.empty(0, 2, dtype=torch.float64)
+                    cdist = torch.cat(cdist) if cdist else torch.empty(0, 2, members + 1, members + 1, dtype=torch.float64)
+                    cvario = torch.cat(cvario) if cvario else torch.empty(0, 2, len(coherence_offsets), 4, dtype=torch.float64)
+                    entry["ensemble"]["coherence"] = aggregate_coherence(ccounts, cdist, cvario, coherence_offsets)
             results[kind][method] = entry
             if keep:
                 if ensemble is not None:
@@ -569,6 +728,8 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
                         "raw": eraw, "member": emember, "rank": erank, "consensus_raw": craw,
                         "maps": torch.cat(emaps) if emaps else torch.empty(0, len(ENSEMBLE_MAP_NAMES), H, W),
                         "x_out": None if x_members is None else x_members.cpu()}
+                    if ensemble_coherence:
+                        kept[kind]["ensemble"][method].update(counts=ccounts, dist=cdist, vario=cvario, offsets=coherence_offsets)
                 kept[kind]["x_out"][method] = None if x_out is None else x_out.cpu()
                 kept[kind]["pred"][method] = pred.cpu()
                 kept[kind]["raw"][method] = raw

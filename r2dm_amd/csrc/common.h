@@ -384,6 +384,10 @@ hipError_t launch_fill_beams(const float* x, const unsigned char* rows, float* o
 size_t ensemble_score_scratch_bytes(int B, int K, long plane);
 hipError_t launch_ensemble_score(const float* samples, const float* target, const float* known, float lo, float hi, int B, int K, long plane,
                                  void* scratch, double* raw, double* member, long long* rank, float* maps, hipStream_t s);
+// ... and its coherence across pixels: counts (B,2), dist (B,2,K+1,K+1) or null, vario (B,2,offsets,4) or null; offsets_hw (offsets,2) on the host
+size_t ensemble_coherence_scratch_bytes(int B, int K, long plane, int offsets);
+hipError_t launch_ensemble_coherence(const float* samples, const float* target, const float* known, float lo, float hi, int B, int K, int H, int W,
+                                     const int* offsets_hw, int offsets, void* scratch, double* counts, double* dist, double* vario, hipStream_t s);
 
 // geometry metrics (geometry.hip): nearest neighbours of P pairs of ragged clouds in both directions -- optional per-point d^2 / index, always
 // sums (P,8) = [sum d^2, sum d, #{d <= tau}] a -> b, the same b -> a, |a|, |b|; status[2] = non-finite points met, pairs that do not check out

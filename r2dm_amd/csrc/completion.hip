@@ -7,6 +7,8 @@
 //                            merged into int64 counts by integer atomics (the scheme of metrics.hip's bev_hist_kernel): exact in any order.
 //  ensemble_score_kernel     K completions of a scan scored as an ensemble: per scan thirteen float64 sums (CRPS, spread, Brier score), the
 //                            per-member errors, the rank histogram and per-pixel maps; the K members of a pixel sorted in registers.
+//  coherence_dist_kernel     the same ensemble across pixels: per scan and channel the float64 squared distances between the K members and the
+//  coherence_vario_kernel    target (the energy score), and per pixel offset the sums of the variogram score of order 0.5; fixed order.
 //  fill_beams_kernel         the baselines: an unknown beam (image row) from the nearest known beam above and below it, nearest or linear.
 #include "common.h"
 #include "wave_ops.h"
@@ -391,6 +393,286 @@ hipError_t launch_ensemble_score(const float* samples, const float* target, cons
         e = ensemble_launch<64>(samples, target, known, part, rank, maps, plane, K, lo, hi, grid, s);
     if (e != hipSuccess) return e;
     ensemble_finalize_kernel<<<B, kEnsThreads, 0, s>>>(part, raw, member, blocks, K);
+    return hipGetLastError();
+}
+
+// ---- ensemble coherence ----------------------------------------------------------------------------------------------------------------
+// The scores above are per pixel: they cannot tell a coherent draw from one whose pixels were shuffled among the members.  These two can.
+// samples, target, known, lo, hi, U, G, E as above; the K + 1 "rows" of a channel are the K members and, as row K, the target.  A member's
+// depth is d if lo < d < hi, else 0; a member's reflectance as stored, NaN read as 0; the target's values as stored (its depth is a return
+// on E).  Everything is widened to float64 first, so every difference is exact.
+//   counts[2]             |U|, |E|
+//   dist[2][K+1][K+1]     sum over E of (v_i - v_j)^2, the difference form (a Gram form cancels when members are close)
+//   vario[2][offsets][4]  per offset (dh, dw), over the ordered pairs p = (h, w) in E, q = (h + dh, (w + dw) mod W) in E with 0 <= h + dh < H:
+//                         the pairs, sum (a - m)^2, sum a^2, sum m^2 with a = sqrt|v_K(p) - v_K(q)| and m = (1/K) sum_k sqrt|v_k(p) - v_k(q)|,
+//                         members added in member order
+// coherence_dist_kernel: the rows in tiles of 8, one wave per (channel, pair of tiles ti <= tj, slab): pixels across the lanes (pixel = slab
+// * 64 + lane, then in steps of slabs * 64), 16 loads per pixel (8 on a diagonal pair), 64 float64 accumulators per lane, a pixel outside E
+// enters as zeros (its mask ANDed into the loaded bits: no branch, every load issued); a row past K re-loads row K and is never written out.  At the end the wave reduces its accumulators
+// eight at a time (wave_sum8_scatter) into part[b][slab][channel][pair][64].  The order in which pixels enter a sum -- lane, exchange tree,
+// slabs in index order in the finalize kernel -- is the same for every (i, j): permuting the members permutes rows and columns bit for bit.
+// A diagonal pair computes (i, j) and (j, i) from terms with equal bits; an off-diagonal pair is written to both places.
+// coherence_vario_kernel: one thread per pixel p, one block row per offset (grid.y); also the two counts.  thread -> wave -> the block's
+// four waves -> part[b][offset][block][9]; the finalize kernel adds a scan's blocks in index order.  Slabs and blocks depend on the plane
+// alone.  No float atomics anywhere.
+constexpr int kCohTile = 8;
+constexpr int kCohMaxSlabs = 256;      // waves per scan, channel and tile pair: 256 x 64 pixels per pass
+constexpr int kCohSlabPixels = 1024;   // ... and at least this many pixels each, so the end-of-wave reduction is paid once per 16 pixels a lane
+constexpr int kCohValues = 9;          // |U|, |E|, pairs, then per channel sum (a - m)^2, sum a^2, sum m^2
+constexpr int kCohMaxOffsets = 16;
+constexpr int kCohThreads = 256;
+constexpr int kCohMaxBlocks = 512;
+struct CohOffsets {
+    int dh[kCohMaxOffsets], dw[kCohMaxOffsets];
+};
+static int coherence_slabs(long plane) {
+    const long n = (plane + kCohSlabPixels - 1) / kCohSlabPixels;
+    return n < 1 ? 1 : n > kCohMaxSlabs ? kCohMaxSlabs : (int)n;
+}
+static int coherence_blocks(long plane) {
+    const long n = (plane + kCohThreads - 1) / kCohThreads;
+    return n < 1 ? 1 : n > kCohMaxBlocks ? kCohMaxBlocks : (int)n;
+}
+static int coherence_tiles(int K) { return (K + 1 + kCohTile - 1) / kCohTile; }
+static size_t coherence_dist_part(int B, int K, long plane) {  // doubles
+    const int nt = coherence_tiles(K);
+    return (size_t)B * coherence_slabs(plane) * 2 * (nt * (nt + 1) / 2) * kCohTile * kCohTile;
+}
+static size_t coherence_vario_part(int B, long plane, int offsets) {
+    return (size_t)B * (offsets < 1 ? 1 : offsets) * coherence_blocks(plane) * kCohValues;
+}
+size_t ensemble_coherence_scratch_bytes(int B, int K, long plane, int offsets) {
+    return (coherence_dist_part(B, K, plane) + coherence_vario_part(B, plane, offsets)) * sizeof(double);
+}
+
+// a row's value at a pixel: channel 0 depth inside the window, else 0 (the target's is inside it wherever the value is used);
+// channel 1 reflectance, a member's NaN read as 0
+__device__ __forceinline__ float coherence_value(float v, int c, bool member, float lo, float hi) {
+    if (c == 0) return lo < v && v < hi ? v : 0.f;
+    return member && v != v ? 0.f : v;
+}
+// the same with the pixel's mask (all ones inside E, else 0) folded in as a bitwise AND: +0 outside E whatever was loaded.  Not a select of
+// the loaded value: the compiler turns that into a branch around the load and waits for each of a pixel's sixteen loads in turn.
+__device__ __forceinline__ float coherence_value_masked(float v, int c, bool member, float lo, float hi, unsigned mask) {
+    const bool window = (lo < v) & (v < hi), number = !(member & (v != v));
+    const bool keep = c == 0 ? window : number;
+    return __uint_as_float(__float_as_uint(v) & (keep ? mask : 0u));
+}
+
+__global__ __launch_bounds__(kCohThreads) void coherence_dist_kernel(const float* __restrict__ samples, const float* __restrict__ target,
+                                                                     const float* __restrict__ known, double* __restrict__ part, long plane, int K,
+                                                                     int tiles, int pairs, float lo, float hi) {
+    constexpr int T = kCohTile;
+    const int lane = threadIdx.x & 63;
+    const int job = __builtin_amdgcn_readfirstlane((int)(blockIdx.y * (kCohThreads / 64) + (threadIdx.x >> 6)));  // (channel, tile pair)
+    if (job >= 2 * pairs) return;  // (no barrier below: a wave may leave)
+    const int c = job / pairs, pair = job - c * pairs;
+    int ti = 0, rest = pair;  // pairs in the order (0,0) (0,1) .. (0,n-1) (1,1) ..
+    while (rest >= tiles - ti) rest -= tiles - ti, ++ti;
+    const int tj = ti + rest;
+    const int b = blockIdx.z, slab = blockIdx.x, slabs = gridDim.x;
+    const float* td = target + (long)b * 5 * plane;
+    const float* kn = known + (long)b * plane;
+    const float* sb = samples + (long)b * K * 5 * plane;
+    const float *pa[T], *pb[T];
+    bool ma[T], mb[T];
+#pragma unroll
+    for (int r = 0; r < T; ++r) {
+        const int i = ti * T + r, j = tj * T + r;
+        ma[r] = i < K, mb[r] = j < K;
+        pa[r] = ma[r] ? sb + ((long)i * 5 + 4 * c) * plane : td + 4L * c * plane;
+        pb[r] = mb[r] ? sb + ((long)j * 5 + 4 * c) * plane : td + 4L * c * plane;
+    }
+    double acc[T][T];
+#pragma unroll
+    for (int i = 0; i < T; ++i)
+#pragma unroll
+        for (int j = 0; j < T; ++j) acc[i][j] = 0.0;
+
+    for (long base = slab * 64L; base < plane; base += slabs * 64L) {  // uniform over the wave
+        const long pix = base + lane;
+        const bool valid = pix < plane;
+        const long at = valid ? pix : plane - 1;  // every lane loads
+        const float kv = kn[at], r0 = td[at];
+        const bool e = valid && kv == 0.f && lo < r0 && r0 < hi;
+        const unsigned em = e ? 0xffffffffu : 0u;
+        float ra[T], rb[T];  // all loads of the pixel in flight together (issuing the next pass's ahead of the arithmetic as well measured no gain)
+#pragma unroll
+        for (int r = 0; r < T; ++r) ra[r] = pa[r][at];
+        if (ti != tj) {  // uniform
+#pragma unroll
+            for (int r = 0; r < T; ++r) rb[r] = pb[r][at];
+        }
+        double x[T], y[T];
+#pragma unroll
+        for (int r = 0; r < T; ++r) x[r] = (double)coherence_value_masked(ra[r], c, ma[r], lo, hi, em);
+        if (ti != tj) {
+#pragma unroll
+            for (int r = 0; r < T; ++r) y[r] = (double)coherence_value_masked(rb[r], c, mb[r], lo, hi, em);
+        } else {
+#pragma unroll
+            for (int r = 0; r < T; ++r) y[r] = x[r];
+        }
+#pragma unroll
+        for (int i = 0; i < T; ++i)
+#pragma unroll
+            for (int j = 0; j < T; ++j) {
+                const double d = x[i] - y[j];
+                acc[i][j] = __builtin_fma(d, d, acc[i][j]);  // (the square is not rounded on its own)
+            }
+    }
+    double* out = part + ((((long)b * slabs + slab) * 2 + c) * pairs + pair) * (T * T);
+#pragma unroll
+    for (int i = 0; i < T; ++i) {
+        const double t = wave_sum8_scatter(acc[i], lane);  // lane L: the wave's total of acc[i][(L >> 3) & 7]
+        if ((lane & 7) == 0) out[i * T + (lane >> 3)] = t;
+    }
+}
+
+__global__ __launch_bounds__(kCohThreads) void coherence_dist_finalize_kernel(const double* __restrict__ part, double* __restrict__ dist, int slabs,
+                                                                              int K, int tiles, int pairs) {
+    constexpr int T = kCohTile;
+    const int R = K + 1, b = blockIdx.y;
+    const int idx = blockIdx.x * kCohThreads + threadIdx.x;
+    if (idx >= 2 * R * R) return;
+    const int c = idx / (R * R), i = (idx - c * R * R) / R, j = idx - c * R * R - i * R;
+    const int lo_ = i < j ? i : j, hi_ = i < j ? j : i;       // the pair of tiles holds (lo, hi); on a diagonal pair both orders have equal bits
+    const int ti = lo_ / T, tj = hi_ / T;
+    const int pair = ti * tiles - ti * (ti - 1) / 2 + (tj - ti);
+    const double* p = part + ((long)b * slabs * 2 + c) * pairs * (T * T) + (long)pair * (T * T) + (lo_ - ti * T) * T + (hi_ - tj * T);
+    const long stride = 2L * pairs * (T * T);
+    double s = 0.0;
+    for (int k0 = 0; k0 < slabs; k0 += 16) {  // sixteen loads in flight, added in index order
+        double v[16];
+#pragma unroll
+        for (int n = 0; n < 16; ++n) v[n] = k0 + n < slabs ? p[(long)(k0 + n) * stride] : 0.0;
+#pragma unroll
+        for (int n = 0; n < 16; ++n)
+            if (k0 + n < slabs) s += v[n];
+    }
+    dist[(long)b * 2 * R * R + idx] = i == j ? 0.0 : s;
+}
+
+__global__ __launch_bounds__(kCohThreads) void coherence_vario_kernel(const float* __restrict__ samples, const float* __restrict__ target,
+                                                                      const float* __restrict__ known, double* __restrict__ part, int H, int W, int K,
+                                                                      int offsets, CohOffsets off, float lo, float hi) {
+    __shared__ double sh[4][kCohValues];
+    const int b = blockIdx.z, o = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long plane = (long)H * W;
+    const float* sb = samples + (long)b * K * 5 * plane;
+    const float* td = target + (long)b * 5 * plane;
+    const float* kn = known + (long)b * plane;
+    const int dh = offsets ? off.dh[o] : 0, dw = offsets ? off.dw[o] : 0;
+    double acc[kCohValues];
+#pragma unroll
+    for (int j = 0; j < kCohValues; ++j) acc[j] = 0.0;
+
+    for (long base = blockIdx.x * (long)kCohThreads; base < plane; base += (long)gridDim.x * kCohThreads) {
+        const long pix = base + tid;
+        if (pix >= plane) continue;
+        const float rp = td[pix];
+        const bool u = kn[pix] == 0.f, e = u && lo < rp && rp < hi;
+        if (u) acc[0] += 1.0;
+        if (e) acc[1] += 1.0;
+        if (!e || !offsets) continue;
+        const int h = (int)(pix / W), w = (int)(pix - (long)h * W);
+        const int hq = h + dh;
+        if (hq < 0 || hq >= H) continue;
+        int wq = w + dw;  // |dw| < W
+        wq += wq < 0 ? W : 0;
+        wq -= wq >= W ? W : 0;
+        const long q = (long)hq * W + wq;
+        const float rq = td[q];
+        if (!(kn[q] == 0.f && lo < rq && rq < hi)) continue;
+        acc[2] += 1.0;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const long ch = 4L * c * plane;
+            const double a = sqrt(fabs((double)coherence_value(td[ch + pix], c, false, lo, hi) - (double)coherence_value(td[ch + q], c, false, lo, hi)));
+            double s = 0.0;
+            for (int k = 0; k < K; ++k) {  // (added in member order; unrolled by 4 the call measured 252 us instead of 189 us)
+                const float* m = sb + (long)k * 5 * plane + ch;
+                s += sqrt(fabs((double)coherence_value(m[pix], c, true, lo, hi) - (double)coherence_value(m[q], c, true, lo, hi)));
+            }
+            const double m = s / (double)K;
+            acc[3 + 3 * c] += (a - m) * (a - m);
+            acc[4 + 3 * c] += a * a;
+            acc[5 + 3 * c] += m * m;
+        }
+    }
+    {
+        double v8[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v8[j] = acc[j];
+        const double t0 = wave_sum8_scatter(v8, lane), t1 = wave_sum_f64(acc[8]);
+        if ((lane & 7) == 0) sh[wave][lane >> 3] = t0;
+        if (lane == 0) sh[wave][8] = t1;
+    }
+    __syncthreads();
+    if (tid < kCohValues)
+        part[(((long)b * gridDim.y + o) * gridDim.x + blockIdx.x) * kCohValues + tid] = ((sh[0][tid] + sh[1][tid]) + sh[2][tid]) + sh[3][tid];
+}
+
+// counts from the first offset's blocks (every offset's blocks count the same pixels), vario from each offset's
+__global__ __launch_bounds__(64) void coherence_vario_finalize_kernel(const double* __restrict__ part, double* __restrict__ counts,
+                                                                      double* __restrict__ vario, int blocks, int offsets) {
+    const int b = blockIdx.x, rows = offsets < 1 ? 1 : offsets;
+    for (int t = threadIdx.x; t < 2 + offsets * 7; t += 64) {
+        const int o = t < 2 ? 0 : (t - 2) / 7, j = t < 2 ? t : 2 + (t - 2) % 7;
+        const double* p = part + ((long)b * rows + o) * blocks * kCohValues + j;
+        double s = 0.0;
+        for (int k0 = 0; k0 < blocks; k0 += 16) {
+            double v[16];
+#pragma unroll
+            for (int n = 0; n < 16; ++n) v[n] = k0 + n < blocks ? p[(long)(k0 + n) * kCohValues] : 0.0;
+#pragma unroll
+            for (int n = 0; n < 16; ++n)
+                if (k0 + n < blocks) s += v[n];
+        }
+        if (t < 2) {
+            counts[(long)b * 2 + t] = s;
+        } else {  // part: pairs, then per channel (a - m)^2, a^2, m^2  ->  vario[b][c][o][4] = pairs, (a - m)^2, a^2, m^2
+            const int v = j - 2;  // 0 pairs, 1..3 channel 0, 4..6 channel 1
+            if (v == 0) {
+                vario[(((long)b * 2 + 0) * offsets + o) * 4] = s;
+                vario[(((long)b * 2 + 1) * offsets + o) * 4] = s;
+            } else {
+                const int c = (v - 1) / 3, n = 1 + (v - 1) % 3;
+                vario[(((long)b * 2 + c) * offsets + o) * 4 + n] = s;
+            }
+        }
+    }
+}
+
+// (arguments validated by r2dm_ensemble_coherence: 1 <= B <= 65535, 1 <= K <= 64, H, W >= 1, H * W < 2^31, 0 <= offsets <= 16, every offset
+// inside the image and not (0, 0); dist or vario may be null; offsets_hw is a host pointer)
+hipError_t launch_ensemble_coherence(const float* samples, const float* target, const float* known, float lo, float hi, int B, int K, int H, int W,
+                                     const int* offsets_hw, int offsets, void* scratch, double* counts, double* dist, double* vario, hipStream_t s) {
+    if (B < 1 || K < 1 || K > kEnsMaxMembers || H < 1 || W < 1 || offsets < 0 || offsets > kCohMaxOffsets) return hipErrorInvalidValue;
+    const long plane = (long)H * W;
+    double* dpart = static_cast<double*>(scratch);
+    double* vpart = dpart + coherence_dist_part(B, K, plane);
+    if (dist) {
+        const int tiles = coherence_tiles(K), pairs = tiles * (tiles + 1) / 2, slabs = coherence_slabs(plane);
+        const dim3 grid((unsigned)slabs, (unsigned)((2 * pairs + 3) / 4), (unsigned)B);
+        coherence_dist_kernel<<<grid, kCohThreads, 0, s>>>(samples, target, known, dpart, plane, K, tiles, pairs, lo, hi);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        const int cells = 2 * (K + 1) * (K + 1);
+        coherence_dist_finalize_kernel<<<dim3((unsigned)((cells + kCohThreads - 1) / kCohThreads), (unsigned)B), kCohThreads, 0, s>>>(dpart, dist, slabs,
+                                                                                                                                    K, tiles, pairs);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    const int used = vario ? offsets : 0;  // without vario only the counts
+    CohOffsets off = {};
+    for (int o = 0; o < used; ++o) off.dh[o] = offsets_hw[2 * o], off.dw[o] = offsets_hw[2 * o + 1];
+    const int blocks = coherence_blocks(plane);
+    coherence_vario_kernel<<<dim3((unsigned)blocks, (unsigned)(used < 1 ? 1 : used), (unsigned)B), kCohThreads, 0, s>>>(samples, target, known, vpart, H,
+                                                                                                                       W, K, used, off, lo, hi);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    coherence_vario_finalize_kernel<<<B, 64, 0, s>>>(vpart, counts, vario, blocks, used);
     return hipGetLastError();
 }
 

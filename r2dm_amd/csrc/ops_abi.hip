@@ -541,6 +541,43 @@ int r2dm_ensemble_score(const float* samples, const float* target, const float* 
     return 0;
 }
 
+static bool coherence_geometry_ok(int32_t B, int32_t K, int32_t H, int32_t W, int32_t offsets) {
+    return H >= 1 && W >= 1 && (int64_t)H * W < (1LL << 31) && offsets >= 0 && offsets <= 16 && ensemble_geometry_ok(B, K, (int64_t)H * W);
+}
+
+size_t r2dm_ensemble_coherence_scratch_bytes(int32_t B, int32_t K, int32_t H, int32_t W, int32_t offsets) {
+    return coherence_geometry_ok(B, K, H, W, offsets) ? ensemble_coherence_scratch_bytes(B, K, (long)H * W, offsets) : 0;
+}
+
+int r2dm_ensemble_coherence(const float* samples, const float* target, const float* known, float lo, float hi, int32_t B, int32_t K, int32_t H,
+                            int32_t W, const int32_t* offsets_hw, int32_t offsets, void* scratch, double* counts, double* dist, double* vario,
+                            void* stream) {
+    if (!samples || !target || !known || !scratch || !counts) return fail(1, "ensemble_coherence: null argument (only dist and vario may be null)");
+    if (B < 1 || B > 65535) return fail(1, "ensemble_coherence: batch must be in [1, 65535], got %d", B);
+    if (K < 1 || K > 64) return fail(1, "ensemble_coherence: members must be in [1, 64], got %d", K);
+    if (H < 1 || W < 1 || (int64_t)H * W >= (1LL << 31))
+        return fail(1, "ensemble_coherence: height and width must be >= 1 and height * width < 2^31, got %d x %d", H, W);
+    if (offsets < 0 || offsets > 16) return fail(1, "ensemble_coherence: offsets must be in [0, 16], got %d", offsets);
+    if (offsets > 0 && !offsets_hw) return fail(1, "ensemble_coherence: null argument (offsets_hw with %d offsets)", offsets);
+    for (int32_t o = 0; o < offsets; ++o) {
+        const int64_t dh = offsets_hw[2 * o], dw = offsets_hw[2 * o + 1];
+        if ((dh == 0 && dw == 0) || dh <= -(int64_t)H || dh >= H || dw <= -(int64_t)W || dw >= W)
+            return fail(1, "ensemble_coherence: offset %d = (%lld, %lld) must satisfy |dh| < %d, |dw| < %d and not be (0, 0)", o, (long long)dh,
+                        (long long)dw, H, W);
+    }
+    const int64_t plane = (int64_t)H * W;
+    if (!ensemble_geometry_ok(B, K, plane)) return fail(1, "ensemble_coherence: samples of more than 2^40 elements");
+    const uintptr_t a = plane % 4 == 0 ? 15 : 3;
+    if (((uintptr_t)samples | (uintptr_t)target | (uintptr_t)known) & a)
+        return fail(1, "ensemble_coherence: samples, target and known must be %d-byte aligned for a plane of %lld elements", (int)a + 1,
+                    (long long)plane);
+    if (((uintptr_t)scratch | (uintptr_t)counts | (uintptr_t)dist | (uintptr_t)vario) & 7)
+        return fail(1, "ensemble_coherence: scratch, counts, dist and vario must be 8-byte aligned");
+    HIP_TRY(launch_ensemble_coherence(samples, target, known, lo, hi, B, K, H, W, offsets_hw, offsets, scratch, counts, dist, vario,
+                                      (hipStream_t)stream));
+    return 0;
+}
+
 int r2dm_confusion_matrix(const int64_t* pred, const int64_t* target, const float* mask, int32_t B, int64_t pixels, int32_t classes, int64_t* counts,
                           int64_t* bad, void* stream) {
     if (!pred || !target || !counts || !bad) return fail(1, "null argument");
