@@ -8,6 +8,7 @@ as colours, and ``samples_bev_normal.png``, the bird's-eye views coloured by the
 reflectance] rows in scan order, r2dm_amd.pointcloud), with ``--points_ply`` also as ``.ply`` coloured by the bird's-eye views' viridis
 height map.  ``--mode dpmpp`` (extension) samples with DPM-Solver++(2M), ``ddpm.sample_dpm``, meant for ``--sampling_steps`` 16 to 32 (``--dpm_eta 1``: its stochastic member, SDE-DPM-Solver++(2M)).  Still missing from the reference's script: the mp4 (no encoder here) and the antialiased 512-pixel resize of its frames."""
 import argparse
+import json
 from pathlib import Path
 
 import torch
@@ -20,10 +21,14 @@ def main(args):
     if args.seed is not None:
         torch.manual_seed(args.seed)
     ddpm, lidar_utils, _ = r2dm_amd.setup_model(args.ckpt, device=args.device, max_batch=args.batch_size)
+    # (extension: the feature cache -- only every cache_interval-th step runs the whole U-Net; the defaults are the sampler without it)
+    cache = dict(cache_interval=args.cache_interval, cache_depth=args.cache_depth, cache_drift=args.cache_drift)
     if args.mode == "dpmpp":  # (extension: DPM-Solver++(2M), meant for 16-32 steps)
-        xs = ddpm.sample_dpm(batch_size=args.batch_size, num_steps=args.sampling_steps, return_all=True, eta=args.dpm_eta).clamp(-1, 1)
+        xs = ddpm.sample_dpm(batch_size=args.batch_size, num_steps=args.sampling_steps, return_all=True, eta=args.dpm_eta, **cache).clamp(-1, 1)
     else:
-        xs = ddpm.sample(batch_size=args.batch_size, num_steps=args.sampling_steps, mode=args.mode, return_all=True).clamp(-1, 1)
+        xs = ddpm.sample(batch_size=args.batch_size, num_steps=args.sampling_steps, mode=args.mode, return_all=True, **cache).clamp(-1, 1)
+    if args.cache_drift and args.cache_interval > 1:  # one more JSON line: how far the cached features moved between full steps, per full step and sample
+        print(json.dumps({"cache_interval": args.cache_interval, "cache_depth": args.cache_depth, "cache_drift": [[None if v != v else v for v in row] for row in ddpm.last_cache_drift.tolist()]}))
     xs = lidar_utils.denormalize(xs)
     xs[:, :, [0]] = lidar_utils.revert_depth(xs[:, :, [0]]) / lidar_utils.max_depth
     points = lidar_utils.postprocess(_last_sample_normalized(xs, lidar_utils))
@@ -90,6 +95,9 @@ def parser():
     parser.add_argument("--mode", choices=["ddpm", "ddim", "dpmpp"], default="ddpm",
                         help="dpmpp (extension): the DPM-Solver++(2M) sampler, ddpm.sample_dpm; use it with --sampling_steps 16 to 32")
     parser.add_argument("--dpm_eta", type=float, default=0.0, help="--mode dpmpp: the share of fresh noise per step (0: deterministic, 1: SDE-DPM-Solver++(2M))")
+    parser.add_argument("--cache_interval", type=int, default=1, help="feature cache (DeepCache): run the whole U-Net only every N-th step (1: no cache)")
+    parser.add_argument("--cache_depth", type=int, default=1, choices=[1, 2, 3], help="--cache_interval: the outermost U-Net levels a shallow step runs")
+    parser.add_argument("--cache_drift", action="store_true", help="--cache_interval: print the drift of the cached features as one more JSON line")
     parser.add_argument("--batch_size", type=int, default=1)
     parser.add_argument("--sampling_steps", type=int, default=256)
     parser.add_argument("--output", type=Path, default=Path("samples.pt"))

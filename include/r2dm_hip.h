@@ -94,6 +94,28 @@ int r2dm_unet_forward(r2dm_handle* h, const float* x, const float* cond, float* 
  * The dispatch tests compare it with tests/golden/forward_listing.json. */
 int r2dm_forward_listing(const r2dm_handle* h, int32_t batch, char* buf, size_t cap, size_t* need);
 
+/* -- the feature cache (DeepCache, Ma et al., CVPR 2024): between adjacent sampler steps the deep part of the U-Net changes slowly, so a "shallow" forward
+ *    runs only the outermost `depth` levels and reads everything below them from what the last full forward left at the topmost skipped join.
+ *    depth d in {1, 2, 3}: live are in_conv, stages [0, d) and [8 - d, 8), out_conv, the time embedding and ada_proj.  The cache, a caller-owned buffer of
+ *    r2dm_cache_bytes(h, B, d) bytes (256-byte aligned), holds [output of stage 7 - d, as the walk stores it: fp32, or fp16 in the one-plane mode
+ *    | the GroupNorm statistics slots of that join, where the walk fuses them | scratch of the drift reduction].  The library keeps no cache state: which
+ *    forward filled the buffer, at which batch and in which precision mode, is the caller's to know (unet.py FeatureCache).
+ *      mode 1 (store): the full forward -- the launches of r2dm_unet_forward in the same order, bit-identical `out` -- whose stage 7 - d writes its output
+ *                      into the cache.  drift != NULL (device, 2 B doubles): the stage writes to the workspace as ever and r2dm_cache_store moves it into the
+ *                      cache, leaving per sample {sum (fresh - old)^2, sum old^2} in drift -- one more pass over the tensor per full step.
+ *      mode 2 (reuse): only the live stages run; stage 8 - d reads cat([cache, skip tensor]) and the join's statistics with the cached half in them.
+ *    Non-zero (r2dm_last_error): depth outside 1..3, mode other than 1 / 2, cache too small or misaligned, batch > max_batch, and what r2dm_unet_forward refuses.
+ *    workspace: as for r2dm_unet_forward (r2dm_workspace_bytes).  r2dm_forward_listing_cached: that walk's listing (host only; the cached tensor's line reads
+ *    out=cache; range sites carry the numbers of the full walk). */
+size_t r2dm_cache_bytes(const r2dm_handle* h, int32_t batch, int32_t depth);
+int r2dm_unet_forward_cached(r2dm_handle* h, const float* x, const float* cond, float* out, int32_t batch, void* workspace, size_t workspace_bytes,
+                             void* stream, void* cache, size_t cache_bytes, int32_t depth, int32_t mode, double* drift);
+int r2dm_forward_listing_cached(const r2dm_handle* h, int32_t batch, int32_t depth, int32_t mode, char* buf, size_t cap, size_t* need);
+/* cached <- fresh, bit for bit, (B, n_per_sample) values of fp32 (f16 = 0) or fp16 (f16 = 1), read once together with the values they replace:
+ * sums[b] = {sum (fresh - old)^2, sum old^2}, differences and squares in float64 from the stored values.  partial: scratch of 2 * 512 * B doubles (per-block
+ * sums; a second launch adds them in a fixed order: no atomics, the same bits from call to call).  Both tensors 16-byte aligned; any n_per_sample >= 1. */
+int r2dm_cache_store(const void* fresh, void* cached_inout, int32_t batch, int64_t n_per_sample, int32_t f16, double* partial, double* sums, void* stream);
+
 /* -- arithmetic of the convolutions / attention core on the 16-bit matrix pipe (tensors and accumulation are fp32 in every mode):
  *      pieces = 2 (default, parity mode): every fp32 operand v is split to 22 bits, v = h + 2^-11 l with h = RNE_f16(v),
  *                 l = RNE_f16(2^11 (v - h)); a product is xh wh + 2^-11 (xh wl + xl wh) -- 3 MFMA products, the l x l term

@@ -70,6 +70,10 @@ SIGNATURES = {
     "r2dm_workspace_bytes": (c_size_t, [_P, c_int32]),
     "r2dm_unet_forward": (c_int32, [_P, _P, _P, _P, c_int32, _P, c_size_t, _P]),
     "r2dm_forward_listing": (c_int32, [_P, c_int32, _P, c_size_t, POINTER(c_size_t)]),
+    "r2dm_cache_bytes": (c_size_t, [_P, c_int32, c_int32]),
+    "r2dm_unet_forward_cached": (c_int32, [_P, _P, _P, _P, c_int32, _P, c_size_t, _P, _P, c_size_t, c_int32, c_int32, _P]),
+    "r2dm_forward_listing_cached": (c_int32, [_P, c_int32, c_int32, c_int32, _P, c_size_t, POINTER(c_size_t)]),
+    "r2dm_cache_store": (c_int32, [_P, _P, c_int32, c_int64, c_int32, _P, _P, _P]),
     "r2dm_set_conv_pieces": (c_int32, [_P, c_int32]),
     "r2dm_check_range": (c_int32, [_P, _P]),
     "r2dm_test_raise_range_bound": (c_int32, [_P, c_float, _P]),

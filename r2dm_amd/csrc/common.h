@@ -234,6 +234,11 @@ __host__ __device__ inline int down_phase_row(int ky, int i, int Ho) {
 hipError_t launch_fir_up2(const float* x, long xbs, float* y, long ybs, int B, int C, int H, int W,
                           hipStream_t s, int* range = nullptr, int x16 = 0, int y16 = 0);  // range[1]: running max |output| as float bits (may be nullptr)
 
+// the feature cache's store (cache.hip): cached <- fresh bit for bit, (B, n) values of fp32 / fp16; sums[b] = {sum (fresh - old)^2, sum old^2} in float64;
+// partial: 2 * cache_store_blocks(B, n) * B doubles (at most 2 * 512 * B).  Both tensors 16-byte aligned.
+hipError_t launch_cache_store(const void* fresh, void* cached, int B, long n, int f16, double* partial, double* sums, hipStream_t s);
+int cache_store_blocks(int B, long n);
+
 // qkv: (B, 3C, N) channel-major [q | k | v]; out (B, C, N)
 // planes: 0 = fp32-input MFMA, 2 = fp16 matrix pipe with split operands, 1 = fp16 matrix pipe, one product (attention.hip)
 hipError_t launch_attention(const float* qkv, float* out, int B, int C, int heads, int N, hipStream_t s, int planes = 0);

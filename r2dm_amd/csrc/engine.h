@@ -123,6 +123,10 @@ struct r2dm_handle {
                             // and anything beyond the table.  Kernels only ever atomicMax `pair + 1`.
     static constexpr int RANGE_SITES = 256;
     std::vector<std::string> site_names;  // labels of the last real walk (index = site)
+    // A handle that has run a cached walk (r2dm_unet_forward_cached) keys its sites by the producer's identity (layer + what it records) and gives a producer its
+    // index when it first sees it: a shallow walk hands out fewer sites than a full one, and walk-order numbers would mix two layers' maxima in one slot.  A handle
+    // that only ever runs the plain forward numbers in walk order, as ever.
+    bool sites_keyed = false;
     float site_bounds[RANGE_SITES] = {};  // what the last r2dm_check_range read (before it reset the device copy)
     int sites_read = 0;
     size_t w1 = 0, b1 = 0, w2 = 0, b2 = 0, freqs = 0, cenc = 0, ada_w = 0, ada_b = 0;
@@ -222,9 +226,45 @@ struct Tensor {
     size_t bytes(int B) const { return (size_t)B * C * H * W * (f16 ? 2 : sizeof(float)); }
 };
 
+// The feature cache of a cached walk (r2dm_unet_forward_cached): the caller's buffer, laid out by cache_layout.
+struct CacheWalk {
+    void* buf = nullptr;
+    int depth = 0;            // 1..3: stages [0, depth) and [8 - depth, 8) are live, stage 7 - depth produces the cached tensor
+    int mode = 0;             // 1: store (the full walk), 2: reuse (the live stages only)
+    double* drift = nullptr;  // store: (B, 2) sums of r2dm_cache_store, device
+};
+// [feature: (B, C, H, W) of stage 7 - depth's output, sized for fp32 | sink: the join's statistics slots ([B][G][slots][2] doubles; 0 bytes where the walk
+// has no fused sink for that join) | partial: scratch of the drift reduction]
+struct CacheLayout {
+    int C = 0, H = 0, W = 0;
+    size_t sink_off = 0, sink_bytes = 0, partial_off = 0, total = 0;
+};
+// whether a GroupNorm over C_total channels takes fused statistics, and its group size (Ctx::make_sink's rule: the epilogue reduction merges whole
+// 8-channel blocks of one wave, so groups are 8, 16, 32 or 64 channels)
+inline bool sink_shape(const r2dm_config& c, int C_total, int* cpg) {
+    const int G = c.gn_num_groups;
+    *cpg = C_total / G;
+    return !(C_total % G || *cpg < 8 || *cpg > 64 || (*cpg & (*cpg - 1)));
+}
+inline CacheLayout cache_layout(const r2dm_handle* h, int B, int depth) {
+    CacheLayout l;
+    const r2dm::Stage& s = h->stages[7 - depth];
+    l.C = s.cout;
+    l.H = h->cfg.height >> (depth - 1);
+    l.W = h->cfg.width >> (depth - 1);
+    l.sink_off = align_up((size_t)B * l.C * l.H * l.W * sizeof(float));
+    int cpg;
+    if (sink_shape(h->cfg, h->stages[8 - depth].cin, &cpg)) l.sink_bytes = (size_t)B * h->cfg.gn_num_groups * conv_stat_slots(l.H, l.W) * 2 * sizeof(double);
+    l.partial_off = l.sink_off + align_up(l.sink_bytes);
+    l.total = l.partial_off + align_up((size_t)B * 512 * 2 * sizeof(double));
+    return l;
+}
+
 // one forward over the arena: dry (Arena::dry) it only measures the workspace, else it enqueues every kernel on `st` (forward.hip);
-// dry with a `listing`: one line per launch it would enqueue, the handle untouched (r2dm_forward_listing)
-int run_forward(r2dm_handle* h, Arena& ar, const float* x, const float* cond, float* out, int B, hipStream_t st, std::string* listing = nullptr);
+// dry with a `listing`: one line per launch it would enqueue, the handle untouched (r2dm_forward_listing).  `cache`: a cached walk; `keyed`: the table that
+// numbers the range sites by identity (null: the handle's own rule -- r2dm_handle::sites_keyed)
+int run_forward(r2dm_handle* h, Arena& ar, const float* x, const float* cond, float* out, int B, hipStream_t st, std::string* listing = nullptr,
+                const CacheWalk* cache = nullptr, std::vector<std::string>* keyed = nullptr);
 
 // ConvParams with the fields every launch sets, in the struct's order; aff / res / scale are null, everything else keeps its default
 inline ConvParams conv_params(const Src& x, const float* w, const float* bias, float* y, long y_bs, int B, int H, int W, int Cin, int CinPad, int Cout, int taps,

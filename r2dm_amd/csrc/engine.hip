@@ -216,6 +216,59 @@ int r2dm_unet_forward(r2dm_handle* h, const float* x, const float* cond, float* 
     return run_forward(h, ar, x, cond, out, B, (hipStream_t)stream);
 }
 
+// ---- the feature cache: a second walk over the same stages (forward.hip run_forward, CacheWalk) ----
+static int cache_refused(const r2dm_handle* h, int32_t B, int32_t depth, int32_t mode) {
+    if (!h) return fail(1, "null argument");
+    if (B < 1) return fail(1, "batch must be >= 1");
+    if (B > h->cfg.max_batch) return fail(1, "feature cache: batch %d exceeds max_batch %d", B, h->cfg.max_batch);
+    if (depth < 1 || depth > 3) return fail(1, "feature cache: depth must be 1, 2 or 3 (the outermost levels that stay live), got %d", depth);
+    if (mode != 1 && mode != 2) return fail(1, "feature cache: mode must be 1 (store: the full forward) or 2 (reuse: the live stages only), got %d", mode);
+    return 0;
+}
+
+size_t r2dm_cache_bytes(const r2dm_handle* h, int32_t B, int32_t depth) {
+    if (!h || B < 1 || depth < 1 || depth > 3) return 0;
+    return cache_layout(h, B, depth).total;
+}
+
+int r2dm_unet_forward_cached(r2dm_handle* h, const float* x, const float* cond, float* out, int32_t B, void* ws, size_t ws_bytes, void* stream, void* cache,
+                             size_t cache_bytes, int32_t depth, int32_t mode, double* drift) {
+    if (!h || !x || !cond || !out || !ws || !cache) return fail(1, "null argument");
+    if (int rc = cache_refused(h, B, depth, mode)) return rc;
+    if ((uintptr_t)cache & (kAlign - 1)) return fail(1, "feature cache: the buffer must be %zu-byte aligned", kAlign);
+    const size_t need = cache_layout(h, B, depth).total;
+    if (cache_bytes < need) return fail(1, "feature cache too small: %zu < %zu bytes (r2dm_cache_bytes)", cache_bytes, need);
+    if (drift && ((uintptr_t)drift & 7)) return fail(1, "feature cache: drift must be 8-byte aligned");
+    if (!h->blob) return fail(1, "weights not loaded (r2dm_bind_blob / r2dm_load_tensor)");
+    char* base = (char*)align_up((size_t)(uintptr_t)ws);
+    if (ws_bytes < (size_t)(base - (char*)ws)) return fail(3, "workspace too small");
+    Arena ar{base, ws_bytes - (size_t)(base - (char*)ws), false};
+    const CacheWalk cw{cache, depth, mode, mode == 1 ? drift : nullptr};
+    h->sites_keyed = true;  // (from here on this handle's range sites are numbered by identity: engine.h)
+    return run_forward(h, ar, x, cond, out, B, (hipStream_t)stream, nullptr, &cw);
+}
+
+int r2dm_forward_listing_cached(const r2dm_handle* hc, int32_t B, int32_t depth, int32_t mode, char* buf, size_t cap, size_t* need) {
+    if (!need) return fail(1, "forward_listing_cached: `need` is null");
+    if (int rc = cache_refused(hc, B, depth, mode)) return rc;
+    r2dm_handle* h = const_cast<r2dm_handle*>(hc);
+    // the full walk first, into a table of its own: it gives every site the number the plain listing shows, and the cached walk looks its sites up there
+    std::vector<std::string> sites;
+    std::string full, s;
+    Arena a0{(char*)kAlign, 0, true};
+    if (int rc = run_forward(h, a0, (const float*)kAlign, (const float*)kAlign, (float*)sizeof(float), B, nullptr, &full, nullptr, &sites)) return rc;
+    Arena ar{(char*)kAlign, 0, true};
+    const CacheWalk cw{(void*)(2 * sizeof(float)), depth, mode, nullptr};  // (like the output: an address the arena never hands out)
+    if (int rc = run_forward(h, ar, (const float*)kAlign, (const float*)kAlign, (float*)sizeof(float), B, nullptr, &s, &cw, &sites)) return rc;
+    *need = s.size() + 1;
+    if (buf && cap) {
+        const size_t n = std::min(s.size(), cap - 1);
+        memcpy(buf, s.data(), n);
+        buf[n] = 0;
+    }
+    return 0;
+}
+
 int r2dm_set_conv_pieces(r2dm_handle* h, int32_t pieces) {
     if (!h && (pieces == 4 || pieces == 5)) {  // per-op tests only: the fp32-input MFMA kernel as the yardstick of the split-operand kernels --
         g_single_kernel_pieces = pieces;       // 4: as the library runs it (two-level accumulation above 128 channels), 5: a plain fmaf chain

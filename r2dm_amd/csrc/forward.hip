@@ -27,14 +27,33 @@ struct Ctx {
     // the fp16 operand range guard, one slot per guarded producer ("site") of the forward, in walk order; `ctx`: which layer the walk is in
     int n_sites = 0;
     std::string ctx;
+    // `keyed` (a handle that runs cached walks, and their listings): the site's index is the one its producer -- layer and what it records -- got when the table
+    // first saw it, so that a shallow walk, which hands out fewer sites, raises the slots the full walk raises for the same layers
+    std::vector<std::string>* keyed = nullptr;
+    size_t key_hint = 1;  // (walks meet their sites in nearly the same order: the search starts behind the last hit)
     int* range_site(const char* what) {
-        const int k = n_sites + 1 < r2dm_handle::RANGE_SITES ? ++n_sites : 0;  // (beyond the table: the shared slot 0 -- still guarded, just not named)
-        if (lst) {  // (the line already names the layer)
-            pend += " site=" + std::to_string(k) + ":\"" + what + "\"";
+        int k = 0;
+        if (keyed) {
+            std::vector<std::string>& v = *keyed;
+            const std::string name = ctx.empty() ? std::string(what) : ctx + ": " + what;
+            if (v.empty()) v.emplace_back();  // (slot 0: the shared one)
+            for (size_t j = 0; j + 1 < v.size() && !k; ++j) {
+                const size_t at = 1 + (key_hint - 1 + j) % (v.size() - 1);
+                if (v[at] == name) k = (int)at;
+            }
+            if (!k && (int)v.size() < r2dm_handle::RANGE_SITES) {  // (beyond the table: the shared slot 0 -- still guarded, just not named)
+                v.push_back(name);
+                k = (int)v.size() - 1;
+            }
+            if (k) key_hint = (size_t)k + 1;
         } else {
-            if ((int)h->site_names.size() <= k) h->site_names.resize(k + 1);
-            h->site_names[k] = ctx.empty() ? std::string(what) : ctx + ": " + what;
+            k = n_sites + 1 < r2dm_handle::RANGE_SITES ? ++n_sites : 0;  // (beyond the table: the shared slot 0 -- still guarded, just not named)
+            if (!lst) {
+                if ((int)h->site_names.size() <= k) h->site_names.resize(k + 1);
+                h->site_names[k] = ctx.empty() ? std::string(what) : ctx + ": " + what;
+            }
         }
+        if (lst) pend += " site=" + std::to_string(k) + ":\"" + what + "\"";  // (the line already names the layer)
         return (int*)blob(h->range_flag) + 2 * k;
     }
 
@@ -42,6 +61,7 @@ struct Ctx {
     // enqueue; the handle stays as it was (site names, profiling state, cmap_ready)
     std::string* lst = nullptr;
     const void* user_out = nullptr;  // the caller's output tensor ("dst" in the listing)
+    const void* cache_out = nullptr;  // a cached walk's feature tensor ("cache")
     std::string pend;                // range sites, profiling class and refusals noted since the last line
     bool skip() const { return dry() && !lst; }  // nothing to launch and nothing to list: only the allocations count
     // "layer | launch | out=<arena offset> [| a convolution's ConvParams: what fixes the kernel instantiation and its side effects; flags only where set] [| notes]"
@@ -52,6 +72,7 @@ struct Ctx {
         s += (ctx.empty() ? std::string("-") : ctx) + " | " + name + " | out=";
         if (tag) s += tag;
         else if (out == user_out) s += "dst";
+        else if (out == cache_out) s += "cache";
         else s += std::to_string((size_t)((const char*)out - ar->base));
         if (p) {
             snprintf(b, sizeof(b), " | algo=%s tile=%dx%d pieces=%d pro=%d cin=%d/%d cout=%d taps=%d hw=%dx%d", algos[p->algo], p->co_tile, p->px_rows, p->pieces, p->prologue, p->Cin,
@@ -118,24 +139,27 @@ struct Ctx {
         double* p = nullptr;
         int C = 0, cpg = 0, slots = 0;  // C: channels of the normalised (possibly concatenated) tensor
         bool incomplete = false;        // a producer could not emit its share: the consumer runs the streaming pass instead
+        bool external = false;          // the slots live outside the arena (a cached walk's join: the feature cache)
         explicit operator bool() const { return p != nullptr && !incomplete; }
         int read_slots() const { return cpg < 64 ? slots / 2 : slots; }  // (groups of fewer than 64 channels leave the second half of their slots zero)
     };
-    Sink make_sink(int C_total, int H, int W) {
+    // `at`: the slots' place outside the arena (null: the arena's)
+    Sink make_sink(int C_total, int H, int W, double* at = nullptr) {
         Sink k;
         const int G = h->cfg.gn_num_groups;
-        const int cpg = C_total / G;
+        int cpg;
         // the epilogue reduction (conv_epilogue.h) merges whole 8-channel blocks of ONE wave: groups must be 8, 16, 32 or
         // 64 channels so that they never straddle waves; anything else takes the separate streaming pass
-        if (C_total % G || cpg < 8 || cpg > 64 || (cpg & (cpg - 1))) return k;
+        if (!sink_shape(h->cfg, C_total, &cpg)) return k;
         k.C = C_total;
         k.cpg = cpg;
         k.slots = conv_stat_slots(H, W);
-        k.p = (double*)ar->alloc((size_t)B * G * k.slots * 2 * sizeof(double));
+        k.p = at ? at : (double*)ar->alloc((size_t)B * G * k.slots * 2 * sizeof(double));
+        k.external = at != nullptr;
         return k;
     }
     void drop_sink(Sink& k) {
-        if (k.p) ar->release(k.p);
+        if (k.p && !k.external) ar->release(k.p);
         k.p = nullptr;
     }
     float2* finalize(const Sink& k, int H, int W, const float* gamma, const float* beta, const float* ada) {
@@ -430,6 +454,10 @@ struct Ctx {
     struct StageIn {
         bool tracked = false;  // the input's producer recorded max|x| in the range flag
         bool f16 = false;      // the input is stored as fp16
+        // a cached walk's store: the up-sampling convolution writes the stage's output here, and `*twin` takes the arena block the output would have had --
+        // allocated all the same, so that every later tensor keeps the offset the plain forward gives it
+        float* out_dst = nullptr;
+        void** twin = nullptr;
     };
     Tensor stage(const Stage& s, const Src& in, int H, int W, const Sink& in_stats, const Sink* out, int out_goff, const StageIn& si) {
         Tensor cur;
@@ -542,6 +570,10 @@ struct Ctx {
             cu.input_bounded = track;
             cu.track_out = s.track_final && h->f16_path();
             cu.x16 = cu.y16 = u.f16;
+            if (si.out_dst) {
+                *si.twin = ar->alloc(Tensor{nullptr, s.uconv.cout, 2 * H, 2 * W, u.f16}.bytes(B));
+                cu.dst = si.out_dst;
+            }
             cur = conv(s.uconv, src1(u), 2 * H, 2 * W, cu);
             drop(u);
         }
@@ -551,11 +583,13 @@ struct Ctx {
 
 }  // namespace
 
-int r2dm::run_forward(r2dm_handle* h, Arena& ar, const float* x, const float* cond, float* out, int B, hipStream_t st, std::string* listing) {
+int r2dm::run_forward(r2dm_handle* h, Arena& ar, const float* x, const float* cond, float* out, int B, hipStream_t st, std::string* listing, const CacheWalk* cw,
+                      std::vector<std::string>* keyed) {
     const r2dm_config& c = h->cfg;
     Ctx k{h, &ar, st, B, nullptr, nullptr};
     k.lst = listing;
     k.user_out = out;
+    k.keyed = keyed ? keyed : h->sites_keyed && !listing ? &h->site_names : nullptr;
     const int H = c.height, W = c.width, T = c.temb_channels;
     float* act = (float*)ar.alloc((size_t)2 * B * T * sizeof(float));  // [SiLU(temb) | hidden scratch]
     float* proj = (float*)ar.alloc((size_t)B * h->ada_rows * sizeof(float));
@@ -584,11 +618,40 @@ int r2dm::run_forward(r2dm_handle* h, Arena& ar, const float* x, const float* co
     // GroupNorm sinks that outlive a stage: the first norm of d_block1 (input = in_conv output) and the first norm of
     // every up stage (input = cat([up-path tensor, skip tensor]): groups [0, G/2) come from the up path, [G/2, G)
     // from the skip tensor produced much earlier on the down path).
+    // A cached walk (r2dm_unet_forward_cached) at depth d stops at join d, the first norm of up stage 8 - d: its store is this walk with stage 7 - d's output
+    // and the join's sink in the feature cache; its reuse runs stages [0, d) and [8 - d, 8) only and reads both from there.  A convolution writes its own
+    // groups' slots and no others (conv_epilogue.h: written, not accumulated), so the cached half [0, G/2) stays put while every forward rewrites [G/2, G).
+    const int depth = cw ? cw->depth : 0;
+    const bool store = cw && cw->mode == 1, reuse = cw && cw->mode == 2;
+    const bool run2 = !reuse || depth >= 2, run3 = !reuse || depth >= 3, run4 = !reuse;  // levels 2, 3 and 4 (with the up stage that returns from each)
+    CacheLayout cl;
+    if (cw) cl = cache_layout(h, B, depth);
+    char* const cbuf = cw ? (char*)cw->buf : nullptr;
+    k.cache_out = cbuf;
+    void* sink_twin = nullptr;  // (store: the arena block the join's sink would have had -- kept, so that every offset stays the plain forward's)
+    auto join_sink = [&](int j) {
+        if (reuse && j > depth) return Ctx::Sink{};  // (neither written nor read)
+        double* const at = cw && j == depth ? (double*)(cbuf + cl.sink_off) : nullptr;
+        Ctx::Sink s = k.make_sink(S[8 - j].cin, H >> (j - 1), W >> (j - 1), reuse ? at : nullptr);
+        if (store && at && s.p) {
+            sink_twin = s.p;
+            s.p = at;
+            s.external = true;
+        }
+        // (reuse: the cached half's producer does not run; where it could not emit its share the store's consumer took the streaming pass, and so does this one)
+        const ConvLayer& up = S[7 - depth].uconv;
+        if (reuse && at && s.p && !conv_emits_stats(up.algo, up.co_tile, up.cout)) s.incomplete = true;
+        return s;
+    };
+    auto drop_join = [&](int j, Ctx::Sink& s) {
+        if (store && j == depth && sink_twin) ar.release(sink_twin);
+        k.drop_sink(s);
+    };
     Ctx::Sink s_d1 = k.make_sink(S[0].cin, H, W);
-    Ctx::Sink s_u1 = k.make_sink(S[7].cin, H, W);
-    Ctx::Sink s_u2 = k.make_sink(S[6].cin, H / 2, W / 2);
-    Ctx::Sink s_u3 = k.make_sink(S[5].cin, H / 4, W / 4);
-    Ctx::Sink s_u4 = k.make_sink(S[4].cin, H / 8, W / 8);
+    Ctx::Sink s_u1 = join_sink(1);
+    Ctx::Sink s_u2 = join_sink(2);
+    Ctx::Sink s_u3 = join_sink(3);
+    Ctx::Sink s_u4 = join_sink(4);
     {
         // fp16 storage of the full-resolution levels (Ctx::lvl16): the one-plane mode, the default network family (every GroupNorm of levels 1 and 2 on fused
         // statistics -- the streaming pass reads fp32 --, in_conv on the few-input kernel, FIR statistics at both levels).  R2DM_FP16_STORAGE=1: only between a
@@ -606,38 +669,80 @@ int r2dm::run_forward(r2dm_handle* h, Arena& ar, const float* x, const float* co
     ci.sink = &s_d1;
     ci.y16 = k.lvl16(H) && s_d1.p != nullptr;
     Tensor h0 = k.conv(h->in_conv, in, H, W, ci);
-    Ctx::StageIn i0, i1, i2, i3, i6, i7;  // (stages 4 and 5 read untracked fp32 tensors)
+    Ctx::StageIn i0, i1, i2, i3, i4, i5, i6, i7;  // (stages 4 and 5 read untracked fp32 tensors)
+    // the cached tensor: stage 7 - depth's output, stored as that stage stores it
+    const Tensor cached{(float*)cbuf, cl.C, cl.H, cl.W, cw && k.lvl16(cl.H) && S[7 - depth].uconv.f2};
+    void* feat_twin = nullptr;
+    // before / after the stage that produces join j's up-path half, and when its consumer is through with it
+    auto produce = [&](int j, Ctx::StageIn& si) {
+        if (store && j == depth && !cw->drift) {
+            si.out_dst = cached.p;
+            si.twin = &feat_twin;
+        }
+    };
+    auto produced = [&](int j, const Tensor& t) {
+        if (!(store && j == depth && cw->drift) || k.skip()) return;
+        if (t.f16 != cached.f16 || t.bs() != cached.bs()) k.note(hipErrorInvalidValue, "feature cache: the stage's output is not what the cache was laid out for");
+        k.ctx = "cache";
+        k.run("cache_store", cached.p, [&] { return launch_cache_store(t.p, cached.p, B, t.bs(), t.f16, (double*)(cbuf + cl.partial_off), cw->drift, st); }, nullptr, "cache");
+    };
+    auto consumed = [&](int j, const Tensor& t) {
+        if (cw && j == depth && t.p == cached.p) {
+            if (feat_twin) ar.release(feat_twin);
+        } else
+            k.drop(t);
+    };
     i0.f16 = h0.f16;
     Tensor h1 = k.stage(S[0], src1(h0), H, W, s_d1, &s_u1, G / 2, i0);
     k.drop(h0);
     k.drop_sink(s_d1);
-    i1.tracked = S[0].out_tracked && h->f16_path();
-    i1.f16 = h1.f16;
-    Tensor h2 = k.stage(S[1], src1(h1), H, W, Ctx::Sink{}, &s_u2, G / 2, i1);
-    i2.tracked = S[1].out_tracked && h->f16_path();
-    i2.f16 = h2.f16;
-    Tensor h3 = k.stage(S[2], src1(h2), H / 2, W / 2, Ctx::Sink{}, &s_u3, G / 2, i2);
-    i3.tracked = S[2].out_tracked && h->f16_path();
-    Tensor h4 = k.stage(S[3], src1(h3), H / 4, W / 4, Ctx::Sink{}, &s_u4, 0, i3);
-    Tensor u = k.stage(S[4], src1(h4), H / 8, W / 8, s_u4, &s_u3, 0, Ctx::StageIn{});
-    k.drop(h4);
-    k.drop_sink(s_u4);
-    Tensor u3 = k.stage(S[5], src2(u, h3), H / 4, W / 4, s_u3, &s_u2, 0, Ctx::StageIn{});
-    k.drop(u);
-    k.drop(h3);
-    k.drop_sink(s_u3);
-    if (u3.f16 != h2.f16 || h3.f16) k.note(hipErrorInvalidValue, "fp16 storage: the two halves of a skip join differ");
-    i6.f16 = u3.f16 && h2.f16;
-    Tensor u2 = k.stage(S[6], src2(u3, h2), H / 2, W / 2, s_u2, &s_u1, 0, i6);
-    k.drop(u3);
-    k.drop(h2);
-    k.drop_sink(s_u2);
+    Tensor h2, h3, u, u3, u2;
+    if (run2) {
+        i1.tracked = S[0].out_tracked && h->f16_path();
+        i1.f16 = h1.f16;
+        h2 = k.stage(S[1], src1(h1), H, W, Ctx::Sink{}, &s_u2, G / 2, i1);
+    }
+    if (run3) {
+        i2.tracked = S[1].out_tracked && h->f16_path();
+        i2.f16 = h2.f16;
+        h3 = k.stage(S[2], src1(h2), H / 2, W / 2, Ctx::Sink{}, &s_u3, G / 2, i2);
+    }
+    if (run4) {
+        i3.tracked = S[2].out_tracked && h->f16_path();
+        Tensor h4 = k.stage(S[3], src1(h3), H / 4, W / 4, Ctx::Sink{}, &s_u4, 0, i3);
+        produce(3, i4);
+        u = k.stage(S[4], src1(h4), H / 8, W / 8, s_u4, &s_u3, 0, i4);
+        k.drop(h4);
+        k.drop_sink(s_u4);
+        produced(3, u);
+    } else if (depth == 3)
+        u = cached;
+    if (run3) {
+        produce(2, i5);
+        u3 = k.stage(S[5], src2(u, h3), H / 4, W / 4, s_u3, &s_u2, 0, i5);
+        consumed(3, u);
+        k.drop(h3);
+        drop_join(3, s_u3);
+        produced(2, u3);
+    } else if (depth == 2)
+        u3 = cached;
+    if (run2) {
+        if (u3.f16 != h2.f16 || h3.f16) k.note(hipErrorInvalidValue, "fp16 storage: the two halves of a skip join differ");
+        i6.f16 = u3.f16 && h2.f16;
+        produce(1, i6);
+        u2 = k.stage(S[6], src2(u3, h2), H / 2, W / 2, s_u2, &s_u1, 0, i6);
+        consumed(2, u3);
+        k.drop(h2);
+        drop_join(2, s_u2);
+        produced(1, u2);
+    } else
+        u2 = cached;
     if (u2.f16 != h1.f16) k.note(hipErrorInvalidValue, "fp16 storage: the two halves of a skip join differ");
     i7.f16 = u2.f16 && h1.f16;
     Tensor u1 = k.stage(S[7], src2(u2, h1), H, W, s_u1, nullptr, 0, i7);
-    k.drop(u2);
+    consumed(1, u2);
     k.drop(h1);
-    k.drop_sink(s_u1);
+    drop_join(1, s_u1);
     k.ctx = "out_conv";
     Ctx::ConvOpts co;
     co.dst = out;

@@ -17,6 +17,18 @@ int r2dm_posterior_step(const float* x_t, const float* pred, const float* noise,
     return 0;
 }
 
+int r2dm_cache_store(const void* fresh, void* cached, int32_t B, int64_t n_per_sample, int32_t f16, double* partial, double* sums, void* stream) {
+    if (!fresh || !cached || !partial || !sums) return fail(1, "cache_store: null argument");
+    if (B < 1 || B > 65535) return fail(1, "cache_store: batch must be in [1, 65535], got %d", B);
+    if (n_per_sample < 1 || n_per_sample > (1LL << 40) / B) return fail(1, "cache_store: n_per_sample (got %lld) must be in [1, 2^40 / batch]", (long long)n_per_sample);
+    if (f16 != 0 && f16 != 1) return fail(1, "cache_store: f16 must be 0 (fp32 values) or 1 (fp16 values), got %d", f16);
+    if (fresh == cached) return fail(1, "cache_store: fresh and cached are the same tensor");
+    if ((((uintptr_t)fresh | (uintptr_t)cached) & 15) || (((uintptr_t)partial | (uintptr_t)sums) & 7))
+        return fail(1, "cache_store: the tensors must be 16-byte aligned, partial and sums 8-byte aligned");
+    HIP_TRY(launch_cache_store(fresh, cached, B, (long)n_per_sample, f16, partial, sums, (hipStream_t)stream));
+    return 0;
+}
+
 // What r2dm_posterior_step_known, r2dm_dpm_step and r2dm_dpm_step_known refuse alike, `name` in front of every message.  `need`: the operands that
 // may not be null (`nullable`: the message's word on the rest); `quads`: every tensor the kernel reads or writes as 16-byte quads, absent ones null.  The geometry is
 // per_sample in `channels` planes of whole quads under a mask of 1 or `channels` planes (one channel: whole quads, nothing more).  x0 given: the DPM

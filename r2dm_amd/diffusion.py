@@ -38,6 +38,7 @@ from torch.special import expm1
 
 from . import _lib
 from .latent import ddim_transfer as _ddim_transfer
+from .unet import step_is_full
 
 try:  # progress bars are optional
     from tqdm.auto import tqdm
@@ -79,6 +80,9 @@ def _early_range_check(model, num_steps: int) -> bool:
         return False
     return check()
 
+
+_NO_CACHE_IN_RESAMPLING = ("the resampling walk jumps back in time, and deep features cached at a later noise level are not a neighbouring step's; "
+                           "complete_dpm (no resampling) takes a feature cache")
 
 _CHECK_EVERY = 32  # steps between two range checks of a sampling loop: one stream synchronisation each, at most so many steps to replay
 
@@ -137,6 +141,20 @@ class _Replay:
             return self.ck_i, self.ck_x
         self.ck_i, self.ck_x, self.noise = i + 1, (x if self.record else None), []
         return i + 1, x
+
+
+def _cache_opts(what: str, cache_interval, cache_depth, cache_drift, refuse: Optional[str] = None):
+    """The feature-cache keywords of a sampler, checked: None for ``cache_interval = 1`` (no cache: the sampler's code path is the one without the
+    keywords), else ``(interval, depth, drift)``.  ``refuse``: why ``what`` cannot run with a cache at all."""
+    if isinstance(cache_interval, bool) or not isinstance(cache_interval, int) or cache_interval < 1:
+        raise ValueError(f"cache_interval must be an integer >= 1 (1: no feature cache), got {cache_interval!r}")
+    if isinstance(cache_depth, bool) or cache_depth not in (1, 2, 3):
+        raise ValueError(f"cache_depth must be 1, 2 or 3 (the outermost U-Net levels a shallow step runs), got {cache_depth!r}")
+    if cache_interval == 1:
+        return None
+    if refuse:
+        raise ValueError(f"{what}: cache_interval = {cache_interval} is not supported: {refuse}")
+    return cache_interval, cache_depth, bool(cache_drift)
 
 
 def _progress_bar(total: int, desc: str, enabled: bool):
@@ -263,6 +281,8 @@ def discrete_tables(num_training_steps: int, schedule: str):
 # --------------------------------------------------------------------------------------
 class GaussianDiffusion(nn.Module):
     """Common state and RNG plumbing (base.py:8-163)."""
+
+    last_cache_drift = None  # the drift table of the last sampler call with ``cache_drift=True`` (FeatureCache.drift)
 
     def __init__(
         self,
@@ -492,7 +512,7 @@ class GaussianDiffusion(nn.Module):
             _rng_restore(snap, rng, self.device)
             return call()
 
-    def _run_loop(self, x, num_steps: int, row, update, draw, progress: bool, return_all: bool, desc: str = "sampling"):
+    def _run_loop(self, x, num_steps: int, row, update, draw, progress: bool, return_all: bool, desc: str = "sampling", cache=None):
         """The step loop every sampler here shares (``sample``, ``sample_from``, ``invert``, ``sample_dpm``, ``complete_dpm``): per step
         ``row(i) -> (cond, coef)``, the step's noise (``draw(x) -> (noise, event)`` ahead of the denoiser call; None: a deterministic update,
         nothing is drawn), one denoiser call, ``update(x, prediction, noise, coef, hist) -> (x, hist)``; under the deferred range guard, with
@@ -500,9 +520,19 @@ class GaussianDiffusion(nn.Module):
         before the first step and for the one-step samplers), and the pair is what ``_Replay`` keeps.  ``_Replay`` only stores the object it
         is given and an update may write ``hist``'s buffer again two steps on, so at a step whose check is due the loop hands on a COPY: the
         checkpoint's history is then a buffer no later step writes.
+        ``cache``: ``_cache_opts``' ``(interval, depth, drift)`` -- the denoiser runs through a feature cache (``EfficientUNet.forward_cached``): step i
+        is a full step when ``i % interval == 0`` or the cache is not valid (``unet.step_is_full``) -- at the loop's start, after a replay has gone back,
+        after a precision switch -- and a shallow one otherwise; with ``drift`` the full steps' drift table lands in ``self.last_cache_drift``.
         -> the last ``x``, or with ``return_all`` the (S+1, ...) stack that starts with the given ``x``."""
         if return_all:
             out = [x]
+        fc = None
+        if cache is not None:
+            interval, depth, drift = cache
+            net = getattr(self.model, "_orig_mod", self.model)  # (torch.compile wrapper)
+            if not callable(getattr(net, "new_cache", None)):
+                raise ValueError(f"cache_interval = {interval} needs a denoiser with a feature cache (r2dm_amd's EfficientUNet), got {type(net).__name__}")
+            fc = net.new_cache(x.shape[0], depth, drift)
         rp = _Replay(self.model, num_steps)  # (a range-guard trip at any step: back to the last checked state, on the recorded noise)
         rp.start((x, None))
         hist = None
@@ -512,13 +542,18 @@ class GaussianDiffusion(nn.Module):
             while i < num_steps:
                 cond_i, coef_i = row(i)
                 noise, drawn = rp.noise_for(i, lambda: draw(x)) if draw is not None else (None, None)
-                prediction = self.model(x, cond_i)
+                if fc is None:
+                    prediction = self.model(x, cond_i)
+                else:
+                    prediction = net.forward_cached(x, cond_i, fc, refresh=step_is_full(i, interval, fc.usable()))
                 if drawn is not None:
                     torch.cuda.current_stream(x.device).wait_event(drawn)
                 x_s, hist = update(x, prediction, noise, coef_i, hist)
                 if hist is not None and rp.record and rp.due(i):
                     hist = hist.clone()
                 nxt, (x, hist) = rp.after_step(i, (x_s, hist))
+                if fc is not None and nxt <= i:
+                    fc.invalidate()  # (a replay: the cached features belong to a later level than the checkpoint's)
                 if return_all:
                     del out[nxt + 1:]  # (after a replay: the steps that are run again; else nothing)
                     if nxt > i:
@@ -528,6 +563,8 @@ class GaussianDiffusion(nn.Module):
                 i = nxt
         if bar is not None:
             bar.close()
+        if fc is not None and drift:
+            self.last_cache_drift = fc.drift()
         return torch.stack(out) if return_all else x
 
     def _refuse_cpu(self, what: str, x):
@@ -738,34 +775,43 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
 
     @torch.inference_mode()
     def sample(self, batch_size: int, num_steps: int, progress: bool = True, rng=None,
-               return_all: bool = False, mode: Literal["ddpm", "ddim"] = "ddpm", ddim_eta: float = 0.0):
-        """Ancestral / DDIM sampling from t=1 to t=0 (continuous_time.py:234-258)."""
+               return_all: bool = False, mode: Literal["ddpm", "ddim"] = "ddpm", ddim_eta: float = 0.0,
+               cache_interval: int = 1, cache_depth: int = 1, cache_drift: bool = False):
+        """Ancestral / DDIM sampling from t=1 to t=0 (continuous_time.py:234-258).
+        ``cache_interval = n > 1`` (not in the reference; DeepCache, Ma et al. 2024): only every n-th step runs the whole U-Net; the steps between run its
+        ``cache_depth`` outermost levels and reuse the deep features of the last full step (``EfficientUNet.forward_cached``) -- an approximation whose cost
+        in sample quality depends on the checkpoint; ``cache_drift`` records how far those features moved between full steps
+        (``self.last_cache_drift``: (full steps, B), NaN where nothing valid was replaced).  The default, 1, is the sampler without a cache."""
         dev = self.device
         self._objective_id()
+        cache = _cache_opts("sample", cache_interval, cache_depth, cache_drift)
         x = self.randn(batch_size, *self.sampling_shape, rng=rng, device=dev)
-        return self._reverse_loop(x, num_steps, 1.0, progress, rng, return_all, mode, ddim_eta)
+        return self._reverse_loop(x, num_steps, 1.0, progress, rng, return_all, mode, ddim_eta, cache=cache)
 
-    def _reverse_loop(self, x, num_steps, t_start, progress, rng, return_all, mode, ddim_eta, clip: Optional[float] = None):
+    def _reverse_loop(self, x, num_steps, t_start, progress, rng, return_all, mode, ddim_eta, clip: Optional[float] = None, cache=None):
         """The reverse process from ``x`` at ``t_start`` to t = 0 over ``linspace(t_start, 0, num_steps + 1)``: ``sample`` and ``sample_from``
         (``clip``: None -- the model's setting, else ``_posterior``'s override)."""
         row, mode_id = self._table_rows(num_steps, x.shape[0], mode, ddim_eta, x.device, t_start)
         return self._run_loop(x, num_steps, row, lambda x, pred, noise, coef, _: (self._posterior(x, pred, noise, coef, mode_id, clip), None),
-                              lambda x: self._randn_like_ahead(x, rng=rng), progress, return_all)
+                              lambda x: self._randn_like_ahead(x, rng=rng), progress, return_all, cache=cache)
 
     @torch.inference_mode()
     def sample_from(self, x_t, num_steps: int, t_start: float = 1.0, progress: bool = True, rng=None, return_all: bool = False,
-                    mode: Literal["ddpm", "ddim"] = "ddpm", ddim_eta: float = 0.0, clip: Optional[bool] = None):
+                    mode: Literal["ddpm", "ddim"] = "ddpm", ddim_eta: float = 0.0, clip: Optional[bool] = None,
+                    cache_interval: int = 1, cache_depth: int = 1, cache_drift: bool = False):
         """``sample``'s reverse loop started from a given ``x_t`` (B,C,H,W) at noise level ``t_start`` instead of a fresh draw at t = 1,
         over ``linspace(t_start, 0, num_steps + 1)``: decodes a latent of ``invert`` or an interpolated one, or -- after
         ``q_step_from_x_0(x_0, t_start)`` -- denoises a partially noised scan.  With ``x_t = randn(B, ...)`` from the same generators and
         ``t_start = 1`` it is ``sample``, bit for bit.  ``clip``: None keeps the model's ``clip_sample`` setting, False switches the clamp
-        of the predicted x_0 off for this call only (a round trip through ``invert`` needs that), True switches it on."""
+        of the predicted x_0 off for this call only (a round trip through ``invert`` needs that), True switches it on.
+        ``cache_interval``, ``cache_depth``, ``cache_drift``: the feature cache, as in ``sample``."""
+        cache = _cache_opts("sample_from", cache_interval, cache_depth, cache_drift)
         self._refuse_cpu("sample_from", x_t)
         _check_level(t_start)
         if x_t.dim() != 4 or x_t.shape[0] < 1:
             raise ValueError(f"x_t must be (B,C,H,W) with B >= 1, got {tuple(x_t.shape)}")
         self._objective_id()
-        return self._reverse_loop(_lib.f32c(x_t), num_steps, float(t_start), progress, rng, return_all, mode, ddim_eta, self._clip(clip))
+        return self._reverse_loop(_lib.f32c(x_t), num_steps, float(t_start), progress, rng, return_all, mode, ddim_eta, self._clip(clip), cache=cache)
 
     # -- DPM-Solver++(2M): a second-order multistep solver of the probability-flow ODE on the log-SNR axis (not in the reference) ------------
     def _dpm_table(self, num_steps: int, batch_size: int, order: int, grid: str, t_start: float, lower_order_final: bool, dev, eta: float = 0.0):
@@ -831,7 +877,7 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
     @torch.inference_mode()
     def sample_dpm(self, batch_size: int, num_steps: int, order: int = 2, grid: Literal["logsnr", "time"] = "logsnr", progress: bool = True, rng=None,
                    return_all: bool = False, x_t=None, t_start: float = 1.0, clip: Optional[bool] = None, lower_order_final: bool = True,
-                   eta: float = 0.0):
+                   eta: float = 0.0, cache_interval: int = 1, cache_depth: int = 1, cache_drift: bool = False):
         """DPM-Solver++(2M) sampling (Lu et al. 2022): a deterministic second-order multistep solver of the probability-flow ODE in
         data-prediction form, on ``num_steps + 1`` log-SNR values from ``t_start`` to t = 0.  Per step one denoiser call at ``cond[i]`` and one
         ``r2dm_dpm_step``, which forms the clamped estimate of x_0 as the other samplers do, keeps it as the next step's history and combines
@@ -855,8 +901,11 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
 
         Runs under the deferred range guard with ``_Replay``'s recovery, whose checkpoint here is the pair (x, previous x_0 estimate): after a
         trip the loop goes back at most ``_CHECK_EVERY`` steps WITH the history those steps were taken with, on the wide-range split.
-        ``schedule_on`` does not apply (see ``_dpm_table``)."""
+        ``schedule_on`` does not apply (see ``_dpm_table``).
+        ``cache_interval``, ``cache_depth``, ``cache_drift``: the feature cache, as in ``sample`` (the log-SNR steps of a 16-32 step grid are far larger than
+        those of a 256-step ancestral run, so the deep features move further between full steps: look at the drift before trusting an interval)."""
         _check_solver(order, grid, eta)
+        cache = _cache_opts("sample_dpm", cache_interval, cache_depth, cache_drift)
         _check_count(num_steps=num_steps)
         _check_level(t_start)
         _check_count(batch_size=batch_size)
@@ -870,10 +919,10 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
             raise NoCPUFallback(f"sample_dpm runs as HIP kernels on an MI355X (model on {self.device}"
                                 + ("" if x_t is None else f", input on {x_t.device}") + "): r2dm_amd has no CPU fallback")
         x = self.randn(batch_size, *self.sampling_shape, rng=rng, device=self.device) if x_t is None else _lib.f32c(x_t)
-        return self._dpm_solve(x, num_steps, order, grid, t_start, lower_order_final, eta, clip, progress, rng, return_all)
+        return self._dpm_solve(x, num_steps, order, grid, t_start, lower_order_final, eta, clip, progress, rng, return_all, cache=cache)
 
     def _dpm_solve(self, x, num_steps, order, grid, t_start, lower_order_final, eta, clip, progress, rng, return_all, known=None, mask=None,
-                  desc: str = "sampling"):
+                  desc: str = "sampling", cache=None):
         """``sample_dpm`` and ``complete_dpm`` from their start tensor: ``_run_loop`` over ``_dpm_table`` with the multistep update, whose history is
         the previous estimate of x_0.  The estimates ping-pong between two buffers (``_run_loop`` copies the one a checkpoint keeps).  The step's
         noise (``eta > 0``) is drawn ahead of the denoiser call; ``known``, ``mask``: the measurement written over every estimate.  With neither
@@ -890,7 +939,7 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
                 return _lib.dpm_step(x, prediction, x0_prev if second_i else None, coef_i, objective, clip, x0_out=target)
             return _lib.dpm_step_known(x, prediction, x0_prev if second_i else None, noise, known, mask, coef_i, objective, clip, x0_out=target)
 
-        return self._run_loop(x, len(second), lambda i: (cond[i], (coef[i], second[i])), update, draw, progress, return_all, desc)
+        return self._run_loop(x, len(second), lambda i: (cond[i], (coef[i], second[i])), update, draw, progress, return_all, desc, cache=cache)
 
     def _transfer_table(self, steps: torch.Tensor, batch_size: int, dev):
         """``(cond (S,B), coef (S,B,4))`` on the device for DDIM transfers along ``steps`` (S+1,): the log-SNR of each step's start and
@@ -947,12 +996,13 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
 
     @torch.inference_mode()
     def repaint(self, known, mask, num_steps: int, num_resample_steps: int = 1, jump_length: int = 1,
-                progress: bool = True, rng=None, return_all: bool = False):
+                progress: bool = True, rng=None, return_all: bool = False, cache_interval: int = 1, cache_depth: int = 1, cache_drift: bool = False):
         """RePaint inpainting on top of the same p_step (continuous_time.py:260-317).  A range-guard trip that only shows after the
         first step (``_early_check``) ends the loop with the denoiser switched to the wide-range split: the call is then repeated
         once, from the generator states it started with -- same draws, no exception (the reference runs any finite checkpoint)."""
         assert num_resample_steps > 0
         assert jump_length > 0
+        _cache_opts("repaint", cache_interval, cache_depth, cache_drift, _NO_CACHE_IN_RESAMPLING)
         dev = self.device
 
         def prepare(r, k):
@@ -1046,7 +1096,7 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
     @torch.inference_mode()
     def complete(self, known, mask, num_steps: int, num_resample_steps: int = 1, jump_length: int = 1, t_start: float = 1.0, init=None,
                  mode: Literal["ddpm", "ddim"] = "ddpm", ddim_eta: float = 0.0, exact_known: bool = True, progress: bool = True, rng=None,
-                 return_all: bool = False):
+                 return_all: bool = False, cache_interval: int = 1, cache_depth: int = 1, cache_drift: bool = False):
         """Completion of ``known`` (B,C,H,W) under ``mask`` (B | 1, 1 | C, H, W; 1 = measured, any weight in [0, 1] is taken as such) with
         one denoiser call per reverse sub-step: the clamped estimate of x_0 gets the measurement written over its known pixels,
         ``x0 = mask * known + (1 - mask) * x0``, and x_s is sampled from the ordinary posterior given that x_0 -- one fused kernel
@@ -1061,7 +1111,9 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
         draws.  ``exact_known``: the result is ``mask * known + (1 - mask) * x`` (``r2dm_repaint_blend``), equal to ``known`` on a binary
         mask; without it the known pixels carry the last step's ``sigma(0) * z``.  ``return_all``: the stack ``repaint`` returns -- the
         start, then the x_s of every resampling, the last one projected like the result.  A range-guard trip is handled as in ``repaint``:
-        the call is repeated once on the wide-range split from the generator states it started with."""
+        the call is repeated once on the wide-range split from the generator states it started with.
+        ``cache_interval`` other than 1 is refused (the resampling walk; ``complete_dpm`` is the completion that takes a feature cache)."""
+        _cache_opts("complete", cache_interval, cache_depth, cache_drift, _NO_CACHE_IN_RESAMPLING)
         known, mask, init = self._completion_args("complete", known, mask, dict(num_steps=num_steps, num_resample_steps=num_resample_steps,
                                                                                 jump_length=jump_length), t_start, init, mode=mode)
         dev = known.device
@@ -1092,7 +1144,7 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
     @torch.inference_mode()
     def complete_dpm(self, known, mask, num_steps: int, order: int = 2, grid: Literal["logsnr", "time"] = "logsnr", eta: float = 1.0,
                      t_start: float = 1.0, init=None, exact_known: bool = True, clip: Optional[bool] = None, lower_order_final: bool = True,
-                     progress: bool = True, rng=None, return_all: bool = False):
+                     progress: bool = True, rng=None, return_all: bool = False, cache_interval: int = 1, cache_depth: int = 1, cache_drift: bool = False):
         """Completion of ``known`` (B,C,H,W) under ``mask`` (B | 1, 1 | C, H, W; 1 = measured, any weight in [0, 1] is taken as such) on
         ``sample_dpm``'s solver: per step one denoiser call and one ``r2dm_dpm_step_known``, which forms the clamped estimate of x_0, writes
         the measurement over it (``x0 = mask * known + (1 - mask) * x0``, ``complete``'s projection), keeps THAT as the next step's history
@@ -1110,10 +1162,12 @@ class ContinuousTimeGaussianDiffusion(GaussianDiffusion):
         ``exact_known``: the result is ``mask * known + (1 - mask) * x`` (``r2dm_repaint_blend``), equal to ``known`` on a binary mask.
         ``return_all``: the (S+1,B,C,H,W) stack from the start, the last entry projected like the result.
         A range-guard trip is handled by ``_Replay`` as in ``sample_dpm``: back at most ``_CHECK_EVERY`` steps with the checkpointed pair
-        (x, previous estimate), on the recorded noise, on the wide-range split."""
+        (x, previous estimate), on the recorded noise, on the wide-range split.
+        ``cache_interval``, ``cache_depth``, ``cache_drift``: the feature cache, as in ``sample_dpm``."""
+        cache = _cache_opts("complete_dpm", cache_interval, cache_depth, cache_drift)
         known, mask, init = self._completion_args("complete_dpm", known, mask, dict(num_steps=num_steps), t_start, init, solver=(order, grid, eta))
         out = self._dpm_solve(self._completion_start(known, init, t_start, rng), num_steps, order, grid, t_start, lower_order_final, eta, clip, progress,
-                              rng, return_all, known, mask, desc="completing")
+                              rng, return_all, known, mask, desc="completing", cache=cache)
         return self._known_exact(out, known, mask, return_all) if exact_known else out
 
 
@@ -1213,8 +1267,11 @@ class DiscreteTimeGaussianDiffusion(GaussianDiffusion):
 
     @torch.inference_mode()
     def sample(self, batch_size: int, num_steps: int, progress: bool = True, rng=None,
-               return_all: bool = False, mode: Literal["ddpm", "ddim"] = "ddpm"):
-        """t = num_steps-1 ... 0 without respacing (discrete_time.py:182-201)."""
+               return_all: bool = False, mode: Literal["ddpm", "ddim"] = "ddpm", cache_interval: int = 1, cache_depth: int = 1, cache_drift: bool = False):
+        """t = num_steps-1 ... 0 without respacing (discrete_time.py:182-201).  ``cache_interval`` other than 1 is refused: the feature cache is
+        wired into the continuous-time samplers only."""
+        _cache_opts("DiscreteTimeGaussianDiffusion.sample", cache_interval, cache_depth, cache_drift,
+                    "the feature cache is implemented for the continuous-time samplers (sample, sample_from, sample_dpm, complete_dpm) only")
         dev = self.device
         self._objective_id()
         x = self.randn(batch_size, *self.sampling_shape, rng=rng, device=dev)

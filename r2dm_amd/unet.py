@@ -158,6 +158,97 @@ class _Engine:
                                            self.workspace.data_ptr(), self.workspace.numel(), _lib.stream_ptr(dev)))
         return out
 
+    # -- the feature cache -------------------------------------------------------------------
+    def listing_cached(self, B: int, depth: int, mode: int) -> str:
+        """The listing of a cached walk (r2dm_forward_listing_cached: host only); ``mode`` 1 = store, 2 = reuse."""
+        L, need = _lib.lib(), ctypes.c_size_t(0)
+        _lib.check(L.r2dm_forward_listing_cached(self.h, B, depth, mode, None, 0, ctypes.byref(need)))
+        buf = ctypes.create_string_buffer(need.value)
+        _lib.check(L.r2dm_forward_listing_cached(self.h, B, depth, mode, buf, need.value, ctypes.byref(need)))
+        return buf.value.decode()
+
+    def cache_bytes(self, B: int, depth: int) -> int:
+        return int(_lib.lib().r2dm_cache_bytes(self.h, B, depth))
+
+    def cached_tensor(self, B: int, depth: int):
+        """``((C, H, W), dtype)`` of the tensor a cached walk keeps, as the store's listing tells it (the line whose output is the cache)."""
+        for ln in self.listing_cached(B, depth, 1).splitlines():
+            f = ln.split(" | ")
+            if f[2] == "out=cache":
+                words = dict(w.split("=", 1) for w in f[3].split() if "=" in w)
+                H, W = (int(v) for v in words["hw"].split("x"))
+                return (int(words["cout"]), H, W), (torch.float16 if " y16" in f[3] else torch.float32)
+        raise _lib.R2DMError("the store's listing names no cached tensor")
+
+    def forward_cached(self, x: torch.Tensor, cond: torch.Tensor, buffer: torch.Tensor, depth: int, mode: int, drift: Optional[torch.Tensor]) -> torch.Tensor:
+        L = _lib.lib()
+        B = x.shape[0]
+        dev = x.device
+        need = int(L.r2dm_workspace_bytes(self.h, B))
+        if self.workspace is None or self.workspace.numel() < need or self.workspace.device != dev:
+            self.workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        out = torch.empty(B, self.out_channels, *x.shape[2:], device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            _lib.check(L.r2dm_unet_forward_cached(self.h, x.data_ptr(), cond.data_ptr(), out.data_ptr(), B, self.workspace.data_ptr(), self.workspace.numel(),
+                                                  _lib.stream_ptr(dev), buffer.data_ptr(), buffer.numel(), depth, mode, drift.data_ptr() if drift is not None else None))
+        return out
+
+
+def step_is_full(i: int, interval: int, cache_valid: bool) -> bool:
+    """Step ``i`` of a sampling loop runs the full network (and refreshes the cache) when the interval says so or there is nothing valid to reuse."""
+    return i % interval == 0 or not cache_valid
+
+
+class FeatureCache:
+    """The deep features one full forward leaves for the shallow forwards that follow it (DeepCache, Ma et al., CVPR 2024): the output of up stage
+    ``7 - depth`` at the topmost skipped skip join, and that join's GroupNorm statistics, in one buffer PyTorch owns.  The library keeps no state
+    about it: this object knows which forward filled it -- ``valid``, and the model's generation at that moment, which ``set_precision``,
+    re-packing the weights and ``invalidate()`` move on, so that a cache filled by other weights or another arithmetic is never reused.
+    Made by ``EfficientUNet.new_cache``; used through ``EfficientUNet.forward_cached``."""
+
+    def __init__(self, model: "EfficientUNet", batch: int, depth: int = 1, drift: bool = False):
+        if depth not in (1, 2, 3):
+            raise ValueError(f"cache depth must be 1, 2 or 3 (the outermost levels that stay live), got {depth}")
+        if not 1 <= batch <= model.max_batch:
+            raise ValueError(f"cache batch must be in [1, max_batch = {model.max_batch}], got {batch}")
+        self.model, self.batch, self.depth = model, int(batch), int(depth)
+        self.precision: Optional[str] = None  # of the forward that filled it
+        self.generation = -1
+        self.valid = False
+        self.buffer: Optional[torch.Tensor] = None
+        self._layout = None  # ((C, H, W), dtype) of the cached tensor in `precision`
+        self._drift = [] if drift else None  # per full step: the (B, 2) sums on the device, or None where nothing valid was replaced
+
+    def usable(self) -> bool:
+        """Filled, and by this model as it stands."""
+        return self.valid and self.generation == self.model._generation and self.precision == self.model.precision
+
+    def invalidate(self):
+        self.valid = False
+
+    def features(self) -> torch.Tensor:
+        """The cached tensor as a ``(B, C, H, W)`` view of the buffer: float32, or float16 in the ``"fp16"`` precision's storage."""
+        if self.buffer is None or self._layout is None or not self.valid:
+            raise _lib.R2DMError("the feature cache holds nothing yet: run forward_cached(..., refresh=True) first")
+        (C, H, W), dtype = self._layout
+        n = self.batch * C * H * W
+        return self.buffer[: n * dtype.itemsize].view(dtype).view(self.batch, C, H, W)
+
+    def drift(self) -> torch.Tensor:
+        """``(full steps, B)`` float64: ``sqrt(sum (fresh - old)^2 / sum old^2)`` of the cached tensor at every full step since the cache was made -- how far
+        the deep features moved over one cache interval; NaN where a full step replaced nothing valid (the first one, the one after a replay).  The sums are
+        left on the device by the steps and evaluated here, once: reading them does not synchronise the loop."""
+        if self._drift is None:
+            raise _lib.R2DMError("this cache records no drift: make it with new_cache(..., drift=True)")
+        if not self._drift:
+            return torch.empty(0, self.batch, dtype=torch.float64)
+        some = next((t for t in self._drift if t is not None), None)
+        if some is None:
+            return torch.full((len(self._drift), self.batch), float("nan"), dtype=torch.float64)
+        nan = torch.full_like(some, float("nan"))
+        sums = torch.stack([nan if t is None else t for t in self._drift])
+        return (sums[..., 0] / sums[..., 1]).sqrt()
+
 
 class EfficientUNet(nn.Module):
     def __init__(
@@ -194,6 +285,7 @@ class EfficientUNet(nn.Module):
             self._register(e, _default_init(e, self.geometry))
         self._engine: Optional[_Engine] = None
         self._packed_for = None
+        self._generation = 0  # moves whenever a FeatureCache filled before may no longer be reused (precision, weights)
         self.precision = "fp32"
         # fp16 range guard of the default operand split: False (default) = a tripped guard switches this model to the wide-range split
         # ("fp32-bf16x3": exact 24-bit operands, fp32 operand range, ~1.6x slower) with ONE warning and the forward is repeated --
@@ -219,6 +311,7 @@ class EfficientUNet(nn.Module):
     def invalidate(self):
         """Forget the packed weights; they are rebuilt on the next forward."""
         self._packed_for = None
+        self._generation = getattr(self, "_generation", 0) + 1
 
     def _apply(self, fn, *args, **kwargs):
         self.invalidate()
@@ -256,6 +349,7 @@ class EfficientUNet(nn.Module):
         sd.update(self._constants(sd))
         self._engine.load(sd, device)
         self._packed_for = key
+        self._generation += 1
 
     # -- weight sharing across GPUs (one RCCL broadcast instead of N loads) ----------------------
     def packed_weights(self, device=None) -> torch.Tensor:
@@ -340,6 +434,7 @@ class EfficientUNet(nn.Module):
         if precision not in self.PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(self.PRECISIONS)}, got {precision!r}")
         self.precision = precision
+        self._generation = getattr(self, "_generation", 0) + 1
         if self._engine is not None:
             _lib.check(_lib.lib().r2dm_set_conv_pieces(self._engine.h, self.PRECISIONS[precision]))
         return self
@@ -457,5 +552,61 @@ class EfficientUNet(nn.Module):
         out = self._engine.forward(x, cond)
         if not self._defer_range_check and self.check_range_or_fall_back():
             out = self._engine.forward(x, cond)  # (again, on the wide-range split)
+            self.check_range()
+        return out
+
+    # -- the feature cache (DeepCache) -------------------------------------------------------------
+    def new_cache(self, batch: int, depth: int = 1, drift: bool = False) -> FeatureCache:
+        """A feature cache for forwards at ``batch``: ``depth`` outermost levels stay live in a shallow forward (1: in_conv, d_block1, u_block1, out_conv);
+        ``drift``: every full step also measures how far the cached tensor moved since the last one (``FeatureCache.drift``; one more pass over it)."""
+        return FeatureCache(self, batch, depth, drift)
+
+    def _forward_cached(self, x, cond, cache: FeatureCache, refresh: bool):
+        eng = self._engine
+        if cache.buffer is None or cache.buffer.device != x.device:
+            cache.buffer = torch.zeros(eng.cache_bytes(cache.batch, cache.depth), dtype=torch.uint8, device=x.device)
+            cache.valid = False
+        if not refresh:
+            return eng.forward_cached(x, cond, cache.buffer, cache.depth, 2, None)
+        sums = None
+        if cache._drift is not None:
+            if cache.usable():  # (else there is nothing to measure against: the stage writes straight into the cache)
+                sums = torch.empty(cache.batch, 2, dtype=torch.float64, device=x.device)
+            cache._drift.append(sums)
+        cache.valid = False
+        out = eng.forward_cached(x, cond, cache.buffer, cache.depth, 1, sums)
+        if cache._layout is None or cache.precision != self.precision:
+            cache._layout = eng.cached_tensor(cache.batch, cache.depth)
+        cache.precision, cache.generation, cache.valid = self.precision, self._generation, True
+        return out
+
+    @torch.compiler.disable
+    def forward_cached(self, images: torch.Tensor, timesteps: torch.Tensor, cache: FeatureCache, refresh: bool) -> torch.Tensor:
+        """``forward`` through a feature cache.  ``refresh=True``: the full network -- the same launches, the same bits as ``forward`` -- which leaves its deep
+        features in ``cache``; ``refresh=False``: the shallow network, which runs only the cache's live levels and reads the rest from it.  A shallow call
+        on a cache that is empty, was filled at another precision or by other weights raises ``R2DMError``.  Arguments and the range check as ``forward``
+        (a guard trip switches the model to the wide-range split and repeats the call as a full one: the cache of the other arithmetic is gone)."""
+        _lib.require_gpu(images, "images")
+        if images.dim() != 4 or images.shape[1] != self.in_channels or tuple(images.shape[2:]) != self.resolution:
+            raise ValueError(f"expected (B,{self.in_channels},{self.resolution[0]},{self.resolution[1]}), "
+                             f"got {tuple(images.shape)}")
+        x = _lib.f32c(images)
+        B = x.shape[0]
+        if timesteps.dim() == 0:
+            timesteps = timesteps[None].repeat_interleave(B, dim=0)
+        cond = _lib.f32c(timesteps.to(x.device))
+        if cond.shape != (B,):
+            raise ValueError(f"timesteps must have shape ({B},), got {tuple(timesteps.shape)}")
+        if not isinstance(cache, FeatureCache) or cache.model is not self:
+            raise ValueError("cache must be a FeatureCache made by this model's new_cache()")
+        if cache.batch != B:
+            raise ValueError(f"the cache was made for batch {cache.batch}, got {B} images")
+        self._ensure_packed(x.device)
+        if not refresh and not (cache.usable() and cache.buffer is not None and cache.buffer.device == x.device):
+            raise _lib.R2DMError("forward_cached(refresh=False) on a feature cache that is empty or stale (filled at another precision or by other weights): "
+                                 "run a full step with refresh=True first")
+        out = self._forward_cached(x, cond, cache, refresh)
+        if not self._defer_range_check and self.check_range_or_fall_back():
+            out = self._forward_cached(x, cond, cache, True)  # (again, on the wide-range split, as a full step)
             self.check_range()
         return out

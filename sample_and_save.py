@@ -13,6 +13,7 @@ its own tolerance class (tests/test_hip_fp16_mode.py).
 ``--mode dpmpp`` (extension) samples with DPM-Solver++(2M), ``ddpm.sample_dpm``: use it with ``--num_steps`` 16 to 32 (``--dpm_eta 1``: its stochastic member).
 ``--points_dir DIR`` (extension) also writes every sample as a Velodyne scan ``DIR/samples_{seed:010d}.bin``: the pixels inside the
 checkpoint's depth window as fp32 [x, y, z, reflectance] rows in scan order (r2dm_amd.pointcloud)."""
+import json
 import os
 from argparse import ArgumentParser
 from pathlib import Path
@@ -55,10 +56,16 @@ def sample(args):
     for i in range(0, len(mine), args.batch_size):
         seeds = mine[i: i + args.batch_size]
         rng = r2dm_amd.setup_rng(seeds, device=device)
+        # (extension: the feature cache -- only every cache_interval-th step runs the whole U-Net; the defaults are the sampler without it)
+        cache = dict(cache_interval=args.cache_interval, cache_depth=args.cache_depth, cache_drift=args.cache_drift)
         if args.mode == "dpmpp":  # (extension: DPM-Solver++(2M), meant for 16-32 steps)
-            samples = ddpm.sample_dpm(batch_size=len(seeds), num_steps=args.num_steps, rng=rng, progress=False, eta=args.dpm_eta).clamp(-1, 1)
+            samples = ddpm.sample_dpm(batch_size=len(seeds), num_steps=args.num_steps, rng=rng, progress=False, eta=args.dpm_eta, **cache).clamp(-1, 1)
         else:
-            samples = ddpm.sample(batch_size=len(seeds), num_steps=args.num_steps, mode=args.mode, rng=rng, progress=False).clamp(-1, 1)
+            samples = ddpm.sample(batch_size=len(seeds), num_steps=args.num_steps, mode=args.mode, rng=rng, progress=False, **cache).clamp(-1, 1)
+        if args.cache_drift and args.cache_interval > 1:  # per batch: (full steps, samples), the drift of the cached features between full steps
+            with open(save_dir / f"cache_drift_{seeds[0]:010d}.json", "w") as f:
+                json.dump({"seeds": list(seeds), "cache_interval": args.cache_interval, "cache_depth": args.cache_depth,
+                           "cache_drift": [[None if v != v else v for v in row] for row in ddpm.last_cache_drift.tolist()]}, f)
         samples = lidar_utils.postprocess(samples)  # denormalize -> revert_depth -> to_xyz -> concat, one kernel
         for seed, s in zip(seeds, samples):
             torch.save(s.clone(), save_dir / f"samples_{seed:010d}.pth")
@@ -81,6 +88,9 @@ def parser():
                         help="dpmpp (extension): the DPM-Solver++(2M) sampler, ddpm.sample_dpm; use it with --num_steps 16 to 32")
     parser.add_argument("--dpm_eta", type=float, default=0.0, help="--mode dpmpp: the share of fresh noise per step (0: deterministic, 1: SDE-DPM-Solver++(2M))")
     parser.add_argument("--precision", choices=["fp32", "fp32-bf16x3", "fp16"], default="fp32")
+    parser.add_argument("--cache_interval", type=int, default=1, help="extension: feature cache (DeepCache): run the whole U-Net only every N-th step (1: no cache)")
+    parser.add_argument("--cache_depth", type=int, default=1, choices=[1, 2, 3], help="extension: --cache_interval: the outermost U-Net levels a shallow step runs")
+    parser.add_argument("--cache_drift", action="store_true", help="extension: --cache_interval: also write cache_drift_<first seed>.json per batch")
     parser.add_argument("--max-batch", type=int, default=0, help="extension: the batch size the layer tilings are planned for (default: --batch_size)")
     parser.add_argument("--points_dir", type=str, default=None, help="extension: also write every sample as a Velodyne scan samples_<seed>.bin there")
     return parser
