@@ -703,6 +703,21 @@ int r2dm_down_gemm_nine(const float* x, const float* w, const float* bias, float
 int32_t r2dm_down_gemm_stat_slots(int32_t cin, int32_t cout, int32_t groups, int32_t height, int32_t width);
 int r2dm_down_gemm(const float* x, const float* w, const float* bias, float* w_packed, float* planes, float* y, double* stat,
                    int32_t batch, int32_t cin, int32_t cout, int32_t groups, int32_t height, int32_t width, void* stream);
+/* The range guard's other producers, one kernel (or the streaming pair) each with the record the engine's walk gives them -- range: device int32[2] or NULL,
+ * [1] takes the running maximum as float bits (positive floats order like their bit patterns, a NaN above all), [0] is never written.  Everything else is the
+ * entry of the same name without _ex (R2DM_TEST_IO16 and R2DM_FIR_UP_WIDE included), whose outputs the record does not change:
+ *   r2dm_group_norm_affine_ex      the bound of gn_bound (csrc/gn_math.h) on |a x + d| with M = the exact max|x| of each group (the streaming pass records it)
+ *   r2dm_group_norm_from_stats_ex  the same bound with M = sqrt(largest slot energy) (1 + 1e-6) of each group
+ *   r2dm_fir_up2_ex                max|y| of the values as STORED (an fp16 store that overflows records +inf)
+ *   r2dm_down_planes_ex, r2dm_down_phase_planes_ex  max|plane value| (the maximum over the distinct planes is the maximum over all nine: the same bits)
+ * Kernel-level test hooks (tests/test_hip_range_producers.py). */
+int r2dm_group_norm_affine_ex(const float* x, const float* gamma, const float* beta, const float* ada, void* scratch, float* aff, float* stats, int32_t batch,
+                              int32_t channels, int32_t height, int32_t width, int32_t groups, float eps, void* stream, int32_t* range);
+int r2dm_group_norm_from_stats_ex(const double* stat, int32_t slots, const float* gamma, const float* beta, const float* ada, float* aff, float* stats,
+                                  int32_t batch, int32_t channels, int32_t height, int32_t width, int32_t groups, float eps, void* stream, int32_t* range);
+int r2dm_fir_up2_ex(const float* x, float* y, int32_t batch, int32_t channels, int32_t height, int32_t width, void* stream, int32_t* range);
+int r2dm_down_planes_ex(const float* x, float* planes, int32_t batch, int32_t channels, int32_t height, int32_t width, void* stream, int32_t* range);
+int r2dm_down_phase_planes_ex(const float* x, float* planes, int32_t batch, int32_t channels, int32_t height, int32_t width, void* stream, int32_t* range);
 /* attention core of nn.MultiheadAttention on channel-major qkv (B,3C,N) -> (B,C,N)
  * (models/efficient_unet.py:34-38,46) */
 int r2dm_attention(const float* qkv, float* out, int32_t batch, int32_t channels, int32_t heads, int32_t tokens,

@@ -160,24 +160,38 @@ int r2dm_conv2d_ring_ex(const float* x, const float* x1, int32_t c1, const float
 
 size_t r2dm_group_norm_scratch_bytes(int32_t B, int32_t groups) { return (size_t)B * groups * 256 * (2 * sizeof(double) + sizeof(float)); }
 
-int r2dm_group_norm_affine(const float* x, const float* gamma, const float* beta, const float* ada, void* scratch,
-                           float* aff, float* stats, int32_t B, int32_t C, int32_t H, int32_t W, int32_t groups,
-                           float eps, void* stream) {
+// range (the _ex entries of the guard's producers): device int32[2] or NULL -- [1] takes the running maximum of the producer's bound as float bits,
+// [0] (the packers' weight flag in the engine) is never written
+int r2dm_group_norm_affine_ex(const float* x, const float* gamma, const float* beta, const float* ada, void* scratch, float* aff, float* stats, int32_t B,
+                              int32_t C, int32_t H, int32_t W, int32_t groups, float eps, void* stream, int32_t* range) {
     if (!x || !scratch || !aff) return fail(1, "null argument");
     GNParams g{Src{x, nullptr, C, 0, (long)C * H * W, 0}, B, H, W, groups, eps, gamma, beta, ada, 2L * C,
                (double*)scratch, (float2*)aff, stats};
     g.partial_max = (float*)((double*)scratch + (size_t)B * groups * 256 * 2);
+    g.range_flag = range;  // (M = the recorded max|x|: gn_partial_kernel's partial_max)
     HIP_TRY(launch_group_norm(g, (hipStream_t)stream));
+    return 0;
+}
+
+int r2dm_group_norm_affine(const float* x, const float* gamma, const float* beta, const float* ada, void* scratch,
+                           float* aff, float* stats, int32_t B, int32_t C, int32_t H, int32_t W, int32_t groups,
+                           float eps, void* stream) {
+    return r2dm_group_norm_affine_ex(x, gamma, beta, ada, scratch, aff, stats, B, C, H, W, groups, eps, stream, nullptr);
+}
+
+int r2dm_group_norm_from_stats_ex(const double* stat, int32_t slots, const float* gamma, const float* beta, const float* ada, float* aff, float* stats,
+                                  int32_t B, int32_t C, int32_t H, int32_t W, int32_t groups, float eps, void* stream, int32_t* range) {
+    if (!stat || !aff) return fail(1, "null argument");
+    if (B < 1 || slots < 1 || groups < 1 || C % groups) return fail(1, "group_norm_from_stats: %d slots, %d channels in %d groups", slots, C, groups);
+    GNParams g{Src{nullptr, nullptr, C, 0, (long)C * H * W, 0}, B, H, W, groups, eps, gamma, beta, ada, 2L * C, const_cast<double*>(stat), (float2*)aff, stats};
+    g.range_flag = range;  // (no partial_max: the finalize kernel reads the sink alone, M = the square root of the largest slot energy)
+    HIP_TRY(launch_group_norm_finalize(g, C, slots, (hipStream_t)stream));
     return 0;
 }
 
 int r2dm_group_norm_from_stats(const double* stat, int32_t slots, const float* gamma, const float* beta, const float* ada, float* aff, float* stats,
                                int32_t B, int32_t C, int32_t H, int32_t W, int32_t groups, float eps, void* stream) {
-    if (!stat || !aff) return fail(1, "null argument");
-    if (B < 1 || slots < 1 || groups < 1 || C % groups) return fail(1, "group_norm_from_stats: %d slots, %d channels in %d groups", slots, C, groups);
-    GNParams g{Src{nullptr, nullptr, C, 0, (long)C * H * W, 0}, B, H, W, groups, eps, gamma, beta, ada, 2L * C, const_cast<double*>(stat), (float2*)aff, stats};
-    HIP_TRY(launch_group_norm_finalize(g, C, slots, (hipStream_t)stream));  // (no partial_max, no range flag: the finalize kernel reads the sink alone)
-    return 0;
+    return r2dm_group_norm_from_stats_ex(stat, slots, gamma, beta, ada, aff, stats, B, C, H, W, groups, eps, stream, nullptr);
 }
 
 int r2dm_affine_act(const float* x, const float* aff, float* y, int32_t B, int32_t C, int64_t hw, int32_t silu,
@@ -201,11 +215,15 @@ int r2dm_fir_down2_stats(const float* x, float* y, double* stat, int32_t B, int3
     return 0;
 }
 
-int r2dm_down_planes(const float* x, float* planes, int32_t B, int32_t C, int32_t H, int32_t W, void* stream) {
+int r2dm_down_planes_ex(const float* x, float* planes, int32_t B, int32_t C, int32_t H, int32_t W, void* stream, int32_t* range) {
     if (!x || !planes) return fail(1, "null argument");
     if (B < 1 || C < 1 || !down_planes_supported(H, W)) return fail(1, "down_planes: needs height %% 4 == 0 and width %% 8 == 0 (>= 16)");
-    HIP_TRY(launch_down_planes(x, (long)C * H * W, planes, 9L * C * (H / 2) * (W / 2), B, C, H, W, (hipStream_t)stream));
+    HIP_TRY(launch_down_planes(x, (long)C * H * W, planes, 9L * C * (H / 2) * (W / 2), B, C, H, W, (hipStream_t)stream, range));
     return 0;
+}
+
+int r2dm_down_planes(const float* x, float* planes, int32_t B, int32_t C, int32_t H, int32_t W, void* stream) {
+    return r2dm_down_planes_ex(x, planes, B, C, H, W, stream, nullptr);
 }
 
 int32_t r2dm_down_gemm_stat_slots(int32_t cin, int32_t cout, int32_t G, int32_t H, int32_t W) {
@@ -214,11 +232,15 @@ int32_t r2dm_down_gemm_stat_slots(int32_t cin, int32_t cout, int32_t G, int32_t 
     return cpg >= 8 && cpg <= 64 && !(cpg & (cpg - 1)) ? conv_stat_slots(H / 2, W / 2) : 0;
 }
 
-int r2dm_down_phase_planes(const float* x, float* planes, int32_t B, int32_t C, int32_t H, int32_t W, void* stream) {
+int r2dm_down_phase_planes_ex(const float* x, float* planes, int32_t B, int32_t C, int32_t H, int32_t W, void* stream, int32_t* range) {
     if (!x || !planes) return fail(1, "null argument");
     if (B < 1 || C < 1 || !down_phase_planes_supported(H, W)) return fail(1, "down_phase_planes: needs height %% 4 == 0 and width %% 8 == 0 (>= 16)");
-    HIP_TRY(launch_down_phase_planes(x, (long)C * H * W, planes, down_phase_planes_floats(C, H, W), B, C, H, W, (hipStream_t)stream));
+    HIP_TRY(launch_down_phase_planes(x, (long)C * H * W, planes, down_phase_planes_floats(C, H, W), B, C, H, W, (hipStream_t)stream, range));
     return 0;
+}
+
+int r2dm_down_phase_planes(const float* x, float* planes, int32_t B, int32_t C, int32_t H, int32_t W, void* stream) {
+    return r2dm_down_phase_planes_ex(x, planes, B, C, H, W, stream, nullptr);
 }
 
 int64_t r2dm_down_phase_planes_floats(int32_t C, int32_t H, int32_t W) {
@@ -255,9 +277,14 @@ int r2dm_down_gemm_nine(const float* x, const float* w, const float* bias, float
     return down_gemm_entry(x, w, bias, w_packed, planes, y, stat, B, cin, cout, G, H, W, stream, false);
 }
 
-int r2dm_fir_up2(const float* x, float* y, int32_t B, int32_t C, int32_t H, int32_t W, void* stream) {
-    HIP_TRY(launch_fir_up2(x, (long)C * H * W, y, (long)C * H * W * 4, B, C, H, W, (hipStream_t)stream, nullptr, test_io16() & 1, (test_io16() >> 1) & 1));
+// (R2DM_TEST_IO16 and R2DM_FIR_UP_WIDE as for r2dm_fir_up2: launch_fir_up2 reads the second, the record is that of the STORED values)
+int r2dm_fir_up2_ex(const float* x, float* y, int32_t B, int32_t C, int32_t H, int32_t W, void* stream, int32_t* range) {
+    HIP_TRY(launch_fir_up2(x, (long)C * H * W, y, (long)C * H * W * 4, B, C, H, W, (hipStream_t)stream, range, test_io16() & 1, (test_io16() >> 1) & 1));
     return 0;
+}
+
+int r2dm_fir_up2(const float* x, float* y, int32_t B, int32_t C, int32_t H, int32_t W, void* stream) {
+    return r2dm_fir_up2_ex(x, y, B, C, H, W, stream, nullptr);
 }
 
 int r2dm_attention(const float* qkv, float* out, int32_t B, int32_t C, int32_t heads, int32_t N, void* stream) {

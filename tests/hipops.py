@@ -158,6 +158,109 @@ def group_norm_from_stats(stat, C, H, W, eps, gamma=None, beta=None, ada=None):
     return aff, stats
 
 
+# ---- the range guard's other producers: the _ex entries with a record ------------------------------------------------------------------------
+RANGE_FLAG = 7  # what [0] of a record holds around a call: the producers never write it
+
+
+def float_bits(v):
+    """The int32 bit pattern of float32(v)."""
+    return int(torch.tensor([v], dtype=torch.float32).view(torch.int32).item())
+
+
+def bits_float(b):
+    """float32 of an int32 bit pattern, as a Python float."""
+    return float(torch.tensor([b], dtype=torch.int32).view(torch.float32).item())
+
+
+def _record(range_init, dev):
+    """The device int32[2] a call starts from: (RANGE_FLAG, bits of range_init); None: no record."""
+    return None if range_init is None else torch.tensor([RANGE_FLAG, float_bits(range_init)], device=dev, dtype=torch.int32)
+
+
+def _recorded(rng):
+    """The record after the call: the bits of [1] (None without a record); [0] must be untouched."""
+    if rng is None:
+        return None
+    flag, bits = rng.cpu().tolist()
+    assert flag == RANGE_FLAG, f"the producer wrote {flag} to [0] of the range record"
+    return bits
+
+
+def group_norm_affine_ex(x, groups, eps, gamma=None, beta=None, ada=None, range_init=None):
+    """(aff, stats, record bits): r2dm_group_norm_affine_ex -- the streaming pass, M = the recorded max|x|.  aff and stats start NaN-filled inside NaN
+    guard bands that must survive the call; range_init: the float the record starts from (None: no record)."""
+    L = _lib.lib()
+    B, C, H, W = x.shape
+    x = _lib.f32c(x)
+    scratch = torch.empty(L.r2dm_group_norm_scratch_bytes(B, groups), dtype=torch.uint8, device=x.device)
+    aff_all, aff = guarded((B, C, 2), torch.float32, 64, x.device)
+    st_all, stats = guarded((B, groups, 2), torch.float32, 64, x.device)
+    rng = _record(range_init, x.device)
+    _lib.check(L.r2dm_group_norm_affine_ex(x.data_ptr(), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(ada), scratch.data_ptr(), aff.data_ptr(), stats.data_ptr(),
+                                           B, C, H, W, groups, eps, _st(x), _lib.ptr(rng)))
+    torch.cuda.synchronize()
+    assert guard_intact(aff_all, 64) and guard_intact(st_all, 64), "write outside aff / stats"
+    return aff, stats, _recorded(rng)
+
+
+def group_norm_from_stats_ex(stat, C, H, W, eps, gamma=None, beta=None, ada=None, range_init=None):
+    """(aff, stats, record bits): r2dm_group_norm_from_stats_ex over a sink (B, groups, slots, 2) float64 -- M = sqrt(largest slot energy); outputs
+    and record as group_norm_affine_ex."""
+    B, groups, slots, two = stat.shape
+    assert two == 2 and stat.dtype == torch.float64 and stat.is_contiguous()
+    aff_all, aff = guarded((B, C, 2), torch.float32, 64, stat.device)
+    st_all, stats = guarded((B, groups, 2), torch.float32, 64, stat.device)
+    rng = _record(range_init, stat.device)
+    _lib.check(_lib.lib().r2dm_group_norm_from_stats_ex(stat.data_ptr(), slots, _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(ada), aff.data_ptr(), stats.data_ptr(),
+                                                        B, C, H, W, groups, eps, _st(stat), _lib.ptr(rng)))
+    torch.cuda.synchronize()
+    assert guard_intact(aff_all, 64) and guard_intact(st_all, 64), "write outside aff / stats"
+    return aff, stats, _recorded(rng)
+
+
+def fir_up2_ex(x, io16=0, range_init=None):
+    """(y, record bits): r2dm_fir_up2_ex; io16 as fir_up2 (with R2DM_TEST_IO16 set by the caller).  y starts NaN-filled inside NaN guard bands of one
+    output row pair that must survive the call, and every element of it must have been written (a finite input leaves no NaN)."""
+    B, C, H, W = x.shape
+    x = _io(x, io16)
+    yg = (4 * W + 63) // 64 * 64
+    y_all, y = guarded((B, C, H * 2, W * 2), torch.float16 if io16 & 2 else torch.float32, yg, x.device)
+    rng = _record(range_init, x.device)
+    _lib.check(_lib.lib().r2dm_fir_up2_ex(x.data_ptr(), y.data_ptr(), B, C, H, W, _st(x), _lib.ptr(rng)))
+    torch.cuda.synchronize()
+    assert guard_intact(y_all, yg), "write outside y"
+    return y, _recorded(rng)
+
+
+def down_planes_ex(x, range_init=None):
+    """(planes (B, 9 C, H / 2, W / 2), record bits): r2dm_down_planes_ex; the planes start NaN-filled inside NaN guard bands of one plane."""
+    B, C, H, W = x.shape
+    x = _lib.f32c(x)
+    g = ((H // 2) * (W // 2) + 63) // 64 * 64
+    a_all, a = guarded((B, 9 * C, H // 2, W // 2), torch.float32, g, x.device)
+    rng = _record(range_init, x.device)
+    _lib.check(_lib.lib().r2dm_down_planes_ex(x.data_ptr(), a.data_ptr(), B, C, H, W, _st(x), _lib.ptr(rng)))
+    torch.cuda.synchronize()
+    assert guard_intact(a_all, g), "write outside the planes"
+    return a, _recorded(rng)
+
+
+def down_phase_planes_ex(x, range_init=None):
+    """(planes (B, 2, C, H + 3, W / 2 + 4), record bits): r2dm_down_phase_planes_ex; the buffer starts NaN-filled inside NaN guard bands of one
+    channel's rows -- what is still NaN after the call, the kernel did not write (floats 0 .. 2 of every row, float 3 of the second phase's)."""
+    L = _lib.lib()
+    B, C, H, W = x.shape
+    x = _lib.f32c(x)
+    assert L.r2dm_down_phase_planes_floats(C, H, W) == 2 * C * (H + 3) * (W // 2 + 4)
+    g = ((H + 3) * (W // 2 + 4) + 63) // 64 * 64
+    a_all, a = guarded((B, 2, C, H + 3, W // 2 + 4), torch.float32, g, x.device)
+    rng = _record(range_init, x.device)
+    _lib.check(L.r2dm_down_phase_planes_ex(x.data_ptr(), a.data_ptr(), B, C, H, W, _st(x), _lib.ptr(rng)))
+    torch.cuda.synchronize()
+    assert guard_intact(a_all, g), "write outside the phase planes"
+    return a, _recorded(rng)
+
+
 def affine_act(x, aff, silu):
     L = _lib.lib()
     B, C, H, W = x.shape
