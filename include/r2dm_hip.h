@@ -715,6 +715,11 @@ int r2dm_group_norm_affine_ex(const float* x, const float* gamma, const float* b
                               int32_t channels, int32_t height, int32_t width, int32_t groups, float eps, void* stream, int32_t* range);
 int r2dm_group_norm_from_stats_ex(const double* stat, int32_t slots, const float* gamma, const float* beta, const float* ada, float* aff, float* stats,
                                   int32_t batch, int32_t channels, int32_t height, int32_t width, int32_t groups, float eps, void* stream, int32_t* range);
+/* r2dm_group_norm_from_stats_ex with the AdaGN rows where the engine has them: sample b's [scale(C) | shift(C)] at ada + b ada_stride (the packed
+ * (B, ada_rows) output of the projection launch; _ex is ada_stride = 2 C).  Returns 1 for ada with ada_stride < 2 C. */
+int r2dm_group_norm_from_stats_strided(const double* stat, int32_t slots, const float* gamma, const float* beta, const float* ada, int64_t ada_stride, float* aff,
+                                       float* stats, int32_t batch, int32_t channels, int32_t height, int32_t width, int32_t groups, float eps, void* stream,
+                                       int32_t* range);
 int r2dm_fir_up2_ex(const float* x, float* y, int32_t batch, int32_t channels, int32_t height, int32_t width, void* stream, int32_t* range);
 int r2dm_down_planes_ex(const float* x, float* planes, int32_t batch, int32_t channels, int32_t height, int32_t width, void* stream, int32_t* range);
 int r2dm_down_phase_planes_ex(const float* x, float* planes, int32_t batch, int32_t channels, int32_t height, int32_t width, void* stream, int32_t* range);
@@ -727,6 +732,10 @@ int r2dm_attention(const float* qkv, float* out, int32_t batch, int32_t channels
 int r2dm_time_embedding(const float* cond, const float* freqs, const float* w1, const float* b1, const float* w2,
                         const float* b2, float* act, float* hidden, int32_t batch, int32_t base, int32_t temb,
                         void* stream);
+/* all AdaGN projections of one forward in one launch (models/ops.py:190-200: Linear(SiLU(temb), 2C) of every residual block, packed row-wise):
+ * out (B, rows) = act (B, T) w^T (rows, T) + bias (rows,), fp64 accumulation.  Returns 1 for a null pointer, batch, temb or rows < 1, and -- the
+ * kernel loads 16 bytes at a time where temb % 256 == 0 -- for an act or w that is not 16-byte aligned then.  Kernel-level test hook. */
+int r2dm_ada_proj(const float* act, const float* w, const float* bias, float* out, int32_t batch, int32_t temb, int32_t rows, void* stream);
 
 #ifdef __cplusplus
 }

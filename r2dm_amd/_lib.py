@@ -119,11 +119,13 @@ SIGNATURES = {
     "r2dm_down_phase_planes_floats": (c_int64, [c_int32, c_int32, c_int32]),
     "r2dm_group_norm_affine_ex": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, _P, _P]),
     "r2dm_group_norm_from_stats_ex": (c_int32, [_P, c_int32, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, _P, _P]),
+    "r2dm_group_norm_from_stats_strided": (c_int32, [_P, c_int32, _P, _P, _P, c_int64, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, _P, _P]),
     "r2dm_fir_up2_ex": (c_int32, [_P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P]),
     "r2dm_down_planes_ex": (c_int32, [_P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P]),
     "r2dm_down_phase_planes_ex": (c_int32, [_P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P]),
     "r2dm_attention": (c_int32, [_P, _P, c_int32, c_int32, c_int32, c_int32, _P]),
     "r2dm_time_embedding": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, _P]),
+    "r2dm_ada_proj": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, _P]),
     "r2dm_bev_histogram": (c_int32, [_P, c_int32, _P, _P, _P, c_int32, c_int64, c_int32, c_float, c_float, c_float, c_float,
                                      _P]),
     "r2dm_bev_hist_sum": (c_int32, [_P, c_int32, _P, c_int64, c_int64, _P]),

@@ -179,14 +179,21 @@ int r2dm_group_norm_affine(const float* x, const float* gamma, const float* beta
     return r2dm_group_norm_affine_ex(x, gamma, beta, ada, scratch, aff, stats, B, C, H, W, groups, eps, stream, nullptr);
 }
 
-int r2dm_group_norm_from_stats_ex(const double* stat, int32_t slots, const float* gamma, const float* beta, const float* ada, float* aff, float* stats,
-                                  int32_t B, int32_t C, int32_t H, int32_t W, int32_t groups, float eps, void* stream, int32_t* range) {
+// ada_stride: floats between two samples' [scale(C) | shift(C)] rows -- the engine reads them out of the packed [B][ada_rows] projection buffer
+int r2dm_group_norm_from_stats_strided(const double* stat, int32_t slots, const float* gamma, const float* beta, const float* ada, int64_t ada_stride, float* aff,
+                                       float* stats, int32_t B, int32_t C, int32_t H, int32_t W, int32_t groups, float eps, void* stream, int32_t* range) {
     if (!stat || !aff) return fail(1, "null argument");
     if (B < 1 || slots < 1 || groups < 1 || C % groups) return fail(1, "group_norm_from_stats: %d slots, %d channels in %d groups", slots, C, groups);
-    GNParams g{Src{nullptr, nullptr, C, 0, (long)C * H * W, 0}, B, H, W, groups, eps, gamma, beta, ada, 2L * C, const_cast<double*>(stat), (float2*)aff, stats};
+    if (ada && ada_stride < 2L * C) return fail(1, "group_norm_from_stats: ada rows of %ld floats do not hold 2 x %d", (long)ada_stride, C);
+    GNParams g{Src{nullptr, nullptr, C, 0, (long)C * H * W, 0}, B, H, W, groups, eps, gamma, beta, ada, (long)ada_stride, const_cast<double*>(stat), (float2*)aff, stats};
     g.range_flag = range;  // (no partial_max: the finalize kernel reads the sink alone, M = the square root of the largest slot energy)
     HIP_TRY(launch_group_norm_finalize(g, C, slots, (hipStream_t)stream));
     return 0;
+}
+
+int r2dm_group_norm_from_stats_ex(const double* stat, int32_t slots, const float* gamma, const float* beta, const float* ada, float* aff, float* stats,
+                                  int32_t B, int32_t C, int32_t H, int32_t W, int32_t groups, float eps, void* stream, int32_t* range) {
+    return r2dm_group_norm_from_stats_strided(stat, slots, gamma, beta, ada, 2L * C, aff, stats, B, C, H, W, groups, eps, stream, range);
 }
 
 int r2dm_group_norm_from_stats(const double* stat, int32_t slots, const float* gamma, const float* beta, const float* ada, float* aff, float* stats,
@@ -298,6 +305,15 @@ int r2dm_time_embedding(const float* cond, const float* freqs, const float* w1, 
     if (!cond || !freqs || !w1 || !b1 || !w2 || !b2 || !act || !hidden) return fail(1, "null argument");
     EmbedParams e{cond, freqs, w1, b1, w2, b2, act, hidden, B, base, T};
     HIP_TRY(launch_time_embedding(e, (hipStream_t)stream));
+    return 0;
+}
+
+// (16-byte loads of act and w where T % 256 == 0: ada_proj_kernel)
+int r2dm_ada_proj(const float* act, const float* w, const float* bias, float* out, int32_t B, int32_t T, int32_t rows, void* stream) {
+    if (!act || !w || !bias || !out) return fail(1, "null argument");
+    if (B < 1 || T < 1 || rows < 1) return fail(1, "ada_proj: batch %d, %d inputs, %d rows", B, T, rows);
+    if (T % 256 == 0 && (((uintptr_t)act | (uintptr_t)w) & 15)) return fail(1, "ada_proj: act and w must be 16-byte aligned where T %% 256 == 0");
+    HIP_TRY(launch_ada_proj(act, w, bias, out, B, T, rows, (hipStream_t)stream));
     return 0;
 }
 

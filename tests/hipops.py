@@ -374,12 +374,66 @@ def attention_padded(qkv, heads, C=None):
     return out
 
 
-def time_embedding(cond, freqs, w1, b1, w2, b2):
+def in_guard(t, guard=64, offset=0):
+    """A float32 copy of t as a contiguous view, `guard + offset` floats into a NaN-filled allocation that goes on `guard` floats past its end: a
+    read past either end of it turns the result NaN instead of faulting.  (guard = 64: 256 bytes, the view keeps the allocation's alignment.)"""
+    t = _lib.f32c(t)
+    whole = torch.full((guard + offset + t.numel() + guard,), float("nan"), device=t.device)
+    view = whole[guard + offset:guard + offset + t.numel()].view(t.shape)
+    view.copy_(t)
+    return view
+
+
+def time_embedding(cond, freqs, w1, b1, w2, b2, return_hidden=False):
+    """act (B, T) = SiLU(time_embedding(cond)) -- with return_hidden (act, hidden), hidden (B, T) = SiLU of the first Linear.  Both start NaN-filled
+    inside NaN guard bands that must survive the call, and with finite operands every element of them must have been written; the operands are views
+    into NaN-filled allocations (in_guard)."""
     B, T, base = cond.shape[0], w1.shape[0], w1.shape[1]
-    act = torch.empty(B, T, device=cond.device)
-    hid = torch.empty(B, T, device=cond.device)
-    _lib.check(_lib.lib().r2dm_time_embedding(cond.data_ptr(), freqs.data_ptr(), w1.data_ptr(), b1.data_ptr(),
-                                             w2.data_ptr(), b2.data_ptr(), act.data_ptr(), hid.data_ptr(), B, base, T,
-                                             _st(cond)))
+    ops = [in_guard(t) for t in (cond, freqs, w1, b1, w2, b2)]
+    act_all, act = guarded((B, T), torch.float32, 64, cond.device)
+    hid_all, hid = guarded((B, T), torch.float32, 64, cond.device)
+    _lib.check(_lib.lib().r2dm_time_embedding(*(t.data_ptr() for t in ops), act.data_ptr(), hid.data_ptr(), B, base, T, _st(cond)))
     torch.cuda.synchronize()
-    return act
+    assert guard_intact(act_all, 64) and guard_intact(hid_all, 64), "write outside act / hidden"
+    if all(bool(torch.isfinite(t).all()) for t in ops):
+        assert not bool(torch.isnan(act).any() or torch.isnan(hid).any()), "an element of act / hidden was not written, or a read left an operand"
+    return (act, hid) if return_hidden else act
+
+
+def ada_proj(act, w, bias, w_offset=0):
+    """out (B, rows) = r2dm_ada_proj(act (B, T), w (rows, T), bias (rows,)).  out starts NaN-filled inside NaN guard bands that must survive the call;
+    act and w are views into NaN-filled allocations (in_guard; w_offset: floats to shift w by, for the alignment refusal), so with finite operands a
+    NaN in out is an element that was not written or a read past an operand's end.  If the entry refuses, out must still be NaN throughout, and the
+    error is raised on."""
+    (B, T), rows = act.shape, w.shape[0]
+    assert w.shape == (rows, T) and bias.shape == (rows,)
+    act, w, bias = in_guard(act), in_guard(w, offset=w_offset), _lib.f32c(bias)
+    out_all, out = guarded((B, rows), torch.float32, 64, act.device)
+    rc = _lib.lib().r2dm_ada_proj(act.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), B, T, rows, _st(act))
+    torch.cuda.synchronize()
+    if rc != 0:
+        assert bool(torch.isnan(out_all).all()), "a refused launch wrote to out"
+        _lib.check(rc)
+    assert guard_intact(out_all, 64), "write outside out"
+    if all(bool(torch.isfinite(t).all()) for t in (act, w, bias)):
+        assert not bool(torch.isnan(out).any()), "an element of out was not written, or a read left act / w"
+    return out
+
+
+def group_norm_from_stats_strided(stat, C, H, W, eps, ada, ada_stride, gamma=None, beta=None, range_init=None):
+    """(aff, stats, record bits): r2dm_group_norm_from_stats_strided -- group_norm_from_stats_ex with sample b's AdaGN row [scale(C) | shift(C)] at
+    ada + b ada_stride floats (ada: a tensor whose first element is sample 0's scale; the caller owns what lies around it); outputs and record as
+    group_norm_from_stats_ex.  If the entry refuses, aff and stats must still be NaN throughout, and the error is raised on."""
+    B, groups, slots, two = stat.shape
+    assert two == 2 and stat.dtype == torch.float64 and stat.is_contiguous()
+    aff_all, aff = guarded((B, C, 2), torch.float32, 64, stat.device)
+    st_all, stats = guarded((B, groups, 2), torch.float32, 64, stat.device)
+    rng = _record(range_init, stat.device)
+    rc = _lib.lib().r2dm_group_norm_from_stats_strided(stat.data_ptr(), slots, _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(ada), ada_stride, aff.data_ptr(),
+                                                       stats.data_ptr(), B, C, H, W, groups, eps, _st(stat), _lib.ptr(rng))
+    torch.cuda.synchronize()
+    if rc != 0:
+        assert bool(torch.isnan(aff_all).all() and torch.isnan(st_all).all()), "a refused launch wrote to aff / stats"
+        _lib.check(rc)
+    assert guard_intact(aff_all, 64) and guard_intact(st_all, 64), "write outside aff / stats"
+    return aff, stats, _recorded(rng)
