@@ -34,7 +34,13 @@ return-probability, mean, std and median maps.
 ``--ensemble_coherence`` (with ``--ensemble``) also scores the members across pixels, which none of the above does: the energy score and
 the variogram score of order 0.5 over ``--coherence_offsets`` (pairs "dh,dw"; default r2dm_amd.completion.DEFAULT_OFFSETS), which tell a
 coherent draw from per-pixel noise with the same marginals (``results[kind][method]["ensemble"]["coherence"]``; DESIGN.md section 4,
-"Ensemble coherence")."""
+"Ensemble coherence").
+
+``--voxel_iou S [S ...]`` also scores the same clouds by voxel occupancy at the voxel sizes S in metres (the literature's column is 0.1):
+IoU, precision, recall and F1 of the occupied voxels, whole image and inpainted pixels (``results[kind][method]["voxel"]``); with
+``--ensemble K`` (at most 63 then) the K members also vote on every voxel -- the members' IoU, the "any" and "consensus" occupancy against
+the scan's, the Brier score of the occupancy probability and its reliability curve (``results[kind][method]["ensemble"]["occupancy"]``;
+DESIGN.md section 4, "Voxel occupancy")."""
 import json
 from argparse import SUPPRESS, ArgumentParser
 from pathlib import Path
@@ -110,7 +116,8 @@ def main(argv=None):
                                          chamfer=args.chamfer, fscore_threshold=args.fscore_threshold, ddnm_resample_steps=args.ddnm_resample_steps,
                                          ddnm_init=None if args.ddnm_init == "none" else args.ddnm_init, ddnm_t_start=args.ddnm_t_start,
                                          **{**dpmpp, "dpmpp_init": None if dpmpp["dpmpp_init"] == "none" else dpmpp["dpmpp_init"]},
-                                         **({"ensemble": args.ensemble} if hasattr(args, "ensemble") else {}), **coherence)
+                                         **({"ensemble": args.ensemble} if hasattr(args, "ensemble") else {}), **coherence,
+                                         **({"voxel_sizes": args.voxel_iou} if hasattr(args, "voxel_iou") else {}))
     results, kept = out if args.save_dir is not None else (out, None)
     info = {"ckpt": str(args.ckpt), "source": str(args.real_scans if args.real_scans is not None else args.real_dir), "num_scans": len(files),
             "resolution": list(cfg.data.resolution), "corruptions": kinds, "methods": list(args.methods), "num_steps": args.num_steps,
@@ -127,6 +134,8 @@ def main(argv=None):
         info["ensemble"] = args.ensemble
     if coherence:
         info["ensemble_coherence"] = True
+    if hasattr(args, "voxel_iou"):
+        info["voxel_sizes"] = args.voxel_iou
     doc = completion.jsonable({"info": info, "results": results})
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     with open(args.out, "w") as f:
@@ -144,14 +153,18 @@ def main(argv=None):
             print(f"{kind:>20} {method:>8}: MAE depth {m['mae_depth']:.4f} m, reflectance {m['mae_reflectance']:.4f}, recall {m['return_recall']:.4f}"
                   + ("" if iou is None else f", mIoU {iou:.4f}")
                   + (f", inpainted CD {entry['geometry']['inpainted']['micro']['cd']:.4f} m, F-score {entry['geometry']['inpainted']['micro']['fscore']:.4f}"
-                     if "geometry" in entry else ""))
+                     if "geometry" in entry else "")
+                  + (f", inpainted voxel IoU {entry['voxel']['inpainted']['micro']['iou'][0]:.4f} at {entry['voxel']['sizes'][0]:g} m"
+                     if "voxel" in entry else ""))
             if "ensemble" in entry:
                 e = entry["ensemble"]
                 print(f"{'':>20} {'':>8}  {e['members']} members: CRPS depth {e['micro']['crps_depth']:.4f} m, spread / skill "
                       f"{e['micro']['spread_skill_depth']:.3f}, Brier {e['micro']['brier_return']:.4f}, best-of-K MAE {e['micro']['best_mae_depth']:.4f} m, "
                       f"consensus MAE {e['consensus']['micro']['mae_depth']:.4f} m"
                       + (f", energy depth {e['coherence']['macro']['energy_depth']:.4f} m, variogram depth "
-                         f"{e['coherence']['micro']['variogram_total_depth']:.4f} m" if "coherence" in e else ""))
+                         f"{e['coherence']['micro']['variogram_total_depth']:.4f} m" if "coherence" in e else "")
+                      + (f", occupancy Brier {e['occupancy']['all']['micro']['brier'][0]:.4f}, consensus voxel IoU "
+                         f"{e['occupancy']['all']['micro']['consensus_iou'][0]:.4f} at {e['occupancy']['sizes'][0]:g} m" if "occupancy" in e else ""))
     print(f"{len(files)} scans -> {args.out}")
     return doc
 
@@ -225,6 +238,9 @@ def build_parser():
     parser.add_argument("--chamfer", action="store_true",
                         help="also Chamfer distance and F-score of the completed scan's points against the real scan's, whole image and inpainted pixels")
     parser.add_argument("--fscore_threshold", type=float, default=0.2, help="the F-score's distance threshold in metres (with --chamfer)")
+    parser.add_argument("--voxel_iou", type=float, nargs="+", default=SUPPRESS, metavar="S",  # (an attribute of the parsed arguments only when given)
+                        help="also the voxel occupancy IoU, precision, recall and F1 of the same clouds at these voxel sizes in metres (1 to 8, e.g. 0.1 0.2); "
+                             "with --ensemble K (at most 63 then) also the members' occupancy vote: Brier score, consensus IoU, reliability curve")
     parser.add_argument("--ensemble", type=int, default=SUPPRESS, metavar="K",  # (an attribute of the parsed arguments only when given)
                         help="draw K members per scan with every stochastic method and score them as an ensemble: CRPS, rank histogram, "
                              "spread against skill, Brier score of ray drop, best-of-K, the consensus scan (--save_dir keeps the per-pixel maps)")

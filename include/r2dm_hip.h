@@ -604,6 +604,37 @@ int r2dm_nn_pairs(const float* a, const int64_t* a_offsets, int64_t a_clouds, in
                   int32_t* idx_ab, const int64_t* out_ab, float* d2_ba, int32_t* idx_ba, const int64_t* out_ba, void* scratch, double* sums,
                   int64_t* status, void* stream);
 
+/* -- voxel occupancy: which cells of a grid clouds occupy -- voxel IoU / precision / recall / F1 of a pair of clouds, and the occupancy scores of
+ *    an ensemble of K clouds against a target (the reference has no code for them) -----------------------------------------------------------
+ * r2dm_voxel_occupancy: clouds as for r2dm_nn_pairs; a holds the member clouds, b the target clouds (they may be one allocation).
+ *    The voxel of a point (x, y, z) at size s is (floor(x / s), floor(y / s), floor(z / s)), each quotient an IEEE round-to-nearest fp32
+ *    division (never a reciprocal multiply: it would move points on a cell face); the grid is axis-aligned and anchored at the origin.
+ *    A point counts if its three coordinates are finite and every floor(q) lies in [-2^20, 2^20), compared in floating point; the others
+ *    are not inserted and are counted in status.
+ *    A group g is the target cloud targets[g] (int64 index into b) and the K member clouds members[g][0..K) (int64 indices into a; a cloud
+ *    may serve any number of groups).  With V(X) the set of voxels of cloud X, o(v) = [v in V(T)], c(v) = #{k: v in V(M_k)} and U the union
+ *    of the K + 1 sets, per group and size, int64, zeroed by the call:
+ *      member_out (G,S,K,2)   = |V(M_k)|, |V(M_k) n V(T)|
+ *      hist_out   (G,S,2,K+1) = #{v in U: o(v) = o, c(v) = c}    ([0][0] is 0)
+ *    A pair of clouds is K = 1: hist[1][1] the intersection, hist[0][1] the voxels of the member alone, hist[1][0] of the target alone.
+ *    Only integers are summed, by integer atomics: the outputs do not depend on the order of the points or on the schedule, bit for bit.
+ *    sizes: S HOST floats, each finite and > 0; 1 <= S <= 8.  1 <= K <= 63 (a voxel's membership mask has 64 bits, bit 63 the target's).
+ *    max_group_points: an upper bound of the points of any group, target and members together, 1 to 2^27.  Per (group, size) the call keeps
+ *    an open-addressing hash set of 63-bit voxel keys with one membership mask per slot in scratch, of capacity = the power of two
+ *    >= 2 * max_group_points (a load factor of at most 0.5 whatever the data): r2dm_voxel_occupancy_scratch_bytes = 16 * groups * sizes *
+ *    capacity + 8 * groups rounded up to 16 bytes; 0 for an empty problem or one beyond the limits (groups <= 65535, groups * sizes *
+ *    capacity <= 2^36 slots).  scratch, a and b are 16-byte aligned, everything else 8-byte aligned.
+ *    status (4) int64, zeroed by the call: [0] points with a non-finite coordinate (once per group they are part of), [1] points outside
+ *    the grid (once per group and size), [2] groups with a cloud index outside [0, clouds), offsets that are not 0 <= begin <= end <=
+ *    total, or more than max_group_points points (nothing is read through them, their outputs stay 0), [3] inserts that found no slot
+ *    (cannot happen at this load factor: the probe loop is bounded so that a defect shows as a status and not as a hang).
+ *    Nothing is allocated, nothing synchronises. */
+size_t r2dm_voxel_occupancy_scratch_bytes(int64_t groups, int64_t sizes, int64_t max_group_points);
+int r2dm_voxel_occupancy(const float* a, const int64_t* a_offsets, int64_t a_clouds, int64_t a_total, const float* b, const int64_t* b_offsets,
+                         int64_t b_clouds, int64_t b_total, const int64_t* members, const int64_t* targets, int64_t groups, int64_t num_members,
+                         const float* sizes, int64_t num_sizes, int64_t max_group_points, void* scratch, int64_t* member_out, int64_t* hist_out,
+                         int64_t* status, void* stream);
+
 /* -- earth mover's distance between clouds of equal size (the reference has no code for it) ------------------------------------------------
  * r2dm_emd_pairs: clouds and pairs as for r2dm_nn_pairs.  For a pair of clouds A, B of n points each,
  *    EMD = (1/n) min over permutations s of sum_i |a_i - b_s(i)| (Euclidean, metres).  The solver is a forward auction with

@@ -26,6 +26,7 @@ from .completion import (aggregate_coherence, aggregate_ensemble, completion_err
                          ensemble_consensus, ensemble_scores, evaluate_completion, fill_beams, iou_from_confusion, member_seed)
 from . import geometry  # noqa: E402  (Chamfer distance, F-score, COV / MMD / 1-NNA on a HIP nearest-neighbour search)
 from .geometry import chamfer_from_sums, chamfer_sums, emd_pairs, nearest_neighbors, pairwise_chamfer, pairwise_emd, set_metrics
+from .geometry import occupancy_from_counts, voxel_from_counts, voxel_iou, voxel_occupancy_counts
 from . import latent  # noqa: E402  (DDIM inversion's transfer kernel, slerp, latent interpolation and reconstruction)
 from .latent import ddim_transfer, interpolate, reconstruct, slerp
 
@@ -41,6 +42,7 @@ __all__ = [
     "ensemble_coherence", "aggregate_coherence",
     "nearest_neighbors", "chamfer_sums", "chamfer_from_sums", "pairwise_chamfer", "set_metrics",
     "emd_pairs", "pairwise_emd",
+    "voxel_iou", "voxel_occupancy_counts", "voxel_from_counts", "occupancy_from_counts",
     "ddim_transfer", "slerp", "interpolate", "reconstruct",
 ]
 __version__ = "0.4.0"

@@ -176,6 +176,9 @@ SIGNATURES = {
     "r2dm_nn_pairs_scratch_bytes": (c_size_t, [c_int64, c_int64]),
     "r2dm_nn_pairs": (c_int32, [_P, _P, c_int64, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, ctypes.c_double, _P, _P, _P, _P, _P, _P, _P,
                                 _P, _P, _P]),
+    "r2dm_voxel_occupancy_scratch_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "r2dm_voxel_occupancy": (c_int32, [_P, _P, c_int64, c_int64, _P, _P, c_int64, c_int64, _P, _P, c_int64, c_int64, POINTER(c_float), c_int64, c_int64,
+                                       _P, _P, _P, _P, _P]),
     "r2dm_emd_max_points": (c_int64, []),
     "r2dm_emd_pairs_scratch_bytes": (c_size_t, [c_int64, c_int64]),
     "r2dm_emd_pairs": (c_int32, [_P, _P, c_int64, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, ctypes.c_double, c_int64, _P, _P, _P, _P, _P,

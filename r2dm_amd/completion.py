@@ -524,7 +524,7 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
                         chamfer: bool = False, fscore_threshold: float = 0.2, ddnm_resample_steps: int = 1, ddnm_init: Optional[str] = None,
                         ddnm_t_start: float = 1.0, dpmpp_eta: float = 1.0, dpmpp_order: int = 2, dpmpp_init: Optional[str] = None,
                         dpmpp_t_start: float = 1.0, ensemble: Optional[int] = None, ensemble_coherence: bool = False,
-                        coherence_offsets=None):
+                        coherence_offsets=None, voxel_sizes=None):
     """Corrupt, complete and score ``planes`` (N,6,H,W), the masked planes of ``project_scans(layout="xyzrdm", apply_mask=True)`` at the
     model's resolution, on the GPU.
 
@@ -565,7 +565,16 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
     ``ensemble_coherence=True`` (with ``ensemble``; without it a ``ValueError``): the members are also scored across pixels
     (``ensemble_coherence_sums`` with ``coherence_offsets``, None: ``DEFAULT_OFFSETS``): every entry's ``"ensemble"`` gains ``"coherence"``
     = ``aggregate_coherence(...)`` (energy score, variogram score, diversity) and ``kept[kind]["ensemble"][method]`` gains ``"counts"``
-    (N,2), ``"dist"`` (N,2,K+1,K+1), ``"vario"`` (N,2,O,4) and ``"offsets"``.  False (the default): none of it is computed."""
+    (N,2), ``"dist"`` (N,2,K+1,K+1), ``"vario"`` (N,2,O,4) and ``"offsets"``.  False (the default): none of it is computed.
+
+    ``voxel_sizes`` = 1 to 8 voxel sizes in metres: also the voxel occupancy of the clouds ``chamfer`` scores (``geometry.voxel_iou``): every
+    entry gains ``"voxel": {"sizes", "all", "inpainted"}``, each the ``geometry.aggregate_voxel`` of the scans (micro and macro ``iou``,
+    ``precision``, ``recall``, ``f1``, a list over the sizes), and ``kept[kind]["voxel_raw"][method]`` = ``{"all", "inpainted"}`` holds the
+    (N,S,3) counts ``[intersection, voxels of the prediction, voxels of the target]``.  With ``ensemble`` (at most 63 members then: a
+    ``ValueError`` for 64) the members vote on every voxel: ``entry["ensemble"]`` gains ``"occupancy": {"sizes", "all", "inpainted"}``, each
+    the ``geometry.aggregate_occupancy`` of the scans (the members' IoU, "any" and "consensus" occupancy against the target, the Brier score
+    of the occupancy probability, the reliability curve), and ``kept[kind]["ensemble"][method]`` gains ``"occupancy"`` = ``{"all",
+    "inpainted"}``, each ``{"member" (N,S,K,2), "hist" (N,S,2,K+1)}``.  None (the default): none of it is computed."""
     from . import geometry
     from .inference import setup_rng
     from .projection import known_from_scan
@@ -594,6 +603,10 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
         raise ValueError(f"ensemble must be None or a number of members in [1, {MAX_MEMBERS}], got {ensemble!r}")
     if ensemble_coherence and ensemble is None:
         raise ValueError("ensemble_coherence scores the members of an ensemble: give ensemble = K as well")
+    if voxel_sizes is not None:
+        voxel_sizes = [float(v) for v in geometry._voxel_sizes(voxel_sizes)]
+        if ensemble is not None:
+            geometry._check_members(ensemble)
     if planes.dim() != 4 or planes.shape[1] != 6:
         raise ValueError(f"expected planes (N,6,H,W) [x, y, z, reflectance, depth, mask], got {tuple(planes.shape)}")
     _lib.require_gpu(planes, "planes")
@@ -632,6 +645,23 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
                                               *geometry.clouds_of_samples(target[k:k + batch_size], lo, hi, reg), tau=fscore_threshold).cpu())
         return torch.cat(raws) if raws else torch.empty(0, len(geometry.RAW_NAMES), dtype=torch.float64)
 
+    def voxel_of(pred, region):
+        raws = []
+        for k in range(0, N, batch_size):
+            reg = None if region is None else region[k:k + batch_size]
+            raws.append(geometry.voxel_iou(*geometry.clouds_of_samples(pred[k:k + batch_size], lo, hi, reg),
+                                           *geometry.clouds_of_samples(target[k:k + batch_size], lo, hi, reg), sizes=voxel_sizes)["counts"].cpu())
+        return torch.cat(raws) if raws else torch.empty(0, len(voxel_sizes), 3, dtype=torch.int64)
+
+    def occupancy_of(samples, tgt, region):
+        """the members of every scan of a batch, (B,K,5,H,W), vote on the voxels: (member (B,S,K,2), hist (B,S,2,K+1)) on the CPU"""
+        B, K = samples.shape[:2]
+        reg = None if region is None else region.repeat_interleave(K, dim=0)
+        res = geometry.voxel_occupancy_counts(*geometry.clouds_of_samples(samples.flatten(0, 1), lo, hi, reg),
+                                              *geometry.clouds_of_samples(tgt, lo, hi, region), torch.arange(B * K).reshape(B, K), torch.arange(B),
+                                              voxel_sizes)
+        return res["member"].cpu(), res["hist"].cpu()
+
     target_labels = labels_of(target) if semseg is not None else None
     results, kept = {}, {}
     for kind, (name, _) in parsed.items():
@@ -645,6 +675,8 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
                 kept[kind].update(target_labels=target_labels.cpu(), labels={}, confusion={})
             if chamfer:
                 kept[kind]["geometry_raw"] = {}
+            if voxel_sizes is not None:
+                kept[kind]["voxel_raw"] = {}
         for method in methods:
             if method in FILL_MODES and name not in ROW_KINDS:
                 results[kind][method] = {"skipped": f"{method} interpolation is defined for masks of whole rows ({', '.join(ROW_KINDS)})"}
@@ -693,9 +725,13 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
             if chamfer:
                 graw = {"all": geometry_of(pred, None), "inpainted": geometry_of(pred, mask == 0)}
                 entry["geometry"] = {where: geometry.aggregate_chamfer(r) for where, r in graw.items()}
+            if voxel_sizes is not None:
+                vraw = {"all": voxel_of(pred, None), "inpainted": voxel_of(pred, mask == 0)}
+                entry["voxel"] = {"sizes": voxel_sizes, **{where: geometry.aggregate_voxel(r, voxel_sizes) for where, r in vraw.items()}}
             if ensemble is not None:
                 eraw, emember, erank, emaps, craw = [], [], [], [], []
                 ccounts, cdist, cvario = [], [], []
+                occ = {"all": ([], []), "inpainted": ([], [])}
                 for k in range(0, N, batch_size):
                     if x_members is None or members == 1:
                         samples = pred[k:k + batch_size, None]
@@ -709,6 +745,10 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
                     if ensemble_coherence:
                         cc, cd, cv, _ = ensemble_coherence_sums(samples, target[k:k + batch_size], mask[k:k + batch_size], lo, hi, coherence_offsets)
                         ccounts.append(cc.cpu()), cdist.append(cd.cpu()), cvario.append(cv.cpu())
+                    if voxel_sizes is not None:
+                        for where, region in (("all", None), ("inpainted", mask[k:k + batch_size] == 0)):
+                            om, oh = occupancy_of(samples, target[k:k + batch_size], region)
+                            occ[where][0].append(om), occ[where][1].append(oh)
                     if keep:
                         emaps.append(maps.cpu())
                 eraw = torch.cat(eraw) if eraw else torch.empty(0, len(ENSEMBLE_RAW_NAMES), dtype=torch.float64)
@@ -721,6 +761,12 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
                     cdist = torch.cat(cdist) if cdist else torch.empty(0, 2, members + 1, members + 1, dtype=torch.float64)
                     cvario = torch.cat(cvario) if cvario else torch.empty(0, 2, len(coherence_offsets), 4, dtype=torch.float64)
                     entry["ensemble"]["coherence"] = aggregate_coherence(ccounts, cdist, cvario, coherence_offsets)
+                if voxel_sizes is not None:
+                    S = len(voxel_sizes)
+                    occ = {where: {"member": torch.cat(m) if m else torch.empty(0, S, members, 2, dtype=torch.int64),
+                                   "hist": torch.cat(h) if h else torch.empty(0, S, 2, members + 1, dtype=torch.int64)} for where, (m, h) in occ.items()}
+                    entry["ensemble"]["occupancy"] = {"sizes": voxel_sizes, **{where: geometry.aggregate_occupancy(o["member"], o["hist"], voxel_sizes)
+                                                                              for where, o in occ.items()}}
             results[kind][method] = entry
             if keep:
                 if ensemble is not None:
@@ -730,6 +776,8 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
                         "x_out": None if x_members is None else x_members.cpu()}
                     if ensemble_coherence:
                         kept[kind]["ensemble"][method].update(counts=ccounts, dist=cdist, vario=cvario, offsets=coherence_offsets)
+                    if voxel_sizes is not None:
+                        kept[kind]["ensemble"][method]["occupancy"] = occ
                 kept[kind]["x_out"][method] = None if x_out is None else x_out.cpu()
                 kept[kind]["pred"][method] = pred.cpu()
                 kept[kind]["raw"][method] = raw
@@ -738,4 +786,6 @@ def evaluate_completion(ddpm, lidar_utils, planes: torch.Tensor, kinds: Sequence
                     kept[kind]["confusion"][method] = conf
                 if chamfer:
                     kept[kind]["geometry_raw"][method] = graw
+                if voxel_sizes is not None:
+                    kept[kind]["voxel_raw"][method] = vraw
     return (results, kept) if keep else results

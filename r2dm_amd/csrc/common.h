@@ -403,6 +403,18 @@ hipError_t launch_nn_pairs(const float* a, const long long* off_a, long clouds_a
                            const long long* out_ab, float* d2_ba, int* idx_ba, const long long* out_ba, void* scratch, double* sums,
                            long long* status, hipStream_t s);
 
+// voxel occupancy (voxel.hip): G groups of one target cloud (from b) and K member clouds (from a) at S voxel sizes (HOST floats) -- a hash set of
+// voxel keys per (group, size) with one membership bit per cloud; member_out (G,S,K,2) = |V(M_k)|, |V(M_k) n V(T)|, hist_out (G,S,2,K+1) =
+// #{voxels: in the target or not, in c members}; status[4] = non-finite points, points outside the grid, groups that do not check out, inserts
+// that found the table full
+long voxel_capacity(long max_group_points);
+bool voxel_geometry_ok(long G, long S, long max_group_points);
+size_t voxel_occupancy_scratch_bytes(long G, long S, long max_group_points);
+hipError_t launch_voxel_occupancy(const float* a, const long long* off_a, long clouds_a, long total_a, const float* b, const long long* off_b,
+                                  long clouds_b, long total_b, const long long* members, const long long* targets, long G, long K, const float* sizes,
+                                  long S, long max_group_points, void* scratch, long long* member_out, long long* hist_out, long long* status,
+                                  hipStream_t s);
+
 // earth mover's distance (emd.hip): a forward auction per pair of equally sized clouds -- out (P,4) = emd, lower, rounds, converged; optional
 // assignment / prices (P, max_points); scratch = one code per pair; status[5] = pairs ended as bad pair, unequal counts, non-finite, eps below
 // its floor, round cap

@@ -647,6 +647,39 @@ int r2dm_nn_pairs(const float* a, const int64_t* a_offsets, int64_t a_clouds, in
     return 0;
 }
 
+size_t r2dm_voxel_occupancy_scratch_bytes(int64_t G, int64_t S, int64_t max_group_points) {
+    return voxel_geometry_ok(G, S, max_group_points) ? voxel_occupancy_scratch_bytes(G, S, max_group_points) : 0;
+}
+
+int r2dm_voxel_occupancy(const float* a, const int64_t* a_offsets, int64_t a_clouds, int64_t a_total, const float* b, const int64_t* b_offsets,
+                         int64_t b_clouds, int64_t b_total, const int64_t* members, const int64_t* targets, int64_t G, int64_t K, const float* sizes,
+                         int64_t S, int64_t max_group_points, void* scratch, int64_t* member_out, int64_t* hist_out, int64_t* status, void* stream) {
+    if (!a_offsets || !b_offsets || !members || !targets || !sizes || !scratch || !member_out || !hist_out || !status) return fail(1, "null argument");
+    if (a_clouds < 1 || b_clouds < 1 || a_total < 0 || b_total < 0 || (!a && a_total) || (!b && b_total))
+        return fail(1, "voxel_occupancy: each set needs at least one cloud, and a pointer unless it has no points");
+    if (G < 1 || K < 1 || S < 1) return fail(1, "voxel_occupancy: groups, members and sizes must be >= 1, got %lld, %lld, %lld", (long long)G, (long long)K, (long long)S);
+    if (K > 63)
+        return fail(1, "voxel_occupancy: at most 63 members per group (a voxel's membership mask has 64 bits and bit 63 is the target's), got %lld", (long long)K);
+    if (S > 8) return fail(1, "voxel_occupancy: at most 8 voxel sizes per call, got %lld", (long long)S);
+    if ((uintptr_t)sizes & 3) return fail(1, "voxel_occupancy: sizes must be 4-byte aligned");
+    for (int64_t i = 0; i < S; ++i)
+        if (!(sizes[i] > 0.0f) || !(sizes[i] <= 3.4028234663852886e38f)) return fail(1, "voxel_occupancy: a voxel size must be finite and > 0, got %g", (double)sizes[i]);
+    if (!voxel_geometry_ok(G, S, max_group_points))
+        return fail(1, "voxel_occupancy: at most 65535 groups, max_group_points in [1, 2^27] and groups * sizes * capacity at most 2^36 slots "
+                       "(capacity: the power of two >= 2 * max_group_points), got %lld groups, %lld sizes, max_group_points = %lld",
+                    (long long)G, (long long)S, (long long)max_group_points);
+    if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)scratch) & 15)
+        return fail(1, "voxel_occupancy: a, b and scratch must be 16-byte aligned (rows and slots are accessed as quads and pairs)");
+    if (((uintptr_t)a_offsets | (uintptr_t)b_offsets | (uintptr_t)members | (uintptr_t)targets | (uintptr_t)member_out | (uintptr_t)hist_out |
+         (uintptr_t)status) & 7)
+        return fail(1, "voxel_occupancy: offsets, members, targets, member_out, hist_out and status must be 8-byte aligned");
+    HIP_TRY(launch_voxel_occupancy(a, reinterpret_cast<const long long*>(a_offsets), a_clouds, a_total, b, reinterpret_cast<const long long*>(b_offsets),
+                                   b_clouds, b_total, reinterpret_cast<const long long*>(members), reinterpret_cast<const long long*>(targets), G, K,
+                                   sizes, S, max_group_points, scratch, reinterpret_cast<long long*>(member_out), reinterpret_cast<long long*>(hist_out),
+                                   reinterpret_cast<long long*>(status), (hipStream_t)stream));
+    return 0;
+}
+
 static bool emd_geometry_ok(int64_t P, int64_t max_points, double eps, int64_t max_rounds) {
     // (eps must also be a normal fp32 number: the auction bids in fp32)
     return P >= 1 && P <= 0x7fffffffLL && max_points >= 1 && max_points <= emd_max_points() && eps >= 1.1754943508222875e-38 && eps <= 3.4028234663852886e38 &&

@@ -13,9 +13,16 @@ Clouds are sets of 3-D points in metres; ``d(x, Y) = min_{y in Y} |x - y|``.
 - earth mover's distance of two clouds of the same number n of points: ``EMD = (1/n) min_sigma sum_i |a_i - b_sigma(i)|`` over the
   permutations sigma (Euclidean, not squared: PointFlow's convention).  ``emd_pairs`` returns a permutation, its true cost ``emd`` and a
   certified ``lower <= EMD <= emd``; the set metrics above take its matrix (``pairwise_emd``) as they take ``cd_sq``'s.
+- voxel occupancy at voxel size s: the voxel of a point is ``floor(x / s), floor(y / s), floor(z / s)`` (IEEE float32 divisions, a grid
+  anchored at the origin), ``V(X)`` the set of voxels of cloud X.  ``voxel_iou``: ``|V(A) n V(B)| / |V(A) u V(B)|`` with precision, recall
+  and F1 of the voxel sets.  For an ensemble of K clouds against a target, ``voxel_occupancy_counts`` gives per voxel of the union the
+  number c of members that occupy it and whether the target does, as a ``2 x (K + 1)`` histogram; ``occupancy_from_counts`` derives the
+  members' IoU, the "any" (c >= 1) and "consensus" (2 c >= K) occupancy against the target, the Brier score of the occupancy probability
+  c / K and its reliability curve.  All of it from integer counts: exact, and the same bits in any order.
 
 The search is one HIP kernel (``r2dm_nn_pairs``, ``r2dm_amd/csrc/geometry.hip``) over a list of cloud pairs, the assignment solver another
-(``r2dm_emd_pairs``, ``r2dm_amd/csrc/emd.hip``); neither has a CPU fallback.
+(``r2dm_emd_pairs``, ``r2dm_amd/csrc/emd.hip``), the voxel sets a hash set in global memory (``r2dm_voxel_occupancy``,
+``r2dm_amd/csrc/voxel.hip``); none has a CPU fallback.
 What is derived from its sums and from distance matrices is plain torch and works on CPU tensors too."""
 from __future__ import annotations
 
@@ -280,6 +287,241 @@ def pairwise_chamfer(A: torch.Tensor, countsA, B: torch.Tensor, countsB) -> torc
         status += st
     _raise_on_status(status)
     return chamfer_from_sums(out)["cd_sq"].reshape(Na, Nb)
+
+
+# ---- voxel occupancy ---------------------------------------------------------------------------------------------------------------------
+VOXEL_STATUS = ("nonfinite", "out_of_grid", "bad_groups", "table_full")
+VOXEL_NAMES = ("iou", "precision", "recall", "f1")
+VOXEL_MAX_SIZES = 8
+VOXEL_MAX_MEMBERS = 63        # a voxel's membership mask has 64 bits, bit 63 is the target's
+VOXEL_SLAB_BYTES = 1 << 30    # voxel_occupancy_counts: the hash tables of one call stay below this (or hold one group)
+
+
+def _voxel_sizes(sizes) -> np.ndarray:
+    try:
+        s = np.asarray(sizes if isinstance(sizes, (list, tuple, np.ndarray)) else [sizes], dtype=np.float64).astype(np.float32)  # the size is its fp32 value
+    except (TypeError, ValueError):
+        raise ValueError(f"voxel sizes: expected 1 to {VOXEL_MAX_SIZES} numbers, got {sizes!r}") from None
+    if s.ndim != 1 or not 1 <= s.size <= VOXEL_MAX_SIZES:
+        raise ValueError(f"voxel sizes: expected 1 to {VOXEL_MAX_SIZES} numbers, got {sizes!r}")
+    if not (np.isfinite(s) & (s > 0)).all():
+        raise ValueError(f"voxel sizes must be finite and > 0 in float32, got {sizes!r}")
+    return s
+
+
+def _check_members(K: int) -> None:
+    if not 1 <= K <= VOXEL_MAX_MEMBERS:
+        raise ValueError(f"voxel occupancy takes 1 to {VOXEL_MAX_MEMBERS} members per group (a voxel's membership mask has 64 bits and one is the "
+                         f"target's), got {K}")
+
+
+def _voxel_capacity(max_group_points: int) -> int:
+    cap = 2
+    while cap < 2 * max_group_points:
+        cap <<= 1
+    return cap
+
+
+def _voxel_launch(a, off_a, clouds_a, b, off_b, clouds_b, members_dev, targets_dev, sizes: np.ndarray, max_group_points: int):
+    """One ``r2dm_voxel_occupancy`` call on device tensors -> ``(member (G,S,K,2), hist (G,S,2,K+1), status (4,))`` int64, nothing read back."""
+    dev, (G, K), S = a.device, members_dev.shape, int(sizes.size)
+    L = _lib.lib()
+    nbytes = L.r2dm_voxel_occupancy_scratch_bytes(G, S, max_group_points)
+    if nbytes == 0:
+        raise ValueError(f"{G} groups of up to {max_group_points} points at {S} sizes: beyond the limits of r2dm_voxel_occupancy (65535 groups, "
+                         "2^27 points per group, groups * sizes * capacity at most 2^36 slots)")
+    scratch = torch.empty(nbytes // 16, 2, dtype=torch.int64, device=dev)
+    member = torch.empty(G, S, K, 2, dtype=torch.int64, device=dev)
+    hist = torch.empty(G, S, 2, K + 1, dtype=torch.int64, device=dev)
+    status = torch.empty(len(VOXEL_STATUS), dtype=torch.int64, device=dev)
+    host_sizes = (_lib.c_float * S)(*sizes.tolist())
+    with torch.cuda.device(dev):
+        _lib.check(L.r2dm_voxel_occupancy(_lib.ptr(a) or None, _lib.ptr(off_a), clouds_a, a.shape[0], _lib.ptr(b) or None, _lib.ptr(off_b), clouds_b,
+                                          b.shape[0], _lib.ptr(members_dev), _lib.ptr(targets_dev), G, K, host_sizes, S, max_group_points,
+                                          _lib.ptr(scratch), _lib.ptr(member), _lib.ptr(hist), _lib.ptr(status), _lib.stream_ptr(dev)))
+    return member, hist, status
+
+
+def _raise_on_voxel_status(status: torch.Tensor) -> None:
+    counts = dict(zip(VOXEL_STATUS, (int(v) for v in status.cpu().tolist())))
+    if counts["bad_groups"]:
+        raise _lib.R2DMError(f"r2dm_voxel_occupancy: {counts['bad_groups']} groups with a cloud index or offsets that do not check out")
+    if counts["table_full"]:
+        raise _lib.R2DMError(f"r2dm_voxel_occupancy: {counts['table_full']} inserts found their hash table full (a defect: the load factor is at most 0.5)")
+    if counts["nonfinite"]:
+        raise ValueError(f"voxel occupancy: {counts['nonfinite']} points with a non-finite coordinate (counted once per group they are part of)")
+    if counts["out_of_grid"]:
+        raise ValueError(f"voxel occupancy: {counts['out_of_grid']} points outside the grid of 2^21 cells per axis, floor(x / size) in [-2^20, 2^20) "
+                         "(counted once per group and size)")
+
+
+def _group_indices(members, targets):
+    mem = members.detach().cpu().numpy() if isinstance(members, torch.Tensor) else np.asarray(members)
+    tgt = targets.detach().cpu().numpy() if isinstance(targets, torch.Tensor) else np.asarray(targets)
+    if mem.ndim != 2 or mem.shape[1] < 1 or (mem.size and mem.dtype.kind not in "iu"):
+        raise ValueError(f"members: expected (G,K) integers, K >= 1 cloud indices into a per group, got shape {mem.shape} {mem.dtype}")
+    if tgt.ndim != 1 or tgt.shape[0] != mem.shape[0] or (tgt.size and tgt.dtype.kind not in "iu"):
+        raise ValueError(f"targets: expected ({mem.shape[0]},) integers, one cloud index into b per group, got shape {tgt.shape} {tgt.dtype}")
+    _check_members(mem.shape[1])
+    return np.ascontiguousarray(mem.astype(np.int64)), np.ascontiguousarray(tgt.astype(np.int64))
+
+
+def voxel_occupancy_counts(a: torch.Tensor, a_offsets, b: torch.Tensor, b_offsets, members, targets, sizes, _raise: bool = True) -> dict:
+    """The voxels that groups of clouds occupy, counted (``r2dm_voxel_occupancy``, ``r2dm_amd/csrc/voxel.hip``).
+
+    Clouds as for ``nearest_neighbors``.  Group g is the target cloud ``targets[g]`` of ``b`` and the K member clouds ``members[g]`` of ``a``
+    (``members`` (G,K), ``targets`` (G,) integers; 1 <= K <= 63; a cloud may be part of any number of groups).  The voxel of a point at size s
+    (metres, rounded to float32) is ``floor(x / s), floor(y / s), floor(z / s)`` with IEEE float32 divisions; ``sizes``: 1 to 8 of them.
+    -> ``{"member": (G,S,K,2), "hist": (G,S,2,K+1)}`` int64 on the device: per group and size ``member[k] = (|V(M_k)|, |V(M_k) n V(T)|)`` and
+    ``hist[o][c]`` = the number of voxels of the union that are in the target (o = 1) or not (o = 0) and in c members.  Integers summed by
+    integer atomics: the same bits for any order of the points, and the member rows permute with the members.
+
+    The groups go through the kernel in slabs, so that the hash tables of one call (16 bytes per slot, the power of two >= 2 * the points of
+    the slab's largest group slots per group and size) stay below ``VOXEL_SLAB_BYTES`` or hold a single group.  A point with a non-finite
+    coordinate or outside the grid (``floor(x / s)`` in [-2^20, 2^20)) raises ``ValueError``, a cloud index outside its set ``R2DMError``.
+    There is no CPU fallback."""
+    a, b = _points(a, "a"), _points(b, "b")
+    if b.device != a.device:
+        raise ValueError(f"a is on {a.device}, b on {b.device}")
+    off_a, off_b = _host_offsets(a_offsets, a.shape[0], "a_offsets"), _host_offsets(b_offsets, b.shape[0], "b_offsets")
+    mem, tgt = _group_indices(members, targets)
+    sizes = _voxel_sizes(sizes)
+    dev, (G, K), S = a.device, mem.shape, int(sizes.size)
+    out = {"member": torch.zeros(G, S, K, 2, dtype=torch.int64, device=dev), "hist": torch.zeros(G, S, 2, K + 1, dtype=torch.int64, device=dev)}
+    status = torch.zeros(len(VOXEL_STATUS), dtype=torch.int64, device=dev)
+    if G:
+        # points per group, to size the tables (an index out of range counts nothing here: the device refuses the group)
+        na, nb = np.diff(off_a), np.diff(off_b)
+        count = lambda n, idx: np.where((idx >= 0) & (idx < n.size), n[np.clip(idx, 0, n.size - 1)], 0)
+        points = count(na, mem).sum(axis=1) + count(nb, tgt)
+        oa, ob = torch.from_numpy(off_a).to(dev), torch.from_numpy(off_b).to(dev)
+        mem_dev, tgt_dev = torch.from_numpy(mem).to(dev), torch.from_numpy(tgt).to(dev)
+        g0 = 0
+        while g0 < G:
+            g1, most = g0 + 1, max(int(points[g0]), 1)
+            while g1 < G and g1 - g0 < 65535:  # grow the slab while its tables fit
+                grown = max(most, int(points[g1]))
+                if (g1 + 1 - g0) * S * _voxel_capacity(grown) * 16 > VOXEL_SLAB_BYTES:
+                    break
+                g1, most = g1 + 1, grown
+            m, h, st = _voxel_launch(a, oa, off_a.size - 1, b, ob, off_b.size - 1, mem_dev[g0:g1].contiguous(), tgt_dev[g0:g1].contiguous(), sizes, most)
+            out["member"][g0:g1], out["hist"][g0:g1] = m, h
+            status += st
+            g0 = g1
+    if _raise:
+        _raise_on_voxel_status(status)
+        return out
+    return {**out, "status": status}
+
+
+def _ratio64(num: torch.Tensor, den: torch.Tensor) -> torch.Tensor:
+    """num / den in float64, NaN where den == 0"""
+    num, den = num.double(), den.double()
+    return torch.where(den != 0, num / torch.where(den != 0, den, torch.ones_like(den)), torch.full_like(den, math.nan))
+
+
+def _set_scores(inter: torch.Tensor, pred: torch.Tensor, target: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """``VOXEL_NAMES`` of a predicted set against a target set from |P n T|, |P|, |T|: IoU = |P n T| / |P u T|, precision = |P n T| / |P|,
+    recall = |P n T| / |T|, F1 = 2 |P n T| / (|P| + |T|) (the harmonic mean of the two wherever both are defined); NaN for a denominator of 0."""
+    return {"iou": _ratio64(inter, pred + target - inter), "precision": _ratio64(inter, pred), "recall": _ratio64(inter, target),
+            "f1": _ratio64(2 * inter, pred + target)}
+
+
+def _integers(t, what: str) -> torch.Tensor:
+    t = torch.as_tensor(t)
+    if t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise ValueError(f"{what}: expected integer counts, got {t.dtype}")
+    return t.long()
+
+
+def voxel_from_counts(counts) -> Dict[str, torch.Tensor]:
+    """``(...,3)`` integers ``[intersection, voxels_a, voxels_b]`` (a is the prediction) -> ``iou``, ``precision``, ``recall``, ``f1`` in float64,
+    NaN where the denominator is 0 (an empty cloud).  Plain torch."""
+    counts = _integers(counts, "counts")
+    if counts.dim() < 1 or counts.shape[-1] != 3:
+        raise ValueError(f"expected (...,3) counts [intersection, voxels_a, voxels_b], got {tuple(counts.shape)}")
+    return _set_scores(counts[..., 0], counts[..., 1], counts[..., 2])
+
+
+def voxel_iou(a: torch.Tensor, a_offsets, b: torch.Tensor, b_offsets, pairs=None, sizes=(0.1,)) -> dict:
+    """Voxel occupancy IoU of cloud pairs: the K = 1 case of ``voxel_occupancy_counts``.  Clouds and ``pairs`` as for ``nearest_neighbors`` (a is
+    the prediction, b the target), ``sizes`` the voxel sizes in metres.  -> a dict of device tensors: ``counts`` (P,S,3) int64
+    ``[intersection, voxels_a, voxels_b]`` and ``iou``, ``precision``, ``recall``, ``f1`` (P,S) float64 (``voxel_from_counts``).  An empty cloud
+    has no voxels: its counts are 0 and the values whose denominator is 0 are NaN."""
+    off_a, off_b = _host_offsets(a_offsets, a.shape[0], "a_offsets"), _host_offsets(b_offsets, b.shape[0], "b_offsets")
+    pr = _pairs(pairs, off_a.size - 1, off_b.size - 1)
+    res = voxel_occupancy_counts(a, off_a, b, off_b, pr[:, :1], pr[:, 1], sizes)
+    hist = res["hist"]                                            # (P,S,2,2)
+    inter = hist[..., 1, 1]
+    counts = torch.stack([inter, inter + hist[..., 0, 1], inter + hist[..., 1, 0]], dim=-1)
+    return {"counts": counts, **voxel_from_counts(counts)}
+
+
+def occupancy_from_counts(member, hist) -> Dict[str, torch.Tensor]:
+    """The occupancy scores of an ensemble from the integers of ``voxel_occupancy_counts``: ``member`` (...,K,2), ``hist`` (...,2,K+1).  In
+    float64, NaN for a denominator of 0, plain torch:
+
+    - ``union`` = |U|, ``voxels_target`` = |V(T)| (int64);
+    - ``member_iou`` / ``member_precision`` / ``member_recall`` / ``member_f1`` (...,K): every member's own voxel set against the target's;
+    - ``any_*``: the voxels at least one member occupies (c >= 1) against the target's;
+    - ``consensus_*``: the voxels at least half of the members occupy (2 c >= K);
+    - ``brier`` = the mean over U of (c / K - o)^2 = sum_c (hist[0][c] c^2 + hist[1][c] (K - c)^2) / (K^2 |U|);
+    - ``reliability`` (...,K+1) = hist[1][c] / (hist[0][c] + hist[1][c]): of the voxels c members occupy, the fraction the target occupies
+      (c / K for a calibrated ensemble)."""
+    member, hist = _integers(member, "member"), _integers(hist, "hist")
+    if hist.dim() < 2 or hist.shape[-2] != 2 or hist.shape[-1] < 2:
+        raise ValueError(f"expected hist (...,2,K+1), got {tuple(hist.shape)}")
+    K = hist.shape[-1] - 1
+    if member.dim() < 2 or tuple(member.shape[-2:]) != (K, 2) or member.shape[:-2] != hist.shape[:-2]:
+        raise ValueError(f"expected member (...,{K},2) next to hist {tuple(hist.shape)}, got {tuple(member.shape)}")
+    c = torch.arange(K + 1, device=hist.device)
+    target = hist[..., 1, :].sum(-1)
+    out = {"union": hist.sum((-2, -1)), "voxels_target": target}
+    for name, v in _set_scores(member[..., 1], member[..., 0], target[..., None]).items():
+        out[f"member_{name}"] = v
+    for head, keep in (("any", c >= 1), ("consensus", 2 * c >= K)):
+        sel = hist * keep.long()
+        for name, v in _set_scores(sel[..., 1, :].sum(-1), sel.sum((-2, -1)), target).items():
+            out[f"{head}_{name}"] = v
+    out["brier"] = _ratio64((hist[..., 0, :] * c * c + hist[..., 1, :] * (K - c) * (K - c)).sum(-1), K * K * out["union"])
+    out["reliability"] = _ratio64(hist[..., 1, :], hist[..., 0, :] + hist[..., 1, :])
+    return out
+
+
+def _mean_defined(v: torch.Tensor) -> torch.Tensor:
+    """the mean over dim 0 of the values that are not NaN; NaN where there is none"""
+    ok = ~v.isnan()
+    return _ratio64(torch.where(ok, v, torch.zeros_like(v)).sum(0), ok.sum(0))
+
+
+def aggregate_voxel(counts, sizes) -> dict:
+    """(N,S,3) per-scan counts -> ``{"scans", "empty", "sizes", "micro", "macro"}`` over the scans whose two clouds both have points (``empty``
+    counts the others): micro = the values of the summed counts, macro = the mean of the per-scan values; each a list over the sizes, NaN if
+    no scan is left."""
+    counts = _integers(counts, "counts").detach().cpu()
+    sizes = [float(s) for s in _voxel_sizes(sizes)]
+    counts = counts.reshape(-1, len(sizes), 3)
+    ok = ((counts[..., 1] > 0) & (counts[..., 2] > 0)).all(dim=1) if counts.shape[0] else torch.zeros(0, dtype=torch.bool)
+    used = counts[ok]
+    return {"scans": int(counts.shape[0]), "empty": int((~ok).sum().item()), "sizes": sizes,
+            "micro": {k: v.tolist() for k, v in voxel_from_counts(used.sum(0)).items()},
+            "macro": {k: _mean_defined(v).tolist() for k, v in voxel_from_counts(used).items()}}
+
+
+def aggregate_occupancy(member, hist, sizes) -> dict:
+    """(N,S,K,2), (N,S,2,K+1) per-scan integers -> ``{"scans", "empty", "members", "sizes", "hist", "micro", "macro"}`` over the scans whose
+    target has voxels (``empty`` counts the others): ``hist`` (S,2,K+1) the summed histogram, micro = ``occupancy_from_counts`` of the summed
+    integers, macro = the mean of the per-scan values that are defined; lists over the sizes (and the members, and c)."""
+    member, hist = _integers(member, "member").detach().cpu(), _integers(hist, "hist").detach().cpu()
+    sizes = [float(s) for s in _voxel_sizes(sizes)]
+    K = hist.shape[-1] - 1
+    member, hist = member.reshape(-1, len(sizes), K, 2), hist.reshape(-1, len(sizes), 2, K + 1)
+    ok = (hist[:, :, 1].sum(-1) > 0).all(dim=1) if hist.shape[0] else torch.zeros(0, dtype=torch.bool)
+    um, uh = member[ok], hist[ok]
+    skip = ("union", "voxels_target")
+    return {"scans": int(hist.shape[0]), "empty": int((~ok).sum().item()), "members": K, "sizes": sizes, "hist": uh.sum(0).tolist(),
+            "micro": {k: v.tolist() for k, v in occupancy_from_counts(um.sum(0), uh.sum(0)).items() if k not in skip},
+            "macro": {k: _mean_defined(v).tolist() for k, v in occupancy_from_counts(um, uh).items() if k not in skip}}
 
 
 # ---- earth mover's distance --------------------------------------------------------------------------------------------------------------
